@@ -14,8 +14,9 @@ the rank.  4096 envs per GPU (BASELINE metric), CubeS, 'normal' hand pose, env i
 
 Timed region (round 3): in ddpg mode the policy is first trained for `--pretrain-updates` (1500) untimed env-steps - the hands
 then close into contact-rich grasps and the envs' episode clocks are spread over the 30 phases - then W warm-up steps, then
-`--repeats` (3) timed windows of EXACTLY K steps each, every one between a barrier + synchronize; the line is the window of median duration
-(`timed_windows_ms_per_step` lists all).  (Rounds 1-2 timed the first episodes of a random policy, the cheapest regime.)
+`--repeats` timed windows of EXACTLY K steps each (default one; three with --full), every one between a barrier + synchronize; the line is
+the window of median duration (`timed_windows_ms_per_step` lists all).  (Rounds 1-2 timed the first episodes of a random policy, the cheapest
+regime.)
 
 Rollout form (--rollout, default auto): the free-running kernel k_rollout (actor + 15 substeps + rays + observation + replay write in one
 persistent launch of --chunk env-steps in which every wave loops over its own four envs, learner graphs beside it) when the widths are LDS-free (256-256 / 128-128 / 64-64) and
@@ -23,9 +24,22 @@ every workgroup is resident in one round; otherwise - config 5, 400-300, --eager
 launch per env-step from HIP graphs.  `config.launch` says which one ran.
 
 Prints ONE JSON line on rank 0 with `roofline` (dominant kernel k_rollout / k_env_step, HIP-event timed on the
-launch stream inside this process), `mfma` (the learner's MLP kernels against the fp32 MFMA peak), `steady_state`
-(a longer window of whole episodes right after the timed one: `value` should agree with it) and `cpu_baseline` (the fp64 CPU
-oracle on the host cores, N=1 only).
+launch stream inside the timed window).  A plain run does nothing else: set-up, warm-up, the timed steps, the outputs
+(--dump-outputs) and the line.  --full adds what takes runs of its own: three timed windows instead of one, `mfma` (the
+learner's MLP kernels replayed alone against the fp32 MFMA peak), `steady_state` (a longer window of whole episodes right after
+the timed one: `value` should agree with it) and `cpu_baseline` (the fp64 CPU oracle on the host cores, N=1 only).
+
+--dump-outputs DIR writes what the last timed step computed, as a caller of the timed path receives it, to DIR/<name>.npy
+(float32; per-env arrays env-major; `<name>.rank<r>.npy` with several ranks): ddpg mode the engine's next observation,
+action, reward and done and the flat parameters of actor, critic and their targets, sim mode the simulator's obs, reward,
+done and info.  At most 64 MB in all: beyond that the per-env arrays keep a fixed seeded sample of env rows.
+
+Reproducibility: the same arguments give the same inputs in every run, and the same outputs as long as no env dropped an
+episode (`config.free_running.episodes_dropped` == 0) and --budget-ms is not given.  For that the free-running form runs
+launch-synchronous (pipeline.AsyncTrainer(launch_synchronous=True)): the actor is published, and the episodes a launch
+finished enter the ring in an order fixed by their contents, only between launches; the learner's updates still run beside
+the launch.  --async-exchange runs the library's default form instead (actor published after every update, episodes
+collected in arrival order: not reproducible run to run).
 
 Multi-GPU: `python bench.py --gpus N` starts N ranks itself (fresh child processes, spawned BEFORE this process touches
 torch or HIP; rendezvous on 127.0.0.1) - the same thing the driver does with `python -m torch.distributed.run
@@ -180,6 +194,32 @@ def update_flops(hidden, rows, n=5, state=82, action=4):
     return 2.0 * rows * (17 * A + 20 * C)
 
 
+DUMP_BYTES_MAX = 64 << 20
+
+
+def dump_outputs(outdir, per_env, whole, suffix=""):
+    """per_env: name -> array whose first axis is the env; whole: name -> array kept entire.  Written as float32 (float64 stays
+    float64) to outdir/<name><suffix>.npy; if the total would pass DUMP_BYTES_MAX, the per-env arrays keep the same fixed,
+    seeded sample of env rows (sorted).  A folder it creates gets a .gitignore that ignores everything in it."""
+    import numpy as np
+    f = lambda a: a if a.dtype in (np.float32, np.float64) else a.astype(np.float32)
+    per_env = {k: f(np.ascontiguousarray(v)) for k, v in per_env.items()}
+    whole = {k: f(np.ascontiguousarray(v)) for k, v in whole.items()}
+    fixed = sum(a.nbytes for a in whole.values())
+    n = min((a.shape[0] for a in per_env.values()), default=0)
+    row = sum(a.nbytes // max(1, a.shape[0]) for a in per_env.values())
+    keep = max(0, (DUMP_BYTES_MAX - fixed) // max(1, row))
+    if n > keep:
+        rows = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+        per_env = {k: v[rows] for k, v in per_env.items()}
+    outdir = Path(outdir)
+    if not outdir.exists():
+        outdir.mkdir(parents=True)
+        (outdir / ".gitignore").write_text("# written by bench.py --dump-outputs\n*\n")     # a folder of outputs never shows up in git status
+    for k, v in {**per_env, **whole}.items():
+        np.save(outdir / f"{k}{suffix}.npy", v)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -217,17 +257,28 @@ def main():
                          "else lockstep (config 5's 8192 envs, 400-300, --eager, --serial-learner).  The JSON line says which (`config.launch`).")
     ap.add_argument("--budget-ms", type=float, default=0.0, help="extra measurement (not the metric): launches with a TIME budget of this many ms instead of a step count "
                     "(free-running wave form only): what the exact count's launch tail costs")
-    ap.add_argument("--repeats", type=int, default=3, help="timed windows of --steps env-steps each; the line reports the median window (all are listed)")
+    ap.add_argument("--repeats", type=int, default=None, help="timed windows of --steps env-steps each; the line reports the median window (all are listed); "
+                    "default 1, or 3 with --full")
     ap.add_argument("--chunk", type=int, default=60, help="free-running rollout: at most this many env-steps per launch (learner and rollout streams meet between launches); "
                     "a launch lasts as long as its slowest workgroup, whose lead over the mean workgroup shrinks with the square root of the steps per launch; the "
                     "learner's stream is paced on the envs' step counters (pipeline.AsyncTrainer.run, kr_wait_min), so finished episodes are collected all the way whatever the length; 60 is kept as the default because the launch pattern of the pre-training decides which policy emerges "
-                    "(launches of 100: ~10 % of the episodes end in a lift and the step is 8 % cheaper; launches of 60 + 40: 37 %, the regime all of this round's numbers are in)")
+                    "(launches of 100: ~10 %% of the episodes end in a lift and the step is 8 %% cheaper; launches of 60 + 40: 37 %%, the regime all of this round's numbers are in)")
+    ap.add_argument("--async-exchange", action="store_true", help="free-running rollout: the library's default AsyncTrainer form - the actor published after "
+                    "every update, episodes collected into the ring in arrival order - instead of the launch-synchronous one (not reproducible run to run)")
     ap.add_argument("--expert-prob", type=float, default=0.0,
                     help="ddpg mode: DDPGfD's demonstration mix (DDPGfD.py:232-254) - an expert ring is filled with one scripted 'combined'-controller "
                          "episode per env before training and every update samples int(64 (1 - p)) agent + the rest expert episodes (reference: 0.3)")
     ap.add_argument("--solver-iterations", type=int, default=None, help="Newton cap per substep (default: kinovagrasping_amd.sim.SOLVER_ITERATIONS)")
-    ap.add_argument("--steady-steps", type=int, default=300, help="length of the steady_state window in env-steps (a multiple of the 30-step episode)")
+    ap.add_argument("--steady-steps", type=int, default=None, help="length of the steady_state window in env-steps (a multiple of the 30-step episode); "
+                    "default 0 (no window), or 300 with --full")
+    ap.add_argument("--full", action="store_true", help="also measure what takes runs of its own: three timed windows, the learner's kernels "
+                    "alone (`mfma`), the steady_state window and the CPU baseline (unless --no-cpu-baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed to DIR/<name>.npy (see the module docstring)")
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 3 if args.full else 1
+    if args.steady_steps is None:
+        args.steady_steps = 300 if args.full else 0
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
     if int(os.environ.get("WORLD_SIZE", "1")) != args.gpus:
@@ -330,7 +381,8 @@ def main():
             free_running = not args.serial_learner and (args.rollout == "free" or (args.rollout == "auto" and fits and tuple(args.hidden) in ((256, 256), (128, 128), (64, 64))))
             if free_running:
                 try:
-                    trainer = AsyncTrainer(sim, policy, replay, eng, batch_episodes=64, expert_replay=expert, expert_prob=args.expert_prob)
+                    trainer = AsyncTrainer(sim, policy, replay, eng, batch_episodes=64, expert_replay=expert, expert_prob=args.expert_prob,
+                                           launch_synchronous=not args.async_exchange, max_launch_steps=args.chunk)
                 except ValueError as e:                       # e.g. widths whose learner needs LDS: the lock-step trainer handles those
                     print(f"bench.py: --rollout free not available ({e}); using the lock-step trainer", file=sys.stderr)
                     free_running = False
@@ -485,10 +537,20 @@ def main():
     if free_running:
         timed_launches, timed_first = pick["timed_launches"], pick["timed_first"]
     upd0 = updates - timed_updates
+    if args.dump_outputs:
+        # what the last timed step handed its caller, before anything else runs on this context
+        torch.cuda.synchronize()
+        host = lambda t: t.detach().cpu().numpy()
+        if args.mode == "sim":
+            per_env, whole = {"obs": host(sim.obs), "reward": host(sim.reward), "done": host(sim.done), "info": host(sim.info).T}, {}
+        else:
+            per_env = {"obs": host(eng.obs), "action": host(eng.action), "reward": host(eng.reward_out), "done": host(eng.done_out)}
+            whole = {f"{k}_params": host(policy._flat_params[k]) for k in ("actor", "critic", "actor_target", "critic_target")}
+        dump_outputs(args.dump_outputs, per_env, whole, suffix=f".rank{rank}" if world > 1 else "")
     # ---- the learner's MLP kernels against the fp32 MFMA peak: the update's graphs replayed ALONE (no simulator beside
     # them), HIP-graph launch gaps and the small glue kernels (sampling, loss gradient, Adam) included
     mfma = None
-    if trainer is not None and updates > upd0:
+    if args.full and trainer is not None and updates > upd0:
         reps = 20
         barrier()
         t1 = time.perf_counter()
@@ -614,7 +676,7 @@ def main():
                                  "between classes - and hand_offsets='fresh-env' = the zero offsets its drivers end up with]"),
                        "mode": args.mode, "envs_per_gpu": n, "frame_skip": 15, "solver": f"newton, <= {iters} iterations per substep (early exit on convergence)", "hidden": list(args.hidden),
                        "learner_updates_timed": timed_updates if args.mode == "ddpg" else 0, "priming_steps": priming,
-                       "launch": (("eager" if args.eager else ("free-running rollout kernel (ks_rollout), <= %d env-steps per launch (timed region: %s) + learner graphs" % (args.chunk, timed_launches)
+                       "launch": (("eager" if args.eager else ("free-running rollout kernel (ks_rollout), <= %d env-steps per launch (timed region: %s) + learner graphs, %s" % (args.chunk, timed_launches, "async exchange" if args.async_exchange else "launch-synchronous")
                                                                 if free_running else "hip-graphs, one stepping launch per env-step")) if args.mode == "ddpg" else "direct"),
                        "free_running": (dict(trainer.counts(), launch_steps=all_launches, first_timed_launch=timed_first, timed_launches=launches) if free_running else None),
                        "init_policy": (init_policy if args.mode == "ddpg" else None),
@@ -656,7 +718,7 @@ def main():
             "replica_checks_during_run": (getattr(trainer, "replica_checks", 0) if world > 1 else None),
             "host_issue_ms_per_step": round(t_issue / args.steps * 1e3, 4),
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(os.cpu_count() or 1, shape="CubeS" if mixed else args.shape)
             mj = cpu_baseline_mujoco()                     # None unless the third-party mujoco package happens to be installed
             if mj is not None:

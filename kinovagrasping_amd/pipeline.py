@@ -345,12 +345,32 @@ class AsyncTrainer(GraphedTrainer):
     has done K steps, but at different wall-clock times), the actor weights an env acts with are the newest PUBLISHED ones
     (triple-buffered, published after every actor Adam step) instead of exactly one update old, and finished episodes reach the
     replay ring in arrival order - training is no longer bit-reproducible run to run (GraphedTrainer remains the reproducible
-    path).  Per env the arithmetic and the noise stream are the lock-step ones (tests/test_gpu_async.py: identical trajectories
+    lock-step path; launch_synchronous=True is the reproducible free-running form, see __init__).  Per env the arithmetic and the noise stream are the lock-step ones (tests/test_gpu_async.py: identical trajectories
     for fixed weights).  The reference's own loop acts with a policy that is a whole episode old (main_DDPGfD.py:466-486)."""
 
-    def __init__(self, sim, policy, replay, engine, batch_episodes=64, expert_replay=None, expert_prob=0.3, updates_per_step=1):
+    def __init__(self, sim, policy, replay, engine, batch_episodes=64, expert_replay=None, expert_prob=0.3, updates_per_step=1,
+                 launch_synchronous=False, max_launch_steps=60):
+        """launch_synchronous (opt-in): what one stream hands the other changes only at launch boundaries, so that the same inputs give the
+        same results in every run (the default form acts with whatever was published last and fills the ring in arrival order).  The
+        actor is published once, before a launch starts: every env of a launch acts with the same weights.  The learner keeps collecting
+        finished episodes beside the launch (paced as in the default form), but into a staging ring; before the next launch they enter
+        the ring in an order fixed by their contents, not by their arrival.  The launch's updates sample a ring that does not change
+        under them.  The same inputs give the same results as long as no env drops an episode (counts()["episodes_dropped"] == 0: an
+        env whose two open-episode buffers both wait for the learner drops, and when depends on timing) and no launch is time-budgeted
+        (run(budget_ms=...)).  max_launch_steps sizes the staging ring: one finished episode per 10 env-steps of the longest launch
+        and env, plus two; what does not fit is kept waiting in the env's buffers, never overwritten."""
         super().__init__(sim, policy, replay, engine, batch_episodes=batch_episodes, overlap=True, expert_replay=expert_replay, expert_prob=expert_prob,
                          updates_per_step=updates_per_step)
+        self.launch_synchronous = bool(launch_synchronous)
+        if self.launch_synchronous:
+            from .replay import DeviceEpisodeReplay
+            self.stage = DeviceEpisodeReplay(replay.n_envs, capacity=(max(1, int(max_launch_steps)) // 10 + 2) * replay.n_envs, horizon=replay.horizon, state_dim=replay.ep_state.shape[2],
+                                             action_dim=replay.ep_action.shape[2], n_steps=replay.n_steps, device=replay.device)
+            self._stage_rank = torch.zeros(self.stage.capacity, dtype=torch.long, device=replay.device)
+            self._stage_pos = torch.arange(1, self.stage.capacity + 1, dtype=torch.long, device=replay.device)
+            g = torch.Generator(device="cpu").manual_seed(0)
+            self._key_w = (torch.rand(replay.horizon * replay.ep_action.shape[2], generator=g, dtype=torch.float64).to(replay.device),
+                           torch.rand(replay.ep_state.shape[2], generator=g, dtype=torch.float64).to(replay.device))
         from .sim import KsRolloutArgs
         eng, dev = engine, self.dev
         if not self.native.lds_free:
@@ -435,6 +455,56 @@ class AsyncTrainer(GraphedTrainer):
                           f"env-step, others {self.groups_per_workgroup - 1} - the launch runs at the pace of the former (the ready queue, KS_ROLLOUT_DEAL=queue, and "
                           "GraphedTrainer's lock-step launches balance such a batch dynamically)", RuntimeWarning)
 
+    def _stage_published(self):
+        """launch-synchronous form, beside a launch: published episodes (buffer 0 first, env order) -> the staging ring, their buffers freed.
+        A staged episode is never overwritten: what does not fit stays published in its buffer (its env drops further episodes -
+        counts()["episodes_dropped"] - until a collection finds room)."""
+        r, st_ = self.replay, self.stage
+        L, P, s = r._lib, r._ptr, r._stream()
+        for b in (0, 1):
+            keep = r._keep2[b]
+            torch.gt(r.pub_len[b], 0, out=keep)
+            r._check(L.kr_rank_episodes(r.n_envs, P(keep), P(st_._rank), P(st_._total), s), "kr_rank_episodes")
+            torch.logical_and(keep, st_._rank + st_._count <= st_.capacity, out=keep)
+            r._check(L.kr_rank_episodes(r.n_envs, P(keep), P(st_._rank), P(st_._total), s), "kr_rank_episodes")
+            r._check(L.kr_commit_episodes(r.n_envs, r.horizon, st_.capacity, P(keep), P(st_._rank), P(st_._head), P(r.a_state[b]), P(r.a_next[b]),
+                                          P(r.a_action[b]), P(r.a_reward[b]), P(r.a_not_done[b]), P(r.pub_len[b]), P(st_.ep_state), P(st_.ep_next),
+                                          P(st_.ep_action), P(st_.ep_reward), P(st_.ep_not_done), P(st_.ep_len), s), "kr_commit_episodes")
+            r._check(L.kr_advance_ring(r.n_envs, st_.capacity, P(st_._total), P(st_._head), P(st_._count), P(keep), P(r.pub_len[b]), s),
+                     "kr_advance_ring")
+
+    def _launch_boundary(self):
+        """between launches: the staged episodes -> the ring (one graph), then the actor is published for the next launch"""
+        self.g_boundary.replay()
+        self.publish()
+
+    def _boundary_commit(self):
+        """launch-synchronous form, between launches (learner's stream, the last launch complete): the episodes it finished - staged or still
+        in the open-episode buffers - enter the ring ordered by a key of their contents (actions, which carry each env's own noise stream,
+        first state, length).  At most the ring's capacity of them, the last ones in key order (the ring would overwrite the others), so
+        that no two rows share a slot.  Fixed-shape device ops: captured as g_boundary."""
+        r, st_ = self.replay, self.stage
+        self._stage_published()
+        cap = st_.capacity
+        valid = torch.arange(cap, device=st_.device) < st_._count
+        key = (st_.ep_action[:cap].reshape(cap, -1).double() * self._key_w[0]).sum(1) + (st_.ep_state[:cap, 0].double() * self._key_w[1]).sum(1) \
+            + st_.ep_len[:cap].double() * 1e-3
+        key = torch.where(valid, key, torch.full_like(key, float("inf")))         # staged rows first, in key order
+        order = torch.sort(key, stable=True).indices
+        self._stage_rank.scatter_(0, order, self._stage_pos)                      # row order[j]: position j + 1
+        skip = (st_._count - r.capacity).clamp(min=0)
+        keep = valid & (self._stage_rank > skip)
+        self._stage_rank.sub_(skip)                                               # kept rows: 1 .. min(count, ring capacity) -> slot head + rank - 1
+        r._total.copy_(torch.clamp(st_._count, max=r.capacity).view(1))
+        L, P, s = r._lib, r._ptr, r._stream()
+        r._check(L.kr_commit_episodes(cap, r.horizon, r.capacity, P(keep), P(self._stage_rank), P(r._head), P(st_.ep_state), P(st_.ep_next),
+                                      P(st_.ep_action), P(st_.ep_reward), P(st_.ep_not_done), P(st_.ep_len), P(r.ep_state), P(r.ep_next),
+                                      P(r.ep_action), P(r.ep_reward), P(r.ep_not_done), P(r.ep_len), s), "kr_commit_episodes")
+        r._check(L.kr_advance_ring(cap, r.capacity, P(r._total), P(r._head), P(r._count), P(keep), P(st_.ep_len), s), "kr_advance_ring")
+        st_._head.zero_()
+        st_._count.zero_()
+        self._stage_published()                      # (episodes a full stage left in their buffers)
+
     def publish(self):
         """make the actor's current weights the newest published version: copy into the buffer two behind the one in use, then
         advance the version counter (stream order: the copy is complete - and written back at its kernel's end - before the counter
@@ -481,6 +551,16 @@ class AsyncTrainer(GraphedTrainer):
         self.g_commit = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.g_commit, **mode):
             self.replay.commit_published()
+        if self.launch_synchronous:                      # (one eager pass first - nothing is published yet - then the two graphs)
+            with torch.cuda.stream(s):
+                self._boundary_commit()
+            self.main.wait_stream(s)
+            torch.cuda.synchronize(self.dev)
+            self.g_stage, self.g_boundary = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self.g_stage, **mode):
+                self._stage_published()
+            with torch.cuda.graph(self.g_boundary, **mode):
+                self._boundary_commit()
         self.g_head = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.g_head, pool=self.g_commit.pool(), **mode):
             self._head()
@@ -514,6 +594,9 @@ class AsyncTrainer(GraphedTrainer):
             raise RuntimeError("AsyncTrainer.run before capture(): the learner's graphs do not exist yet")
         main, side = self.main, self.side
         side.wait_stream(main)
+        if self.launch_synchronous:
+            with torch.cuda.stream(side):
+                self._launch_boundary()
         main.wait_stream(side)
         if budget_ms is not None:
             self.args.budget_ticks = max(1, int(budget_ms * 1e5))           # 100 MHz device clock
@@ -528,11 +611,15 @@ class AsyncTrainer(GraphedTrainer):
                 if self.pace_lead >= 0 and k > self.pace_lead and (k - self.pace_lead) % 4 == 1:      # (every 4th update: the lead varies between 8 and 11)
                     self._lib.kr_wait_min_counted(self.steps_total.data_ptr(), n, done + k - self.pace_lead, 5.0, self.pace_timeouts.data_ptr(),
                                                   torch.cuda.current_stream(self.dev).cuda_stream)
-                self.g_commit.replay()
+                if self.launch_synchronous:
+                    self.g_stage.replay()
+                else:
+                    self.g_commit.replay()
                 if learn:
                     for _ in range(self.updates_per_step):
                         self.g_head.replay()
-                        self.publish()
+                        if not self.launch_synchronous:
+                            self.publish()
                         self._body()
         self.env_steps += n_steps
         if learn and self.replica_sync == "average-per-launch":
@@ -562,7 +649,8 @@ class AsyncTrainer(GraphedTrainer):
         for b in bufs:
             b.copy_(flat[off:off + b.numel()].view_as(b))
             off += b.numel()
-        self.publish()
+        if not self.launch_synchronous:                  # (launch-synchronous: the next run() publishes it before its launch starts)
+            self.publish()
 
     def step(self):
         self.run(1)
@@ -571,7 +659,10 @@ class AsyncTrainer(GraphedTrainer):
     def flush(self, finish_update=False):
         self.side.wait_stream(self.main)
         with torch.cuda.stream(self.side):
-            self.g_commit.replay() if self.g_commit is not None else self.replay.commit_published()
+            if self.launch_synchronous:
+                self._launch_boundary()
+            else:
+                self.g_commit.replay() if self.g_commit is not None else self.replay.commit_published()
             if finish_update:
                 self.native.finish_pending()
                 self.publish()

@@ -77,7 +77,7 @@ def classify(con_l, nc_l, cons_o):
     return None, None
 
 
-VARIANTS = {   # host builds of the kernel source with experiment switches (fp32 lane); built once by the parent process into /tmp
+VARIANTS = {   # host builds of the kernel source with experiment switches (fp32 lane); built once by the parent process into tests/native/
     "r4": ["-DKS_MPR_SM=0", "-DKS_REFINE_F64=0", "-DKS_PLANE_F64=0"],                                  # round 4's fp32 read-offs
     "r4+planehook": ["-DKS_MPR_SM=0", "-DKS_REFINE_F64=0", "-DKS_PLANE_F64=0", "-DKS_PLANE_HOOK"],     # ... with every plane pair's first vertex from an fp64 evaluation
     "r4+mink64": ["-DKS_MPR_SM=0", "-DKS_REFINE_F64=0", "-DKS_PLANE_F64=0", "-DKS_MINK_F64=1"],        # ... with the Minkowski points formed in fp64
@@ -91,7 +91,8 @@ VARIANTS = {   # host builds of the kernel source with experiment switches (fp32
 
 
 def _variant_so(name):
-    return f"/tmp/libks_lanecheck_{name.replace('+', '_')}.so"
+    from tests import native_build
+    return str(native_build.HERE / f"libks_lanecheck_{name.replace('+', '_')}.so")
 
 
 def build_variants(names=None):

@@ -276,3 +276,44 @@ def test_time_budgeted_launch_advances_envs_by_time_on_their_lock_step_trajector
     with pytest.raises(RuntimeError):
         sim.rollout(3, tr.args)
     sim.close()
+
+
+def _launch_synchronous_run(n, horizon, launch, ring_capacity, max_launch_steps):
+    from kinovagrasping_amd.pipeline import AsyncTrainer
+    from kinovagrasping_amd.replay import DeviceEpisodeReplay
+    from kinovagrasping_amd.rollout import RolloutEngine
+    sim, policy, _, _ = _setup(n, horizon)
+    replay = DeviceEpisodeReplay(n, capacity=ring_capacity, horizon=horizon, device=sim.device)
+    eng = RolloutEngine(sim, policy, replay, expl_noise=0.1)
+    eng.start(sim.obs.clone())
+    tr = AsyncTrainer(sim, policy, replay, eng, batch_episodes=16, launch_synchronous=True, max_launch_steps=max_launch_steps)
+    tr.capture()
+    tr.run(horizon + 6, learn=False)
+    for _ in range(2):
+        tr.run(launch)
+    tr.flush(finish_update=True)
+    torch.cuda.synchronize()
+    ring = [(len(e["reward"]), e["state"].tobytes(), e["action"].tobytes(), e["next_state"].tobytes(), e["reward"].tobytes(), e["not_done"].tobytes())
+            for e in replay.host_episodes()]                        # oldest first: slot order
+    out = (tr.counts(), replay.count, ring, policy._flat_params["actor"].cpu().clone(), tr.stage.capacity)
+    sim.close()
+    return out
+
+
+def test_launch_synchronous_trainer_is_reproducible_and_never_overwrites_episodes():
+    """AsyncTrainer(launch_synchronous=True), the bench's free-running form.  Sized for its launches, two runs give the same ring (same episodes
+    in the same slots) and the same weights.  With a staging ring and a replay ring far too small for a launch (12-step episodes, 60-step
+    launches, room for 3 staged episodes per env, a ring of n / 2), nothing is overwritten: every committed episode is one env's consecutive
+    transitions, the ring holds exactly its capacity, and what did not fit is counted as dropped."""
+    n = 512
+    a = _launch_synchronous_run(n, 30, 60, 8 * n, 60)
+    b = _launch_synchronous_run(n, 30, 60, 8 * n, 60)
+    assert a[0]["episodes_dropped"] == 0 and a[0] == b[0] and a[1] == b[1] > 0, (a[0], b[0], a[1], b[1])
+    assert a[2] == b[2] and torch.equal(a[3], b[3])
+    c, count, eps, _, stage_cap = _launch_synchronous_run(n, 12, 60, n // 2, 10)
+    assert stage_cap == 3 * n and count == n // 2 and c["episodes_dropped"] > 0, (c, count, stage_cap)
+    for L, S, A, NX, R, ND in eps:
+        s = np.frombuffer(S, dtype=np.float32).reshape(L, -1)
+        nx = np.frombuffer(NX, dtype=np.float32).reshape(L, -1)
+        nd = np.frombuffer(ND, dtype=np.float32)
+        assert np.array_equal(nx[:-1], s[1:]) and (nd[:-1] == 1).all() and nd[-1] == 0

@@ -310,7 +310,7 @@ def test_multi_geom_fp32_long_horizon_through_the_env_step_path():
     assert sum(within.values()) >= 41 and min(within.values()) >= 3, within
 
 
-def test_every_object_of_the_reference_in_one_context():
+def test_every_object_of_the_reference_in_one_context(tmp_path):
     """all 42 keys of KinovaGripper_Env.all_objects (ENV:150-208) in ONE context of the multi-geom library, 8 envs each: reset through the
     reference's reset rule (table row / empty-file rule + the 5 cm correction), three env-steps; every env's reset observation carries its own
     object's size slots, nothing non-finite, no status flag but the solver cap"""
@@ -319,7 +319,7 @@ def test_every_object_of_the_reference_in_one_context():
     assert len(shapes) == 42
     n = 8 * len(shapes)
     env = KinovaGripperVecEnv(n, shapes, seed=1, auto_reset=False, hand_offsets="pose")
-    env.Generate_Latin_Square(n, "/tmp/ks_objects_all.csv", shape_keys=shapes)
+    env.Generate_Latin_Square(n, str(tmp_path / "ks_objects_all.csv"), shape_keys=shapes)
     obs = env.reset(shape_keys=shapes, hand_orientation="random", with_noise=False)
     names = env.get_random_shape()
     assert sorted(set(names)) == sorted(shapes) and all(names.count(s) == 8 for s in shapes)
