@@ -209,6 +209,10 @@ typedef struct {
      * object otherwise paces every env) - at the price of an uneven object mix in what is collected.  Needs the wave form (ks_rollout_plan:
      * KS_PLAN_WAVES), KS_ERR_STATE otherwise. */
     int64_t budget_ticks;
+    /* Optional (NULL = not counted): int64 [1], incremented once per actor forward that was repeated because the version counter had
+     * advanced by two or more while the forward read buffer (ver % 3) - once per deciding workgroup (KS_PLAN_WORKGROUPS / queue / deals)
+     * or per wave (KS_PLAN_WAVES).  Diagnostic of the weight hand-off above; every word of counters[] is taken. */
+    int64_t *repeats;
 } ks_rollout_args;
 int ks_rollout(ks_ctx *ctx, int32_t n_iter, const ks_rollout_args *args_host, void *stream);
 

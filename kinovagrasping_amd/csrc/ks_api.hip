@@ -732,6 +732,7 @@ __device__ __noinline__ void rollout_policy(const ks_rollout_args* __restrict__ 
         if (threadIdx.x == 0) vbox[1] = (long long)__hip_atomic_load(ra.actor_ver, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - ver;
         __syncthreads();
         const bool stale = vbox[1] >= 2;
+        if (stale && threadIdx.x == 0 && ra.repeats) atomicAdd((unsigned long long*)ra.repeats, 1ull);
         if (!stale) {
             if (mine) {
                 float nz[4];
@@ -961,6 +962,7 @@ __device__ __noinline__ void rollout_policy_wave(const ks_rollout_args* __restri
             }
             return;
         }
+        if (lane == 0 && ra.repeats) atomicAdd((unsigned long long*)ra.repeats, 1ull);
     }
 }
 

@@ -434,6 +434,8 @@ class AsyncTrainer(GraphedTrainer):
         a.cur_state, a.cur_next, a.cur_action = P(replay.a_state), P(replay.a_next), P(replay.a_action)
         a.cur_reward, a.cur_not_done, a.cur_len = P(replay.a_reward), P(replay.a_not_done), P(replay.a_len)
         a.cur_sel, a.pub_len, a.counters = P(replay.a_sel), P(replay.pub_len), P(self.counters)
+        self.repeats = torch.zeros(1, dtype=torch.long, device=dev)          # actor forwards repeated because two versions were published meanwhile
+        a.repeats = P(self.repeats)
         # pacing: the learner's stream waits (kr_wait_min on the envs' step counters) so that update k of a launch starts when EVERY env
         # has done k - lead env-steps.  Without it the learner (0.9 ms per update) finishes its share of a long launch far ahead of the
         # rollout (1.1 ms per env-step) and nobody collects the episodes published after that.
@@ -669,6 +671,11 @@ class AsyncTrainer(GraphedTrainer):
         self.main.wait_stream(self.side)
         if self.distributed and self.native.exchange is not None:
             self.native.exchange.check()
+
+    def repeated_forwards(self) -> int:
+        """in-kernel actor forwards repeated so far because the version counter advanced by two or more while they read the weights (the
+        rollout kernel's torn-read guard; host sync).  Kept out of counts(), whose content is the bench line's."""
+        return int(self.repeats.item())
 
     def counts(self):
         c = self.counters[:4].tolist()
