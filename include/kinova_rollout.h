@@ -137,10 +137,12 @@ int kr_soft_update(int64_t count, const float *param, float *target, float tau, 
  *     out[n,out_dim] = f(W3 relu(W2 relu(W1 x + b1) + b2) + b3),   f = identity (KR_ACT_NONE) or scale * sigmoid
  * x = the first in_a columns from xa ([n, >= in_a], row stride lda) followed by in_b columns from xb (row stride ldb;
  * in_b = 0: xb unused) - the critic's cat([state, action], 1) without materialising it.  Weights in torch.nn.Linear
- * layout (W [out][in] row-major, b [out]).  Limits: in_a + in_b <= 96, out_dim <= 4, hidden widths 256-256 (BASELINE),
- * 400-300 (reference), 128-128, 64-64; any other width returns KS_ERR_INVALID and the caller keeps its GEMM path.
- * h1_out [n,h1] / h2_out [n,h2] (optional, NULL to skip): the hidden activations (after the ReLU), which the backward
- * pass of a training step needs; they require h % 4 == 0 and 16-byte aligned buffers. */
+ * layout (W [out][in] row-major, b [out]).  Limits: in_a + in_b <= 96, out_dim <= 4.  Hidden widths: any pair whose tile
+ * counts (ceil(h1/16), ceil(h2/16)) are those of an instantiation - (16,16) for 256-256 (BASELINE), (25,19) for 400-300
+ * (reference), (8,8) for 128-128, (4,4) for 64-64 - so partial last tiles such as 250-250, 390-290, 120-116 or 60-52 run
+ * too (h % 4 != 0 takes the scalar weight loads); any other tile pair returns KS_ERR_INVALID and the caller keeps its GEMM
+ * path.  h1_out [n,h1] / h2_out [n,h2] (optional, NULL to skip): the hidden activations (after the ReLU), which the
+ * backward pass of a training step needs; they require h % 4 == 0 and 16-byte aligned buffers. */
 #define KR_ACT_NONE 0
 #define KR_ACT_SIGMOID 1
 int kr_mlp3_forward(int32_t n, int32_t in_a, int32_t in_b, int32_t h1, int32_t h2, int32_t out_dim, const float *xa, int32_t lda,
@@ -149,7 +151,8 @@ int kr_mlp3_forward(int32_t n, int32_t in_a, int32_t in_b, int32_t h1, int32_t h
 
 /* The same forward WITHOUT LDS (one wavefront per 16 rows, everything in registers, <= 168 registers per lane): its
  * waves can be resident beside a kernel that holds a CU's whole LDS (k_env_step), so a learner's forward-only passes
- * run in that kernel's shadow instead of behind it.  Widths 256-256, 128-128, 64-64; otherwise KS_ERR_INVALID. */
+ * run in that kernel's shadow instead of behind it.  Widths 256-256, 128-128, 64-64 (whole 16-wide tiles only: h % 16 == 0);
+ * otherwise KS_ERR_INVALID. */
 int kr_mlp3_forward_shadow(int32_t n, int32_t in_a, int32_t in_b, int32_t h1, int32_t h2, int32_t out_dim, const float *xa, int32_t lda,
                            const float *xb, int32_t ldb, const float *W1, const float *b1, const float *W2, const float *b2,
                            const float *W3, const float *b3, int32_t act, float scale, float *out, float *h1_out, float *h2_out,
@@ -160,10 +163,11 @@ int kr_mlp3_forward_shadow(int32_t n, int32_t in_a, int32_t in_b, int32_t h1, in
  *                             either may be NULL) and optionally  dx = dz1 W1[:, col0 : col0 + ncol]  ([n,ncol], ncol <= 4:
  *                             dQ/da through the critic's first layer), followed - when act_out [n,ncol] is given - by the
  *                             backward of a = scale * sigmoid(z):  dx *= a (1 - a / scale).  dz3 [n,out_dim], h1 / h2 the
- *                             activations kr_mlp3_forward* stored.  Widths: multiples of 16 up to 256.
+ *                             activations kr_mlp3_forward* stored.  Widths 256-256, 128-128, 64-64.
  *   kr_weight_grad_shadow     dW [M,N] = dz^T [ha | hb]  and  db [M] = column sums of dz, dz [n,M], ha [n,>=Na] (row stride
  *                             lda), hb [n,>=Nb] (ldb; Nb = 0: unused); the batch rows are split into `chunks` partial sums
- *                             in `workspace` (chunks * (M*N + M) floats) that a second launch adds up in chunk order. */
+ *                             in `workspace` (chunks * (M*N + M) floats) that a second launch adds up in chunk order.
+ *                             Each chunk covers a multiple of 16 rows: chunks beyond ceil(n / that) are not used. */
 /* kr_mlp3_forward_shadow with the tiles of each layer split over `waves` (2 or 4) wavefronts of a workgroup: the same LDS-free
  * launch at ~1/waves of the latency (one wave per 16 rows is a serial chain of ~1400 MFMAs: 87 us whatever the batch).  The
  * waves exchange layer 1's output through global memory: h1_out when the caller keeps it, else `scratch`; scratch_floats >=
@@ -189,8 +193,8 @@ int kr_weight_grad_shadow(int32_t n, int32_t M, int32_t Na, int32_t Nb, const fl
 
 /* Actor forward + exploration noise + kr_select_action in ONE launch (main_DDPGfD.py:424-451): the epilogue of the
  * fused MLP applies the selection rule to its own output.  obs .. ready and action .. lifting as in kr_select_action;
- * W1 .. b3 the actor (82 -> h1 -> h2 -> 4).  Noise: either `noise` [n,4] ~ N(0,1) (then rng_state = NULL), or
- * noise = NULL and rng_state = int64[2] on the device, zero-initialised by the caller: the kernel draws
+ * W1 .. b3 the actor (82 -> h1 -> h2 -> 4; any hidden widths kr_mlp3_forward accepts, partial last tiles included).
+ * Noise: either `noise` [n,4] ~ N(0,1) (then rng_state = NULL), or noise = NULL and rng_state = int64[2] on the device, zero-initialised by the caller: the kernel draws
  * Philox4x32-10 / Box-Muller normals keyed by (seed, rng_state[0], env) and advances rng_state[0] by one per launch
  * (rng_state[1] is its scratch word) - no host-side generator state, so the launch replays from a HIP graph.
  * actor_out [n,4] (optional, may be NULL) receives pi(obs). */

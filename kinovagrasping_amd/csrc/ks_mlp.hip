@@ -761,6 +761,9 @@ int kr_weight_grad_shadow(int32_t n, int32_t M, int32_t Na, int32_t Nb, const fl
     const int N = Na + Nb, n_blocks = (N + 16 * WG_TN - 1) / (16 * WG_TN), m_tiles = (M + 15) / 16;
     int rows_per_chunk = (n + chunks - 1) / chunks;
     rows_per_chunk = (rows_per_chunk + 15) / 16 * 16;
+    // the rounding can leave trailing chunks that start at or past n: launch (and reduce) only the chunks that hold rows.  A chunk
+    // with r0 > n would otherwise take full_end = r0 - 16 in k_wgrad_wave and add rows the previous chunk already counted.
+    chunks = (n + rows_per_chunk - 1) / rows_per_chunk;
     hipLaunchKernelGGL(k_wgrad_wave, dim3(m_tiles * n_blocks, chunks), dim3(64), 0, s, n, M, Na, Nb, rows_per_chunk, dz, ha, lda, hb, ldb, workspace);
     const long total = (long)M * N + M;
     hipLaunchKernelGGL(k_wgrad_reduce, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (long)M * N, (long)M, chunks, workspace, dW, db);

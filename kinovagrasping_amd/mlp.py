@@ -19,10 +19,13 @@ def layers_of(module):
 
 
 def supported(layers, in_dim: int, shadow: bool = False) -> bool:
+    """True when the fused forward (shadow: its LDS-free form) runs these layers: the tile pair has an instantiation and,
+    for the LDS-free form, both hidden widths are whole tiles (kr_mlp3_forward_shadow refuses h % 16 != 0)"""
     (w1, _), (w2, _), (w3, _) = layers
     tiles = ((w1.shape[0] + 15) // 16, (w2.shape[0] + 15) // 16)
-    return (w1.is_cuda and w1.dtype == torch.float32 and tiles in (SHADOW_TILES if shadow else SUPPORTED_TILES) and in_dim <= 96 and w3.shape[0] <= 4
-            and all(w.is_contiguous() and b.is_contiguous() for w, b in layers))
+    whole = not shadow or (w1.shape[0] % 16 == 0 and w2.shape[0] % 16 == 0)
+    return (w1.is_cuda and w1.dtype == torch.float32 and tiles in (SHADOW_TILES if shadow else SUPPORTED_TILES) and whole and in_dim <= 96
+            and w3.shape[0] <= 4 and all(w.is_contiguous() and b.is_contiguous() for w, b in layers))
 
 
 def _split_waves(n: int) -> int:

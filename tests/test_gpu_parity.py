@@ -506,11 +506,13 @@ def test_rollout_kernels_equal_torch_bookkeeping():
         assert torch.equal(x, y)
 
 
-@pytest.mark.parametrize("hidden,form", [((256, 256), "lds_free"), ((400, 300), "library_gemm")])
+@pytest.mark.parametrize("hidden,form", [((256, 256), "lds_free"), ((400, 300), "library_gemm"), ((128, 128), "lds_free"), ((64, 64), "lds_free"),
+                                         ((248, 248), "fused_lds_targets")])
 def test_native_learner_update_equals_autograd_update(hidden, form):
     """learner_native against DDPGfD.train_on_batch (autograd + torch.optim.Adam): same losses and the same parameters /
-    targets after several updates on masked fixed-shape batches - in both of its forms: the LDS-free MFMA kernels
-    (BASELINE widths 256-256) and the library GEMMs + kr_* glue kernels (the reference's 400-300)."""
+    targets after several updates on masked fixed-shape batches - in all of its forms: the LDS-free MFMA kernels
+    (BASELINE widths 256-256, and 128-128 / 64-64), the library GEMMs + kr_* glue kernels (the reference's 400-300), and
+    the library GEMMs with the fused LDS kernel for the forward-only passes (248-248: whole tile count, not whole tiles)."""
     from kinovagrasping_amd.ddpgfd import DDPGfD
     from kinovagrasping_amd.learner_native import NativeDDPGfDUpdate
     dev = torch.device("cuda", 0)
@@ -519,7 +521,7 @@ def test_native_learner_update_equals_autograd_update(hidden, form):
     torch.manual_seed(7)
     pb = DDPGfD(82, 4, 0.8, 5, hidden=hidden, device=dev)
     nat = NativeDDPGfDUpdate(pb)
-    assert nat.lds_free == (form == "lds_free") and nat.fused_targets
+    assert nat.lds_free == (form == "lds_free") and nat.shadow == (form == "lds_free") and nat.fused_targets
     g = torch.Generator(device=dev).manual_seed(3)
     R, n = 320, 5
     for it in range(12):                      # crosses the soft target update of the 10th call
@@ -1095,7 +1097,7 @@ def test_lds_free_backward_matches_autograd(split, monkeypatch):
         monkeypatch.setenv("KS_MLP_SPLIT", split)
     from kinovagrasping_amd.ddpgfd import Actor, Critic
     dev = torch.device("cuda", 0)
-    for hidden, n in (((256, 256), 1600), ((256, 256), 8000), ((64, 64), 333)):
+    for hidden, n in (((256, 256), 1600), ((256, 256), 8000), ((128, 128), 500), ((64, 64), 333)):
         torch.manual_seed(5)
         actor, critic = Actor(82, 4, 0.8, hidden).to(dev), Critic(82, 4, hidden).to(dev)
         s = torch.randn(n, 82, device=dev)
