@@ -24,7 +24,7 @@
  *     every buffer; the library owns only its context and scratch.  Pointers are borrowed for the
  *     duration of the stream operation.
  *   - Real-valued buffers have the context precision: float for precision 32 (the product), double
- *     for precision 64 (algorithm-exactness checks only).
+ *     for precision 64 (the exact mode: parity checks, and rollout / training through ks_rollout).
  *   - Batched arrays are struct-of-arrays, field-major: x[k * n_envs + env].  The observation may be
  *     requested env-major (obs[env * 82 + k]) with obs_env_major = 1.
  *   - Every call is asynchronous on `stream` (a hipStream_t passed as void*); no hidden host syncs.
@@ -166,7 +166,7 @@ int ks_obs_from_snapshot(ks_ctx *ctx, const void *snap, const void *rays, void *
  * keeps one persistent workgroup per compute unit; the groups are taken from a ready queue - a workgroup steps the group at its
  * head once and puts it back behind the others - so that no workgroup idles while a group is ready and every env still does
  * exactly n_iter env-steps per launch (environment variable KS_ROLLOUT_DEAL=static / rr: fixed deals instead; the multi-geom
- * build keeps the round-robin deal).
+ * build keeps the round-robin deal; the exact mode below always deals them).
  *
  * Actor weights: `actor_pub` holds 3 parameter buffers of `actor_stride` floats (layout: offsets off_*, torch.nn.Linear
  * layout); `actor_ver` is a device counter that the learner increments AFTER it has completely written buffer
@@ -176,7 +176,15 @@ int ks_obs_from_snapshot(ks_ctx *ctx, const void *snap, const void *rays, void *
  * main_DDPGfD.py:469-471) is handed over by setting pub_len[buf][env] = len (release) and switching to the other buffer; the
  * consumer (the learner's stream: kr_rank / kr_commit / kr_advance_ring on buffer `buf` with cur_len = pub_len + buf * n) clears
  * it.  If the other buffer has not been consumed yet the finished episode is dropped and counted in `dropped`.
- * fp32 contexts with observations in the stepping kernel only (the default); obs layout env-major; one model or many. */
+ * Contexts: env-major observations and auto_reset; one model or many.
+ *   precision 32: observations in the stepping kernel (the default).
+ *   precision 64, the exact mode (libkinova_sim.so only; libkinova_sim_mg.so refuses it): the physics state, contacts, rays,
+ *     observation, reward and done are fp64, with the arithmetic of ks_step on that context, and go to the fp64 sim_* buffers.
+ *     The policy and the replay stay fp32: the actor reads the fp32 rounding of the fp64 observation (obs / prev_obs), the replay
+ *     rows are that same rounding, the reward is rounded once.  So per env the trajectory equals the lock-step
+ *     kr_actor_select -> ks_step -> (sim outputs rounded to fp32) -> kr_store_transition, bit for bit.  One persistent workgroup
+ *     per compute unit steps its 16-env groups in turn, barrier-joined (KS_PLAN_WORKGROUPS, or KS_PLAN_RUNS / KS_PLAN_ROUND_ROBIN
+ *     with more groups than workgroups); no ready queue, no time budget (budget_ticks != 0: KS_ERR_STATE). */
 typedef struct {
     const float *actor_pub;
     const int64_t *actor_ver;
@@ -193,8 +201,8 @@ typedef struct {
     int64_t *t, *steps_total;        /* [n] steps in the episode / since the start (the noise counter; stored device-visibly: kr_wait_min paces the learner's stream on it) */
     float *action, *action_t;        /* [n, 4], [4, n] */
     float *reward_out; uint8_t *done_out;
-    /* ks_step's outputs (as passed to ks_step) */
-    float *sim_obs, *sim_reward; uint8_t *sim_done; float *sim_info, *sim_final_obs;
+    /* ks_step's outputs (as passed to ks_step): sim_obs, sim_reward, sim_info and sim_final_obs have the context's precision */
+    void *sim_obs, *sim_reward; uint8_t *sim_done; void *sim_info, *sim_final_obs;
     /* open episodes */
     int32_t horizon, n_steps;
     float *cur_state, *cur_next, *cur_action, *cur_reward, *cur_not_done;

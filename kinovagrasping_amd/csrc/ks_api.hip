@@ -510,6 +510,25 @@ constexpr int POOL_LINGER_LAST = KS_POOL_LINGER_LAST;
 #endif
 #define KS_ROLLOUT_REGS __attribute__((amdgpu_num_vgpr(KS_ROLLOUT_NUM_VGPR)))
 #define KS_STEP_REGS __attribute__((amdgpu_num_vgpr(KS_STEP_NUM_VGPR)))
+
+// One env-step of one env on the global-scratch path (fp64 contexts: USE_LDS = false) by its 16-lane team: the state in registers,
+// the scratch the env's field-major block of global memory, no pair memory (every query starts cold, as in ks_substep).  Shared by
+// k_env_step<double> and the exact-mode rollout kernel (k_rollout_f64), so that both step an env with the same arithmetic: out of line,
+// ONE compiled copy (inlined into two kernels, fp64 multiply-adds may be contracted differently in each).
+template <typename T>
+__device__ __noinline__ void env_step_global(const Model<T>& m, const Hulls<T>& hu, const Buffers<T>& b, int env, int N, const T* hq, const T* act,
+                                                Team<SUBS> team, ColW<T> snap, int frame_skip, int iters, int tap, int& ncon, int& status) {
+    LaneState<T> st;
+    load_state(b, env, N, st);
+    Scratch<T> scr{b.gscratch + env, N};
+    load_env_params(scr, team, b, env, N);
+    lane_env_step(m, hu, st, hq, act, scr, team, snap, frame_skip, iters, ncon, status);
+    if (team.sub == 0) {
+        for (int k = 0; k < (tap ? ncon * CON_STRIDE : 0); k++) b.contact[(long)k * N + env] = scr(SCR_CON + k);
+        store_state(b, env, N, st);
+    }
+}
+
 // obs_in_step: the observation / reward / done / auto-reset of the workgroup's envs are produced here too (wg_obs), the
 // separate k_obs launch of a step is gone; needs rays_in_step (fp32 / LDS variant).
 template <typename T, bool USE_LDS>
@@ -628,15 +647,7 @@ __device__ __forceinline__ void env_step_body(const Model<T>* __restrict__ model
         team.sync();
         store_state_team<T, SUBS>(b, env, N, stp, team.sub);
     } else {
-        LaneState<T> st;
-        load_state(b, env, N, st);
-        Scratch<T> scr{b.gscratch + env, N};
-        load_env_params(scr, team, b, env, N);
-        lane_env_step(m, hu, st, hq, act, scr, team, snap, frame_skip, iters, ncon, status);
-        if (team.sub == 0) {
-            for (int k = 0; k < (tap ? ncon * CON_STRIDE : 0); k++) b.contact[(long)k * N + env] = scr(SCR_CON + k);
-            store_state(b, env, N, st);
-        }
+        env_step_global(m, hu, b, env, N, hq, act, team, snap, frame_skip, iters, tap, ncon, status);
     }
     if (status) atomicOr(&b.status[env], status);
     if (team.sub == 0) b.ncon[env] = ncon;
@@ -690,7 +701,9 @@ __global__ __launch_bounds__(WG) KS_STEP_REGS void k_env_step_f32(const Model<fl
 // pool is off (every workgroup casts its own envs' rays).  The two added phases are out-of-line and reach their arguments
 // through a pointer to device memory: nothing of them stays in registers across the stepping phase, whose footprint (344 of
 // the 512 registers per lane) is what lets the learner's LDS-free waves run beside this kernel for its whole life.
-template <int NT1, int NT2>
+// (EXACT: the exact-mode kernel's own instantiation of the same body - one out-of-line callee shared with k_rollout_f64, which has no register
+// cap, changes the callee's frame and so k_rollout's scratch size)
+template <int NT1, int NT2, bool EXACT = false>
 __device__ __noinline__ void rollout_policy(const ks_rollout_args* __restrict__ rap, int N, int row_env, KS_LDS float* blocks) {
     const ks_rollout_args& ra = *rap;
     const int S = krsel::S, A = krsel::A;
@@ -746,12 +759,15 @@ __device__ __noinline__ void rollout_policy(const ks_rollout_args* __restrict__ 
     }
 }
 
-// replay write + per-env bookkeeping of one env by its 16-lane team (k_store_transition of ks_rollout.hip + the episode hand-over)
+// replay write + per-env bookkeeping of one env by its 16-lane team (k_store_transition of ks_rollout.hip + the episode hand-over).
+// R: the type of the context's outputs (sim_*): float, or double in the exact mode - rounded to float once, here, as the lock-step
+// RolloutEngine rounds them before kr_store_transition.
+template <typename R>
 __device__ __noinline__ void rollout_store(const ks_rollout_args* __restrict__ rap, int N, int i, int sub) {
     const ks_rollout_args& ra = *rap;
     const int S = krsel::S, A = krsel::A, H = ra.horizon;
     const bool done = ra.sim_done[i] != 0, lift = ra.lifting[i] != 0;
-    const float rew = ra.sim_reward[i];
+    const float rew = (float)((const R*)ra.sim_reward)[i];
     const bool store = ra.with_replay && !lift;
     const int sel = ra.with_replay ? ra.cur_sel[i] : 0;
     const long bi = (long)sel * N + i;
@@ -759,9 +775,9 @@ __device__ __noinline__ void rollout_store(const ks_rollout_args* __restrict__ r
     const long tt = len0 < H - 1 ? len0 : H - 1;
     const long row = bi * H + tt;
     for (int c = sub; c < S; c += SUBS) {
-        const float so = ra.sim_obs[(long)i * S + c];
+        const float so = (float)((const R*)ra.sim_obs)[(long)i * S + c];
         const float st = ra.obs[(long)i * S + c];
-        const float nx = done ? ra.sim_final_obs[(long)i * S + c] : so;          // (auto-reset contexts: the terminal observation)
+        const float nx = done ? (float)((const R*)ra.sim_final_obs)[(long)i * S + c] : so;          // (auto-reset contexts: the terminal observation)
         if (store) { ra.cur_state[row * S + c] = st; ra.cur_next[row * S + c] = nx; }
         ra.prev_obs[(long)i * S + c] = done ? so : st;
         ra.obs[(long)i * S + c] = so;
@@ -907,7 +923,7 @@ __device__ __forceinline__ void rollout_iter(const Model<float>& m, const Hulls<
     wg_obs<false>(m, b, N, grp * epw, epw, w, *out);
     __threadfence_block();
     __syncthreads();
-    if (active) rollout_store(rap, N, env, team.sub);
+    if (active) rollout_store<float>(rap, N, env, team.sub);
     __threadfence_block();
     __syncthreads();
     KS_RS(3)
@@ -1026,7 +1042,7 @@ __device__ __forceinline__ void rollout_iter_wave(const Model<float>& m, const H
     C::sync();
     wg_obs<true>(m, b, N, wslot0, wepw, w, *out);
     C::sync();
-    if (active) rollout_store(rap, N, env, team.sub);
+    if (active) rollout_store<float>(rap, N, env, team.sub);
     C::sync();
 }
 
@@ -1400,14 +1416,15 @@ template <typename T> struct GroupBound {
 };
 
 constexpr int RAY_ENVS = WAVE / RG;
-template <typename T> __global__ __launch_bounds__(WAVE) void k_rays(const Model<T>* __restrict__ models, Buffers<T> b, int N, int masked) {
-    const int g = 1 + (threadIdx.x & (RG - 1));
-    const int env = blockIdx.x * RAY_ENVS + (threadIdx.x >> RG_BITS), ray = blockIdx.y;
-    const bool live = env < N && !(masked && !b.flag[env]);
+// The per-lane body of k_rays: lane `lane` of a wave casts ray `ray` of `env` against mesh geom 1 + (lane & (RG - 1)) (and the ground on
+// the group's first lane); `pub` [WAVE] and `stk` [RAY_STACK][WAVE] are the wave's own LDS.  Every lane of the wave calls it (the
+// butterfly), `live` or not.  Shared by k_rays and the exact-mode rollout kernel (k_rollout_f64).
+template <typename T>
+__device__ __forceinline__ void ray_lane(const Model<T>* __restrict__ models, const Buffers<T>& b, int N, int env, int ray, bool live, unsigned lane,
+                                         KS_LDS T* pub, KS_LDS unsigned* stk) {
+    const int g = 1 + (lane & (RG - 1));
     T best = T(-1);
-    __shared__ T pub[WAVE];
-    __shared__ unsigned stk[RAY_STACK * WAVE];
-    pub[threadIdx.x] = Lim<T>::big;
+    pub[lane] = Lim<T>::big;
     if (live) {
         const Model<T>& m = models[b.obj_id[env]];
         Col<T> snap{b.snap + env, N};
@@ -1415,26 +1432,41 @@ template <typename T> __global__ __launch_bounds__(WAVE) void k_rays(const Model
         const int sb = ray_origin(m, snap, ray, pnt, vec);
         if (g == 1) {
             best = ray_ground(m, pnt, vec);
-            if (best >= 0) pub[threadIdx.x] = best;
+            if (best >= 0) pub[lane] = best;
         }
 #ifdef KS_RAY_COUNT
         // diagnostic build: ray_mesh returns its node visits; they go to the contact tap buffer, rows ray * 8 + (g - 1)
         T cnt = T(0);
         if (g < m.ngeom && m.geom_body[g] != sb) {
-            cnt = ray_geom(m, snap, g, pnt, vec, GroupBound<T>{(KS_LDS T*)pub + (threadIdx.x & ~(RG - 1)), (int)(threadIdx.x & (RG - 1))},
-                           LdsStack<T>{(KS_LDS unsigned*)stk + threadIdx.x, WAVE});
+            cnt = ray_geom(m, snap, g, pnt, vec, GroupBound<T>{pub + (lane & ~(RG - 1)), (int)(lane & (RG - 1))},
+                           LdsStack<T>{stk + lane, WAVE});
             if (cnt < 0) cnt = T(0);
         }
         b.contact[((long)ray * RG + (g - 1)) * N + env] = cnt;
 #else
         if (g < m.ngeom && m.geom_body[g] != sb)
-            best = ray_nearer(best, ray_geom(m, snap, g, pnt, vec, GroupBound<T>{(KS_LDS T*)pub + (threadIdx.x & ~(RG - 1)), (int)(threadIdx.x & (RG - 1))},
-                                              LdsStack<T>{(KS_LDS unsigned*)stk + threadIdx.x, WAVE}));
+            best = ray_nearer(best, ray_geom(m, snap, g, pnt, vec, GroupBound<T>{pub + (lane & ~(RG - 1)), (int)(lane & (RG - 1))},
+                                              LdsStack<T>{stk + lane, WAVE}));
 #endif
     }
     KS_UNROLL
     for (int mask = 1; mask < RG; mask <<= 1) best = ray_nearer(best, (T)__shfl_xor(best, mask));
     if (live && g == 1) b.rays[(long)ray * N + env] = best;
+}
+
+// fp64: ONE compiled copy of the body, called by k_rays<double> and k_rollout_f64 (the same contractions in both)
+__device__ __noinline__ void ray_lane_f64(const Model<double>* __restrict__ models, const Buffers<double>& b, int N, int env, int ray, bool live, unsigned lane,
+                                          KS_LDS double* pub, KS_LDS unsigned* stk) {
+    ray_lane(models, b, N, env, ray, live, lane, pub, stk);
+}
+
+template <typename T> __global__ __launch_bounds__(WAVE) void k_rays(const Model<T>* __restrict__ models, Buffers<T> b, int N, int masked) {
+    const int env = blockIdx.x * RAY_ENVS + (threadIdx.x >> RG_BITS), ray = blockIdx.y;
+    const bool live = env < N && !(masked && !b.flag[env]);
+    __shared__ T pub[WAVE];
+    __shared__ unsigned stk[RAY_STACK * WAVE];
+    if constexpr (sizeof(T) == 8) ray_lane_f64(models, b, N, env, ray, live, threadIdx.x, (KS_LDS T*)pub, (KS_LDS unsigned*)stk);
+    else ray_lane(models, b, N, env, ray, live, threadIdx.x, (KS_LDS T*)pub, (KS_LDS unsigned*)stk);
 }
 
 // phase 1 (part = -1: all of it; 0..3: that quarter of the slots, see build_obs): the observation, straight to its destination
@@ -1510,6 +1542,13 @@ __device__ __forceinline__ void obs_epilogue(const Model<T>& m, const Buffers<T>
     obs_finish(m, b, env, N, mode, o, snap, rscr);
 }
 
+// fp64: ONE compiled copy, called by k_obs<double> and k_rollout_f64; an auto-reset's kinematics use the env's global scratch block (dead after
+// the step: k_obs runs behind the stepping kernel, ks_reset's and ks_obs_from_snapshot's passes restart nothing)
+__device__ __noinline__ void obs_epilogue_f64(const Model<double>& m, const Buffers<double>& b, int env, int N, int mode, const ObsOut<double>& o,
+                                              const double* rays) {
+    obs_epilogue(m, b, env, N, mode, o, Col<double>{b.snap + env, N}, rays, Scratch<double>{b.gscratch + env, N});
+}
+
 template <typename T>
 __global__ __launch_bounds__(WAVE) void k_obs(const Model<T>* __restrict__ models, Buffers<T> b, int N, int mode, ObsOut<T> o) {
     __shared__ T rlds[SCR_CON * WAVE];      // scratch of an auto-reset's forward kinematics (body-pose part only, as in k_reset)
@@ -1523,7 +1562,8 @@ __global__ __launch_bounds__(WAVE) void k_obs(const Model<T>* __restrict__ model
     T rays[NRAY];
     KS_UNROLL
     for (int i = 0; i < NRAY; i++) rays[i] = b.rays[(long)i * N + env];
-    obs_epilogue(models[b.obj_id[env]], b, env, N, mode, o, snap, rays, Scratch<T, KS_LDS T*>{(KS_LDS T*)rlds + threadIdx.x, WAVE});
+    if constexpr (sizeof(T) == 8) obs_epilogue_f64(models[b.obj_id[env]], b, env, N, mode, o, rays);
+    else obs_epilogue(models[b.obj_id[env]], b, env, N, mode, o, snap, rays, Scratch<T, KS_LDS T*>{(KS_LDS T*)rlds + threadIdx.x, WAVE});
 }
 
 // The tail of the stepping kernel (fp32 / LDS variant, after the rays): the workgroup finishes its envs' step - the 82-d
@@ -1627,6 +1667,113 @@ __device__ __noinline__ void wg_ray_pool(const Model<float>* models, const Model
     }
     __syncthreads();
 }
+
+#ifndef KS_MULTI_GEOM
+// ---- exact mode: the free-running rollout of an fp64 context (ks_rollout on precision 64; standard library only).  k_env_step<double>'s
+// stepping path inside a per-workgroup loop, with k_rollout's policy in front and k_rays<double> / k_obs<double>'s work and the replay
+// write behind it - every phase the same device function the lock-step calls run, so per env the trajectory is theirs bit for bit.
+// The physics, rays, observation, reward and done are fp64; the actor reads, and the replay stores, their fp32 rounding.
+// Per env-step of a 16-env group, the phases joined by barriers:
+//   policy      rollout_policy on the engine's fp32 rows (noise, check_grasp, scripted lift), its tile in this kernel's dynamic LDS
+//   15 substeps env_step_global: state in registers, scratch the env's global block, the hull tables in LDS as k_env_step<double> has them
+//   rays        the group's 16 x 17 rays as 2 x 17 wave tasks of k_rays' shape (8 envs x 8 geoms per wave), one wave's LDS each
+//   observation obs_epilogue per env (lane 0 of its team), the auto-reset's kinematics in the env's (dead) global scratch block
+//   replay      rollout_store<double>: the fp64 outputs rounded to fp32 once
+// Groups are dealt as k_rollout's fixed deals (contiguous runs, or round-robin for mixed objects): no queue - its agent-scope acquire per
+// task drops cached lines of global memory, where this path keeps its scratch - and no wait on another workgroup, so a launch finishes
+// whatever is resident.  No register cap: a workgroup takes a CU's whole register file; the learner runs between its workgroups.
+constexpr int F64_RAY_TASKS = (EPW_MAX + RAY_ENVS - 1) / RAY_ENVS * NRAY;            // wave tasks of a group's rays
+constexpr int F64_RAY_WAVE_BYTES = WAVE * (int)sizeof(double) + RAY_STACK * WAVE * (int)sizeof(unsigned);     // pub + stack of one wave
+constexpr int F64_RAY_BYTES = (WG / WAVE) * F64_RAY_WAVE_BYTES;
+
+template <int NT1, int NT2>
+__device__ __forceinline__ void rollout_iter_f64(const Model<double>* __restrict__ models, const Model<double>& m, const Hulls<double>& hu,
+                                                 const Buffers<double>& b, int N, int frame_skip, int iters, int epw, const ObsOut<double>& o,
+                                                 const ks_rollout_args* __restrict__ rap, KS_LDS float* ws, int grp) {
+    using T = double;
+    const int e = threadIdx.x / LANE_STRIDE;
+    const Team<SUBS> team{(int)threadIdx.x % LANE_STRIDE};
+    const int env = e < epw ? b.slot_env[grp * epw + e] : -1;
+    const bool active = !(team.sub >= SUBS || env < 0);
+    {
+        const int nn = threadIdx.x & 15;
+        const int row_env = nn < epw ? b.slot_env[grp * epw + nn] : -1;
+        rollout_policy<NT1, NT2, true>(rap, N, row_env, ws);
+    }
+    __threadfence_block();
+    __syncthreads();
+    if (active) {
+        T hq[4], act[4];
+        KS_UNROLL
+        for (int i = 0; i < 4; i++) { hq[i] = b.hand_quat[(long)i * N + env]; act[i] = (T)rap->action_t[(long)i * N + env]; }
+        int ncon = 0, status = 0;
+        env_step_global(m, hu, b, env, N, hq, act, team, ColW<T>{b.snap + env, N}, frame_skip, iters, 0, ncon, status);
+        if (status) atomicOr(&b.status[env], status);
+        if (team.sub == 0) b.ncon[env] = ncon;
+    }
+    __threadfence_block();
+    __syncthreads();
+    {
+        const int wave = threadIdx.x / WAVE;
+        const unsigned lane = threadIdx.x % WAVE;
+        KS_LDS unsigned char* wb = (KS_LDS unsigned char*)ws + wave * F64_RAY_WAVE_BYTES;
+        for (int task = wave; task < F64_RAY_TASKS; task += WG / WAVE) {
+            const int ray = task % NRAY, re = task / NRAY * RAY_ENVS + (lane >> RG_BITS);
+            const int renv = re < epw ? b.slot_env[grp * epw + re] : -1;
+            ray_lane_f64(models, b, N, renv, ray, renv >= 0, lane, (KS_LDS T*)wb, (KS_LDS unsigned*)(wb + WAVE * sizeof(T)));
+        }
+    }
+    __threadfence_block();
+    __syncthreads();
+    if (active && team.sub == 0) {
+        T rays[NRAY];
+        KS_UNROLL
+        for (int i = 0; i < NRAY; i++) rays[i] = b.rays[(long)i * N + env];
+        obs_epilogue_f64(models[b.obj_id[env]], b, env, N, 0, o, rays);
+    }
+    __threadfence_block();
+    __syncthreads();
+    if (active) rollout_store<double>(rap, N, env, team.sub);
+    __threadfence_block();
+    __syncthreads();
+}
+
+template <int NT1, int NT2>
+__global__ __launch_bounds__(WG) void k_rollout_f64(const Model<double>* __restrict__ models, Buffers<double> b, const Buffers<double>* __restrict__ bdev,
+                                                    int N, int frame_skip, int iters, int epw, const ObsOut<double>* __restrict__ out,
+                                                    const ks_rollout_args* __restrict__ rap, int n_iter, int n_groups, int ws_offset) {
+    using T = double;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    // k_rollout's deal (n_groups < 0: round-robin)
+    const bool deal_rr = n_groups < 0;
+    if (deal_rr) n_groups = -n_groups;
+    const int g0 = deal_rr ? (int)blockIdx.x : (int)((long)blockIdx.x * n_groups / gridDim.x);
+    const int g1 = deal_rr ? n_groups : (int)((long)(blockIdx.x + 1) * n_groups / gridDim.x);
+    const int gstep = deal_rr ? (int)gridDim.x : 1;
+    KS_LDS T* const lds = (KS_LDS T*)smem;                                   // the hull tables, as k_env_step<double> stages them
+    KS_LDS float* const ws = (KS_LDS float*)(smem + ws_offset);              // behind them: the policy tile, then the ray stacks
+    int staged = __builtin_amdgcn_readfirstlane(b.wg_model[g0]);
+    int hull_words = 0;
+    Hulls<T> hu;
+    stage_hulls<T, false>(models[staged], lds, hull_words, hu);
+#pragma clang loop unroll(disable)
+    for (int it = 0; it < n_iter; it++) {
+#pragma clang loop unroll(disable)
+        for (int grp = g0; grp < g1; grp += gstep) {
+            if (g1 - g0 > gstep) {
+                // another group of this workgroup: restage the tables and rebuild the descriptor when its object differs
+                const int want = __builtin_amdgcn_readfirstlane(b.wg_model[grp]);
+                if (want != staged) {
+                    staged = want;
+                    __syncthreads();
+                    stage_hulls<T, false>(models[staged], lds, hull_words, hu);
+                }
+            }
+            rollout_iter_f64<NT1, NT2>(models, models[staged], hu, *bdev, N, frame_skip, iters, epw, *out, rap, ws, grp);
+        }
+    }
+}
+#endif
 
 struct CtxBase {
     ks_config cfg;
@@ -1961,35 +2108,88 @@ template <typename T> struct Ctx : CtxBase {
         HIPCHK(hipGetLastError());
         return KS_OK;
     }
+    // the checks of ks_rollout's arguments that every form makes: the buffers ...
+    int check_rollout_buffers(int n_iter, const ks_rollout_args* ra) {
+        if (!ra || n_iter <= 0 || !ra->actor_pub || !ra->actor_ver || !ra->obs || !ra->prev_obs || !ra->has_prev || !ra->ready || !ra->lifting ||
+            !ra->t || !ra->steps_total || !ra->action || !ra->action_t || !ra->reward_out || !ra->done_out || !ra->sim_obs || !ra->sim_reward ||
+            !ra->sim_done || !ra->sim_info || !ra->sim_final_obs || !ra->counters) { error = "ks_rollout: NULL argument"; return KS_ERR_INVALID; }
+        if (ra->with_replay && (!ra->cur_state || !ra->cur_next || !ra->cur_action || !ra->cur_reward || !ra->cur_not_done || !ra->cur_len ||
+                                !ra->cur_sel || !ra->pub_len || ra->horizon <= ra->n_steps)) { error = "ks_rollout: replay buffers"; return KS_ERR_INVALID; }
+        return KS_OK;
+    }
+    // ... and the actor's layout
+    int check_rollout_actor(const ks_rollout_args* ra) {
+        if ((ra->off_w2 | ra->off_w3 | ra->actor_stride) & 3) { error = "ks_rollout: weight offsets must be multiples of 4 floats"; return KS_ERR_INVALID; }
+        if ((ra->h1 | ra->h2) & 3) { error = "ks_rollout: hidden widths must be multiples of 4"; return KS_ERR_INVALID; }
+        return KS_OK;
+    }
+    // the launch's output record (the context's sim_* buffers) and argument record -> device memory
+    int send_rollout_records(const ks_rollout_args* ra, hipStream_t s) {
+        const ObsOut<T> out{(T*)ra->sim_obs, (T*)ra->sim_reward, ra->sim_done, (T*)ra->sim_info, (T*)ra->sim_final_obs, cfg.horizon, cfg.auto_reset, cfg.obs_env_major};
+        const bool capturing = stream_is_capturing(s);
+        ObsOut<T>* slot = pinned_record(capturing, h_out, (unsigned)h_out_next++, captured_out);
+        if (!slot) { error = "ks_rollout: more captured calls than the context keeps output records for"; return KS_ERR_STATE; }
+        *slot = out;
+        out_valid = false;                                     // a following ks_step re-sends its own record
+        HIPCHK(hipMemcpyAsync(d_out, slot, sizeof out, hipMemcpyHostToDevice, s));
+        ks_rollout_args* rslot = pinned_record(capturing, h_ra, h_ra_next++, captured_ra);
+        if (!rslot) { error = "ks_rollout: more captured calls than the context keeps argument records for"; return KS_ERR_STATE; }
+        *rslot = *ra;
+        HIPCHK(hipMemcpyAsync(d_ra, rslot, sizeof *ra, hipMemcpyHostToDevice, s));
+        return KS_OK;
+    }
+    // exact mode (fp64 contexts, standard library): k_rollout_f64
+    int rollout_exact(int n_iter, const ks_rollout_args* ra, hipStream_t s) {
+#ifdef KS_MULTI_GEOM
+        (void)n_iter; (void)ra; (void)s;
+        error = "ks_rollout: libkinova_sim_mg.so runs fp32 contexts only (the exact mode, precision 64, is in libkinova_sim.so)";
+        return KS_ERR_INVALID;
+#else
+        int r;
+        if ((r = check_rollout_buffers(n_iter, ra))) return r;
+        if (!cfg.obs_env_major || !cfg.auto_reset) { error = "ks_rollout needs env-major observations and auto_reset"; return KS_ERR_STATE; }
+        if ((r = check_rollout_actor(ra))) return r;
+        if (ra->budget_ticks != 0) { error = "ks_rollout: a time budget needs the wave form of the rollout kernel (ks_rollout_plan: KS_PLAN_WAVES); fp64 contexts have none"; return KS_ERR_STATE; }
+        // dynamic LDS: the hull tables (k_env_step<double>'s step_lds), then the policy tile or the ray stacks (phases apart)
+        const size_t ws_offset = (step_lds + 15) / 16 * 16;
+        const size_t policy_bytes = (size_t)(((ra->h1 + 15) / 16 + (ra->h2 + 15) / 16) * 4 + 4) * 16 * 16 + 16;
+        const size_t lds = ws_offset + std::max(policy_bytes, (size_t)F64_RAY_BYTES);
+        if (lds > 160 * 1024) { error = "ks_rollout: no LDS for the policy beside this object's hull tables"; return KS_ERR_STATE; }
+        if ((r = send_rollout_records(ra, s))) return r;
+        const int N = cfg.n_envs;
+#define KS_ROLLOUT_F64_CASE(A, B)                                                                                                                     \
+    if ((ra->h1 + 15) / 16 == A && (ra->h2 + 15) / 16 == B) {                                                                                             \
+        HIPCHK(hipFuncSetAttribute((const void*)k_rollout_f64<A, B>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                          \
+        hipLaunchKernelGGL((k_rollout_f64<A, B>), dim3(n_groups < resident_wgs ? n_groups : resident_wgs), dim3(WG), lds, s, d_model, b,                  \
+                           (const Buffers<T>*)d_b, N, cfg.frame_skip, cfg.solver_iterations, lpw, (const ObsOut<T>*)d_out, (const ks_rollout_args*)d_ra,    \
+                           n_iter, rollout_round_robin ? -n_groups : n_groups, (int)ws_offset);                                                           \
+        HIPCHK(hipGetLastError());                                                                                                                    \
+        return KS_OK;                                                                                                                                 \
+    }
+        KS_ROLLOUT_F64_CASE(16, 16)
+        KS_ROLLOUT_F64_CASE(25, 19)
+        KS_ROLLOUT_F64_CASE(8, 8)
+        KS_ROLLOUT_F64_CASE(4, 4)
+#undef KS_ROLLOUT_F64_CASE
+        error = "ks_rollout: hidden widths must be 256-256, 400-300, 128-128 or 64-64";
+        return KS_ERR_INVALID;
+#endif
+    }
     int rollout(int n_iter, const ks_rollout_args* ra, hipStream_t s) override {
         if (!model_loaded) { error = "ks_rollout before ks_load_model"; return KS_ERR_STATE; }
-        if constexpr (sizeof(T) != 4) { error = "ks_rollout: fp32 contexts only"; return KS_ERR_INVALID; }
+        if constexpr (sizeof(T) != 4) return rollout_exact(n_iter, ra, s);
         else {
-            if (!ra || n_iter <= 0 || !ra->actor_pub || !ra->actor_ver || !ra->obs || !ra->prev_obs || !ra->has_prev || !ra->ready || !ra->lifting ||
-                !ra->t || !ra->steps_total || !ra->action || !ra->action_t || !ra->reward_out || !ra->done_out || !ra->sim_obs || !ra->sim_reward ||
-                !ra->sim_done || !ra->sim_info || !ra->sim_final_obs || !ra->counters) { error = "ks_rollout: NULL argument"; return KS_ERR_INVALID; }
-            if (ra->with_replay && (!ra->cur_state || !ra->cur_next || !ra->cur_action || !ra->cur_reward || !ra->cur_not_done || !ra->cur_len ||
-                                    !ra->cur_sel || !ra->pub_len || ra->horizon <= ra->n_steps)) { error = "ks_rollout: replay buffers"; return KS_ERR_INVALID; }
+            int r;
+            if ((r = check_rollout_buffers(n_iter, ra))) return r;
             if (!obs_in_step || !cfg.obs_env_major || !cfg.auto_reset) { error = "ks_rollout needs the in-kernel observation path, env-major observations and auto_reset"; return KS_ERR_STATE; }
-            if ((ra->off_w2 | ra->off_w3 | ra->actor_stride) & 3) { error = "ks_rollout: weight offsets must be multiples of 4 floats"; return KS_ERR_INVALID; }
-            if ((ra->h1 | ra->h2) & 3) { error = "ks_rollout: hidden widths must be multiples of 4"; return KS_ERR_INVALID; }
+            if ((r = check_rollout_actor(ra))) return r;
             if ((size_t)(((ra->h1 + 15) / 16 + (ra->h2 + 15) / 16) * 4 + 4) * 16 * 16 + 16 > (size_t)SCR_TOTAL * lpw * sizeof(T)) { error = "ks_rollout: no LDS for the policy"; return KS_ERR_STATE; }
             const int N = cfg.n_envs;
             if (ra->budget_ticks != 0 && (ra->budget_ticks < 0 || !(plan_waves() && (size_t)(((ra->h1 + 15) / 16 + (ra->h2 + 15) / 16) * 4) * 4 * 16 <= (size_t)SCR_TOTAL * 4 * sizeof(T)))) {
                 error = "ks_rollout: a time budget needs the wave form of the rollout kernel (ks_rollout_plan: KS_PLAN_WAVES)";
                 return KS_ERR_STATE;
             }
-            const ObsOut<T> out{(T*)ra->sim_obs, (T*)ra->sim_reward, ra->sim_done, (T*)ra->sim_info, (T*)ra->sim_final_obs, cfg.horizon, cfg.auto_reset, cfg.obs_env_major};
-            const bool capturing = stream_is_capturing(s);
-            ObsOut<T>* slot = pinned_record(capturing, h_out, (unsigned)h_out_next++, captured_out);
-            if (!slot) { error = "ks_rollout: more captured calls than the context keeps output records for"; return KS_ERR_STATE; }
-            *slot = out;
-            out_valid = false;                                     // a following ks_step re-sends its own record
-            HIPCHK(hipMemcpyAsync(d_out, slot, sizeof out, hipMemcpyHostToDevice, s));
-            ks_rollout_args* rslot = pinned_record(capturing, h_ra, h_ra_next++, captured_ra);
-            if (!rslot) { error = "ks_rollout: more captured calls than the context keeps argument records for"; return KS_ERR_STATE; }
-            *rslot = *ra;
-            HIPCHK(hipMemcpyAsync(d_ra, rslot, sizeof *ra, hipMemcpyHostToDevice, s));
+            if ((r = send_rollout_records(ra, s))) return r;
             // more groups than resident workgroups: the ready queue (k_rollout); else one group per workgroup, nothing to deal
             const bool use_queue = plan_queue();
             const bool wave_free = plan_waves() && (size_t)(((ra->h1 + 15) / 16 + (ra->h2 + 15) / 16) * 4) * 4 * 16 <= (size_t)SCR_TOTAL * 4 * sizeof(T);
@@ -2027,7 +2227,10 @@ template <typename T> struct Ctx : CtxBase {
     }
     int rollout_plan(int32_t* mode, int32_t* groups, int32_t* workgroups) override {
         if (!model_loaded) { error = "ks_rollout_plan before ks_load_model"; return KS_ERR_STATE; }
-        if (mode) *mode = plan_waves() ? KS_PLAN_WAVES : (n_groups <= resident_wgs ? KS_PLAN_WORKGROUPS : (plan_queue() ? KS_PLAN_QUEUE : (rollout_round_robin ? KS_PLAN_ROUND_ROBIN : KS_PLAN_RUNS)));
+        if constexpr (sizeof(T) != 4) {
+            // exact mode (k_rollout_f64): barrier-joined workgroups, groups beyond one per workgroup in a fixed deal - never the queue
+            if (mode) *mode = n_groups <= resident_wgs ? KS_PLAN_WORKGROUPS : (rollout_round_robin ? KS_PLAN_ROUND_ROBIN : KS_PLAN_RUNS);
+        } else if (mode) *mode = plan_waves() ? KS_PLAN_WAVES : (n_groups <= resident_wgs ? KS_PLAN_WORKGROUPS : (plan_queue() ? KS_PLAN_QUEUE : (rollout_round_robin ? KS_PLAN_ROUND_ROBIN : KS_PLAN_RUNS)));
         if (groups) *groups = n_groups;
         if (workgroups) *workgroups = n_groups < resident_wgs ? n_groups : resident_wgs;
         return KS_OK;

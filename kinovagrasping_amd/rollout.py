@@ -64,6 +64,11 @@ class RolloutEngine:
             from . import sim as _sim
             self._lib, self._ptr = _sim.load_library(), _sim._ptr
             self._keep = torch.zeros(self.n, dtype=torch.bool, device=dev)
+        # exact mode (an fp64 KinovaSim): the policy and the replay stay fp32 - post() rounds the sim's fp64 outputs into these buffers
+        # once per step (preallocated: the step stays capture-safe), as the free-running kernel does (ks_rollout, include/kinova_sim.h)
+        self._sim32 = None
+        if getattr(sim, "dtype", torch.float32) != torch.float32:
+            self._sim32 = (torch.zeros(sim.obs.shape, device=dev), torch.zeros(sim.final_obs.shape, device=dev), torch.zeros(sim.reward.shape, device=dev))
         self.device_noise = (generator is None) if device_noise is None else bool(device_noise)
         self.noise_seed = int(torch.initial_seed()) & 0xFFFFFFFFFFFFFFFF
         self.rng_state = torch.zeros(2, dtype=torch.long, device=dev)        # [launch counter, scratch] of kr_actor_select
@@ -139,18 +144,28 @@ class RolloutEngine:
         if self.native and self.replay is not None:
             self.replay.commit_native(self._keep, self.done_out)
 
+    def _sim_outputs(self):
+        """(obs, final_obs, reward) of the sim's last step in fp32: the sim's own buffers, or (fp64 sim) their rounding"""
+        sim = self.sim
+        if self._sim32 is None:
+            return sim.obs, sim.final_obs, sim.reward
+        for dst, src in zip(self._sim32, (sim.obs, sim.final_obs, sim.reward)):
+            dst.copy_(src)
+        return self._sim32
+
     @torch.no_grad()
     def post(self, commit=True):
         """Consume the sim's output buffers: replay writes and per-env bookkeeping for the next step.  commit=False
         (kernel path only) leaves the ring update to commit()."""
         sim = self.sim
+        sim_obs, sim_final, sim_reward = self._sim_outputs()
         if self.native:
             rp, P = self.replay, self._ptr
             N = lambda *a: [None] * len(a) if rp is None else list(a)
             cur = N("cur_state", "cur_next", "cur_action", "cur_reward", "cur_not_done", "cur_len")
             cur = [None if c is None else P(getattr(rp, c)) for c in cur]
             rc = self._lib.kr_store_transition(self.n, rp.horizon if rp else 1, rp.n_steps if rp else 0, int(sim.cfg.auto_reset), int(rp is not None),
-                                               P(sim.obs), P(sim.final_obs), P(sim.reward), P(sim.done), P(self.obs), P(self.prev_obs),
+                                               P(sim_obs), P(sim_final), P(sim_reward), P(sim.done), P(self.obs), P(self.prev_obs),
                                                P(self.has_prev), P(self.t), P(self.ready), P(self.lifting), P(self.action), *cur,
                                                P(self.reward_out), P(self.done_out), P(self._keep), self._stream())
             if rc != 0:
@@ -158,11 +173,11 @@ class RolloutEngine:
             if rp is not None and commit:
                 rp.commit_native(self._keep, self.done_out)
             return
-        obs, reward = sim.obs, sim.reward
+        obs, reward = sim_obs, sim_reward
         done_b = sim.done != 0
         state, lifting = self.obs, self.lifting
         # the transition's next_state is the terminal observation for envs that just finished
-        next_state = torch.where(done_b.unsqueeze(1), sim.final_obs, obs) if sim.cfg.auto_reset else obs
+        next_state = torch.where(done_b.unsqueeze(1), sim_final, obs) if sim.cfg.auto_reset else obs
         if self.replay is not None:
             self.replay.add(state, self.action, next_state, reward, done_b, store_mask=~lifting)
             self.replay.replace_last(done_b & lifting, reward)

@@ -31,14 +31,16 @@ class KinovaGripperVecEnv:
 
     def __init__(self, n_envs: int, shape="CubeS", device: int = 0, frame_skip: int = 15, max_episode_steps: int = 30,
                  auto_reset: bool = True, solver_iterations: int = SOLVER_ITERATIONS, seed: int = 0, hand_offsets: str = "fresh-env",
-                 host_only: bool = False):
+                 host_only: bool = False, precision: int = 32):
         """shape: one object name, or a list of them (mixed-object batches, BASELINE config 5).
         hand_offsets: where the 'rotated' / 'top' hands start (determine_hand_location, ENV:1286-1307) - "fresh-env" (default: what the
         reference's drivers do): zero, because main_DDPGfD.py:381 / expert_data.py recreate the env for every episode and a fresh env's
         Tfw is zero; "pose": with the pose's own palm rotation - what determine_hand_location is written to do, the hand hovers over
         the object - (scenarios.hand_slide_offsets; BASELINE config 5 and bench.py ask for "pose" explicitly).
         host_only: no device, no simulator - reset() then RETURNS the start states it drew ({"qpos": [16, n], "hand_quat": [4, n]}) instead
-        of observations: the reset's sampling is host code and is pinned against the reference's on CPU (tests/test_reset_golden.py)."""
+        of observations: the reset's sampling is host code and is pinned against the reference's on CPU (tests/test_reset_golden.py).
+        precision: 32 (the product) or 64 - the exact mode: fp64 physics, observations returned as float64 (as the reference's mujoco-py
+        returns them) and actions taken in float64."""
         if hand_offsets not in ("fresh-env", "pose"):
             raise ValueError('KinovaGripperVecEnv: hand_offsets is "fresh-env" (the reference drivers\' zero offsets) or "pose"')
         self.hand_offsets = hand_offsets
@@ -51,7 +53,8 @@ class KinovaGripperVecEnv:
         self.action_space = SimpleNamespace(low=np.full(4, -0.8, np.float32), high=np.full(4, 0.8, np.float32), shape=(4,), dtype=np.float32)
         self.observation_dim = NOBS
         self.sim = None if host_only else KinovaSim(n_envs, shape if isinstance(shape, str) else self.shapes, device=device, frame_skip=frame_skip,
-                                                    horizon=max_episode_steps, solver_iterations=solver_iterations, auto_reset=auto_reset, obs_env_major=True)
+                                                    horizon=max_episode_steps, solver_iterations=solver_iterations, auto_reset=auto_reset, obs_env_major=True,
+                                                    precision=precision)
         self.np_random = np.random.RandomState(seed)
         self.orientation = ["normal"] * n_envs
         self.obj_coords = np.zeros((n_envs, 3))
@@ -309,7 +312,7 @@ class KinovaGripperVecEnv:
     def step(self, action, graspnetwork=False):
         """action: [N,4] (wrist, finger1..3) torch tensor or array.  Returns (obs [N,82], reward [N],
         done [N] bool, info dict of [N] tensors)."""
-        a = torch.as_tensor(action, dtype=torch.float32, device=self.sim.device)
+        a = torch.as_tensor(action, dtype=self.sim.dtype, device=self.sim.device)
         if a.shape != (self.n_envs, 4):
             raise ValueError(f"action must be [{self.n_envs}, 4], got {tuple(a.shape)}")
         obs, reward, done, info = self.sim.step(a.t().contiguous())
