@@ -21,8 +21,9 @@ import pytest
 import torch
 
 from oracle import ko_py as ko
-from kinovagrasping_amd import scenarios
+from kinovagrasping_amd import model_compiler as mc, scenarios
 from kinovagrasping_amd.sim import SOLVER_ITERATIONS
+from tests.ray_poses import object_hit_slots
 
 pytestmark = pytest.mark.gpu
 POSES = ("normal", "rotated", "top")
@@ -165,8 +166,9 @@ def test_post_step_observation_reward_done_from_oracle_states(orientation):
     """The product observation path (k_env_step's in-kernel rays -> k_obs) AFTER stepping, in every pose: 96 envs (4 start
     rows x 24 points of a random-action episode) are put into the oracle's state at that point (ks_set_state) and take ONE
     env.step with the same action; the 82-d observation, reward, done and qpos / qvel are compared with the oracle's."""
+    blob = mc.read_blob(scenarios.model_blob("CubeS"))
     model = ko.OracleModel(scenarios.model_blob("CubeS"))
-    states, acts, ref = [], [], []
+    states, acts, ref, on_object, hits = [], [], [], 0, 0
     for row in (0, 700, 2100, 3900):
         q0, hq = pose_start("CubeS", orientation, row)
         o = ko.OracleSim(model, hq, solver_iterations=SOLVER_ITERATIONS)
@@ -177,6 +179,7 @@ def test_post_step_observation_reward_done_from_oracle_states(orientation):
             states.append((q0, o.view("qpos").copy(), o.view("qvel").copy(), o.view("qacc_warmstart").copy()))
             ob, r, d, info = o.env_step(a[t])
             acts.append(a[t]); ref.append((ob, r, d, o.view("qpos").copy(), o.view("qvel").copy()))
+            on_object += int(object_hit_slots(blob, o).sum()); hits += int((ob[50:67] != 6).sum())
     n = len(states)
     hqn = np.repeat(hq[:, None], n, 1)
     for precision, tol in ((64, 1e-8), (32, 2e-4)):
@@ -197,7 +200,8 @@ def test_post_step_observation_reward_done_from_oracle_states(orientation):
         on = eq <= (1e-8 if precision == 64 else 2e-5)
         print(f"{orientation} fp{precision}: {n} env-steps, on-trajectory {on.mean():.3f}; obs slots beyond tolerance "
               f"(non-ray) {int(bad[on][:, NON_RAY].sum())}, (ray) {int(bad[on][:, RAY_SLOTS].sum())} of {int(on.sum()) * len(RAY_SLOTS)}; "
-              f"|dqpos| median {np.median(eq):.2e} max {eq.max():.2e}; |dqvel| median {np.median(ev):.2e}")
+              f"|dqpos| median {np.median(eq):.2e} max {eq.max():.2e}; |dqvel| median {np.median(ev):.2e}; of the {17 * n} rangefinder slots "
+              f"{hits} hit something and {on_object} hit the OBJECT (tests/test_gpu_rays.py aims the object at the rays)")
         assert on.mean() >= (0.95 if precision == 64 else 0.93)                 # (fp32 measured 0.969 / 1.000 / 1.000)
         assert not bad[on][:, NON_RAY].any(), np.argwhere(bad[on][:, NON_RAY])[:5]
         assert bad[on][:, RAY_SLOTS].mean() <= 0.01
@@ -336,9 +340,9 @@ def test_fourteen_shapes_three_poses_observations_track_the_oracle():
     fp32 a ballistic, tumbling object is only required to stay finite (its error is reported) - everything else must track."""
     per = 4
     act = np.array([0.0, 0.6, 0.5, 0.7])
-    summary, launched_total = [], 0
+    summary, launched_total, ray_slots_compared, ray_slots_on_object = [], 0, 0, 0
     for sh in scenarios.SHAPES:
-        model = ko.OracleModel(scenarios.model_blob(sh))
+        model, blob = ko.OracleModel(scenarios.model_blob(sh)), mc.read_blob(scenarios.model_blob(sh))
         q0s, hqs = [], []
         for ori in POSES:
             for k in range(per):
@@ -370,6 +374,7 @@ def test_fourteen_shapes_three_poses_observations_track_the_oracle():
             if rel32[i] <= 1e-4:
                 bad = np.abs(og[32][i] - ob) > t_obs + t_obs * np.abs(ob)
                 nbad += int(bad[NON_RAY].sum()); nray += int(bad[RAY_SLOTS].sum())
+                ray_slots_compared += 17; ray_slots_on_object += int(object_hit_slots(blob, o).sum())
         tame = ~launched
         launched_total += int(launched.sum())
         summary.append((sh, float(np.median(rel32[tame])), float(rel32[tame].max()), int((rel32[tame] <= 2e-4).sum()), int(tame.sum()),
@@ -378,6 +383,7 @@ def test_fourteen_shapes_three_poses_observations_track_the_oracle():
         print("%-10s fp32 tame envs: median rel qpos %.2e max %.2e, %d/%d within 2e-4; launched max %.2e; fp64 third-worst %.1e; "
               "obs slots off: %d non-ray, %d ray" % row)
     print("launched envs:", launched_total, "of", 14 * 12)
+    print(f"rangefinder slots compared: {ray_slots_compared}, of which {ray_slots_on_object} hit the OBJECT (tests/test_gpu_rays.py aims the object at the rays)")
     assert all(r[1] <= 5e-5 for r in summary), summary
     assert all(r[3] >= r[4] - 2 for r in summary), summary       # at most two tame grasps per shape flipped a contact
     assert all(np.isfinite(r[5]) for r in summary), summary
