@@ -11,7 +11,7 @@
      (The lift rate of the TRAINING rollouts is depressed by the exploration noise on the wrist channel: clip(pi + N(0, 0.08), 0, 0.8) lifts the
      hand by ~5 mm per env-step on average while the fingers close - as in the reference, main_DDPGfD.py:443-446.)
 
-    python examples/train_ddpgfd.py --envs 1024 --steps 600 --hidden 256 256 [--free-running] [--expert-prob 0]
+    python examples/train_ddpgfd.py --envs 1024 --steps 600 --hidden 256 256 [--free-running] [--expert-prob 0] [--starts-per-env 64]
 
 Measured curves: profiles/r04_training_curves.txt.  One update per env-step of 4096 envs (BASELINE config 3's workload) is 1e4 times fewer
 updates per stored transition than the reference's 100 updates per episode of one env (main_DDPGfD.py:474-476); with the reference's target
@@ -57,6 +57,8 @@ def main():
     ap.add_argument("--expert-prob", type=float, default=0.3, help="share of expert episodes in a batch (DDPGfD.py:232-254); 0: plain DDPG, no demonstrations")
     ap.add_argument("--eval-every", type=int, default=600, help="env-steps between evaluations without exploration noise (0: none)")
     ap.add_argument("--free-running", action="store_true", help="the persistent rollout kernel (ks_rollout) instead of one launch per env-step")
+    ap.add_argument("--starts-per-env", type=int, default=0, help="K > 0: every training env holds a pool of K start positions and each of its episodes starts from one "
+                    "drawn inside the stepping kernel (ks_set_start_pool); 0: an env replays the one start it was reset to")
     ap.add_argument("--batch-episodes", type=int, default=64, help="episodes per update (x 25 five-step windows each); the reference: 64")
     ap.add_argument("--updates-per-step", type=int, default=1, help="learner updates per env-step of the whole batch of envs")
     ap.add_argument("--actor-lr", type=float, default=1e-4, help="reference: 1e-4 (DDPGfD.py:57)")
@@ -91,14 +93,21 @@ def main():
     #    one launch inside the captured update (pipeline.GraphedTrainer; --free-running: the persistent rollout kernel, AsyncTrainer)
     from kinovagrasping_amd.pipeline import AsyncTrainer, GraphedTrainer
     sim = KinovaSim(n, args.shape, auto_reset=True, horizon=30)
-    q0, hq = start_states(n, args.shape, rng)
+    if args.starts_per_env > 0:
+        qp, hqp, _ = scenarios.draw_start_pool([args.shape] * n, "normal", args.starts_per_env, rng)
+        print(f"start pool: {args.starts_per_env} starts per env, {qp.shape[0] * n * 102 * 4 / 1e6:.0f} MB on the device")
+    else:
+        q0, hq = start_states(n, args.shape, rng)
     policy = DDPGfD(82, 4, 0.8, 5, tau=args.tau, batch_size=args.batch_episodes, hidden=tuple(args.hidden), device=dev)
     policy.network_repl_freq = args.target_every
     policy.actor_optimizer.param_groups[0]["lr"] = args.actor_lr
     policy.critic_optimizer.param_groups[0]["lr"] = args.critic_lr
     agent = DeviceEpisodeReplay(n, capacity=max(4 * n, 4096), device=dev)
     eng = RolloutEngine(sim, policy, agent, expl_noise=args.expl_noise)
-    eng.start(sim.reset(torch.as_tensor(q0), torch.as_tensor(hq)))
+    if args.starts_per_env > 0:
+        eng.start(sim.set_start_pool(torch.as_tensor(qp), torch.as_tensor(hqp), seed=args.seed))
+    else:
+        eng.start(sim.reset(torch.as_tensor(q0), torch.as_tensor(hq)))
     Trainer = AsyncTrainer if args.free_running else GraphedTrainer
     tr = Trainer(sim, policy, agent, eng, batch_episodes=args.batch_episodes, expert_replay=expert, expert_prob=args.expert_prob if expert is not None else 0.3,
                  updates_per_step=args.updates_per_step)

@@ -11,6 +11,8 @@
  *   ks_reset_objects         <- the per-episode object choice: select_object + load of another XML   ENV:986-1005, 1180-1222
  *   ks_reset                 <- KinovaGripper_Env.reset: write_xml (hand euler) + _set_state
  *                               + sim.forward() + _get_obs()                        ENV:1310-1410, 851-881, 692-703
+ *   ks_set_start_pool        <- the NEW start every reset() draws (orientation class, coordinate-table row, hand euler), for the
+ *                               resets that happen inside ks_step / ks_rollout                       ENV:1310-1410
  *   ks_step                  <- KinovaGripper_Env.step: action->ctrl, 15 x sim.step(),
  *                               _get_obs(), _get_reward()                           ENV:1495-1552
  *                               + gym TimeLimit (max_episode_steps)                 gym_kinova_gripper/__init__.py:3-7, main_DDPGfD.py:384
@@ -70,15 +72,16 @@ typedef struct {
     int32_t horizon;            /* episode time limit in env steps, 30 (main_DDPGfD.py:384); <= 0 disables */
     int32_t solver_iterations;  /* Newton iterations per substep */
     int32_t precision;          /* 32 or 64 */
-    int32_t auto_reset;         /* 1: envs that finish are reset to their stored initial state inside ks_step */
+    int32_t auto_reset;         /* 1: envs that finish are reset inside ks_step: to their stored initial state, or - with a start
+                                   pool, ks_set_start_pool - to a start drawn from the env's pool */
     int32_t obs_env_major;      /* 0: obs[k*N+env], 1: obs[env*82+k] */
     int32_t envs_per_wave;      /* envs per stepping workgroup (256 threads = 16 lanes per env): 0 = automatic (16,
                                    or fewer when the model's hull tables leave less LDS); else 1..16 */
     int32_t contact_tap;        /* 1: keep the per-contact records of the last substep for ks_get_state (parity) */
     int32_t pair_memory;        /* 1 (default): every env carries what its hull pairs remember of their last narrow-phase
-                                   queries (support hints, closest-feature simplex, penetration portal: vertex ids only)
-                                   from one ks_step to the next, so no substep starts its queries cold; 0: cold start
-                                   at every ks_step.  Same contacts to the queries' 1e-6 tolerance either way. */
+                                   queries (support hints and the closest-feature simplex: vertex ids only) from one
+                                   ks_step to the next, so no substep starts its queries cold; 0: cold start at every
+                                   ks_step.  Same contacts to the queries' 1e-6 tolerance either way. */
     int32_t reserved[2];
 } ks_config;
 
@@ -108,6 +111,7 @@ int ks_reset(ks_ctx *ctx, const int32_t *env_ids, int32_t n, const void *qpos0, 
 /* ks_reset that also chooses every reset env's object and (optionally) its randomised parameters - the reference's
  * reset(): select_object (ENV:986-1005) + select_orienation (ENV:1180-1222) + _set_state (ENV:692-703).
  * object_id: device int32 [n], index into the blobs of ks_load_models, or NULL (objects stay);
+ * A call with object_id CLEARS the context's start pool (ks_set_start_pool): a pool entry is a start of the object the env held.
  * mass_friction: device [2, n] (row 0 object mass in kg - the inertia scales with it -, row 1 friction of the seven
  * object-hand pairs), or NULL: an env whose object is (re)assigned takes that object's compiled mass / friction, other
  * envs keep theirs.  (Mass / friction randomisation is an extension: the reference fixes 0.1 kg, XML:153, and mu 1,
@@ -115,6 +119,33 @@ int ks_reset(ks_ctx *ctx, const int32_t *env_ids, int32_t n, const void *qpos0, 
  * stream is being captured - WAITS for the stream once to read back how many 16-env groups hold envs (what ks_rollout schedules: ks_rollout_plan). */
 int ks_reset_objects(ks_ctx *ctx, const int32_t *env_ids, int32_t n, const void *qpos0, const void *hand_quat, const int32_t *object_id,
                      const void *mass_friction, void *obs, void *stream);
+
+/* Start pool: k prepared starts per env, one of which every AUTO-RESET of the env draws inside the stepping kernels (ks_step and
+ * ks_rollout, both precisions, both libraries) - instead of replaying the one stored initial state for as long as the context lives.
+ * qpos0: [k][16][N], hand_quat: [k][4][N] (entry j of env e: qpos0[(j * 16 + i) * N + e]), as ks_reset takes them.
+ * The call behaves like a ks_reset of ALL envs:
+ *   - it copies the pool (context precision) into storage the context owns - (16 + 4 + 82) * k * N values, 107 MB for k = 64,
+ *     N = 4096 in fp32; grown on demand, kept until ks_destroy; when it cannot be allocated: KS_ERR_HIP, the message states the size;
+ *   - it computes the observation of every one of the k * N starts once, with ks_reset's own kernels and therefore its bits: the
+ *     reset pass (state <- start, kinematics, rays, observation) is looped over the k entries, all envs per pass, reading the entry
+ *     in the pool and writing into the pool and into preparation buffers of the context's - no env's live state is touched;
+ *   - it zeroes every env's episode counter, resets every env to its draw for episode 0 and writes `obs` (optional, as ks_reset).
+ * The draw, for callers that want to reproduce it:
+ *     r = Philox4x32-10(counter = (env, episode low word, episode high word, 0x5350), key = (seed low word, seed high word))
+ *     index = (uint64(r[0]) * k) >> 32
+ * where `episode` counts the auto-resets the env has done since the pool was set (episode 0: the call's own reset).  On an auto-reset
+ * the kernel bumps the counter, draws, copies the entry (start, hand orientation, cached observation) over the env's stored
+ * initial state and restarts the env from it exactly as without a pool: a copy and forward kinematics, no rays.
+ * ks_reset of some envs keeps the pool: those envs run the caller's start until their next auto-reset draws again.
+ * ks_reset_objects with object_id clears the pool.  (An object per episode is not part of this: it regroups the work list.)
+ * k = 0 clears the pool (qpos0 / hand_quat / obs ignored, no reset): every env keeps the start of its running episode as its stored
+ * initial state, as if ks_reset had set it.  1 <= k <= 1024 otherwise.
+ * No host synchronisation, like ks_reset - except that a call which has to allocate (the first, or a larger k) allocates, and
+ * waits for the device before it gives a smaller storage back.  Not for stream capture. */
+int ks_set_start_pool(ks_ctx *ctx, int32_t k, const void *qpos0, const void *hand_quat, uint64_t seed, void *obs, void *stream);
+/* index: int32 [N], the pool entry every env's running episode started from (an env that was ks_reset since: its last draw);
+ * episode: int64 [N], its auto-resets since the pool was set.  Either may be NULL.  KS_ERR_STATE without a pool. */
+int ks_get_start_index(ks_ctx *ctx, int32_t *index, int64_t *episode, void *stream);
 
 /* One env.step() for every env.  action: [4, N] (wrist, finger1..3), obs: N x 82, reward: [N],
  * done: uint8 [N] (bit0 lifted, bit1 time limit), info: [3, N] (finger, grasp, lift reward).
@@ -158,7 +189,7 @@ int ks_obs_from_snapshot(ks_ctx *ctx, const void *snap, const void *rays, void *
  *     check_grasp / scripted-lift rule  ->  15 substeps  ->  rangefinder rays  ->  observation / reward / done / auto-reset
  *     ->  replay write (open-episode buffers) + episode hand-over
  * i.e. what kr_actor_select + ks_step + kr_store_transition do per env-step (main_DDPGfD.py:424-464 around ENV:1495-1552), fused.
- * A lock-step launch lasts as long as its slowest wave (1.6 - 1.9 x the median); here a wave (round 6: with one 16-env group per
+ * A lock-step launch lasts as long as its slowest wave; here a wave (round 6: with one 16-env group per
  * workgroup the four waves of a workgroup never meet inside a launch; otherwise a workgroup) starts its next env-step the
  * moment it has finished the last.  Per env the arithmetic, the noise stream (Philox keyed by seed, the env's own step count,
  * env) and therefore the trajectory are those of the lock-step calls for the same weights.

@@ -10,6 +10,9 @@
 //   k_rays       17 rangefinder rays x 8 mesh geoms as a launch of their own, one (env, ray, geom) per lane, grid
 //                (N/8, 17): ks_reset, fp64 contexts, KS_RAYS_IN_STEP=0
 //   k_substep    one mj_step with explicit controls (parity tap)
+//   k_pool_begin the start pool (ks_set_start_pool): its record, every env at its draw for episode 0; the pool's observations come
+//                from k_reset / k_rays / k_obs run once per entry into buffers of their own; an auto-reset draws the next entry in
+//                start_pool_restart (out of line, called where obs_finish restarts an episode)
 // No CPU fallback exists in this library.
 #include <hip/hip_runtime.h>
 
@@ -34,6 +37,18 @@ namespace {
 
 constexpr int WAVE = 64;
 thread_local std::string g_create_error;
+
+// The start pool of a context (ks_set_start_pool): k prepared starts per env with their observations, and what an auto-reset needs
+// to draw one of them - one record in device memory, written by the stream (k_pool_begin / k_pool_clear), so that a captured
+// ks_step / ks_rollout sees whatever pool the context holds when the graph is replayed.  k = 0: no pool.
+template <typename T> struct StartPool {
+    int32_t k, pad;
+    uint64_t seed;
+    const T *qpos0, *hand_quat, *obs0;          // [k][16][N], [k][4][N], [k][N][82]
+    T *env_qpos0, *env_hand_quat, *env_obs0;    // the envs' stored initial state (Buffers): a restart copies the drawn entry there
+    int64_t *episode;                           // [N] auto-resets since the pool was set
+    int32_t *index;                             // [N] the entry every env's running episode started from
+};
 
 template <typename T> struct Buffers {
     T *qpos, *qvel, *warm;        // [16|15|15][N]
@@ -62,6 +77,7 @@ template <typename T> struct Buffers {
     // [3] workgroups that have started,
     // [4 .. 4 + n_wg) the published workgroups in order, [4 + n_wg .. 4 + 2 n_wg) their done flags; all zero between launches
     int32_t *rayq;
+    StartPool<T> *pool;           // [1] the start pool's record (k = 0: none); read only where an episode restarts
 };
 
 template <typename T> struct ColW {
@@ -1469,6 +1485,57 @@ template <typename T> __global__ __launch_bounds__(WAVE) void k_rays(const Model
     else ray_lane(models, b, N, env, ray, live, threadIdx.x, (KS_LDS T*)pub, (KS_LDS unsigned*)stk);
 }
 
+// The start pool's draw (include/kinova_sim.h, ks_set_start_pool): entry of `env` for its episode number `episode`.
+__device__ __forceinline__ int start_pool_index(uint64_t seed, uint64_t episode, int env, int k) {
+    uint32_t r[4];
+    krsel::philox4x32((uint32_t)env, (uint32_t)episode, (uint32_t)(episode >> 32), 0x5350u, (uint32_t)seed, (uint32_t)(seed >> 32), r);
+    return (int)(((uint64_t)r[0] * (uint64_t)(uint32_t)k) >> 32);
+}
+
+// entry j of the pool -> the env's stored initial state (start configuration, hand orientation, cached observation).  Rolled loops,
+// one value in flight: a handful of registers (this runs once per episode, 102 values)
+template <typename T> __device__ __forceinline__ void start_pool_fetch(const StartPool<T>& p, int j, int env, int N) {
+    const T* sq = p.qpos0 + (long)j * NQ * N + env;
+    T* dq = p.env_qpos0 + env;
+#pragma clang loop unroll(disable)
+    for (int i = 0; i < NQ; i++) dq[(long)i * N] = sq[(long)i * N];
+    const T* sh = p.hand_quat + (long)j * 4 * N + env;
+    T* dh = p.env_hand_quat + env;
+#pragma clang loop unroll(disable)
+    for (int i = 0; i < 4; i++) dh[(long)i * N] = sh[(long)i * N];
+    const T* so = p.obs0 + ((long)j * N + env) * NOBS;
+    T* dob = p.env_obs0 + (long)env * NOBS;
+#pragma clang loop unroll(disable)
+    for (int i = 0; i < NOBS; i++) dob[i] = so[i];
+}
+
+// An episode of `env` restarts (obs_finish): with a pool, count the episode, draw its entry and make it the env's stored initial
+// state - the restart itself then runs as it always did.  Out of line: ONE copy per precision whose registers are its own; the
+// stepping kernels' budgets (amdgpu_num_vgpr) stay what they are.  Without a pool: one load and back.
+template <typename T> __device__ __noinline__ void start_pool_restart(const StartPool<T>* pool, int env, int N) {
+    if (pool->k <= 0) return;
+    const StartPool<T> p = *pool;
+    const int64_t ep = p.episode[env] + 1;
+    p.episode[env] = ep;
+    const int j = start_pool_index(p.seed, (uint64_t)ep, env, p.k);
+    p.index[env] = j;
+    start_pool_fetch(p, j, env, N);
+}
+
+// ks_set_start_pool's last step before the reset pass: the pool's record (thread 0), every env at episode 0 with its draw as the
+// stored initial state, flagged for k_reset / k_rays / k_obs.  k_pool_clear: back to no pool.
+template <typename T> __global__ void k_pool_begin(Buffers<T> b, StartPool<T> p, int N) {
+    const int env = blockIdx.x * blockDim.x + threadIdx.x;
+    if (env == 0) *b.pool = p;
+    if (env >= N) return;
+    p.episode[env] = 0;
+    const int j = start_pool_index(p.seed, 0, env, p.k);
+    p.index[env] = j;
+    start_pool_fetch(p, j, env, N);
+    b.flag[env] = 1;
+}
+template <typename T> __global__ void k_pool_clear(Buffers<T> b) { b.pool->k = 0; }
+
 // phase 1 (part = -1: all of it; 0..3: that quarter of the slots, see build_obs): the observation, straight to its destination
 template <typename T, typename SnapT>
 __device__ __forceinline__ void obs_write(const Model<T>& m, const Buffers<T>& b, int env, int N, int mode, const ObsOut<T>& o, SnapT snap,
@@ -1510,6 +1577,8 @@ __device__ __forceinline__ void obs_finish(const Model<T>& m, const Buffers<T>& 
         if (o.info) { o.info[env] = T(0); o.info[(long)N + env] = T(0); o.info[2L * N + env] = rew; }
     }
     if (restart) {
+        // with a start pool (ks_set_start_pool) the next episode's start is drawn here: its entry becomes the stored initial state
+        start_pool_restart(b.pool, env, N);
         if (o.obs) {
             for (int j = 0; j < NOBS; j++) o.obs[base + j * stride] = b.obs0[(long)env * NOBS + j];
         }
@@ -1793,6 +1862,8 @@ struct CtxBase {
     virtual int kernel_time(int reset, double* avg_ms, int64_t* launches) = 0;
     virtual int rollout(int n_iter, const ks_rollout_args* args, hipStream_t s) = 0;
     virtual int rollout_plan(int32_t* mode, int32_t* groups, int32_t* workgroups) = 0;
+    virtual int set_start_pool(int k, const void* q0, const void* hq, uint64_t seed, void* obs, hipStream_t s) = 0;
+    virtual int get_start_index(int32_t* index, int64_t* episode, hipStream_t s) = 0;
 };
 
 #define HIPCHK(expr)                                                                         \
@@ -1833,6 +1904,16 @@ template <typename T> struct Ctx : CtxBase {
         return cap != hipStreamCaptureStatusNone;
     }
     Model<T>* d_model = nullptr;          // [n_models] model table
+    // the start pool (ks_set_start_pool): its storage ([k][16][N] + [k][4][N] + [k][N][82] values, grown on demand, kept until the
+    // context goes), the per-env counters, and the buffers the pool's observations are prepared in - a second set of the reset pass's
+    // state / snapshot / ray buffers, so that preparing a pool touches nothing an env lives in
+    static constexpr int POOL_K_MAX = 1024, POOL_VALUES = NQ + 4 + NOBS;
+    int pool_k = 0;
+    T* pool_store = nullptr;
+    size_t pool_cap = 0;                  // entries per env the storage holds
+    int64_t* pool_episode = nullptr;
+    int32_t* pool_index = nullptr;
+    Buffers<T> pb{};                      // b with the reset pass's outputs redirected (pb.snap != nullptr once allocated)
     int n_models = 0, n_wg = 0;
     int32_t n_groups = 0;                 // groups of the slot list that hold envs (<= n_wg): what ks_rollout deals
     std::map<std::pair<size_t, uint64_t>, void*> shared;      // uploaded arrays by (bytes, content hash): the hand's meshes are
@@ -1875,12 +1956,16 @@ template <typename T> struct Ctx : CtxBase {
         if ((r = alloc(&b.step_count, N))) return r;
         if ((r = alloc(&b.flag, N))) return r;
         if ((r = alloc(&b.obj_id, N))) return r;
+        if ((r = alloc(&b.pool, (size_t)1))) return r;          // zeroed: k = 0, no pool
+        if ((r = alloc(&pool_episode, N))) return r;
+        if ((r = alloc(&pool_index, N))) return r;
         ev0.resize(NEV); ev1.resize(NEV);
         for (int i = 0; i < NEV; i++) { HIPCHK(hipEventCreate(&ev0[i])); HIPCHK(hipEventCreate(&ev1[i])); }
         return KS_OK;
     }
     ~Ctx() override {
         for (void* p : allocs) (void)hipFree(p);
+        if (pool_store) (void)hipFree(pool_store);
         if (h_out) (void)hipHostFree(h_out);
         if (h_ra) (void)hipHostFree(h_ra);
         if (d_ra) (void)hipFree(d_ra);
@@ -2055,6 +2140,11 @@ template <typename T> struct Ctx : CtxBase {
         if (n <= 0 || n > cfg.n_envs || !q0 || !hq || (!ids && n != cfg.n_envs)) { error = "ks_reset: bad arguments"; return KS_ERR_INVALID; }
         hipLaunchKernelGGL((k_store_init<T>), dim3((n + 255) / 256), dim3(256), 0, s, b, ids, n, (const T*)q0, (const T*)hq, object_id,
                            (const T*)mass_friction, n_models, cfg.n_envs);
+        // a pool entry is a start of the object the env held when the pool was set: a call that (re)assigns objects ends the pool
+        if (object_id && pool_k > 0) {
+            hipLaunchKernelGGL((k_pool_clear<T>), dim3(1), dim3(1), 0, s, b);
+            pool_k = 0;
+        }
         // objects changed: regroup the stepping kernel's work list by object
         if (object_id && n_models > 1)
         {
@@ -2235,6 +2325,77 @@ template <typename T> struct Ctx : CtxBase {
         if (workgroups) *workgroups = n_groups < resident_wgs ? n_groups : resident_wgs;
         return KS_OK;
     }
+    int set_start_pool(int k, const void* q0, const void* hq, uint64_t seed, void* obs, hipStream_t s) override {
+        if (!model_loaded) { error = "ks_set_start_pool before ks_load_model"; return KS_ERR_STATE; }
+        if (k == 0) {                                           // no pool: auto-resets return to the stored initial state again
+            if (pool_k > 0) hipLaunchKernelGGL((k_pool_clear<T>), dim3(1), dim3(1), 0, s, b);
+            pool_k = 0;
+            HIPCHK(hipGetLastError());
+            return KS_OK;
+        }
+        if (k < 1 || k > POOL_K_MAX || !q0 || !hq) { error = "ks_set_start_pool: 1 <= k <= 1024 starts per env (0 clears the pool), qpos0 and hand_quat required"; return KS_ERR_INVALID; }
+        const size_t N = cfg.n_envs;
+        int r;
+        if (!pb.snap) {
+            Buffers<T> t = b;
+            if ((r = alloc(&t.qpos, NQ * N))) return r;
+            if ((r = alloc(&t.qvel, NV * N))) return r;
+            if ((r = alloc(&t.warm, NV * N))) return r;
+            if ((r = alloc(&t.rays, NRAY * N))) return r;
+            if ((r = alloc(&t.ncon, N))) return r;
+            if ((r = alloc(&t.step_count, N))) return r;
+            if ((r = alloc(&t.flag, N))) return r;
+            if ((r = alloc(&t.snap, SNAP_TOTAL * N))) return r;
+            pb = t;
+        }
+        if ((size_t)k > pool_cap) {
+            // (hipFree waits for the device: nothing that is still running reads the storage it gives back)
+            if (pool_store) { (void)hipFree(pool_store); pool_store = nullptr; pool_cap = 0; }
+            const size_t bytes = (size_t)k * N * POOL_VALUES * sizeof(T);
+            if (hipMalloc((void**)&pool_store, bytes) != hipSuccess) {
+                (void)hipGetLastError();
+                pool_store = nullptr;
+                if (pool_k > 0) hipLaunchKernelGGL((k_pool_clear<T>), dim3(1), dim3(1), 0, s, b);      // (the old pool went with its storage)
+                pool_k = 0;
+                error = "ks_set_start_pool: no device memory for " + std::to_string(k) + " starts x " + std::to_string(N) + " envs x " +
+                        std::to_string(POOL_VALUES) + " values (" + std::to_string(bytes) + " bytes)";
+                return KS_ERR_HIP;
+            }
+            pool_cap = (size_t)k;
+        }
+        T* pq = pool_store;
+        T* ph = pq + (size_t)k * NQ * N;
+        T* po = ph + (size_t)k * 4 * N;
+        HIPCHK(hipMemcpyAsync(pq, q0, (size_t)k * NQ * N * sizeof(T), hipMemcpyDefault, s));
+        HIPCHK(hipMemcpyAsync(ph, hq, (size_t)k * 4 * N * sizeof(T), hipMemcpyDefault, s));
+        // the observation of every entry: the reset pass (k_reset, k_rays, k_obs in mode 1 - ks_reset's kernels, hence its bits) once per
+        // entry, over all envs, reading the entry as the stored initial state and leaving its observation in the pool; state, snapshot
+        // and rays go to the preparation buffers
+        for (int j = 0; j < k; j++) {
+            Buffers<T> e = pb;
+            e.qpos0 = pq + (size_t)j * NQ * N;
+            e.hand_quat = ph + (size_t)j * 4 * N;
+            e.obs0 = po + (size_t)j * N * NOBS;
+            HIPCHK(hipMemsetAsync(e.flag, 1, N, s));
+            hipLaunchKernelGGL((k_reset<T, USE_LDS>), dim3(blocks()), dim3(WAVE), 0, s, d_model, e, (int)N, 0);
+            hipLaunchKernelGGL((k_rays<T>), dim3(((int)N + RAY_ENVS - 1) / RAY_ENVS, NRAY), dim3(WAVE), 0, s, d_model, e, (int)N, 1);
+            hipLaunchKernelGGL((k_obs<T>), dim3(blocks()), dim3(WAVE), 0, s, d_model, e, (int)N, 1,
+                               ObsOut<T>{nullptr, nullptr, nullptr, nullptr, nullptr, cfg.horizon, cfg.auto_reset, cfg.obs_env_major});
+        }
+        HIPCHK(hipGetLastError());
+        // ... and every env to its draw for episode 0
+        const StartPool<T> rec{k, 0, seed, pq, ph, po, b.qpos0, b.hand_quat, b.obs0, pool_episode, pool_index};
+        hipLaunchKernelGGL((k_pool_begin<T>), dim3(((int)N + 255) / 256), dim3(256), 0, s, b, rec, (int)N);
+        pool_k = k;
+        return post_reset(obs, s);
+    }
+    int get_start_index(int32_t* index, int64_t* episode, hipStream_t s) override {
+        if (pool_k <= 0) { error = "ks_get_start_index: the context holds no start pool (ks_set_start_pool)"; return KS_ERR_STATE; }
+        const size_t N = cfg.n_envs;
+        if (index) HIPCHK(hipMemcpyAsync(index, pool_index, N * sizeof(int32_t), hipMemcpyDefault, s));
+        if (episode) HIPCHK(hipMemcpyAsync(episode, pool_episode, N * sizeof(int64_t), hipMemcpyDefault, s));
+        return KS_OK;
+    }
     int substep(const void* ctrl, hipStream_t s) override {
         if (!model_loaded) { error = "ks_substep before ks_load_model"; return KS_ERR_STATE; }
         hipLaunchKernelGGL((k_substep<T, USE_LDS>), dim3(n_wg), dim3(WG), step_lds, s, d_model, b, (const T*)ctrl, cfg.n_envs,
@@ -2389,6 +2550,14 @@ int ks_rollout(ks_ctx* ctx, int32_t n_iter, const ks_rollout_args* args_host, vo
 int ks_rollout_plan(ks_ctx* ctx, int32_t* mode, int32_t* groups, int32_t* workgroups) {
     if (!ctx) return KS_ERR_INVALID;
     return ctx->impl->rollout_plan(mode, groups, workgroups);
+}
+int ks_set_start_pool(ks_ctx* ctx, int32_t k, const void* qpos0, const void* hand_quat, uint64_t seed, void* obs, void* stream) {
+    if (!ctx) return KS_ERR_INVALID;
+    return ctx->impl->set_start_pool(k, qpos0, hand_quat, seed, obs, (hipStream_t)stream);
+}
+int ks_get_start_index(ks_ctx* ctx, int32_t* index, int64_t* episode, void* stream) {
+    if (!ctx) return KS_ERR_INVALID;
+    return ctx->impl->get_start_index(index, episode, (hipStream_t)stream);
 }
 int ks_substep(ks_ctx* ctx, const void* ctrl, void* stream) {
     if (!ctx) return KS_ERR_INVALID;

@@ -95,7 +95,7 @@ def policy_basename(policy_dir) -> str:
 
 
 def run_stage(plan, policy, n_envs: int = 1024, rounds: int = 10, updates_per_round: int = 100, expert_prob: float = 0.3, seed: int = 2,
-              device: int = 0, load_previous: bool = True, save: bool = True, eval_envs: int | None = None):
+              device: int = 0, load_previous: bool = True, save: bool = True, eval_envs: int | None = None, starts_per_env: int = 0):
     """One stage of the curriculum on the GPU simulator (the batched counterpart of rl_experiment + train_policy,
     main_DDPGfD.py:600-621, 776-800): start from the previous stage's policy and agent replay, mix in the expert
     replay of the stage's shapes at `expert_prob` (DDPGfD.py:232-254), train, evaluate, save policy + replay + info.
@@ -106,7 +106,12 @@ def run_stage(plan, policy, n_envs: int = 1024, rounds: int = 10, updates_per_ro
     Every shape key of the reference's stages has a compiled asset since round 4 - the multi-geom Bottle / Bowl / TBottle / RBowl
     objects included (a stage that holds one runs on libkinova_sim_mg.so, sim.KinovaSim picks it) -; a key without one would be
     listed under `skipped_shapes`.  Where the reference has no start-coordinate file for a (shape, orientation) - Normal/BowlS - the
-    start is drawn by the reference's empty-file rule (scenarios.fallback_start).  Returns a dict (num_success, num_total, paths, ...)."""
+    start is drawn by the reference's empty-file rule (scenarios.fallback_start).
+    starts_per_env = K > 0: the stage runs an AUTO-RESET simulator whose envs each hold a pool of K starts drawn by the same rules
+    (scenarios.draw_start_pool) and take one of them at every episode inside the stepping kernel (ks_set_start_pool): no host reset
+    between rounds - a round is then 30 env-steps of every env, whose episodes end and restart on their own -, and `distinct_starts`
+    in the result counts the (env, start) pairs that were run.  0: the host reset per round, as before (same draws from the same rng).
+    Returns a dict (num_success, num_total, paths, ...)."""
     import torch
 
     from .evaluate import eval_policy
@@ -124,7 +129,7 @@ def run_stage(plan, policy, n_envs: int = 1024, rounds: int = 10, updates_per_ro
     dev = torch.device("cuda", device)
     if load_previous:
         policy.load(str(dirs["prev_policy_dir"] / policy_basename(dirs["prev_policy_dir"])))
-    sim = MultiShapeSim(n_envs, shapes, device=device, auto_reset=False, horizon=30)
+    sim = MultiShapeSim(n_envs, shapes, device=device, auto_reset=starts_per_env > 0, horizon=30)
     replay = DeviceEpisodeReplay(n_envs, capacity=max(4 * n_envs, 1024), horizon=30, device=dev)
     if load_previous and dirs["prev_replay_dir"].is_dir():
         replay.load(dirs["prev_replay_dir"])
@@ -162,10 +167,20 @@ def run_stage(plan, policy, n_envs: int = 1024, rounds: int = 10, updates_per_ro
     native = NativeDDPGfDUpdate(policy)
     mix = expert is not None and expert.count >= 2
     losses = []
+    seen = None
+    if starts_per_env > 0:
+        shape_ids = sim.shape_of_env.cpu().numpy()
+        qp, hqp, _ = scenarios.draw_start_pool([sim.shapes[i] for i in shape_ids], plan["requested_orientation"], starts_per_env, rng)
+        eng.start(sim.set_start_pool(torch.as_tensor(qp), torch.as_tensor(hqp), seed=seed))
+        seen = torch.zeros(n_envs, starts_per_env, dtype=torch.bool, device=dev)      # (env, start) pairs that were run
+        all_envs = torch.arange(n_envs, device=dev)
     for r in range(rounds):
-        obs0, _ = reset_all(sim, n_envs)
-        eng.start(obs0)
+        if starts_per_env <= 0:
+            obs0, _ = reset_all(sim, n_envs)
+            eng.start(obs0)
         for t in range(30):
+            if seen is not None:
+                seen[all_envs, sim.start_index()[0].long()] = True
             eng.step()
         if replay.count >= 2:
             for u in range(updates_per_round):
@@ -176,7 +191,8 @@ def run_stage(plan, policy, n_envs: int = 1024, rounds: int = 10, updates_per_ro
     obs0, classes = reset_all(sim, n_envs)
     res = eval_policy(sim, policy, obs0, horizon=30, orientation=plan["requested_orientation"])
     out = {"expert_episodes": 0 if expert is None else int(expert.count), "num_success": res["num_success"], "num_total": n_envs, "avg_reward": res["avg_reward"], "skipped_shapes": skipped, "shapes": shapes,
-           "updates": len(losses), "orientation_counts": {c: classes.count(c) for c in sorted(set(classes))}}
+           "updates": len(losses),
+           "distinct_starts": n_envs * rounds if seen is None else int(seen.sum()), "orientation_counts": {c: classes.count(c) for c in sorted(set(classes))}}
     if save:
         for k in ("policy_dir", "replay_dir", "output_dir"):
             Path(dirs[k]).mkdir(parents=True, exist_ok=True)

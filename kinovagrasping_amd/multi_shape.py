@@ -30,10 +30,22 @@ class MultiShapeSim(KinovaSim):
             object_id = np.repeat(np.arange(k), counts)
         self.shape_of_env = torch.as_tensor(np.asarray(object_id), dtype=torch.int32, device=self.device)
         self._mass_friction = None
+        self._pool_set = False
+
+    def set_start_pool(self, qpos0, hand_quat=None, seed: int = 0):
+        """KinovaSim.set_start_pool; entry j of env e is a start of the object env e holds NOW (scenarios.draw_start_pool(self.shapes[...]))
+        - a later reset that passes object ids ends the pool (ks_reset_objects)."""
+        obs = super().set_start_pool(qpos0, hand_quat, seed)
+        self._pool_set = obs is not None
+        return obs
 
     def reset(self, qpos0: torch.Tensor, hand_quat: torch.Tensor, env_ids=None, object_id=None, mass_friction=None):
         """All envs (or env_ids): object ids default to the env's current shape; mass_friction [2, n] defaults to what
         set_env_params stored (else every object's compiled values)."""
+        if object_id is None and self._pool_set and mass_friction is None and self._mass_friction is None:
+            # objects stay and a start pool is set: the plain ks_reset, which keeps the pool (the envs run this start until their next auto-reset)
+            return super().reset(qpos0, hand_quat, env_ids)
+        self._pool_set = False
         if object_id is None:
             object_id = self.shape_of_env if env_ids is None else self.shape_of_env[torch.as_tensor(env_ids).long()]
         else:

@@ -246,6 +246,65 @@ def select_orientation(shape: str, hand_orientation: str, rng=np.random) -> str:
     return "rotated"
 
 
+def select_orientations(shape: str, hand_orientation: str, count: int, rng=np.random) -> np.ndarray:
+    """`count` draws of select_orientation for one shape at once (the same thresholds and per-shape rules, array draws): class names [count].
+    A class name ('normal' / 'rotated' / 'top') is taken as is, anything but 'random' gives 'normal' (as select_orientation does)."""
+    if hand_orientation in ORIENTATION_EULER:
+        return np.full(count, hand_orientation, dtype="<U7")
+    t = np.full(count, 0.330)
+    if hand_orientation == "random":
+        if "RBowl" in shape:
+            t = rng.uniform(0.333, 1, count)
+        elif "Lemon" in shape:
+            c1, c2 = rng.uniform(0, 0.333, count), rng.uniform(0.667, 1, count)
+            t = np.where(rng.randint(0, 2, count) == 0, c1, c2)
+        else:
+            t = rng.uniform(0.0, 1.0, count)
+    return np.where(t < 0.333, "normal", np.where(t > 0.667, "top", "rotated")).astype("<U7")
+
+
+def draw_start_pool(shapes_of_env, orientation, k: int, rng, mode: str = "train", hand_offsets: str = "fresh-env"):
+    """K prepared starts for every env of a batch (sim.KinovaSim.set_start_pool), drawn by the rules `KinovaGripperVecEnv.reset(with_noise=False)`
+    and `curriculum.run_stage` apply per env and episode: the orientation class by select_orientation's rule for the env's shape
+    (`orientation` = 'random', or a class name taken as is), the object at a random row of that class's no-noise coordinate table of the
+    shape - where the reference has no such file (Normal/BowlS) by its empty-file rule, fallback_start -, moved by the reset's 5 cm body
+    correction (reset_body_position), the class's hand quaternion (hand_quat_for) and slide offsets (hand_slide_offsets, `hand_offsets`).
+    Vectorised: one pass per (shape, class) over all its (entry, env) cells, array draws from `rng` (np.random.RandomState or the module).
+    shapes_of_env: the shape name of every env [N].  Returns qpos0 [K, 16, N], hand_quat [K, 4, N], classes [K, N] (names)."""
+    names = np.asarray([shapes_of_env] if isinstance(shapes_of_env, str) else list(shapes_of_env))
+    n = len(names)
+    if k < 1 or n < 1:
+        raise ValueError("draw_start_pool: k >= 1 starts for >= 1 envs")
+    q = np.zeros((k, 16, n))
+    hq = np.zeros((k, 4, n))
+    q[:, 12] = 1.0
+    classes = np.empty((k, n), dtype="<U7")
+    for shape in sorted(set(names.tolist())):
+        envs = np.nonzero(names == shape)[0]
+        cls = select_orientations(shape, orientation, k * len(envs), rng).reshape(k, len(envs))
+        classes[:, envs] = cls
+        for o in ORIENTATION_EULER:
+            jj, ee = np.nonzero(cls == o)
+            if not len(jj):
+                continue
+            if has_start_table(shape, o, mode):
+                tab = start_coord_table(shape, o, mode)
+                xyz = tab[rng.randint(0, len(tab), len(jj))]
+            else:                                        # fallback_start's rule, array draws
+                from .model_compiler import read_blob
+                so = read_blob(ASSETS / f"{shape}.ksm")["obj_size_obs"]
+                xyz = np.zeros((len(jj), 3))
+                if o != "rotated":
+                    theta, r = rng.uniform(0, 2 * np.pi, len(jj)), rng.uniform(0, so[0] / 2, len(jj))
+                    xyz[:, 0], xyz[:, 1] = np.sin(theta) * r, np.cos(theta) * r
+                xyz[:, 2] = so[2] / 2.0 / 2
+            cols = envs[ee]
+            q[jj, 9:12, cols] = reset_body_position(shape, xyz)
+            q[jj, 0:3, cols] = hand_slide_offsets(o, shape, hand_offsets)
+            hq[jj, :, cols] = hand_quat_for(o)
+    return q, hq, classes
+
+
 def config5_env_params(n_envs: int, seed: int = 5):
     """BASELINE config 5 domain randomisation: object mass ~ U[0.05, 0.15] kg and finger-object
     friction ~ U[0.5, 1.0] per env, Generator(PCG64(seed)); returns (mass [N], mu [N]) float64."""

@@ -46,7 +46,8 @@ class KsRolloutArgs(C.Structure):
 
 
 EXPORTS = ["ks_default_config", "ks_create", "ks_destroy", "ks_last_error", "ks_load_model", "ks_load_models", "ks_reset", "ks_reset_objects", "ks_step",
-           "ks_get_state", "ks_set_state", "ks_set_env_params", "ks_substep", "ks_rollout", "ks_rollout_plan", "ks_obs_from_snapshot", "ks_kernel_time", "ks_version"]
+           "ks_get_state", "ks_set_state", "ks_set_env_params", "ks_substep", "ks_rollout", "ks_rollout_plan", "ks_obs_from_snapshot", "ks_kernel_time", "ks_version",
+           "ks_set_start_pool", "ks_get_start_index"]
 # include/kinova_rollout.h
 ROLLOUT_EXPORTS = ["kr_select_action", "kr_store_transition", "kr_rank_episodes", "kr_wait_min", "kr_wait_min_counted", "kr_commit_episodes", "kr_advance_ring",
                    "kr_sample_windows", "kr_sample_windows_draw", "kr_sample_windows_mixed", "kr_xchg_create", "kr_xchg_connect", "kr_xchg_allreduce_mean", "kr_xchg_status",
@@ -115,6 +116,8 @@ def _bind(L):
     L.ks_obs_from_snapshot.argtypes = [vp] * 8
     L.ks_kernel_time.argtypes = [vp, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
     L.ks_rollout_plan.argtypes = [vp, i32p, i32p, i32p]
+    L.ks_set_start_pool.argtypes = [vp, C.c_int32, vp, vp, C.c_uint64, vp, vp]
+    L.ks_get_start_index.argtypes = [vp, vp, vp, vp]
     i32, f32 = C.c_int32, C.c_float
     L.kr_select_action.argtypes = [i32] + [vp] * 7 + [f32, f32, i32] + [vp] * 4
     L.kr_store_transition.argtypes = [i32] * 5 + [vp] * 21
@@ -235,6 +238,30 @@ class KinovaSim:
         self._check(self.lib.ks_reset_objects(self.ctx, _ptr(ids), n, _ptr(qpos0), _ptr(hand_quat), _ptr(oid), _ptr(mf), _ptr(self.obs), self._stream()))
         self._keep = (qpos0, hand_quat, ids, oid, mf)
         return self.obs
+
+    def set_start_pool(self, qpos0: torch.Tensor | None, hand_quat: torch.Tensor | None = None, seed: int = 0):
+        """K prepared starts per env - qpos0 [K, 16, N], hand_quat [K, 4, N] - one of which every auto-reset of the env draws inside the
+        stepping kernels (ks_set_start_pool; the draw: include/kinova_sim.h).  Resets every env to its draw for episode 0 and returns the
+        obs buffer.  qpos0 None (or K = 0) clears the pool: auto-resets return to the stored initial state again (no reset, returns None)."""
+        if qpos0 is None or qpos0.shape[0] == 0:
+            self._check(self.lib.ks_set_start_pool(self.ctx, 0, None, None, 0, None, self._stream()))
+            return None
+        qpos0 = qpos0.to(self.device, self.dtype).contiguous()
+        hand_quat = hand_quat.to(self.device, self.dtype).contiguous()
+        k = qpos0.shape[0]
+        if tuple(qpos0.shape) != (k, NQ, self.n_envs) or tuple(hand_quat.shape) != (k, 4, self.n_envs):
+            raise ValueError("set_start_pool: qpos0 [K, 16, N], hand_quat [K, 4, N]")
+        self._check(self.lib.ks_set_start_pool(self.ctx, k, _ptr(qpos0), _ptr(hand_quat), int(seed) & (2 ** 64 - 1), _ptr(self.obs), self._stream()))
+        self._keep_pool = (qpos0, hand_quat)
+        return self.obs
+
+    def start_index(self):
+        """(index int32 [N], episode int64 [N]): the pool entry every env's running episode started from, and the env's auto-resets since
+        the pool was set (ks_get_start_index).  Raises without a pool."""
+        index = torch.empty(self.n_envs, dtype=torch.int32, device=self.device)
+        episode = torch.empty(self.n_envs, dtype=torch.int64, device=self.device)
+        self._check(self.lib.ks_get_start_index(self.ctx, _ptr(index), _ptr(episode), self._stream()))
+        return index, episode
 
     def step(self, action: torch.Tensor):
         """action [4, N].  Returns (obs, reward, done, info) views of the context's output buffers."""

@@ -308,6 +308,28 @@ class KinovaGripperVecEnv:
                              mass_friction=obj_params if (obj_params is not None and not isinstance(obj_params, (list, tuple))) else None)
         return obs
 
+    def set_start_pool(self, k: int, hand_orientation="normal", seed: int = 0, mode="train"):
+        """Give every env K prepared starts of its current object, one of which each AUTO-RESET draws inside the stepping kernels
+        (KinovaSim.set_start_pool) - so that an env on the fast paths, which never come back to the host between episodes, sees new starts
+        as the reference's reset() gives them: orientation class by select_orienation's rule (`hand_orientation` = "random", or a class
+        name), a row of that class's no-noise coordinate table (with_noise=False's start states), this env's `hand_offsets`.  The starts are
+        drawn from the env's np_random (scenarios.draw_start_pool), `seed` keys the in-kernel choice among them.  Resets all envs to their
+        draw for episode 0 and returns the observations; k = 0 clears the pool.  `start_pool` keeps (qpos0, hand_quat, classes);
+        sim.start_index() says which entry an env is running."""
+        if k == 0:
+            self.start_pool = None
+            return self.sim.set_start_pool(None)
+        names = self.random_shape if isinstance(self.random_shape, list) else [self.random_shape] * self.n_envs
+        q, hq, classes = scenarios.draw_start_pool(names, hand_orientation, k, self.np_random, mode, self.hand_offsets)
+        self.with_noise, self.mode, self.start_pool = False, mode, (q, hq, classes)
+        obs = self.sim.set_start_pool(torch.as_tensor(q), torch.as_tensor(hq), seed)
+        idx = self.sim.start_index()[0].cpu().numpy()
+        e = np.arange(self.n_envs)
+        self.hand_quat = hq[idx, :, e].T.copy()
+        self.orientation = classes[idx, e].tolist()
+        self.orientation_idx[:] = -1
+        return obs
+
     # -- step -------------------------------------------------------------------------------------
     def step(self, action, graspnetwork=False):
         """action: [N,4] (wrist, finger1..3) torch tensor or array.  Returns (obs [N,82], reward [N],
