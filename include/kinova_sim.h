@@ -110,8 +110,11 @@ int ks_reset(ks_ctx *ctx, const int32_t *env_ids, int32_t n, const void *qpos0, 
 
 /* ks_reset that also chooses every reset env's object and (optionally) its randomised parameters - the reference's
  * reset(): select_object (ENV:986-1005) + select_orienation (ENV:1180-1222) + _set_state (ENV:692-703).
+ * env_ids must not name an env twice in one call (each entry is stored by its own thread: which of two would win is not defined).
  * object_id: device int32 [n], index into the blobs of ks_load_models, or NULL (objects stay);
  * A call with object_id CLEARS the context's start pool (ks_set_start_pool): a pool entry is a start of the object the env held.
+ * An env whose object CHANGES also forgets what its lanes remember of its hull pairs' last queries (the pair memory of fp32 contexts names vertices of
+ * the object it held) and continues like an env of a new context of its new object.
  * mass_friction: device [2, n] (row 0 object mass in kg - the inertia scales with it -, row 1 friction of the seven
  * object-hand pairs), or NULL: an env whose object is (re)assigned takes that object's compiled mass / friction, other
  * envs keep theirs.  (Mass / friction randomisation is an extension: the reference fixes 0.1 kg, XML:153, and mu 1,

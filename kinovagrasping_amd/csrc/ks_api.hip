@@ -627,7 +627,9 @@ __device__ __forceinline__ void env_step_body(const Model<T>* __restrict__ model
         // Pair memory: what this lane remembers of its hull pairs' narrow-phase queries (GJK simplex, MPR portal: vertex ids)
         // lives in registers across the substeps and comes back from the previous launch, so the first substep of an
         // env-step starts as warm as the other fourteen (a cold GJK is ~10 iterations, a warm one 1-2: the first substep
-        // used to cost as much as five of the others).  A stale memory (after a reset) is still a valid start: any ids are.
+        // used to cost as much as five of the others).  A stale memory of the SAME object (after a reset or ks_set_state) is still a valid
+        // start: any vertex ids of the pair's own hulls are.  Ids of another object's hulls are not - they may lie beyond the new tables -
+        // so ks_reset_objects clears the block of every env whose object it changes (k_store_init).
         constexpr int WPL = (NPAIR_MAX + SUBS - 1) / SUBS;              // pairs per lane
         PairWarm gw[WPL];
         unsigned* pm = b.pairmem + ((long)env * SUBS + team.sub) * (WPL * WARM_WORDS);
@@ -1326,6 +1328,14 @@ __global__ void k_store_init(Buffers<T> b, const int32_t* __restrict__ env_ids, 
     if (object_id) {
         int o = object_id[i];
         o = o < 0 ? 0 : (o >= n_models ? n_models - 1 : o);
+        // The env's pair memory names vertices of the object it held: gjk_distance rebuilds the remembered simplex from those ids without
+        // a range check, and another object's hull may have fewer vertices.  Cleared, the env starts like a fresh context of its new object
+        // (an env that keeps its object keeps its memory, as after ks_reset: ids of the pair's own hulls are always a valid start).
+        if (b.pairmem && o != b.obj_id[env]) {
+            constexpr int ENV_WARM_WORDS = SUBS * ((NPAIR_MAX + SUBS - 1) / SUBS) * WARM_WORDS;
+            unsigned* pm = b.pairmem + (long)env * ENV_WARM_WORDS;
+            for (int k = 0; k < ENV_WARM_WORDS; k++) pm[k] = 0u;
+        }
         b.obj_id[env] = o;
         if (!mass_friction) { b.envp[env] = b.nominal[2 * o]; b.envp[(long)N + env] = b.nominal[2 * o + 1]; }   // the new object's own mass / friction
     }

@@ -1695,6 +1695,9 @@ template <typename T> KS_HD void gjk_remember(PairWarm* ws, const Simplex<T>& S)
     ws->w[1] = pack3(S.ib[0], S.ib[1], S.ib[2], 0);
 }
 
+#if defined(KS_GJK_COUNT_IDS) && !defined(__HIP_DEVICE_COMPILE__)
+inline long ks_gjk_ids_out_of_range = 0;
+#endif
 template <typename T, typename TV> KS_NARROW int gjk_distance(PairGeo<T, TV>& g, T margin, T* dist, T* normal, T* pos, PairWarm* ws = nullptr) {
     Simplex<T> S;
     T lam[4] = {1, 0, 0, 0}, v[3], d[3];
@@ -1726,6 +1729,12 @@ template <typename T, typename TV> KS_NARROW int gjk_distance(PairGeo<T, TV>& g,
         for (int i = 0; i < 3; i++) {
             if (i < S.n) {
                 S.ia[i] = wia[i]; S.ib[i] = wib[i];
+#if defined(KS_GJK_COUNT_IDS) && !defined(__HIP_DEVICE_COMPILE__)
+                // tests/native/ks_lanecheck.cpp only: remembered ids beyond the pair's own tables are counted and replaced by vertex 0,
+                // so that the host lane documents a stale memory of another object without reading out of range itself
+                if (S.ia[i] >= g.n1) { ks_gjk_ids_out_of_range++; S.ia[i] = 0; }
+                if (S.ib[i] >= g.n2) { ks_gjk_ids_out_of_range++; S.ib[i] = 0; }
+#endif
                 hull_point(g.R1, g.p1, g.V1, S.ia[i], S.a[i]);
                 hull_point(g.R2, g.p2, g.V2, S.ib[i], S.b[i]);
                 minkowski_point_ids(g, S.ia[i], S.ib[i], S.a[i], S.b[i], S.y[i]);

@@ -270,6 +270,17 @@ int lc_reset_obs(void* h, int prec, double* qpos, double* qvel, double* warm, co
                       : env_step_t<float>(l->f.m, qpos, qvel, warm, hq, nullptr, 0, 0, obs, reward, done, rays, 1);
 }
 void lc_set_warm(void* h, int on) { LC* l = (LC*)h; l->warm = on != 0; std::memset(l->gw, 0, sizeof l->gw); }
+// the lane's pair memory (NPAIR_MAX x WARM_WORDS words, one PairWarm per hull pair in hull-list order): read it after a query, write it before
+// one - lc_put_warm also switches the memory on - so that a test can hand one pose's (or one OBJECT's) memory to another
+int lc_warm_words() { return NPAIR_MAX * WARM_WORDS; }
+void lc_get_warm(void* h, unsigned* out) { std::memcpy(out, ((LC*)h)->gw, sizeof(PairWarm) * NPAIR_MAX); }
+void lc_put_warm(void* h, const unsigned* in) { LC* l = (LC*)h; l->warm = true; std::memcpy(l->gw, in, sizeof(PairWarm) * NPAIR_MAX); }
+// remembered simplex ids that gjk_distance found beyond the pair's own hull tables since the last call (ks_core.h: KS_GJK_COUNT_IDS, this build only)
+#ifdef KS_GJK_COUNT_IDS
+long lc_gjk_ids_out_of_range() { const long n = ks::ks_gjk_ids_out_of_range; ks::ks_gjk_ids_out_of_range = 0; return n; }
+#else
+long lc_gjk_ids_out_of_range() { return -1; }           // (the study builds of this file do not count)
+#endif
 void lc_set_mixed_variant(int v) { g_mixed_variant = v % 10; g_state_rounding = v / 10; }
 int lc_con_stride() { return CON_STRIDE; }
 int lc_ncon_max() { return NCON_MAX; }

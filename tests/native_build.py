@@ -17,7 +17,7 @@ def lanecheck_lib(multi_geom: bool = False):
     so, src = HERE / ("libks_lanecheck_mg.so" if multi_geom else "libks_lanecheck.so"), HERE / "ks_lanecheck.cpp"
     deps = [src] + sorted(CSRC.glob("*.h"))
     if not so.exists() or any(d.stat().st_mtime > so.stat().st_mtime for d in deps):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared"] + (["-DKS_MULTI_GEOM"] if multi_geom else []) + ["-o", str(so), str(src)])
+        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-DKS_GJK_COUNT_IDS"] + (["-DKS_MULTI_GEOM"] if multi_geom else []) + ["-o", str(so), str(src)])
     L = C.CDLL(str(so))
     L.lc_create.restype = C.c_void_p
     L.lc_create.argtypes = [C.c_char_p, C.c_size_t]
@@ -25,6 +25,10 @@ def lanecheck_lib(multi_geom: bool = False):
     L.lc_substep.argtypes = [C.c_void_p, C.c_int, dp, dp, dp, dp, dp, C.c_int, C.POINTER(C.c_int), dp]
     L.lc_env_step.argtypes = [C.c_void_p, C.c_int, dp, dp, dp, dp, dp, C.c_int, C.c_int, dp, dp, C.POINTER(C.c_int), dp]
     L.lc_reset_obs.argtypes = [C.c_void_p, C.c_int, dp, dp, dp, dp, dp, dp, C.POINTER(C.c_int), dp]
+    L.lc_get_warm.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
+    L.lc_put_warm.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
+    L.lc_set_warm.argtypes = [C.c_void_p, C.c_int]
+    L.lc_gjk_ids_out_of_range.restype = C.c_long
     return L
 
 
@@ -62,3 +66,22 @@ class Lane:
         obs, rays, rew, done = np.zeros(82), np.zeros(17), C.c_double(0), C.c_int(0)
         self.L.lc_reset_obs(self.h, self.prec, P(a), P(b), P(c), P(np.array(hq, dtype=np.float64)), P(obs), C.byref(rew), C.byref(done), P(rays))
         return obs, rays
+
+    # ---- pair memory (fp32 lane): what the lane remembers of its hull pairs' last queries (ks_core.h: PairWarm)
+    def set_warm(self, on: bool):
+        """on: remember from one substep() to the next, starting from nothing; off: cold queries"""
+        self.L.lc_set_warm(self.h, int(on))
+
+    def get_warm(self):
+        out = np.zeros(self.L.lc_warm_words(), dtype=np.uint32)
+        self.L.lc_get_warm(self.h, out.ctypes.data_as(C.POINTER(C.c_uint32)))
+        return out
+
+    def put_warm(self, words):
+        w = np.ascontiguousarray(words, dtype=np.uint32)
+        assert w.size == self.L.lc_warm_words()
+        self.L.lc_put_warm(self.h, w.ctypes.data_as(C.POINTER(C.c_uint32)))
+
+    def ids_out_of_range(self):
+        """remembered simplex ids beyond the pair's hull tables that gjk_distance met since the last call (process-wide counter)"""
+        return int(self.L.lc_gjk_ids_out_of_range())
