@@ -12,6 +12,12 @@
      hand by ~5 mm per env-step on average while the fingers close - as in the reference, main_DDPGfD.py:443-446.)
 
     python examples/train_ddpgfd.py --envs 1024 --steps 600 --hidden 256 256 [--free-running] [--expert-prob 0] [--starts-per-env 64]
+                                    [--success-map DIR]
+
+--success-map DIR (with --free-running): the stepping kernel logs every finished training episode (ks_set_episode_log); at every report
+the script folds the log (metrics.EpisodeLedger) and writes DIR/per_shape_success.jsonl and the success / fail start coordinates of the
+report's episodes as DIR/train/<orientation>/*.npy (metrics.save_heatmap_coords), and the periodic noise-free evaluation runs on the
+free-running path as well (evaluate.eval_policy_free_running; its coordinates: DIR/eval).
 
 Measured curves: profiles/r04_training_curves.txt.  One update per env-step of 4096 envs (BASELINE config 3's workload) is 1e4 times fewer
 updates per stored transition than the reference's 100 updates per episode of one env (main_DDPGfD.py:474-476); with the reference's target
@@ -32,10 +38,11 @@ sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
 from kinovagrasping_amd import scenarios                       # noqa: E402
 from kinovagrasping_amd.ddpgfd import DDPGfD                   # noqa: E402
 from kinovagrasping_amd.demonstrators import run_controller_episodes  # noqa: E402
-from kinovagrasping_amd.evaluate import eval_policy            # noqa: E402
+from kinovagrasping_amd.evaluate import eval_policy, eval_policy_free_running  # noqa: E402
+from kinovagrasping_amd.metrics import EpisodeLedger, save_heatmap_coords      # noqa: E402
 from kinovagrasping_amd.replay import DeviceEpisodeReplay      # noqa: E402
 from kinovagrasping_amd.rollout import RolloutEngine           # noqa: E402
-from kinovagrasping_amd.sim import KinovaSim                   # noqa: E402
+from kinovagrasping_amd.sim import EPISODE_LOG_CAPACITY_MAX, KinovaSim      # noqa: E402
 
 
 def start_states(n, shape, rng):
@@ -59,6 +66,8 @@ def main():
     ap.add_argument("--free-running", action="store_true", help="the persistent rollout kernel (ks_rollout) instead of one launch per env-step")
     ap.add_argument("--starts-per-env", type=int, default=0, help="K > 0: every training env holds a pool of K start positions and each of its episodes starts from one "
                     "drawn inside the stepping kernel (ks_set_start_pool); 0: an env replays the one start it was reset to")
+    ap.add_argument("--success-map", default=None, help="with --free-running: keep the in-kernel episode log and write per-shape success and the success / fail "
+                    "heatmap coordinates of the training episodes into this directory at every report; the evaluation runs through ks_rollout too")
     ap.add_argument("--batch-episodes", type=int, default=64, help="episodes per update (x 25 five-step windows each); the reference: 64")
     ap.add_argument("--updates-per-step", type=int, default=1, help="learner updates per env-step of the whole batch of envs")
     ap.add_argument("--actor-lr", type=float, default=1e-4, help="reference: 1e-4 (DDPGfD.py:57)")
@@ -70,6 +79,8 @@ def main():
                     "(tools/r06/reference_learner_on_replay.py runs the REFERENCE's train_batch on it)")
     ap.add_argument("--save", default=None, help="write the trained policy as the reference's 4-file checkpoint with this prefix")
     args = ap.parse_args()
+    if args.success_map and not args.free_running:
+        ap.error("--success-map needs --free-running")
     torch.manual_seed(args.seed)
     rng = np.random.RandomState(args.seed)
     dev = torch.device("cuda", 0)
@@ -94,7 +105,7 @@ def main():
     from kinovagrasping_amd.pipeline import AsyncTrainer, GraphedTrainer
     sim = KinovaSim(n, args.shape, auto_reset=True, horizon=30)
     if args.starts_per_env > 0:
-        qp, hqp, _ = scenarios.draw_start_pool([args.shape] * n, "normal", args.starts_per_env, rng)
+        qp, hqp, pool_classes = scenarios.draw_start_pool([args.shape] * n, "normal", args.starts_per_env, rng)
         print(f"start pool: {args.starts_per_env} starts per env, {qp.shape[0] * n * 102 * 4 / 1e6:.0f} MB on the device")
     else:
         q0, hq = start_states(n, args.shape, rng)
@@ -116,7 +127,14 @@ def main():
         tr.run(36, learn=False)
         tr.flush()
     lifted = episodes = 0
-    sim_eval = KinovaSim(1024, args.shape, auto_reset=False, horizon=30)
+    ledger = None
+    if args.success_map:
+        import json
+        map_dir = Path(args.success_map)
+        map_dir.mkdir(parents=True, exist_ok=True)
+        ledger = EpisodeLedger(n, 1, args.starts_per_env or None)
+        sim.set_episode_log(min(n * 60, EPISODE_LOG_CAPACITY_MAX))           # a report's 60 env-steps: at most one record per env and env-step
+    sim_eval = KinovaSim(1024, args.shape, auto_reset=bool(args.success_map), horizon=30)
     qe, hqe = start_states(1024, args.shape, np.random.RandomState(args.seed + 1))
     qe, hqe = torch.as_tensor(qe), torch.as_tensor(hqe)
     t0 = time.perf_counter()
@@ -128,6 +146,11 @@ def main():
             c = tr.counts()
             d_ep, d_lift = c["episodes_finished"] - episodes, c["lifted"] - lifted
             episodes, lifted = c["episodes_finished"], c["lifted"]
+            if ledger is not None:
+                ledger.add(sim.episode_log())
+                with open(map_dir / "per_shape_success.jsonl", "a") as f:
+                    f.write(json.dumps({"step": it + 60, "episodes": ledger.episodes, "lost": ledger.lost, "per_shape": ledger.per_object([args.shape])}) + "\n")
+                save_heatmap_coords(*ledger.coords(pool_classes if args.starts_per_env > 0 else "normal", clear=True), it + 60, map_dir / "train")
         else:
             d_ep = d_lift = 0
             for _ in range(60):
@@ -142,7 +165,11 @@ def main():
             te = time.perf_counter()
             tr.flush(finish_update=True)                     # the actor the next rollout step would use
             torch.cuda.synchronize()
-            res = eval_policy(sim_eval, policy, sim_eval.reset(qe, hqe))
+            if ledger is not None:
+                res = eval_policy_free_running(sim_eval, policy, obs0=sim_eval.reset(qe, hqe), classes="normal", object_names=[args.shape])
+                save_heatmap_coords(res["success_coords"], res["fail_coords"], it + 60, map_dir / "eval")
+            else:
+                res = eval_policy(sim_eval, policy, sim_eval.reset(qe, hqe))
             ev = f"  eval (no noise, 1024 starts): lift success {res['num_success'] / 1024:.3f}"
             t_eval += time.perf_counter() - te
         print(f"step {it + 60:5d}  episodes {d_ep:7d}  training lift rate {d_lift / max(1, d_ep):.3f}  critic loss {ls[0]:9.3f}  {n * (it + 60) / dt:9.0f} env-steps/s{ev}")

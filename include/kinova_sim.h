@@ -13,6 +13,9 @@
  *                               + sim.forward() + _get_obs()                        ENV:1310-1410, 851-881, 692-703
  *   ks_set_start_pool        <- the NEW start every reset() draws (orientation class, coordinate-table row, hand euler), for the
  *                               resets that happen inside ks_step / ks_rollout                       ENV:1310-1410
+ *   ks_set_episode_log /
+ *   ks_get_episode_log       <- the per-episode outcome eval_policy collects: success / fail start coordinates per orientation,
+ *                               main_DDPGfD.py:130-272, 310-330 - for the episodes that end inside ks_step / ks_rollout
  *   ks_step                  <- KinovaGripper_Env.step: action->ctrl, 15 x sim.step(),
  *                               _get_obs(), _get_reward()                           ENV:1495-1552
  *                               + gym TimeLimit (max_episode_steps)                 gym_kinova_gripper/__init__.py:3-7, main_DDPGfD.py:384
@@ -149,6 +152,48 @@ int ks_set_start_pool(ks_ctx *ctx, int32_t k, const void *qpos0, const void *han
 /* index: int32 [N], the pool entry every env's running episode started from (an env that was ks_reset since: its last draw);
  * episode: int64 [N], its auto-resets since the pool was set.  Either may be NULL.  KS_ERR_STATE without a pool. */
 int ks_get_start_index(ks_ctx *ctx, int32_t *index, int64_t *episode, void *stream);
+
+/* Episode log: one fixed-size record per episode that ENDS and restarts inside the stepping kernels (ks_step and ks_rollout, both
+ * precisions, both libraries) - which env, object and start it was and how it ended; what the four totals of ks_rollout_args.counters
+ * cannot say.  The record is written where the auto-reset happens, just before the next start is drawn (ks_set_start_pool), into a
+ * ring in device memory that the context owns.  32 bytes, 8 little-endian 32-bit words:
+ *   word 0     env          int32  env id
+ *   word 1     object       int32  the env's object (index into the blobs of ks_load_models; 0 in a one-model context)
+ *   word 2     start_index  int32  pool entry the finished episode started from (what ks_get_start_index gave while it ran); -1 without a pool
+ *   word 3     steps        int32  env-steps of the episode
+ *   word 4     done         int32  done bits of its last step (1 lifted, 2 time limit)
+ *   word 5, 6  start_x, _y  float  obs[21], obs[22] of the episode's first observation: the object's start position in the palm frame
+ *                                  (what eval_policy keeps per episode, main_DDPGfD.py:130-272).  fp64 contexts: rounded to float once.
+ *   word 7     episode      int32  ordinal of this episode among the env's logged episodes since the log was set: 0, 1, ...
+ * Every record takes a ticket (a device int64 counter, `written`: records since the log was set, never wraps) and goes to slot
+ * ticket % capacity: the ring overwrites its oldest records, and a reader that knows `written` knows which tickets the slots hold.
+ * Tickets are taken in the order the hardware runs the envs: within one ks_step the order of the envs is not defined, the records of
+ * ONE env are always in ticket order.
+ * ks_set_episode_log: n_envs <= capacity <= KS_EPISODE_LOG_CAPACITY_MAX records (2^24: 512 MB), KS_ERR_INVALID otherwise.  At least one
+ * record per env, so that the records of one LOCK-STEP launch (ks_step: at most one per env) never share a slot.  That guarantee is
+ * ks_step's only: a ks_rollout launch in which the envs finish more than `capacity` episodes wraps the ring while it runs, and a writer
+ * that is held up between taking its ticket and storing its record may then store over, or into, the record of the ticket `capacity`
+ * later.  A ring that wraps inside one free-running launch is best effort; size it for the launch (steps / shortest episode records per
+ * env) where every record counts.  Allocates the ring - grown on demand, kept until ks_destroy; when it
+ * cannot be allocated: KS_ERR_HIP, the message states the size -, zeroes it, `written` and every env's ordinal.  capacity = 0 clears
+ * the log.  KS_ERR_STATE on a context without auto_reset (nothing would ever be written) or before ks_load_model.  No host
+ * synchronisation - except that a call which has to allocate allocates, and waits for the device before it gives a smaller ring back.
+ * Not for stream capture; but the log's descriptor lives in device memory and is written by the stream, so a ks_step / ks_rollout
+ * captured BEFORE the call logs when it is replayed after it.
+ * The log is untouched by ks_reset and ks_reset_objects (an episode that a host reset cuts off is not logged: it did not end), by
+ * ks_set_start_pool (set or cleared) and by budget_ticks launches.  A context that never sets a log computes what it always did.
+ * ks_get_episode_log: device-to-device copies of the whole ring (ring_out: `capacity` records) and of `written` (written_out: device
+ * int64 [1]), asynchronous on `stream`, no host synchronisation; either pointer may be NULL.  KS_ERR_STATE without a log.  Defined for
+ * reads that are stream-ordered after the launches whose episodes they want; reading beside a running launch is not (a slot may be
+ * half written, `written` may be ahead of the slots). */
+#define KS_EPISODE_LOG_CAPACITY_MAX (1 << 24)
+typedef struct {
+    int32_t env, object, start_index, steps, done;
+    float start_x, start_y;
+    int32_t episode;
+} ks_episode_record;
+int ks_set_episode_log(ks_ctx *ctx, int32_t capacity, void *stream);
+int ks_get_episode_log(ks_ctx *ctx, ks_episode_record *ring_out, int64_t *written_out, void *stream);
 
 /* One env.step() for every env.  action: [4, N] (wrist, finger1..3), obs: N x 82, reward: [N],
  * done: uint8 [N] (bit0 lifted, bit1 time limit), info: [3, N] (finger, grasp, lift reward).

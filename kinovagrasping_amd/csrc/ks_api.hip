@@ -13,6 +13,8 @@
 //   k_pool_begin the start pool (ks_set_start_pool): its record, every env at its draw for episode 0; the pool's observations come
 //                from k_reset / k_rays / k_obs run once per entry into buffers of their own; an auto-reset draws the next entry in
 //                start_pool_restart (out of line, called where obs_finish restarts an episode)
+//   k_elog_begin the episode log (ks_set_episode_log): its record and zeroed counters; a finished episode's record is written in
+//                episode_log_write (out of line, called at the same place, just before the next start is drawn)
 // No CPU fallback exists in this library.
 #include <hip/hip_runtime.h>
 
@@ -50,6 +52,19 @@ template <typename T> struct StartPool {
     int32_t *index;                             // [N] the entry every env's running episode started from
 };
 
+// The episode log of a context (ks_set_episode_log): a ring of ks_episode_record and what the stepping kernels need to write one where
+// an episode restarts - like the start pool's, one record in device memory that the stream writes (k_elog_begin / k_elog_clear), so
+// that a captured ks_step / ks_rollout logs into whatever ring the context holds when the graph is replayed.  capacity = 0: no log.
+template <typename T> struct EpisodeLog {
+    int32_t capacity, pad;
+    unsigned long long *written;                // [1] records written since the log was set (the next ticket); never wraps
+    ks_episode_record *ring;                    // [capacity], record of ticket t in slot t % capacity
+    int32_t *ordinal;                           // [N] episodes of the env logged since the log was set
+    const int32_t *obj_id;                      // [N] (Buffers)
+    const T *obs0;                              // [N][82] observation of the env's stored initial state: the finished episode's start
+    const StartPool<T> *pool;                   // the start pool's record: index[env] is the entry the finished episode started from
+};
+
 template <typename T> struct Buffers {
     T *qpos, *qvel, *warm;        // [16|15|15][N]
     T *hand_quat, *qpos0;         // [4][N], [16][N]   stored initial state
@@ -78,6 +93,7 @@ template <typename T> struct Buffers {
     // [4 .. 4 + n_wg) the published workgroups in order, [4 + n_wg .. 4 + 2 n_wg) their done flags; all zero between launches
     int32_t *rayq;
     StartPool<T> *pool;           // [1] the start pool's record (k = 0: none); read only where an episode restarts
+    EpisodeLog<T> *elog;          // [1] the episode log's record (capacity = 0: none); read only where an episode restarts
 };
 
 template <typename T> struct ColW {
@@ -1546,6 +1562,31 @@ template <typename T> __global__ void k_pool_begin(Buffers<T> b, StartPool<T> p,
 }
 template <typename T> __global__ void k_pool_clear(Buffers<T> b) { b.pool->k = 0; }
 
+// An episode of `env` is over and restarts (obs_finish, before the next start is drawn): with an episode log, its record
+// (include/kinova_sim.h, ks_episode_record) goes to the ring slot of the next ticket.  Out of line for the reason start_pool_restart
+// is: ONE copy per precision with registers of its own.  Without a log: one load and back.
+template <typename T> __device__ __noinline__ void episode_log_write(const EpisodeLog<T>* log, int env, int steps, int done) {
+    if (log->capacity <= 0) return;
+    const EpisodeLog<T> l = *log;
+    const int ord = l.ordinal[env];
+    l.ordinal[env] = ord + 1;
+    const int start = l.pool->k > 0 ? l.pool->index[env] : -1;
+    const T* o = l.obs0 + (long)env * NOBS;
+    const float sx = (float)o[21], sy = (float)o[22];
+    const unsigned long long ticket = atomicAdd(l.written, 1ull);
+    uint4* slot = (uint4*)(l.ring + ticket % (unsigned long long)l.capacity);
+    slot[0] = make_uint4((unsigned)env, (unsigned)l.obj_id[env], (unsigned)start, (unsigned)steps);
+    slot[1] = make_uint4((unsigned)done, __float_as_uint(sx), __float_as_uint(sy), (unsigned)ord);
+}
+
+// ks_set_episode_log: the log's record and a zeroed ticket counter (thread 0), every env's ordinal at 0.  k_elog_clear: back to no log.
+template <typename T> __global__ void k_elog_begin(Buffers<T> b, EpisodeLog<T> l, int N) {
+    const int env = blockIdx.x * blockDim.x + threadIdx.x;
+    if (env == 0) { *l.written = 0; *b.elog = l; }
+    if (env < N) l.ordinal[env] = 0;
+}
+template <typename T> __global__ void k_elog_clear(Buffers<T> b) { b.elog->capacity = 0; }
+
 // phase 1 (part = -1: all of it; 0..3: that quarter of the slots, see build_obs): the observation, straight to its destination
 template <typename T, typename SnapT>
 __device__ __forceinline__ void obs_write(const Model<T>& m, const Buffers<T>& b, int env, int N, int mode, const ObsOut<T>& o, SnapT snap,
@@ -1587,7 +1628,10 @@ __device__ __forceinline__ void obs_finish(const Model<T>& m, const Buffers<T>& 
         if (o.info) { o.info[env] = T(0); o.info[(long)N + env] = T(0); o.info[2L * N + env] = rew; }
     }
     if (restart) {
-        // with a start pool (ks_set_start_pool) the next episode's start is drawn here: its entry becomes the stored initial state
+        // with an episode log (ks_set_episode_log) the finished episode's record is written here, while the env's stored initial
+        // state is still that episode's start ...
+        episode_log_write(b.elog, env, sc, (int)d);
+        // ... and with a start pool (ks_set_start_pool) the next episode's start is drawn: its entry becomes the stored initial state
         start_pool_restart(b.pool, env, N);
         if (o.obs) {
             for (int j = 0; j < NOBS; j++) o.obs[base + j * stride] = b.obs0[(long)env * NOBS + j];
@@ -1874,6 +1918,8 @@ struct CtxBase {
     virtual int rollout_plan(int32_t* mode, int32_t* groups, int32_t* workgroups) = 0;
     virtual int set_start_pool(int k, const void* q0, const void* hq, uint64_t seed, void* obs, hipStream_t s) = 0;
     virtual int get_start_index(int32_t* index, int64_t* episode, hipStream_t s) = 0;
+    virtual int set_episode_log(int capacity, hipStream_t s) = 0;
+    virtual int get_episode_log(ks_episode_record* ring_out, int64_t* written_out, hipStream_t s) = 0;
 };
 
 #define HIPCHK(expr)                                                                         \
@@ -1924,6 +1970,13 @@ template <typename T> struct Ctx : CtxBase {
     int64_t* pool_episode = nullptr;
     int32_t* pool_index = nullptr;
     Buffers<T> pb{};                      // b with the reset pass's outputs redirected (pb.snap != nullptr once allocated)
+    // the episode log (ks_set_episode_log): its ring (grown on demand, kept until the context goes), the ticket counter and the
+    // per-env ordinals
+    int elog_capacity = 0;
+    ks_episode_record* elog_ring = nullptr;
+    size_t elog_cap = 0;                  // records the ring's storage holds
+    unsigned long long* elog_written = nullptr;
+    int32_t* elog_ordinal = nullptr;
     int n_models = 0, n_wg = 0;
     int32_t n_groups = 0;                 // groups of the slot list that hold envs (<= n_wg): what ks_rollout deals
     std::map<std::pair<size_t, uint64_t>, void*> shared;      // uploaded arrays by (bytes, content hash): the hand's meshes are
@@ -1969,6 +2022,9 @@ template <typename T> struct Ctx : CtxBase {
         if ((r = alloc(&b.pool, (size_t)1))) return r;          // zeroed: k = 0, no pool
         if ((r = alloc(&pool_episode, N))) return r;
         if ((r = alloc(&pool_index, N))) return r;
+        if ((r = alloc(&b.elog, (size_t)1))) return r;          // zeroed: capacity = 0, no log
+        if ((r = alloc(&elog_written, (size_t)1))) return r;
+        if ((r = alloc(&elog_ordinal, N))) return r;
         ev0.resize(NEV); ev1.resize(NEV);
         for (int i = 0; i < NEV; i++) { HIPCHK(hipEventCreate(&ev0[i])); HIPCHK(hipEventCreate(&ev1[i])); }
         return KS_OK;
@@ -1976,6 +2032,7 @@ template <typename T> struct Ctx : CtxBase {
     ~Ctx() override {
         for (void* p : allocs) (void)hipFree(p);
         if (pool_store) (void)hipFree(pool_store);
+        if (elog_ring) (void)hipFree(elog_ring);
         if (h_out) (void)hipHostFree(h_out);
         if (h_ra) (void)hipHostFree(h_ra);
         if (d_ra) (void)hipFree(d_ra);
@@ -2406,6 +2463,47 @@ template <typename T> struct Ctx : CtxBase {
         if (episode) HIPCHK(hipMemcpyAsync(episode, pool_episode, N * sizeof(int64_t), hipMemcpyDefault, s));
         return KS_OK;
     }
+    int set_episode_log(int capacity, hipStream_t s) override {
+        if (!model_loaded) { error = "ks_set_episode_log before ks_load_model"; return KS_ERR_STATE; }
+        if (!cfg.auto_reset) { error = "ks_set_episode_log: the log is written where an episode restarts inside the stepping kernels - the context needs auto_reset"; return KS_ERR_STATE; }
+        if (capacity == 0) {                                    // no log: the ring keeps its storage and its last content
+            if (elog_capacity > 0) hipLaunchKernelGGL((k_elog_clear<T>), dim3(1), dim3(1), 0, s, b);
+            elog_capacity = 0;
+            HIPCHK(hipGetLastError());
+            return KS_OK;
+        }
+        const int N = cfg.n_envs;
+        if (capacity < N || capacity > KS_EPISODE_LOG_CAPACITY_MAX) {
+            error = "ks_set_episode_log: n_envs <= capacity <= " + std::to_string(KS_EPISODE_LOG_CAPACITY_MAX) + " records (0 clears the log)";
+            return KS_ERR_INVALID;
+        }
+        if ((size_t)capacity > elog_cap) {
+            // (hipFree waits for the device: nothing that is still running writes the storage it gives back)
+            if (elog_ring) { (void)hipFree(elog_ring); elog_ring = nullptr; elog_cap = 0; }
+            const size_t bytes = (size_t)capacity * sizeof(ks_episode_record);
+            if (hipMalloc((void**)&elog_ring, bytes) != hipSuccess) {
+                (void)hipGetLastError();
+                elog_ring = nullptr;
+                if (elog_capacity > 0) hipLaunchKernelGGL((k_elog_clear<T>), dim3(1), dim3(1), 0, s, b);      // (the old log went with its storage)
+                elog_capacity = 0;
+                error = "ks_set_episode_log: no device memory for " + std::to_string(capacity) + " records (" + std::to_string(bytes) + " bytes)";
+                return KS_ERR_HIP;
+            }
+            elog_cap = (size_t)capacity;
+        }
+        HIPCHK(hipMemsetAsync(elog_ring, 0, (size_t)capacity * sizeof(ks_episode_record), s));
+        const EpisodeLog<T> rec{capacity, 0, elog_written, elog_ring, elog_ordinal, b.obj_id, b.obs0, b.pool};
+        hipLaunchKernelGGL((k_elog_begin<T>), dim3((N + 255) / 256), dim3(256), 0, s, b, rec, N);
+        HIPCHK(hipGetLastError());
+        elog_capacity = capacity;
+        return KS_OK;
+    }
+    int get_episode_log(ks_episode_record* ring_out, int64_t* written_out, hipStream_t s) override {
+        if (elog_capacity <= 0) { error = "ks_get_episode_log: the context holds no episode log (ks_set_episode_log)"; return KS_ERR_STATE; }
+        if (ring_out) HIPCHK(hipMemcpyAsync(ring_out, elog_ring, (size_t)elog_capacity * sizeof(ks_episode_record), hipMemcpyDeviceToDevice, s));
+        if (written_out) HIPCHK(hipMemcpyAsync(written_out, elog_written, sizeof(int64_t), hipMemcpyDeviceToDevice, s));
+        return KS_OK;
+    }
     int substep(const void* ctrl, hipStream_t s) override {
         if (!model_loaded) { error = "ks_substep before ks_load_model"; return KS_ERR_STATE; }
         hipLaunchKernelGGL((k_substep<T, USE_LDS>), dim3(n_wg), dim3(WG), step_lds, s, d_model, b, (const T*)ctrl, cfg.n_envs,
@@ -2568,6 +2666,14 @@ int ks_set_start_pool(ks_ctx* ctx, int32_t k, const void* qpos0, const void* han
 int ks_get_start_index(ks_ctx* ctx, int32_t* index, int64_t* episode, void* stream) {
     if (!ctx) return KS_ERR_INVALID;
     return ctx->impl->get_start_index(index, episode, (hipStream_t)stream);
+}
+int ks_set_episode_log(ks_ctx* ctx, int32_t capacity, void* stream) {
+    if (!ctx) return KS_ERR_INVALID;
+    return ctx->impl->set_episode_log(capacity, (hipStream_t)stream);
+}
+int ks_get_episode_log(ks_ctx* ctx, ks_episode_record* ring_out, int64_t* written_out, void* stream) {
+    if (!ctx) return KS_ERR_INVALID;
+    return ctx->impl->get_episode_log(ring_out, written_out, (hipStream_t)stream);
 }
 int ks_substep(ks_ctx* ctx, const void* ctrl, void* stream) {
     if (!ctx) return KS_ERR_INVALID;

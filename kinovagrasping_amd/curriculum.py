@@ -110,7 +110,10 @@ def run_stage(plan, policy, n_envs: int = 1024, rounds: int = 10, updates_per_ro
     starts_per_env = K > 0: the stage runs an AUTO-RESET simulator whose envs each hold a pool of K starts drawn by the same rules
     (scenarios.draw_start_pool) and take one of them at every episode inside the stepping kernel (ks_set_start_pool): no host reset
     between rounds - a round is then 30 env-steps of every env, whose episodes end and restart on their own -, and `distinct_starts`
-    in the result counts the (env, start) pairs that were run.  0: the host reset per round, as before (same draws from the same rng).
+    in the result counts the (env, start) pairs that were run.  The stage then also keeps the in-kernel episode log (ks_set_episode_log)
+    over the rounds and returns its fold: `episodes` (episodes that ended in the rounds) and `per_shape_success` ({shape: attempts,
+    successes, mean_steps}, by the object the record names; with several shapes every env is given its shape's object before the pool
+    is set).  0: the host reset per round, as before (same draws from the same rng).
     Returns a dict (num_success, num_total, paths, ...)."""
     import torch
 
@@ -171,9 +174,19 @@ def run_stage(plan, policy, n_envs: int = 1024, rounds: int = 10, updates_per_ro
     if starts_per_env > 0:
         shape_ids = sim.shape_of_env.cpu().numpy()
         qp, hqp, _ = scenarios.draw_start_pool([sim.shapes[i] for i in shape_ids], plan["requested_orientation"], starts_per_env, rng)
+        if len(shapes) > 1:
+            # the context starts with every env on object 0: give each env its shape's object (ks_reset_objects, which would end a pool:
+            # so before the pool is set), at a start of that shape
+            sim.reset(torch.as_tensor(qp[0]), torch.as_tensor(hqp[0]), object_id=sim.shape_of_env)
         eng.start(sim.set_start_pool(torch.as_tensor(qp), torch.as_tensor(hqp), seed=seed))
         seen = torch.zeros(n_envs, starts_per_env, dtype=torch.bool, device=dev)      # (env, start) pairs that were run
         all_envs = torch.arange(n_envs, device=dev)
+        # which shape succeeded: one record per episode that ends in a round; the ring holds a round's 30 records per env at most and is
+        # read after every round, so it never wraps
+        from .metrics import EpisodeLedger
+        from .sim import EPISODE_LOG_CAPACITY_MAX
+        ledger = EpisodeLedger(n_envs, len(shapes), starts_per_env, keep_coords=False)
+        sim.set_episode_log(min(n_envs * 30, EPISODE_LOG_CAPACITY_MAX))
     for r in range(rounds):
         if starts_per_env <= 0:
             obs0, _ = reset_all(sim, n_envs)
@@ -182,17 +195,23 @@ def run_stage(plan, policy, n_envs: int = 1024, rounds: int = 10, updates_per_ro
             if seen is not None:
                 seen[all_envs, sim.start_index()[0].long()] = True
             eng.step()
+        if seen is not None:
+            ledger.add(sim.episode_log())
         if replay.count >= 2:
             for u in range(updates_per_round):
                 batch = replay.sample_mixed(expert, policy.batch_size, expert_prob) if mix else replay.sample_batch_nstep(policy.batch_size)
                 st, ac, ns, rw, nd, w = batch[:6]
                 losses.append(native.train_on_batch(st, ac, ns, rw, w))
+    if seen is not None:
+        sim.set_episode_log(0)                # (the evaluation's episodes end in the kernel too: they are not the stage's)
     # final evaluation: one deterministic episode per env (eval_policy, main_DDPGfD.py:130-272)
     obs0, classes = reset_all(sim, n_envs)
     res = eval_policy(sim, policy, obs0, horizon=30, orientation=plan["requested_orientation"])
     out = {"expert_episodes": 0 if expert is None else int(expert.count), "num_success": res["num_success"], "num_total": n_envs, "avg_reward": res["avg_reward"], "skipped_shapes": skipped, "shapes": shapes,
            "updates": len(losses),
            "distinct_starts": n_envs * rounds if seen is None else int(seen.sum()), "orientation_counts": {c: classes.count(c) for c in sorted(set(classes))}}
+    if seen is not None:
+        out.update(episodes=ledger.episodes, per_shape_success=ledger.per_object(shapes))
     if save:
         for k in ("policy_dir", "replay_dir", "output_dir"):
             Path(dirs[k]).mkdir(parents=True, exist_ok=True)

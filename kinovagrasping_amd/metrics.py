@@ -5,6 +5,8 @@ boxplot_plot.py) and tensorboard are not reproduced; these are the data files th
     save_heatmap_coords   plotting_code/heatmap_coords.py:34-99 (filter_heatmap_coords -> save_coordinates)
     save_boxplot_rewards  main_DDPGfD.py:521-528
     ScalarLog             main_DDPGfD.py:310-330 (write_tensor_plot): same tags, written as JSON lines
+    EpisodeLedger         eval_policy's per-episode bookkeeping (main_DDPGfD.py:130-272, add_heatmap_coords :310-330) for the episodes that
+                          end inside the stepping kernels: folds the in-kernel episode log (sim.KinovaSim.episode_log)
 """
 from __future__ import annotations
 
@@ -91,3 +93,92 @@ class ScalarLog:
 
     def read(self):
         return [json.loads(l) for l in open(self.path)] if self.path.exists() else []
+
+
+class EpisodeLedger:
+    """Which env, object and start succeeded: the fold of the in-kernel episode log's records (sim.KinovaSim.episode_log(); include/
+    kinova_sim.h: ks_episode_record).  add(records) accumulates, as torch ops on the device the records live on:
+        totals, success_rate()             an episode is a success when it ended lifted (done bit 0: the 50-point lift reward)
+        per_object()                       attempts / successes / mean steps of every object of the context  [n_objects]
+        attempts_table / successes_table   with a start pool (starts_per_env = K): [N, K] counts per (env, pool entry)
+        coords(classes)                    success_coords / fail_coords dicts {x, y, orientation} as save_heatmap_coords takes them
+    Records without a pool entry (start_index -1: no pool) count in the totals and per object only.  keep_coords=False drops the
+    per-episode start coordinates (a long training run that only wants the tables)."""
+
+    def __init__(self, n_envs: int, n_objects: int, starts_per_env: int | None = None, keep_coords: bool = True):
+        self.n_envs, self.n_objects, self.starts_per_env = int(n_envs), int(n_objects), (int(starts_per_env) if starts_per_env else None)
+        self.keep_coords = keep_coords
+        self.episodes = self.successes = self.lost = 0
+        self._dev = None
+        self._coords = []
+
+    def _tables(self, dev):
+        import torch
+        if self._dev is None:
+            self._dev = dev
+            z = lambda *shape: torch.zeros(*shape, dtype=torch.long, device=dev)
+            self.object_attempts, self.object_successes, self.object_steps = z(self.n_objects), z(self.n_objects), z(self.n_objects)
+            if self.starts_per_env:
+                self.attempts_table, self.successes_table = z(self.n_envs, self.starts_per_env), z(self.n_envs, self.starts_per_env)
+
+    def add(self, records: dict):
+        """records: env, object, start_index, steps, done [m] and start_xy [m, 2] (extra keys are ignored; `lost` is summed)"""
+        import torch
+        env, obj, start = records["env"].long(), records["object"].long(), records["start_index"].long()
+        self._tables(env.device)
+        self.lost += int(records.get("lost", 0))
+        if env.numel() == 0:
+            return self
+        ok = (records["done"] & 1) != 0
+        okl = ok.long()
+        self.object_attempts.index_add_(0, obj, torch.ones_like(obj))
+        self.object_successes.index_add_(0, obj, okl)
+        self.object_steps.index_add_(0, obj, records["steps"].long())
+        if self.starts_per_env:
+            pooled = start >= 0
+            flat = (env * self.starts_per_env + start)[pooled]
+            self.attempts_table.view(-1).index_add_(0, flat, torch.ones_like(flat))
+            self.successes_table.view(-1).index_add_(0, flat, okl[pooled])
+        if self.keep_coords:
+            self._coords.append((env, start, records["start_xy"].float(), ok))
+        self.episodes += int(env.numel())
+        self.successes += int(okl.sum())
+        return self
+
+    def success_rate(self) -> float:
+        return self.successes / self.episodes if self.episodes else 0.0
+
+    def per_object(self, names=None) -> dict:
+        """{object (or names[object]): {"attempts", "successes", "mean_steps"}} for every object of the context"""
+        if self._dev is None:
+            a = s = t = [0] * self.n_objects
+        else:
+            a, s, t = self.object_attempts.tolist(), self.object_successes.tolist(), self.object_steps.tolist()
+        return {(names[i] if names is not None else i): {"attempts": a[i], "successes": s[i], "mean_steps": (t[i] / a[i] if a[i] else 0.0)}
+                for i in range(self.n_objects)}
+
+    def coords(self, classes, clear: bool = False):
+        """(success_coords, fail_coords) of the episodes added so far (since the last clear).  classes: the orientation class of every
+        pool entry as scenarios.draw_start_pool returns it ([K, N] array of "normal" / "rotated" / "top": a record's orientation is
+        classes[start_index, env]); or [N] (one class per env), or one string - the only forms a record without a pool entry can use."""
+        import torch
+        if isinstance(classes, str):
+            look = lambda e, j: np.full(len(e), classes, dtype=object)
+        else:
+            cl = np.asarray(classes, dtype=object)
+            if cl.ndim == 1:
+                look = lambda e, j: cl[e]
+            else:
+                def look(e, j):
+                    if (j < 0).any():
+                        raise ValueError("EpisodeLedger.coords: records without a pool entry need one class per env, not a [K, N] table")
+                    return cl[j, e]
+        if self._coords:
+            env, start, xy, ok = (torch.cat([c[i] for c in self._coords]).cpu().numpy() for i in range(4))
+        else:
+            env, start, xy, ok = np.zeros(0, int), np.zeros(0, int), np.zeros((0, 2), np.float32), np.zeros(0, bool)
+        orient = look(env, start)
+        pick = lambda m: {"x": xy[m, 0].tolist(), "y": xy[m, 1].tolist(), "orientation": [str(o) for o in orient[m]]}
+        if clear:
+            self._coords = []
+        return pick(ok), pick(~ok)

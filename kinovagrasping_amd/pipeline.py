@@ -333,6 +333,38 @@ class GraphedTrainer:
             self.native.exchange.check()
 
 
+def rollout_args(sim, policy, eng, pub, pub_ver, steps_total, counters, replay=None, repeats=None, sigma=None):
+    """The ks_rollout_args record (include/kinova_sim.h) of a free-running launch on `sim`: the actor's published parameter buffers
+    (pub [3, stride] with the layout of policy's flat actor parameters, pub_ver the version counter), the engine's state tensors,
+    the context's output buffers and - with a replay in its asynchronous form - the open-episode buffers (with_replay = 1); without
+    one nothing is stored (with_replay = 0).  sigma: the exploration noise's std, the engine's unless given.  Borrows every tensor:
+    the caller keeps them alive for as long as the record is used."""
+    from .rollout import SKIP_NUM_TS
+    from .sim import KsRolloutArgs
+    flat, actor = policy._flat_params["actor"], policy.actor
+    off = lambda t: (t.data_ptr() - flat.data_ptr()) // 4
+    P = lambda t: t.data_ptr()
+    a = KsRolloutArgs()
+    a.actor_pub, a.actor_ver, a.actor_stride = P(pub), P(pub_ver), pub.shape[1]
+    a.off_w1, a.off_b1, a.off_w2, a.off_b2, a.off_w3, a.off_b3 = (off(actor.l1.weight), off(actor.l1.bias), off(actor.l2.weight), off(actor.l2.bias),
+                                                                  off(actor.l3.weight), off(actor.l3.bias))
+    a.h1, a.h2 = actor.l1.weight.shape[0], actor.l2.weight.shape[0]
+    a.sigma, a.max_action, a.skip_steps, a.with_replay, a.seed = (eng.sigma if sigma is None else sigma), eng.max_action, SKIP_NUM_TS, int(replay is not None), eng.noise_seed
+    a.obs, a.prev_obs, a.has_prev, a.ready, a.lifting = P(eng.obs), P(eng.prev_obs), P(eng.has_prev), P(eng.ready), P(eng.lifting)
+    a.t, a.steps_total, a.action, a.action_t = P(eng.t), P(steps_total), P(eng.action), P(eng.action_t)
+    a.reward_out, a.done_out = P(eng.reward_out), P(eng.done_out)
+    a.sim_obs, a.sim_reward, a.sim_done, a.sim_info, a.sim_final_obs = P(sim.obs), P(sim.reward), P(sim.done), P(sim.info), P(sim.final_obs)
+    if replay is not None:
+        a.horizon, a.n_steps = replay.horizon, replay.n_steps
+        a.cur_state, a.cur_next, a.cur_action = P(replay.a_state), P(replay.a_next), P(replay.a_action)
+        a.cur_reward, a.cur_not_done, a.cur_len = P(replay.a_reward), P(replay.a_not_done), P(replay.a_len)
+        a.cur_sel, a.pub_len = P(replay.a_sel), P(replay.pub_len)
+    a.counters = P(counters)
+    if repeats is not None:
+        a.repeats = P(repeats)
+    return a
+
+
 class AsyncTrainer(GraphedTrainer):
     """Free-running rollout + learner (single GPU or one rank of several): the whole rollout side of an env-step - actor forward,
     exploration noise, check_grasp / scripted lift, the 15 substeps, rays, observation, replay write - is ONE persistent launch
@@ -371,7 +403,6 @@ class AsyncTrainer(GraphedTrainer):
             g = torch.Generator(device="cpu").manual_seed(0)
             self._key_w = (torch.rand(replay.horizon * replay.ep_action.shape[2], generator=g, dtype=torch.float64).to(replay.device),
                            torch.rand(replay.ep_state.shape[2], generator=g, dtype=torch.float64).to(replay.device))
-        from .sim import KsRolloutArgs
         eng, dev = engine, self.dev
         if not self.native.lds_free:
             raise ValueError("AsyncTrainer needs the LDS-free learner kernels (hidden widths 256-256 / 128-128 / 64-64): the persistent rollout kernel "
@@ -406,8 +437,6 @@ class AsyncTrainer(GraphedTrainer):
         if not (eng.native and eng.device_noise and eng._fused_actor_layers() is not None and sim.cfg.auto_reset and sim.obs_env_major):
             raise ValueError("AsyncTrainer needs the fused actor path (3-layer MLP at a supported width, in-kernel noise), auto_reset and env-major obs")
         flat = policy._flat_params["actor"]
-        actor = policy.actor
-        off = lambda t: (t.data_ptr() - flat.data_ptr()) // 4
         self.actor_flat = flat
         stride = (flat.numel() + 3) // 4 * 4
         self.pub = torch.zeros(3, stride, device=dev)
@@ -418,24 +447,8 @@ class AsyncTrainer(GraphedTrainer):
         self.steps_total = torch.zeros(eng.n, dtype=torch.long, device=dev)
         self.counters = torch.zeros(8 + 4 * 512 + 8 + (eng.n if os.environ.get("KS_DEBUG_DROPS") else 0), dtype=torch.long, device=dev)      # episodes finished, lifted, kept, dropped (+ 4 phase timers and 4 x 512
                                                                           # per-workgroup stamps of the -DKS_ROLLOUT_STAMP diagnostic build)
-        P = lambda t: t.data_ptr()
-        a = KsRolloutArgs()
-        a.actor_pub, a.actor_ver, a.actor_stride = P(self.pub), P(self.pub_ver), stride
-        a.off_w1, a.off_b1, a.off_w2, a.off_b2, a.off_w3, a.off_b3 = (off(actor.l1.weight), off(actor.l1.bias), off(actor.l2.weight), off(actor.l2.bias),
-                                                                      off(actor.l3.weight), off(actor.l3.bias))
-        a.h1, a.h2 = actor.l1.weight.shape[0], actor.l2.weight.shape[0]
-        from .rollout import SKIP_NUM_TS
-        a.sigma, a.max_action, a.skip_steps, a.with_replay, a.seed = eng.sigma, eng.max_action, SKIP_NUM_TS, 1, eng.noise_seed
-        a.obs, a.prev_obs, a.has_prev, a.ready, a.lifting = P(eng.obs), P(eng.prev_obs), P(eng.has_prev), P(eng.ready), P(eng.lifting)
-        a.t, a.steps_total, a.action, a.action_t = P(eng.t), P(self.steps_total), P(eng.action), P(eng.action_t)
-        a.reward_out, a.done_out = P(eng.reward_out), P(eng.done_out)
-        a.sim_obs, a.sim_reward, a.sim_done, a.sim_info, a.sim_final_obs = P(sim.obs), P(sim.reward), P(sim.done), P(sim.info), P(sim.final_obs)
-        a.horizon, a.n_steps = replay.horizon, replay.n_steps
-        a.cur_state, a.cur_next, a.cur_action = P(replay.a_state), P(replay.a_next), P(replay.a_action)
-        a.cur_reward, a.cur_not_done, a.cur_len = P(replay.a_reward), P(replay.a_not_done), P(replay.a_len)
-        a.cur_sel, a.pub_len, a.counters = P(replay.a_sel), P(replay.pub_len), P(self.counters)
         self.repeats = torch.zeros(1, dtype=torch.long, device=dev)          # actor forwards repeated because two versions were published meanwhile
-        a.repeats = P(self.repeats)
+        a = rollout_args(sim, policy, eng, self.pub, self.pub_ver, self.steps_total, self.counters, replay=replay, repeats=self.repeats)
         # pacing: the learner's stream waits (kr_wait_min on the envs' step counters) so that update k of a launch starts when EVERY env
         # has done k - lead env-steps.  Without it the learner (0.9 ms per update) finishes its share of a long launch far ahead of the
         # rollout (1.1 ms per env-step) and nobody collects the episodes published after that.

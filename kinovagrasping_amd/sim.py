@@ -45,9 +45,43 @@ class KsRolloutArgs(C.Structure):
                 [("budget_ticks", C.c_int64), ("repeats", C.c_void_p)])
 
 
+class KsEpisodeRecord(C.Structure):
+    """ks_episode_record (include/kinova_sim.h): one finished episode of the in-kernel episode log, 8 words of 32 bits"""
+    _fields_ = [("env", C.c_int32), ("object", C.c_int32), ("start_index", C.c_int32), ("steps", C.c_int32), ("done", C.c_int32),
+                ("start_x", C.c_float), ("start_y", C.c_float), ("episode", C.c_int32)]
+
+
+EPISODE_RECORD_WORDS = 8
+EPISODE_LOG_CAPACITY_MAX = 1 << 24      # KS_EPISODE_LOG_CAPACITY_MAX of include/kinova_sim.h (tests/test_episode_log_cpu.py compares them)
+
+
+def decode_episode_ring(ring: torch.Tensor, written: int, cursor: int, capacity: int):
+    """The records of tickets [cursor, written) that a ring of `capacity` slots still holds, oldest first: (records [m, 8] int32, lost).
+    ring: int32 [capacity, 8], the record of ticket t in slot t % capacity (ks_get_episode_log); written: records since the log was set;
+    cursor: the first ticket the reader has not seen.  lost = max(0, written - cursor - capacity): the unseen records that were
+    overwritten before this read.  Pure tensor indexing on whatever device `ring` lives on."""
+    written, cursor, capacity = int(written), int(cursor), int(capacity)
+    if tuple(ring.shape) != (capacity, EPISODE_RECORD_WORDS) or ring.dtype != torch.int32:
+        raise ValueError("decode_episode_ring: ring int32 [capacity, 8]")
+    if not 0 <= cursor <= written:
+        raise ValueError("decode_episode_ring: 0 <= cursor <= written")
+    first = max(cursor, written - capacity)
+    tickets = torch.arange(first, written, dtype=torch.long, device=ring.device)
+    return ring[tickets % capacity], first - cursor
+
+
+def episode_records(words: torch.Tensor) -> dict:
+    """records [m, 8] int32 (decode_episode_ring) -> the fields of ks_episode_record as tensors: env, object, start_index, steps, done,
+    episode int32 [m]; start_xy float32 [m, 2]"""
+    words = words.contiguous()
+    out = {k: words[:, i] for i, k in ((0, "env"), (1, "object"), (2, "start_index"), (3, "steps"), (4, "done"), (7, "episode"))}
+    out["start_xy"] = words[:, 5:7].contiguous().view(torch.float32)
+    return out
+
+
 EXPORTS = ["ks_default_config", "ks_create", "ks_destroy", "ks_last_error", "ks_load_model", "ks_load_models", "ks_reset", "ks_reset_objects", "ks_step",
            "ks_get_state", "ks_set_state", "ks_set_env_params", "ks_substep", "ks_rollout", "ks_rollout_plan", "ks_obs_from_snapshot", "ks_kernel_time", "ks_version",
-           "ks_set_start_pool", "ks_get_start_index"]
+           "ks_set_start_pool", "ks_get_start_index", "ks_set_episode_log", "ks_get_episode_log"]
 # include/kinova_rollout.h
 ROLLOUT_EXPORTS = ["kr_select_action", "kr_store_transition", "kr_rank_episodes", "kr_wait_min", "kr_wait_min_counted", "kr_commit_episodes", "kr_advance_ring",
                    "kr_sample_windows", "kr_sample_windows_draw", "kr_sample_windows_mixed", "kr_xchg_create", "kr_xchg_connect", "kr_xchg_allreduce_mean", "kr_xchg_status",
@@ -118,6 +152,8 @@ def _bind(L):
     L.ks_rollout_plan.argtypes = [vp, i32p, i32p, i32p]
     L.ks_set_start_pool.argtypes = [vp, C.c_int32, vp, vp, C.c_uint64, vp, vp]
     L.ks_get_start_index.argtypes = [vp, vp, vp, vp]
+    L.ks_set_episode_log.argtypes = [vp, C.c_int32, vp]
+    L.ks_get_episode_log.argtypes = [vp, vp, vp, vp]
     i32, f32 = C.c_int32, C.c_float
     L.kr_select_action.argtypes = [i32] + [vp] * 7 + [f32, f32, i32] + [vp] * 4
     L.kr_store_transition.argtypes = [i32] * 5 + [vp] * 21
@@ -262,6 +298,35 @@ class KinovaSim:
         episode = torch.empty(self.n_envs, dtype=torch.int64, device=self.device)
         self._check(self.lib.ks_get_start_index(self.ctx, _ptr(index), _ptr(episode), self._stream()))
         return index, episode
+
+    def set_episode_log(self, capacity: int):
+        """A ring of `capacity` episode records (n_envs <= capacity <= 2^24; include/kinova_sim.h: ks_set_episode_log) that the stepping
+        kernels write where an episode ends and restarts: ks_step and ks_rollout on this auto-reset context.  Starts an empty log (record
+        counter, per-env ordinals and the read cursor of episode_log() at 0).  capacity 0 clears the log."""
+        self._check(self.lib.ks_set_episode_log(self.ctx, int(capacity), self._stream()))
+        self._elog_capacity, self._elog_cursor = int(capacity), 0
+
+    def episode_log_raw(self):
+        """(ring int32 [capacity, 8], written int64 [1]): device copies of the log as it stands behind the work queued on the current
+        stream (ks_get_episode_log; no synchronisation).  Raises without a log."""
+        cap = getattr(self, "_elog_capacity", 0)
+        ring = torch.empty((max(cap, 1), EPISODE_RECORD_WORDS), dtype=torch.int32, device=self.device)
+        written = torch.zeros(1, dtype=torch.int64, device=self.device)
+        self._check(self.lib.ks_get_episode_log(self.ctx, _ptr(ring), _ptr(written), self._stream()))
+        return ring, written
+
+    def episode_log(self):
+        """The episodes logged since the previous call (or since set_episode_log), oldest first, as device tensors: a dict with env, object,
+        start_index, steps, done, episode (int32 [m]) and start_xy (float32 [m, 2]) - ks_episode_record's fields - plus `lost`, the number
+        of records the ring overwrote before they were read (max(0, written - cursor - capacity)), and `written`, the log's total.
+        Reads `written` on the host: waits for the work queued on the current stream."""
+        ring, written = self.episode_log_raw()
+        total = int(written.item())
+        words, lost = decode_episode_ring(ring, total, self._elog_cursor, self._elog_capacity)
+        self._elog_cursor = total
+        out = episode_records(words)
+        out["lost"], out["written"] = lost, total
+        return out
 
     def step(self, action: torch.Tensor):
         """action [4, N].  Returns (obs, reward, done, info) views of the context's output buffers."""
