@@ -329,6 +329,11 @@ struct SlotBound {
 constexpr int RG_BITS = MULTI_GEOM ? 4 : 3, RG = 1 << RG_BITS;        // mesh geom slots of an env in the ray kernels (geoms 1 .. RG)
 static_assert(RG == NGEOM - 1, "ray tasks: one slot per mesh geom");
 constexpr int WG_RAY_TASKS = NRAY * RG;                                // per env
+#ifndef KS_WG_LEAF_BATCH
+#define KS_WG_LEAF_BATCH 4
+#endif
+constexpr int WG_LEAF_BATCH = KS_WG_LEAF_BATCH;                        // triangles of a node's leaves loaded together (ks_obs.h: RayWalk), 9 registers each;
+                                                                       // 1 (A/B builds): a triangle at a time through generic pointers, as before the batching
 constexpr int WG_SNAP = 97;                                            // body poses of an env (96 floats), odd stride
 // the walk queue: every surviving (env, ray, geom) task + the subtrees that busy walkers hand to idle lanes
 __host__ __device__ constexpr int wg_ray_queue(int epw) { return epw * WG_RAY_TASKS + 64 * epw; }
@@ -376,7 +381,7 @@ struct SharingStack {
 #ifdef KS_ROLLOUT_STAMP
 #define KS_RAY_PROF_PARAM , long long* rprof
 #define KS_RAY_PROF_ARG(p) , p
-#define KS_RP(i) { const long long t1_ = wall_clock64(); if (rprof && threadIdx.x == 0) atomicAdd((unsigned long long*)&rprof[i], (unsigned long long)(t1_ - rtk)); rtk = t1_; }
+#define KS_RP(i) { const long long t1_ = wall_clock64(); if (rprof && tid == 0) atomicAdd((unsigned long long*)&rprof[i], (unsigned long long)(t1_ - rtk)); rtk = t1_; }
 #else
 #define KS_RAY_PROF_PARAM
 #define KS_RAY_PROF_ARG(p)
@@ -400,6 +405,7 @@ __device__ __noinline__ void wg_rays(const Model<float>& m, const Buffers<float>
 #ifdef KS_ROLLOUT_STAMP
     long long rtk = wall_clock64();
     int my_visits = 0;
+    unsigned wave_iters = 0, wave_trips = 0;      // of this lane's wave: loop iterations in which a lane visited a node, and their serial triangle round trips (-DKS_ROLLOUT_STAMP=2)
 #endif
     KS_LDS unsigned* hit = w;                                          // [epw][17] nearest hit so far (float bits), big = none
     KS_LDS unsigned* ctl = w + epw * NRAY;                             // [8]: queue tail, tickets, unfinished walks
@@ -442,7 +448,10 @@ __device__ __noinline__ void wg_rays(const Model<float>& m, const Buffers<float>
     const unsigned nlist = ctl[0];
 #endif
     const SharedWalks sh{ctl, q, cap};
-    RayWalk<float, SlotBound, SharingStack> walk;
+    // (the tables are global memory, but the Model's copy in LDS hands out generic pointers: as global ones the reads are global_load
+    // and their waits leave the LDS counter alone)
+    using Table = std::conditional_t<WG_LEAF_BATCH == 1, const float*, KS_GLOBAL const float*>;
+    RayWalk<float, SlotBound, SharingStack, WG_LEAF_BATCH, Table> walk;
     KS_LDS unsigned* slot = hit;
     bool busy = false;
     unsigned ticket = 0xffffffffu;
@@ -450,6 +459,9 @@ __device__ __noinline__ void wg_rays(const Model<float>& m, const Buffers<float>
     // for every lane: a uniform branch).  A lane without work makes one attempt per iteration and falls through - it must never spin
     // in a loop of its own: the entry it waits for may have to be appended by a lane of its own wave.
     while (*(volatile KS_LDS unsigned*)(ctl + 2) != 0u) {
+#ifdef KS_ROLLOUT_STAMP
+        bool stepped = false;
+#endif
         if (!busy) {
             if (ticket == 0xffffffffu) ticket = atomicAdd((unsigned*)(ctl + 1), 1u);
             const unsigned t1 = ticket < (unsigned)cap ? *(volatile KS_LDS unsigned*)(q + 2 * ticket + 1) : 0u;
@@ -465,7 +477,7 @@ __device__ __noinline__ void wg_rays(const Model<float>& m, const Buffers<float>
                 slot = hit + e * NRAY + r;
                 const int mesh = m.geom_mesh[g];
                 SharingStack st{LdsStack<float>{stk + tid, NTH}, sh, t1};
-                busy = walk.start(m.mesh_tri[mesh], m.mesh_bvh_box[mesh], m.geom_size[g], lp, lv, SlotBound{slot}, st);
+                busy = walk.start((Table)m.mesh_tri[mesh], (Table)m.mesh_bvh_box[mesh], m.geom_size[g], lp, lv, SlotBound{slot}, st);
                 if (node != 0) {                                         // a subtree handed over by another walker: still in front of the nearest hit?
                     const float te = __int_as_float((int)(w0 & 0xffff0000u));
                     const float best = __int_as_float((int)*(volatile KS_LDS unsigned*)slot);
@@ -477,6 +489,7 @@ __device__ __noinline__ void wg_rays(const Model<float>& m, const Buffers<float>
         } else {
 #ifdef KS_ROLLOUT_STAMP
             my_visits++;
+            stepped = true;
 #endif
             if (!walk.step()) {
                 if (walk.best >= 0) atomicMin((unsigned*)slot, (unsigned)__float_as_int(walk.best));
@@ -490,10 +503,32 @@ __device__ __noinline__ void wg_rays(const Model<float>& m, const Buffers<float>
                 walk.stack.push(pn, pt);
             }
         }
+#ifdef KS_ROLLOUT_STAMP
+        if (__builtin_amdgcn_ballot_w64(stepped) != 0ull) wave_iters++;
+#if KS_ROLLOUT_STAMP >= 2
+        {
+            // (-DKS_ROLLOUT_STAMP=2: the reductions below cost time of their own - read the phase times from a plain stamp build)
+            // serial triangle round trips of this iteration: the wave waits for its slowest lane.  A triangle at a time, the four child slots one after
+            // the other: per slot the longest leaf any lane met there.  Batched: the longest leaf list of any lane, in chunks of WG_LEAF_BATCH.
+            const auto wave_max = [](int c) { for (int d = 1; d < WAVE; d <<= 1) { const int o = __shfl_xor(c, d); c = o > c ? o : c; } return c; };
+            if constexpr (WG_LEAF_BATCH == 1) {
+                KS_UNROLL
+                for (int k = 0; k < 4; k++) wave_trips += (unsigned)wave_max(stepped ? walk.lcnt_[k] : 0);
+            } else {
+                wave_trips += (unsigned)wave_max(stepped ? (walk.lcnt_[0] + walk.lcnt_[1] + walk.lcnt_[2] + walk.lcnt_[3] + WG_LEAF_BATCH - 1) / WG_LEAF_BATCH : 0);
+            }
+        }
+#endif
+#endif
         if (__builtin_amdgcn_ballot_w64(busy) == 0ull) __builtin_amdgcn_s_sleep(1);   // a wave with nothing to do: leave the LDS to the others
     }
 #ifdef KS_ROLLOUT_STAMP
-    if (rprof) {                          // [2] surviving tasks, [3] node visits in total, [4] sum over workgroups of the busiest lane's visits
+    if (rprof) {                          // [2] surviving tasks, [3] node visits in total, [4] sum over workgroups of the busiest lane's visits,
+                                          // [6] loop iterations with a node visit, summed over waves, [7] their serial triangle round trips (-DKS_ROLLOUT_STAMP=2)
+        if ((threadIdx.x & (WAVE - 1)) == 0) {
+            atomicAdd((unsigned long long*)&rprof[6], (unsigned long long)wave_iters);
+            atomicAdd((unsigned long long*)&rprof[7], (unsigned long long)wave_trips);
+        }
         if (tid == 0) { atomicAdd((unsigned long long*)&rprof[2], (unsigned long long)nlist); ctl[4] = 0; }
         C::sync();
         atomicAdd((unsigned long long*)&rprof[3], (unsigned long long)my_visits);
@@ -1032,12 +1067,20 @@ __device__ __forceinline__ void rollout_iter_wave(const Model<float>& m, const H
     const int wslot0 = grp * epw + 4 * wave, wepw = epw - 4 * wave < 4 ? (epw - 4 * wave < 0 ? 0 : epw - 4 * wave) : 4;   // this wave's slots
     KS_LDS T* wblocks = blocks + 4 * wave * SCR_TOTAL;
     KS_LDS unsigned* w = (KS_LDS unsigned*)wblocks;
+#ifdef KS_ROLLOUT_STAMP
+    // diagnostic build: the same four phase sums as rollout_iter's (counters[4..7]), here over WAVES and env-steps
+    long long tk = wall_clock64();
+#define KS_RS(i) { const long long t1_ = wall_clock64(); if (lane == 0) atomicAdd((unsigned long long*)&rap->counters[4 + i], (unsigned long long)(t1_ - tk)); tk = t1_; }
+#else
+#define KS_RS(i)
+#endif
     {
         const int nn = lane & 15;
         const int row_env = nn < wepw ? b.slot_env[wslot0 + nn] : -1;
         rollout_policy_wave<NT1, NT2>(rap, N, row_env, wblocks);
     }
     C::sync();
+    KS_RS(0)
     if (active) {
         T hq[4], act[4];
         KS_UNROLL
@@ -1072,12 +1115,16 @@ __device__ __forceinline__ void rollout_iter_wave(const Model<float>& m, const H
         if (team.sub == 0) b.ncon[env] = ncon;
     }
     C::sync();
-    wg_rays<true>(m, b, N, wslot0, wepw, w KS_RAY_PROF_ARG(nullptr));
+    KS_RS(1)
+    wg_rays<true>(m, b, N, wslot0, wepw, w KS_RAY_PROF_ARG((long long*)&rap->counters[8 + 4 * 512]));
     C::sync();
+    KS_RS(2)
     wg_obs<true>(m, b, N, wslot0, wepw, w, *out);
     C::sync();
     if (active) rollout_store<float>(rap, N, env, team.sub);
     C::sync();
+    KS_RS(3)
+#undef KS_RS
 }
 
 // another object's model constants and hull tables into the workgroup's LDS (out of line: nothing of it may stay in registers across

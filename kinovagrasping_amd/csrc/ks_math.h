@@ -10,11 +10,13 @@
 #define KS_UNROLL _Pragma("unroll")
 #define KS_FN __host__ __device__ __attribute__((noinline))
 #define KS_LDS __attribute__((address_space(3)))
+#define KS_GLOBAL __attribute__((address_space(1)))
 #else
 #define KS_HD inline
 #define KS_UNROLL
 #define KS_FN inline
 #define KS_LDS
+#define KS_GLOBAL
 #endif
 
 // Where the convex-hull tables of the collision code live.  Standard build (one object hull of a few hundred vertices beside the hand's):

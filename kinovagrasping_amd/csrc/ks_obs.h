@@ -146,9 +146,17 @@ template <typename T> struct LdsStack {
 // The walk as a resumable object: start() does the bounding-box pre-test and the per-walk constants, step() visits ONE
 // node and says whether there is another.  ray_mesh below just loops; the stepping kernel's in-step ray pass (ks_api.hip:
 // wg_rays) interleaves the walks of different tasks on one lane, a node at a time.
-template <typename T, typename Bound = OwnBound, typename Stack = LocalStack<T>> struct RayWalk {
-    const float* tri;
-    const float* wnode;
+// LEAF_BATCH: how many triangles of a node's leaf children are loaded together before they are tested.  1: the leaves one after the
+// other, a triangle at a time - every triangle is a memory round trip of its own, which is what k_rays' eight waves per SIMD hide and
+// costs nothing on the host.  > 1: the ranges of all (<= 4) leaf children that passed their box test are one list, walked in chunks of
+// LEAF_BATCH - all loads of a chunk are issued, then its tests run (ray_tri on the registers): the stepping kernels' in-step pass
+// (wg_rays), one wave per SIMD, where a node with four 7-triangle leaves was 28 dependent round trips for the wave.  The set a step()
+// tests is fixed before its leaves are visited (te[] comes from tmax) and the result is a minimum over it, so the order changes nothing.
+// FP: the pointer type of the two tables (wg_rays: global address space, the Model in LDS holds generic pointers).
+template <typename T, typename Bound = OwnBound, typename Stack = LocalStack<T>, int LEAF_BATCH = 1, typename FP = const float*> struct RayWalk {
+    static_assert(LEAF_BATCH >= 1 && LEAF_BATCH <= 8, "a chunk of the leaf list");
+    FP tri;
+    FP wnode;
     T lp[3], lv[3], inv[3];
     bool par[3];
     T best;
@@ -158,7 +166,10 @@ template <typename T, typename Bound = OwnBound, typename Stack = LocalStack<T>>
 #ifdef KS_RAY_COUNT
     int visits_;
 #endif
-    KS_HD bool start(const float* tri_, const float* wnode_, const T* size, const T* lp_, const T* lv_, Bound bound_, Stack stack_) {
+#if defined(KS_ROLLOUT_STAMP) && KS_ROLLOUT_STAMP >= 2
+    int lcnt_[4];                        // diagnostic build: triangles of the leaf children (by child slot) that the last step() tested
+#endif
+    KS_HD bool start(FP tri_, FP wnode_, const T* size, const T* lp_, const T* lv_, Bound bound_, Stack stack_) {
         T lo[3] = {-size[0], -size[1], -size[2]}, hi[3] = {size[0], size[1], size[2]};
         if (!ray_box(lp_, lv_, lo, hi, Lim<T>::big)) return false;
         tri = tri_; wnode = wnode_; bound = bound_; stack = stack_;
@@ -188,15 +199,54 @@ template <typename T, typename Bound = OwnBound, typename Stack = LocalStack<T>>
             te[k] = id[k] == RAY_EMPTY ? T(-1) : bvh_box_entry_inv(w + 6 * k, lp, inv, par, tmax);
         }
         // leaves among the children first: their hits tighten the bound for the rest
-        KS_UNROLL
-        for (int k = 0; k < 4; k++) {
-            if (te[k] >= 0 && id[k] < 0) {
-                const int code = -id[k] - 1, first = code >> 3, cnt = code & 7;
-                for (int i = first; i < first + cnt; i++) {
-                    const T tt = ray_tri(&tri[9 * (long)i], lp, lv);
-                    if (tt >= 0 && (best < 0 || tt < best)) best = tt;
+        if constexpr (LEAF_BATCH == 1) {
+            KS_UNROLL
+            for (int k = 0; k < 4; k++) {
+#if defined(KS_ROLLOUT_STAMP) && KS_ROLLOUT_STAMP >= 2
+                lcnt_[k] = (te[k] >= 0 && id[k] < 0) ? ((-id[k] - 1) & 7) : 0;
+#endif
+                if (te[k] >= 0 && id[k] < 0) {
+                    const int code = -id[k] - 1, first = code >> 3, cnt = code & 7;
+                    for (int i = first; i < first + cnt; i++) {
+                        const T tt = ray_tri(&tri[9 * (long)i], lp, lv);
+                        if (tt >= 0 && (best < 0 || tt < best)) best = tt;
+                    }
+                    te[k] = T(-1);
                 }
-                te[k] = T(-1);
+            }
+        } else {
+            // entry j of the list is triangle j + off[k] of the table, k the child slot with end[k - 1] <= j < end[k]
+            int off[4], end[4], total = 0;
+            KS_UNROLL
+            for (int k = 0; k < 4; k++) {
+                const bool leaf = te[k] >= 0 && id[k] < 0;
+                const int code = leaf ? -id[k] - 1 : 0;
+                off[k] = (code >> 3) - total;
+                total += leaf ? (code & 7) : 0;
+                end[k] = total;
+                if (leaf) te[k] = T(-1);
+#if defined(KS_ROLLOUT_STAMP) && KS_ROLLOUT_STAMP >= 2
+                lcnt_[k] = leaf ? (code & 7) : 0;
+#endif
+            }
+            for (int j0 = 0; j0 < total; j0 += LEAF_BATCH) {
+                float v[LEAF_BATCH][9];
+                KS_UNROLL
+                for (int c = 0; c < LEAF_BATCH; c++) {
+                    // past the end of the list: its last triangle again (a triangle of the last leaf - never beyond the table), result discarded
+                    const int j = j0 + c < total ? j0 + c : total - 1;
+                    const int i = j + (j < end[0] ? off[0] : j < end[1] ? off[1] : j < end[2] ? off[2] : off[3]);
+                    KS_UNROLL
+                    for (int q = 0; q < 9; q++) v[c][q] = tri[9 * (long)i + q];
+                }
+#if defined(__HIP_DEVICE_COMPILE__)
+                __builtin_amdgcn_sched_barrier(0);           // all loads of the chunk are in flight before the first test waits for one
+#endif
+                KS_UNROLL
+                for (int c = 0; c < LEAF_BATCH; c++) {
+                    const T tt = ray_tri(v[c], lp, lv);
+                    if (j0 + c < total && tt >= 0 && (best < 0 || tt < best)) best = tt;
+                }
             }
         }
         // inner children still in front of the nearest hit: nearest first, the others wait on the stack (farthest pushed first)

@@ -1,5 +1,8 @@
 #!/usr/bin/env python3
 """Free-running rollout: how fast is the rollout launch alone, the learner alone (one-wave kernels, KS_MLP_SPLIT=0), and both?
+With a -DKS_ROLLOUT_STAMP build (KS_LIB=...) it also prints the kernel's phase stamps: per workgroup in the workgroup forms, per wave in the
+free-running wave form (policy | 15 substeps | rays: snapshot + cull, walks | observation + replay write; walk-loop iterations; with
+-DKS_ROLLOUT_STAMP=2 the serial triangle round trips per iteration as well - that build's reductions cost time, read times from a plain one).
 usage (GPU box): python tools/debug/async_parts.py [chunk]"""
 import sys
 import time
@@ -53,20 +56,29 @@ def learner_only():
 
 learn = timed(learner_only, 30)
 ph = tr.counters[4:8].tolist()
+waves = tr.rollout_plan == "waves"       # the free-running waves stamp per WAVE (4 envs), the workgroup forms per workgroup (16 envs)
+unit, nunit, lanes, tasks = ("wave", n // 4, 64, 4 * 136) if waves else ("workgroup", n // 16, 256, 16 * 136)
 if sum(ph):
     import numpy as np
-    nwg = n // 16
     for label, fn in (("rollout alone", lambda: tr.run(chunk, learn=False)), ("rollout + learner", lambda: tr.run(chunk))):
         tr.flush(); torch.cuda.synchronize()
         ph0, st0, rp0 = tr.counters[4:8].clone(), tr.env_steps, tr.counters[8 + 4 * 512:].clone()
         for _ in range(3):
             fn()
         tr.flush(); torch.cuda.synchronize()
-        dph = ((tr.counters[4:8] - ph0).double() / ((tr.env_steps - st0) * nwg) / 100.0).tolist()
-        print(f"{label}: phases, mean per workgroup and env-step [us]: policy %.1f  15 substeps %.1f  rays %.1f  observation + replay write %.1f" % tuple(dph))
-        rp = ((tr.counters[8 + 4 * 512:] - rp0).double() / ((tr.env_steps - st0) * nwg)).tolist()
-        print(f"{label}: rays per workgroup and env-step: snapshot + culling %.1f us, walks %.1f us; surviving (ray, geom) tasks %.0f of 2176, node visits %.0f "
-              f"(= %.1f per lane), the busiest lane's visits %.0f, subtrees handed to waiting lanes %.0f" % (rp[0] / 100.0, rp[1] / 100.0, rp[2], rp[3], rp[3] / 256.0, rp[4], rp[5]))
+        dph = ((tr.counters[4:8] - ph0).double() / ((tr.env_steps - st0) * nunit) / 100.0).tolist()
+        print(f"{label}: phases, mean per {unit} and env-step [us]: policy %.1f  15 substeps %.1f  rays %.1f  observation + replay write %.1f" % tuple(dph))
+        rp = ((tr.counters[8 + 4 * 512:] - rp0).double() / ((tr.env_steps - st0) * nunit)).tolist()
+        print(f"{label}: rays per {unit} and env-step: snapshot + culling %.1f us, walks %.1f us; surviving (ray, geom) tasks %.0f of {tasks}, node visits %.0f "
+              f"(= %.1f per lane), the busiest lane's visits %.0f, subtrees handed to waiting lanes %.0f" % (rp[0] / 100.0, rp[1] / 100.0, rp[2], rp[3], rp[3] / lanes, rp[4], rp[5]))
+        # (iterations are counted per wave of 64 lanes in every form; the round trips only by a -DKS_ROLLOUT_STAMP=2 build, whose times are not to be read)
+        per_wave = 1.0 if waves else 4.0
+        if rp[6]:
+            print(f"{label}: walk loop per wave and env-step: %.1f iterations with a node visit = %.2f us each; serial triangle round trips %.1f = %.2f per iteration%s"
+                  % (rp[6] / per_wave, rp[1] / 100.0 / (rp[6] / per_wave), rp[7] / per_wave, rp[7] / rp[6], "" if rp[7] else " (not counted by this build)"))
+        if waves:
+            continue                     # (the per-workgroup launch stamps below are written by the workgroup forms only)
+        nwg = nunit
         raw = tr.counters[8:8 + 4 * 512].cpu().numpy().reshape(4, 512)[:, :nwg].astype(np.float64)
         mhz = raw[3] / (raw[2] / 100.0)
         print(f"{label}: shader clock during the loop (cycles / wall time) mean {mhz.mean():.0f} MHz  min {mhz.min():.0f}  max {mhz.max():.0f}")
@@ -77,7 +89,7 @@ if sum(ph):
               f"loop mean {loop.mean():.0f}  p50 {np.median(loop):.0f}  p90 {np.percentile(loop, 90):.0f}  max {loop.max():.0f}; first entry -> last exit {end.max():.0f} "
               f"= {end.max() / chunk:.0f} per env-step (mean loop / step {loop.mean() / chunk:.0f})")
 if sum(ph):
-    tot = tr.env_steps * (n // 16)
-    print("k_rollout phases, mean per workgroup and env-step [us]: policy %.1f  15 substeps %.1f  rays %.1f  observation + replay write %.1f" % tuple(p / tot / 100.0 for p in ph))
+    tot = tr.env_steps * nunit
+    print(f"k_rollout phases, mean per {unit} and env-step [us]: policy %.1f  15 substeps %.1f  rays %.1f  observation + replay write %.1f" % tuple(p / tot / 100.0 for p in ph))
 print(f"chunk {chunk}: per env-step  rollout + learner {both:.4f} ms   rollout alone {roll:.4f} ms   learner alone {learn:.4f} ms", flush=True)
 sim.close()

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Dev tool: the kernel source (host lane-check build, one lane = the serial algorithm) under sanitizers on the CPU.
-#   1. ASan + UBSan: the CPU lane tests with a sanitized libks_lanecheck.so
+#   1. ASan + UBSan: the CPU lane tests with a sanitized libks_lanecheck.so (and libks_raybatch.so: the ray walk's leaf batching)
 #   2. MSan (uninitialised reads): a closing grasp + lift driver, fp32 and fp64, cube and vase
 # GPU sanitizers are not available on the pool; this covers everything that is not DPP / LDS specific.
 set -e
@@ -26,6 +26,10 @@ cp tests/native/libks_lanecheck.so /tmp/ks_lc_backup.so
 (cd tests/native && g++ -O1 -g -std=c++17 -fPIC -shared -fsanitize=address,undefined -fno-omit-frame-pointer -o libks_lanecheck.so ks_lanecheck.cpp)
 LD_PRELOAD=$(gcc -print-file-name=libasan.so):$(gcc -print-file-name=libubsan.so) ASAN_OPTIONS=detect_leaks=0 python -m pytest tests/test_kernel_source_cpu.py -x -q | tail -2
 cp /tmp/ks_lc_backup.so tests/native/libks_lanecheck.so
+# the ray walk's batched leaf loop (RayWalk<..., LEAF_BATCH>): the tables are heap blocks of exactly their size, a chunk load past a mesh's last leaf is a finding
+(cd tests/native && g++ -O1 -g -std=c++17 -fPIC -shared -fsanitize=address,undefined -fno-omit-frame-pointer -o libks_raybatch.so ks_raybatch.cpp)
+LD_PRELOAD=$(gcc -print-file-name=libasan.so):$(gcc -print-file-name=libubsan.so) ASAN_OPTIONS=detect_leaks=0 python -m pytest tests/test_ray_leaf_batch_cpu.py -x -q | tail -2
+rm tests/native/libks_raybatch.so          # (the test builds its plain library again when it next runs)
 cp tests/native/libks_lanecheck_mg.so /tmp/ks_lc_mg_backup.so
 (cd tests/native && g++ -O1 -g -std=c++17 -fPIC -shared -DKS_MULTI_GEOM -fsanitize=address,undefined -fno-omit-frame-pointer -o libks_lanecheck_mg.so ks_lanecheck.cpp)
 LD_PRELOAD=$(gcc -print-file-name=libasan.so):$(gcc -print-file-name=libubsan.so) ASAN_OPTIONS=detect_leaks=0 python -m pytest tests/test_multi_geom_cpu.py -x -q -k "kernel_source or env_step" | tail -2
