@@ -23,31 +23,10 @@
 
 namespace ks {
 
-// Which stages are real (out-of-line) device functions.  The narrow-phase queries are inlined into `collision`
-// (measured: +2.3 % env-steps/s, and the parity suite is indifferent to it now - see DESIGN.md on the round-1 "inlining
-// breaks parity" symptom); -DKS_OUTLINE_NARROW restores the calls.  Of the other stages the solver is inlined into the
-// substep as well (+1.9 %; collision and dynamics measured +1 % alone and nothing in combination, so they stay calls):
-// KS_INLINE_COLLISION / KS_INLINE_DYNAMICS / KS_OUTLINE_SOLVER are the experiment switches.
-#ifdef KS_OUTLINE_NARROW
-#define KS_NARROW KS_FN
-#else
-#define KS_NARROW KS_HD
-#endif
-#ifdef KS_INLINE_COLLISION
-#define KS_FN_COLLISION KS_HD
-#else
-#define KS_FN_COLLISION KS_FN
-#endif
-#ifdef KS_INLINE_DYNAMICS
-#define KS_FN_DYNAMICS KS_HD
-#else
-#define KS_FN_DYNAMICS KS_FN
-#endif
-#ifdef KS_OUTLINE_SOLVER
-#define KS_FN_SOLVER KS_FN
-#else
-#define KS_FN_SOLVER KS_HD
-#endif
+// Which stages are real (out-of-line) device functions: `dynamics_rows` and `collision` (KS_FN).  The narrow-phase
+// queries are inlined into `collision` (measured: +2.3 % env-steps/s, and the parity suite is indifferent to it - see
+// DESIGN.md on the round-1 "inlining breaks parity" symptom) and the solver into the substep (+1.9 %; collision and
+// dynamics measured +1 % alone and nothing in combination, so they stay calls): all KS_HD.
 
 // ---------------------------------------------------------------- scratch layout (units of T)
 // body poses b = 2..9: 12 each (R row-major 9, p 3)
@@ -417,7 +396,7 @@ template <typename T, typename S> KS_HD void geom_pose_cached(S scr, int g, T* R
 // (SCR_BP / SCR_AX) and its part of the mass matrix and of qfrc_smooth = passive - bias + actuator into the
 // env's LDS block; consumers read them by row (load_dynamics_row).  With SUBS = 1 one lane plays all roles.
 template <typename T, typename S, int SUBS>
-KS_FN_DYNAMICS void dynamics_rows(const Model<T>& m, const T* qpos, const T* qvel, const T* ctrl, const T* R7, S scr, Team<SUBS> team) {
+KS_FN void dynamics_rows(const Model<T>& m, const T* qpos, const T* qvel, const T* ctrl, const T* R7, S scr, Team<SUBS> team) {
     // entries no role writes (finger-finger cross terms, hand-object) stay zero
     for (int k = team.sub; k < 81 + 36; k += SUBS) scr(SCR_MH + k) = T(0);
     team.sync();
@@ -595,7 +574,7 @@ template <typename T> struct Supp {
     int i1, i2;                // hull vertex ids of v1 / v2 (support points only)
 };
 
-// (TV: the hull tables' element type - T everywhere but in the multi-geom build's fp64 distance query, which runs on the fp32 tables: KS_MG_GJK_F64)
+// (TV: the hull tables' element type - T everywhere but in the multi-geom build's fp64 distance query, which runs on the fp32 tables: MG_GJK_F64)
 template <typename T, typename TV = T> struct PairGeo {
     T R1[9], p1[3], R2[9], p2[3];
     KS_TAB const TV* V1; KS_TAB const TV* V2;
@@ -614,11 +593,7 @@ template <typename T, typename TV = T> struct PairGeo {
 // Hull vertex tables are stored padded: stride 4 reals (x, y, z, 0) and the count rounded up to a
 // multiple of HULL_CHUNK with copies of vertex 0 (a copy never wins a strict arg-max / arg-min).
 constexpr int HULL_CHUNK = 8;
-#ifdef KS_SUPPORT_SKEW_OVERRIDE
-constexpr double SUPPORT_SKEW = KS_SUPPORT_SKEW_OVERRIDE;
-#else
 constexpr double SUPPORT_SKEW = 1e-6;
-#endif
 constexpr double SKEW_X = 0.5377, SKEW_Y = -0.6240, SKEW_Z = 0.5671;   // see pair_support
 
 // Support vertex of a convex hull along `dir` by hill climbing on the hull graph: from `hint`, move to
@@ -658,7 +633,9 @@ KS_HD void hull_climb(const T* R, const T* p, KS_TAB const TV* V, KS_TAB const u
     // (Experiment, measured in round 4 and NOT kept: scan the neighbours of `hint` first and consult `tab` - several hundred cycles of L2
     // latency away - only when the climb has to move, once, after its first hop.  Same support vertex (a local maximiser is the global one);
     // A/B on one box: training 2.92 M against 3.04 M env-steps/s, sim-only 4.16 against 4.32 M, random-init protocol 3.38 against 3.49 M: the
-    // directions of successive support queries differ enough that `hint` is rarely the answer, and the table read was already overlapped.)
+    // directions of successive support queries differ enough that `hint` is rarely the answer, and the table read was already overlapped.
+    // Nothing builds the switch any more; it stays because deleting `tab_pending` and its branch below, dead as they are, changes the
+    // device code of `collision`: profiles/switch_retirement.txt.)
     bool tab_pending = true;
 #endif
     for (int guard = 0; guard < 4096; guard++) {
@@ -737,7 +714,8 @@ template <typename T, typename TV> KS_HD void pair_support(PairGeo<T, TV>& g, co
     }
     // (Experiment, off: SCAN_MAX = 0.)  A hull of at most SCAN_MAX vertices (the cubes: 24) scanned outright - its reads are independent
     // and pipeline through the LDS, a climb is a chain of dependent rounds plus a table read from L2; same vertex.  Measured slower: a warm
-    // climb is one hop, and a wave whose lanes mix small and large hulls runs both code paths.
+    // climb is one hop, and a wave whose lanes mix small and large hulls runs both code paths.  Nothing builds the switch any more; it stays
+    // because `n <= 0` is not a compile-time fact: the scan is part of the product's device code (profiles/switch_retirement.txt).
     const bool scan1 = g.n1 <= SCAN_MAX, scan2 = g.n2 <= SCAN_MAX;
     const int tab1 = scan1 ? 0 : g.dir1[support_cell(ld1)], tab2 = scan2 ? 0 : g.dir2[support_cell(ld2)];
     if (scan1) hull_scan(g.R1, g.p1, g.V1, g.n1, g.hint1, ld1, dir, hm, out1);
@@ -887,11 +865,12 @@ KS_HD void find_pos(const Supp<T>& v0, const Supp<T>& v1, const Supp<T>& v2, con
 //   GJK: the vertex ids of the final simplex (<= 3 points).  The next query starts GJK from that simplex - the poses
 //        have barely moved, so it is usually still the closest feature and the query ends after one confirming support
 //        instead of ~10 iterations.
-//   MPR: the vertex ids of the final portal.  While the origin ray still passes through it, the next query skips the
-//        portal discovery and refines from there (a few supports instead of ~22).
+//   MPR: nothing - every penetration query is cold (see "Round 6" below).
 // Four 32-bit words per pair: vertex ids are < 1024 (checked when the model is loaded), three ids per word, a count in the
-// two top bits; word 0 = GJK ids on hull 1 + simplex size, 1 = GJK ids on hull 2, 2 = portal ids on hull 1 + 3 if valid,
-// 3 = portal ids on hull 2.  All zeros = nothing remembered (cold start).  The stepping kernel keeps the words in registers
+// two top bits; word 0 = GJK ids on hull 1 + simplex size, 1 = GJK ids on hull 2.  Words 2 and 3 held the final portal of
+// rounds 3-5's warm penetration query; word 2 is still written (1 = the last query reached MPR, 0 = it did not), nothing reads
+// either, and the word count stays because it fixes the layout of the pair memory (see collide_hull_hull).
+// All zeros = nothing remembered (cold start).  The stepping kernel keeps the words in registers
 // across the substeps of a launch and carries them from one launch to the next through global memory (ks_api.hip), so the
 // first substep of an env-step starts as warm as the other fourteen.
 constexpr int WARM_WORDS = 4;
@@ -917,7 +896,7 @@ template <typename T, typename TV> KS_HD void hull_point(const T* R, const T* p,
 
 // ---- Round 6: the penetration query of the fp32 PRODUCT (mpr_penetration_sm below; the template above stays the fp64 instantiation's - the
 // parity instrument's - and the KS_MPR_SM=0 fall-back).
-// (1) COLD again.  Rounds 3-5 started the product's query from the previous substep's final portal whenever that still was one (KS_MPR_WARM).
+// (1) COLD again.  Rounds 3-5 started the product's query from the previous substep's final portal whenever that still was one.
 //     That is a different - equally valid - run of MPR, and on flat features it ends on another triangle of the same Minkowski facet: another
 //     contact POINT.  The long-horizon parity tests never saw it: they step through ks_substep, whose queries are cold.  Measured through ks_step
 //     in round 6 (tests/studies/long_horizon_envstep.py), the warm start left 76 of the 168 grasp-and-lift envs within 1e-4 of the oracle after
@@ -932,9 +911,9 @@ template <typename T, typename TV> KS_HD void hull_point(const T* R, const T* p,
 //     instruction stream; the phases' own arithmetic (cross products, sign tests) is short and predicated.
 // Measured and not kept (round 6): a PATH memory - the vertex pair each support of the previous substep's query returned, as the start of this
 // substep's climbs (one confirming round per hull, no cube-map read): +1 % in training, -3 % sim-only, 8 MB of state; skipping the distance query
-// for a pair that penetrated in the previous substep (KS_MPR_FIRST=3): nothing.  The cube map already puts a climb within a hop of its answer.
+// for a pair that penetrated in the previous substep: nothing.  The cube map already puts a climb within a hop of its answer.
 #ifndef KS_MPR_SM
-#define KS_MPR_SM 1             // 0: the fp32 product runs the template above (fp32 points, cold unless KS_MPR_WARM=1): A/B and the divergence study
+#define KS_MPR_SM 1             // 0: the fp32 product runs the template above (fp32 points, cold): A/B and the divergence study
 #endif
 // The query is inlined into `collision` like the other narrow-phase queries.  That takes the stepping kernels' own register count past what leaves room
 // for the learner's waves beside them (k_rollout 256 + 122 where 376 is the limit: training at 0.7 x) - the kernels' budgets are therefore SET in the
@@ -1080,7 +1059,7 @@ KS_HD bool mpr_readoff_f64(const PairGeo<T>& g, const SuppD& v0, const SuppD& v1
 // stand on the same portal (tests/studies/divergence_table.py: 162 of 168 grasp-and-lift envs within 1e-4 after 200 substeps; fp32 points: 146).
 enum { MPR_S_V1 = 0, MPR_S_V2 = 1, MPR_S_V3 = 2, MPR_S_INSIDE = 3, MPR_S_REFINE = 4 };
 template <typename T>
-KS_NARROW bool mpr_penetration_sm(PairGeo<T>& g_io, T tol_, int max_iter, T* depth_o, T* dir_o, T* pos_o) {
+KS_HD bool mpr_penetration_sm(PairGeo<T>& g_io, T tol_, int max_iter, T* depth_o, T* dir_o, T* pos_o) {
     // (the pair record and the result slots are worked on in local copies and written once at the end)
     PairGeo<T> g = g_io;
     T depth_[1] = {0}, dir[3] = {0, 0, 0}, pos[3] = {0, 0, 0};
@@ -1400,7 +1379,7 @@ __device__ __forceinline__ bool mpr_penetration_pair(const PairGeo<T>& g_own, bo
 #endif
 
 template <typename T>
-KS_NARROW bool mpr_penetration(PairGeo<T>& g, T tol, int max_iter, T* depth, T* dir, T* pos, PairWarm* ws = nullptr) {
+KS_HD bool mpr_penetration(PairGeo<T>& g, T tol, int max_iter, T* depth, T* dir, T* pos) {
     Supp<T> v0, v1, v2, v3, v4;
     T d[3], va[3], vb[3];
     copy3(v0.v1, g.p1);
@@ -1408,32 +1387,10 @@ KS_NARROW bool mpr_penetration(PairGeo<T>& g, T tol, int max_iter, T* depth, T* 
     sub3(v0.v, v0.v1, v0.v2);
     if (vec_is_zero(v0.v)) v0.v[0] += T(1e-5);
     v0.i1 = 0; v0.i2 = 0;
-    bool have_portal = false;
-    int ma[3] = {0, 0, 0}, mb[3] = {0, 0, 0}, mn = 0, unused = 0;
     // The portal MPR ends on - hence depth, normal and above all the contact POINT on flat features - depends on the path within
-    // its 1e-6 tolerance.  The cold path below is libccd's, which the oracle follows and which reproduces real MuJoCo 1.50 to 1e-9
-    // through 18 rows of contact (tests/test_mujoco_recorded.py): the fp64 instantiation (the parity instrument) always takes it.
-    // The fp32 product starts from the previous substep's portal when that still is one (KS_MPR_WARM, default on): fp32 rounding
-    // of the supports' near-ties changes the path anyway, and a warm query is 1 - 2 support pairs instead of 6 - 10.
-#ifndef KS_MPR_WARM
-#define KS_MPR_WARM 0           // (round 6: off - see the path memory above; 1 restores rounds 3-5's warm start for A/B)
-#endif
-    constexpr bool mpr_warm = (KS_MPR_WARM != 0) && sizeof(T) == 4;
-    if (mpr_warm && ws != nullptr) { unpack3(ws->w[2], ma, mn); unpack3(ws->w[3], mb, unused); }
-    if (mn == 3) {
-        // the previous query's portal at the current poses: still a portal if the origin ray (from v0 through the
-        // origin) passes through the triangle, i.e. the origin is on the inner side of the three planes (v0, vi, vj)
-        v1.i1 = ma[0]; v1.i2 = mb[0]; v2.i1 = ma[1]; v2.i2 = mb[1]; v3.i1 = ma[2]; v3.i2 = mb[2];
-        hull_point(g.R1, g.p1, g.V1, ma[0], v1.v1); hull_point(g.R2, g.p2, g.V2, mb[0], v1.v2); minkowski_point_ids(g, ma[0], mb[0], v1.v1, v1.v2, v1.v);
-        hull_point(g.R1, g.p1, g.V1, ma[1], v2.v1); hull_point(g.R2, g.p2, g.V2, mb[1], v2.v2); minkowski_point_ids(g, ma[1], mb[1], v2.v1, v2.v2, v2.v);
-        hull_point(g.R1, g.p1, g.V1, ma[2], v3.v1); hull_point(g.R2, g.p2, g.V2, mb[2], v3.v2); minkowski_point_ids(g, ma[2], mb[2], v3.v1, v3.v2, v3.v);
-        T c13[3], c32[3], c21[3], e1[3], e2[3], nn[3];
-        cross3(c13, v1.v, v3.v); cross3(c32, v3.v, v2.v); cross3(c21, v2.v, v1.v);
-        sub3(e1, v2.v, v1.v); sub3(e2, v3.v, v1.v); cross3(nn, e1, e2);
-        have_portal = dot3(c13, v0.v) >= 0 && dot3(c32, v0.v) >= 0 && dot3(c21, v0.v) >= 0 && dot3(nn, nn) > T(1e-24);
-        ws->w[2] = 0;                                   // valid again only if this query ends on a portal
-    }
-    if (!have_portal) {
+    // its 1e-6 tolerance.  Every query takes the cold path below: it is libccd's, which the oracle follows and which reproduces real
+    // MuJoCo 1.50 to 1e-9 through 18 rows of contact (tests/test_mujoco_recorded.py).
+    {   // portal discovery (a scope of its own, where the warm start's `if` stood: without it the locals' lifetimes, and with them the fp64 kernels' code, change)
     scl3(d, v0.v, T(-1));
     normalize3(d);
     mpr_support(g, d, v1);
@@ -1482,7 +1439,7 @@ KS_NARROW bool mpr_penetration(PairGeo<T>& g, T tol, int max_iter, T* depth, T* 
         cross3(d, va, vb);
         normalize3(d);
     }
-    }   // portal discovery
+    }
     T dt;
     for (int it = 0;; it++) {
         if (it > 100) return false;
@@ -1528,18 +1485,13 @@ KS_NARROW bool mpr_penetration(PairGeo<T>& g, T tol, int max_iter, T* depth, T* 
                 const double nn = std::sqrt(witd[0] * witd[0] + witd[1] * witd[1] + witd[2] * witd[2]);
                 dir[0] = (T)(witd[0] / nn); dir[1] = (T)(witd[1] / nn); dir[2] = (T)(witd[2] / nn);
                 find_pos(v0, v1, v2, v3, pos);
-                goto refined_;
+                return true;
             }
             *depth = ksqrt(origin_tri_dist2(v1.v, v2.v, v3.v, wit));
             if (vec_is_zero(wit)) return false;
             copy3(dir, wit);
             normalize3(dir);
             find_pos(v0, v1, v2, v3, pos);
-        refined_:
-            if (mpr_warm && ws != nullptr && packable(v1.i1, v2.i1, v3.i1, v1.i2, v2.i2, v3.i2)) {
-                ws->w[2] = pack3(v1.i1, v2.i1, v3.i1, 3);
-                ws->w[3] = pack3(v1.i2, v2.i2, v3.i2, 0);
-            }
             return true;
         }
         expand_portal(v0, v1, v2, v3, v4);
@@ -1698,7 +1650,7 @@ template <typename T> KS_HD void gjk_remember(PairWarm* ws, const Simplex<T>& S)
 #if defined(KS_GJK_COUNT_IDS) && !defined(__HIP_DEVICE_COMPILE__)
 inline long ks_gjk_ids_out_of_range = 0;
 #endif
-template <typename T, typename TV> KS_NARROW int gjk_distance(PairGeo<T, TV>& g, T margin, T* dist, T* normal, T* pos, PairWarm* ws = nullptr) {
+template <typename T, typename TV> KS_HD int gjk_distance(PairGeo<T, TV>& g, T margin, T* dist, T* normal, T* pos, PairWarm* ws = nullptr) {
     Simplex<T> S;
     T lam[4] = {1, 0, 0, 0}, v[3], d[3];
 #ifndef KS_GJK_TOL
@@ -1767,18 +1719,12 @@ template <typename T, typename TV> KS_NARROW int gjk_distance(PairGeo<T, TV>& g,
         gjk_support(g, nd, w, wa, wb);
         T vw = dot3(v, w);
         last_vw = vw;
-#ifdef KS_DEBUG_GJK
-        printf("  gjk[%d] it %d n %d vv %.9g vw %.9g |v| %.9g\n", (int)sizeof(T), it, S.n, (double)vv, (double)vw, (double)ksqrt(vv));
-#endif
         if (vw > 0 && vw * vw >= margin * margin * vv) { gjk_remember(ws, S); return 0; }
         if (vv - vw <= tol * vv + gap * ksqrt(vv)) break;
         bool dup = false;
         KS_UNROLL
         for (int i = 0; i < 4; i++)
             if (i < S.n && S.y[i][0] == w[0] && S.y[i][1] == w[1] && S.y[i][2] == w[2]) dup = true;
-#ifdef KS_DEBUG_GJK
-        if (dup) printf("  -> dup\n");
-#endif
         if (dup) break;
         Simplex<T> prev = S;
         T plam[4] = {lam[0], lam[1], lam[2], lam[3]}, pv[3] = {v[0], v[1], v[2]};
@@ -1794,9 +1740,6 @@ template <typename T, typename TV> KS_NARROW int gjk_distance(PairGeo<T, TV>& g,
 #else
         if (gjk_closest(S, lam, v)) { gjk_remember(ws, S); return 2; }
 #endif
-#ifdef KS_DEBUG_GJK
-        printf("  -> new vv %.9g (n %d) lam %.4g %.4g %.4g %.4g%s\n", (double)dot3(v, v), S.n, (double)lam[0], (double)lam[1], (double)lam[2], (double)lam[3], dot3(v, v) >= vv ? " NO DECREASE" : "");
-#endif
         if (dot3(v, v) >= vv) {
             copy3(v, pv);
             S = prev;
@@ -1809,11 +1752,7 @@ template <typename T, typename TV> KS_NARROW int gjk_distance(PairGeo<T, TV>& g,
     // (v.w < 0): v is then no certified separation - a flat tetrahedron of a near-touching pair can stop here a few um "apart"
     // although the hulls overlap (found on a 64-gon cylinder against a finger: +4.9 um reported, 34 um of penetration).  Such a
     // result is handed to the penetration query first (return 3); only if that finds no overlap does the caller keep it.
-#ifndef KS_NO_OPEN_FALLBACK     // (experiment switch)
     const bool open = last_vw < 0;
-#else
-    const bool open = false;
-#endif
     T dd = norm3(v);
     if (dd < T(1e-12)) return 2;
     if (dd >= margin) return open ? 2 : 0;
@@ -2148,10 +2087,11 @@ KS_HD void fill_pair_geo(PairGeo<T>& pg, const unsigned short* dirtab, S scr, KS
     pg.cnt_support = 0; pg.cnt_steps = 0; pg.t_sup = 0; pg.t_clo = 0;
 #endif
 }
-// The multi-geom build's fp64 distance query of the fp32 product (KS_MG_GJK_F64, see collide_hull_hull): OUT OF LINE, and it reads the pair's record itself.
+// The multi-geom build's fp64 distance query of the fp32 product (MG_GJK_F64, see collide_hull_hull): OUT OF LINE, and it reads the pair's record itself.
 // Inlined into `collision` its fp64 simplex takes that function to 256 + 156 registers - past the stepping kernels' budget (ks_api.hip: KS_ROLLOUT_NUM_VGPR),
 // the learner's waves no longer fit beside them and its stream falls behind (episodes dropped); with `collision` itself inlined into the kernels the budget
 // holds but everything spills (BottleS 3.09 -> 2.46 M env-steps/s); out of line with the caller's pair record live across the call 256 + 134.
+constexpr bool MG_GJK_F64 = MULTI_GEOM;
 template <typename T, typename S>
 KS_FN int gjk_distance_f64(const unsigned short* dirtab, S scr, KS_LDS const PairRec<T>* prp, bool obj_first, int& h1, int& h2, T* dist, T* dir, T* pos, PairWarm* ws) {
     PairGeo<double, T> pd;
@@ -2198,9 +2138,7 @@ KS_HD bool hull_pair_may_touch(S scr, KS_LDS const PairRec<T>* prp) {
     geom_pose_cached(scr, g2, R2, p2);
     sub3(t, p1, p2);
     if (dot3(t, t) > bound * bound) return false;
-#ifndef KS_NO_OBB
     if (obb_separated(R1, p1, size1, R2, p2, size2, margin)) return false;
-#endif
     return true;
 }
 
@@ -2228,14 +2166,8 @@ KS_HD int collide_hull_hull(const Model<T>& m, const unsigned short* dirtab, S s
     // recorded MuJoCo 1.50 trajectory agree to 2e-10 / 8e-8 with the object first, to 1.3e-6 with the hand geom first.  For these pairs
     // the queries run on the exchanged operands (hull 1 of `pg` = the object) and the direction is flipped back to g1 -> g2; the
     // hints and the warm words then describe `pg`'s order, consistently from one substep to the next.
-#ifndef KS_OBJ_FIRST
-#define KS_OBJ_FIRST 1          // 0: the operand order of rounds 1-4 (diagnostic A/B only: tools/r05/operand_order_fp32.py)
-#endif
-    const bool obj_first = (KS_OBJ_FIRST != 0) && (g2 == OBJ_GEOM);
-#ifndef KS_MG_GJK_F64
-#define KS_MG_GJK_F64 1         // 0: the fp32 distance query (first half of round 6: 37 of 48 long-horizon envs, 10 - 12 % faster)
-#endif
-    // Multi-geom build, fp32 product (KS_MG_GJK_F64): the DISTANCE query in fp64 arithmetic on the fp32 poses and the fp32 hull tables - what the fp64
+    const bool obj_first = g2 == OBJ_GEOM;
+    // Multi-geom build, fp32 product (MG_GJK_F64): the DISTANCE query in fp64 arithmetic on the fp32 poses and the fp32 hull tables - what the fp64
     // instantiation runs.  These objects' pieces collide dynamically in the 1 mm margin zone, where the closest-feature query decides which contact exists; with
     // the penetration query already on fp64 points this is the host study's "hull pairs from an fp64 collision stage" (tools/r06/mg_host_study.py: 44 of 48;
     // on the GPU 43 of 48 through ks_step against 37).  The query runs out of line on its own copy of the pair record (gjk_distance_f64); this function's
@@ -2245,24 +2177,7 @@ KS_HD int collide_hull_hull(const Model<T>& m, const unsigned short* dirtab, S s
 #ifdef KS_STAMP_HULL
     const long long th1 = clock64();
 #endif
-    // (Experiment, off by default.)  A pair without margin (the explicit object pairs) that PENETRATED in the previous substep goes straight
-    // to the penetration query (fp32 product only, KS_MPR_FIRST): since round 4 every object contact is a penetration contact, and the distance query in
-    // front of it - whose only job for such a pair is to say "overlap" - needs the most iterations of the wave to do so (it must
-    // enclose the origin), while the lanes with separated pairs confirm their cached separation in one.  MPR decides overlap itself;
-    // the two can only disagree within their tolerances of touching.  The fp64 instantiation keeps the oracle's order.
-#ifndef KS_MPR_FIRST
-#define KS_MPR_FIRST 0          // measured in round 4 (one box, A/B): sim-only 4.28 M with it, 4.36 M without - the waves run in lockstep, the lanes
-#endif                          // that skip the distance query wait for those that do not, and the extra branch costs more than it saves: off
-    // (KS_MPR_FIRST=2: EVERY margin-0 pair, penetrating before or not - no distance query at all for the object pairs.  Measured, A/B on one
-    // box: training 2.71 M against 3.03 M env-steps/s, sim-only 3.94 against 4.31 M: a separated pair costs the distance query one iteration
-    // (its cached separating simplex), the penetration query a cold portal discovery.)
-    // Round 6 (KS_MPR_FIRST = 3, with the state-machine query): a margin-0 pair whose previous query got as far as MPR - pair memory word 2 - skips the distance
-    // query.  For such a pair MuJoCo itself asks libccd for the penetration only; the distance query in front of it is this repo's shortcut for SEPARATED pairs
-    // (a warm confirmation of the cached separating simplex), and for a penetrating pair it is the expensive case (it must enclose the origin).
-    const bool mpr_first = (KS_MPR_FIRST == 3) ? (use_sm && ws != nullptr && ws->w[2] != 0u && !(margin > T(0)))
-                         : (KS_MPR_FIRST == 2) ? (sizeof(T) == 4 && !(margin > T(0)))
-                                               : ((KS_MPR_FIRST != 0) && (KS_MPR_WARM != 0) && sizeof(T) == 4 && ws != nullptr && (ws->w[2] >> 30) == 3u && !(margin > T(0)));
-    constexpr bool gjk_f64 = MULTI_GEOM && (KS_MG_GJK_F64 != 0) && sizeof(T) == 4 && (KS_MPR_FIRST == 0);
+    constexpr bool gjk_f64 = MG_GJK_F64 && sizeof(T) == 4;
     if constexpr (gjk_f64) {
         int hh1 = h1_out, hh2 = h2_out;
         r = gjk_distance_f64(dirtab, scr, prp, obj_first, hh1, hh2, &dist, dir, pos, ws);
@@ -2293,7 +2208,7 @@ KS_HD int collide_hull_hull(const Model<T>& m, const unsigned short* dirtab, S s
 #ifdef KS_STAMP_HULL
         pg.cnt_support = 0; pg.cnt_steps = 0; pg.t_sup = 0; pg.t_clo = 0;
 #endif
-        if (!mpr_first) r = gjk_distance(pg, margin, &dist, dir, pos, ws);
+        r = gjk_distance(pg, margin, &dist, dir, pos, ws);
     }
 #ifdef KS_STAMP_HULL
     if (prof) { prof[24] += 1.f; prof[25] += (float)pg.cnt_support; prof[27] += (float)(clock64() - th1); prof[28] += (float)pg.t_sup; prof[29] += (float)pg.t_clo; }
@@ -2313,9 +2228,9 @@ KS_HD int collide_hull_hull(const Model<T>& m, const unsigned short* dirtab, S s
 #endif
         if constexpr (use_sm) {
             hit = mpr_penetration_sm(pg, m.mpr_tol, m.mpr_iters, &depth, mdir, mpos);
-            if (ws != nullptr) ws->w[2] = 1u;                   // (pair memory word 2: the pair's last query got as far as MPR - KS_MPR_FIRST=3)
+            if (ws != nullptr) ws->w[2] = 1u;                   // (nothing reads it; it lands in the pair memory: removing the store is a separate, measured change)
         } else {
-            hit = mpr_penetration(pg, m.mpr_tol, m.mpr_iters, &depth, mdir, mpos, ws);
+            hit = mpr_penetration(pg, m.mpr_tol, m.mpr_iters, &depth, mdir, mpos);
         }
 #ifdef KS_STAMP_HULL
         if (prof) { prof[7] += (float)(clock64() - tm0); prof[22] += (float)(pg.cnt_support - sup0) * 0.5f; prof[26] += 1.f; prof[29] += (float)(pg.t_clo - clo0); }     // MPR cycles, support pairs, queries, cycles inside its supports (diagnostic)
@@ -2327,7 +2242,6 @@ KS_HD int collide_hull_hull(const Model<T>& m, const unsigned short* dirtab, S s
             return 1;
         }
         if (r == 3) { stage_contact(scr, slot, body1, body2, pi, mu, dist, pos, dir); return 1; }
-        if (use_sm && mpr_first && ws != nullptr) ws->w[2] = 0u;        // no longer penetrating: the next query starts with the distance query again
     }
     return 0;
 }
@@ -2337,18 +2251,15 @@ KS_HD int collide_hull_hull(const Model<T>& m, const unsigned short* dirtab, S s
 // lane 8 places away as their helper - when both lanes of such a couple have an overlapping pair the lower one goes first and helps the other
 // afterwards (a second turn of the loop below, rare: the pairs that overlap together - object against finger links - sit on neighbouring lanes).
 static_assert(NCON_MAX * CON_STRIDE >= 16 * 24, "the contact region holds a 24-word portal per lane of a team");
-#ifndef KS_MPR_SPLIT
-#ifdef KS_MULTI_GEOM
-#define KS_MPR_SPLIT 0          // the multi-geom build keeps the one-lane query: measured with the two-lane one BottleS 3.09 -> 3.02 M, BowlS 2.07 -> 2.03 M env-steps/s, the 14-key
-#else                           //  stage context 0.545 -> 0.543 M (up to six passes per substep that every lane of the wave now takes, hull tables in global memory)
-#define KS_MPR_SPLIT 1          // 0: every penetration query on its owner's lane alone (mpr_penetration_sm), the A/B of the two-lane query
-#endif
-#endif
+// The standard build only.  The multi-geom build keeps the one-lane query (mpr_penetration_sm): measured with the two-lane one BottleS 3.09 -> 3.02 M,
+// BowlS 2.07 -> 2.03 M env-steps/s, the 14-key stage context 0.545 -> 0.543 M (up to six passes per substep that every lane of the wave now takes, hull
+// tables in global memory).
+constexpr bool MPR_SPLIT = !MULTI_GEOM;
 #if defined(__HIP_DEVICE_COMPILE__)
 template <typename T, typename S, int SUBS>
 __device__ __forceinline__ int collide_hull_hull_split(const Model<T>& m, const unsigned short* dirtab, S scr, Team<SUBS> team, bool have, KS_LDS const PairRec<T>* prp,
                                                        int slot, int packed_in, int& h1_out, int& h2_out, PairWarm* ws, float* prof = nullptr) {
-    static_assert(SUBS == 16 && KS_MPR_FIRST == 0, "the two-lane query: 16-lane teams, the distance query first");
+    static_assert(SUBS == 16, "the two-lane query: 16-lane teams");
 #ifdef KS_STAMP_SPLIT
     const long long ts0_ = clock64();     // diagnostic build (tools/r06/split_stamp.py): wave-level cycles of the distance-query part and of the penetration part of a pass
 #endif
@@ -2363,7 +2274,7 @@ __device__ __forceinline__ int collide_hull_hull_split(const Model<T>& m, const 
         const int g1 = pr.g1, g2 = pr.g2;
         const int flags = pr.obj_hand;
         const T margin = pr.margin;
-        obj_first = (KS_OBJ_FIRST != 0) && (g2 == OBJ_GEOM);       // (operand order: see collide_hull_hull)
+        obj_first = g2 == OBJ_GEOM;       // (operand order: see collide_hull_hull)
         if (obj_first) {
             pg.V1 = pr.V2; pg.n1 = pr.n2; pg.off1 = pr.off2; pg.adj1 = pr.adj2;
             pg.V2 = pr.V1; pg.n2 = pr.n1; pg.off2 = pr.off1; pg.adj2 = pr.adj1;
@@ -2407,18 +2318,12 @@ __device__ __forceinline__ int collide_hull_hull_split(const Model<T>& m, const 
         if (own || help) {
             int hh1 = 0, hh2 = 0;
             T dd = 0, md[3] = {0, 0, 0}, mp[3] = {0, 0, 0};
-#ifdef KS_SPLIT_USE_SM
-            // diagnostic build: the split caller around the ONE-lane query (what the change of the caller alone does to the bits)
-            bool ht = false;
-            if (own) { PairGeo<T> pc = pg; ht = mpr_penetration_sm(pc, m.mpr_tol, m.mpr_iters, &dd, md, mp); hh1 = pc.hint1; hh2 = pc.hint2; }
-#else
 #ifdef KS_STAMP_SPLIT
             int turns_ = 0;
             const bool ht = mpr_penetration_pair(pg, own, (KS_LDS double*)(scr.base + SCR_CON + 24 * team.sub), m.mpr_tol, m.mpr_iters, hh1, hh2, &dd, md, mp, &turns_);
             if (prof && own) prof[29] += (float)turns_;
 #else
             const bool ht = mpr_penetration_pair(pg, own, (KS_LDS double*)(scr.base + SCR_CON + 24 * team.sub), m.mpr_tol, m.mpr_iters, hh1, hh2, &dd, md, mp);
-#endif
 #endif
 #ifdef KS_SPLIT_CHECK
             if (own) {      // diagnostic build: the one-lane query on the same pair record must return the same bits
@@ -2469,7 +2374,7 @@ template <typename T, typename S, int SUBS> KS_HD void reset_pair_words(S scr, T
 }
 
 template <typename T, typename S, int SUBS>
-KS_FN_COLLISION void collision(const Model<T>& m, const Hulls<T>& hu, S scr, Team<SUBS> team, int& ncon, int& status, PairWarm* warm = nullptr,
+KS_FN void collision(const Model<T>& m, const Hulls<T>& hu, S scr, Team<SUBS> team, int& ncon, int& status, PairWarm* warm = nullptr,
                      float* prof = nullptr) {
     KS_T0
     const int npair = hu.npair, nhull = hu.nhull;
@@ -2571,7 +2476,7 @@ KS_FN_COLLISION void collision(const Model<T>& m, const Hulls<T>& hu, S scr, Tea
         }
 #endif
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(KS_STAMP_HULL)
-        constexpr bool split_queries = (KS_MPR_SPLIT != 0) && (KS_MPR_SM != 0) && sizeof(T) == 4 && SUBS == 16 && KS_MPR_FIRST == 0;
+        constexpr bool split_queries = MPR_SPLIT && (KS_MPR_SM != 0) && sizeof(T) == 4 && SUBS == 16;
 #else
         constexpr bool split_queries = false;
 #endif
@@ -2603,7 +2508,7 @@ KS_FN_COLLISION void collision(const Model<T>& m, const Hulls<T>& hu, S scr, Tea
             if constexpr (HPL == 2) { r = (todo & 1u) ? 0 : 1; pi_r = r ? pi_[1] : pi_[0]; word_r = r ? word_[1] : word_[0]; slot_r = r ? slot_[1] : slot_[0]; }
             else {
                 r = kctz(todo);
-                if constexpr (MULTI_GEOM && (KS_MG_GJK_F64 != 0) && sizeof(T) == 4) {
+                if constexpr (MG_GJK_F64 && sizeof(T) == 4) {
                     // (the pair of round r re-derived from the lists in LDS instead of kept in 3 x HPL registers across the out-of-line distance query:
                     //  what `collision` holds across that call decides whether the stepping kernels stay inside their register budget)
                     const int left = nhull - r * SUBS, cnt = left < SUBS ? left : SUBS;
@@ -2958,7 +2863,7 @@ KS_HD void rows_replicate(Team<SUBS> team, const T (&x)[RPL], T (&out)[NV]) {
 // The stage also builds the constraint rows (S5), solves M qacc_smooth = qfrc_smooth and finishes with the
 // semi-implicit Euler update (S7): everything that needs the mass matrix by rows lives in one function.
 template <typename T, typename S, int SUBS>
-KS_FN_SOLVER void constrained_step(const Model<T>& m, T* qpos, T* qvel, T* warm, S scr, Team<SUBS> team, int ncon, int iterations, int& status,
+KS_HD void constrained_step(const Model<T>& m, T* qpos, T* qvel, T* warm, S scr, Team<SUBS> team, int ncon, int iterations, int& status,
                             float* prof = nullptr) {
     static_assert(SUBS == 1 || SUBS == 16, "row distribution: one lane or one DPP row per env");
     constexpr int RPL = (NV + SUBS - 1) / SUBS;         // rows per lane
@@ -3437,25 +3342,7 @@ KS_HD void mj_forward_step(const Model<T>& m, const Hulls<T>& hu, T* qpos, T* qv
     after_kinematics();
     KS_TICK(0)
     int ncon = 0;
-#if defined(KS_SCRATCH_PROBE) && defined(__HIP_DEVICE_COMPILE__)
-    // EXPERIMENT (tools/experiments/scratch_probe.sh): KS_SCRATCH_PROBE (a power of two) extra private-memory words per lane stored
-    // before the out-of-line `collision` and loaded after it - the pattern of the register frame that lives there ("no build
-    // without those stores exists to compare" - one WITH MORE of them does, and the slope of the run time over their number is what one of them costs).
-    // The array is indexed with a run-time offset (always 0) so that it stays in private memory; stores and loads are independent and issue back to back
-    // like a spill sequence.
-    T probe_[KS_SCRATCH_PROBE];
-    KS_UNROLL
-    for (int i = 0; i < KS_SCRATCH_PROBE; i++) probe_[(i + (status >> 30)) & (KS_SCRATCH_PROBE - 1)] = qvel[i % NV];
-#endif
     collision(m, hu, scr, team, ncon, status, gjk_warm, prof);
-#if defined(KS_SCRATCH_PROBE) && defined(__HIP_DEVICE_COMPILE__)
-    {
-        T acc_ = T(0);
-        KS_UNROLL
-        for (int i = 0; i < KS_SCRATCH_PROBE; i++) acc_ += probe_[(i + (ncon >> 30)) & (KS_SCRATCH_PROBE - 1)];
-        if (acc_ == T(-12345.678)) status |= ST_CONTACT_OVERFLOW;       // (never: keeps the loads)
-    }
-#endif
     KS_TICK(1)
     ncon_out = ncon;
     if (!integrate) return;

@@ -19,6 +19,8 @@ changed at a time (VARIANTS); on the fp64 lane with Gaussian noise added to qpos
 fp32 state's own rounding is ~3e-8 relative); and on a MIXED lane (tests/native/ks_lanecheck.cpp: substep_mixed) with fp64 in one stage at a time - which stage's
 precision decides.  Outcome (round 5): not the state and not the solver - quantities of the collision stage that keep the same rounding error while a contact rests on
 the same vertices: the depth read off MPR's final portal and the plane pairs' vertex distances (which also pick the rim vertices of a round base).
+The variants "r5warm" (rounds 3-5's warm-portal penetration query) and "r6first" (a pair that penetrated skips the distance query) went with their
+switches in ks_core.h: the results recorded beside profiles/r05_divergence_table.txt stay (host-lane column of profiles/r06_mpr_variants.txt), and commit 2dfb63a is the last tree that builds them.
 usage: python -m tests.studies.divergence_table > profiles/r05_divergence_table.txt"""
 import sys
 from collections import Counter
@@ -83,11 +85,9 @@ VARIANTS = {   # host builds of the kernel source with experiment switches (fp32
     "r4+mink64": ["-DKS_MPR_SM=0", "-DKS_REFINE_F64=0", "-DKS_PLANE_F64=0", "-DKS_MINK_F64=1"],        # ... with the Minkowski points formed in fp64
     "r5a": ["-DKS_MPR_SM=0", "-DKS_PLANE_F64=0"],                                  # depth / direction of MPR's final portal in fp64 (KS_REFINE_F64=1), plane pairs fp32
     "r5a+plane1": ["-DKS_MPR_SM=0", "-DKS_PLANE_F64=1"],                           # ... + the staged plane contacts' depths in fp64
-    "r5": ["-DKS_MPR_SM=0"],                                      # round 5's product arithmetic, cold queries (the lane's; the GPU's queries were warm: "r5warm/warm")
-    "r5warm": ["-DKS_MPR_SM=0", "-DKS_MPR_WARM=1"],               # ... as the GPU ran it through ks_step (run as "r5warm/warm": the lane keeps its pair memory)
-    "r6": [],
-    "r6first": ["-DKS_MPR_FIRST=3"],                              # ... and a pair that penetrated in the previous substep skips the distance query                                                     # round 6, the product: the penetration query cold, on fp64 Minkowski points, one support site
-}
+    "r5": ["-DKS_MPR_SM=0"],                                      # round 5's product arithmetic, cold queries (the lane's; the GPU's penetration queries were warm)
+    "r6": [],                                                     # round 6, the product: the penetration query cold, on fp64 Minkowski points, one support site
+}                                                                 # (a name run as "<name>/warm": the lane keeps its pair memory from substep to substep, as the GPU's lanes do)
 
 
 def _variant_so(name):

@@ -230,6 +230,26 @@ def test_learner_and_rollout_glue_kernels_use_no_lds():
     assert len(re.findall(r"__shared__", mlp)) == 3          # H1, H2, P of k_mlp3
 
 
+def test_every_build_switch_is_in_the_switch_table():
+    """docs/kernels.md, "Build switches", lists every KS_* macro that a preprocessor conditional in csrc/ tests, with its default, kind and
+    user - and nothing else: a new switch has to be written down with who builds it, a retired one has to leave the table."""
+    tested = set()
+    for f in (ROOT / "kinovagrasping_amd" / "csrc").iterdir():
+        for line in f.read_text().splitlines():
+            if re.match(r"\s*#\s*(if|ifdef|ifndef|elif)\b", line):
+                tested.update(re.findall(r"\bKS_[A-Z0-9_]+\b", line))
+    doc = (ROOT / "docs" / "kernels.md").read_text()
+    section = doc.split("\n## Build switches\n", 1)[1].split("\n## ", 1)[0]
+    rows = [re.match(r"\| `(KS_[A-Z0-9_]+)` \|(.*)\|\s*$", line) for line in section.splitlines() if line.startswith("| `")]
+    assert rows and all(rows), section
+    table = [r.group(1) for r in rows]
+    assert len(table) == len(set(table)), sorted(n for n in table if table.count(n) > 1)
+    assert set(table) == tested, (sorted(tested - set(table)), sorted(set(table) - tested))
+    for r in rows:                                           # default | kind | user: none of them left empty
+        cells = [c.strip() for c in r.group(2).split("|")]
+        assert len(cells) == 3 and all(cells), r.group(0)
+
+
 def test_orientation_noise_is_zero_mean_truncated_and_seeded():
     """reset(with_noise="zero-mean") (SURVEY note N5's extension): class Euler constants + zero-mean N(0, 0.087), then the reference's
     5-character truncation (ENV:870-874); without an rng exactly the class quaternion."""
