@@ -12,7 +12,7 @@
      hand by ~5 mm per env-step on average while the fingers close - as in the reference, main_DDPGfD.py:443-446.)
 
     python examples/train_ddpgfd.py --envs 1024 --steps 600 --hidden 256 256 [--free-running] [--expert-prob 0] [--starts-per-env 64]
-                                    [--success-map DIR]
+                                    [--success-map DIR] [--demonstrations free-running]
 
 --success-map DIR (with --free-running): the stepping kernel logs every finished training episode (ks_set_episode_log); at every report
 the script folds the log (metrics.EpisodeLedger) and writes DIR/per_shape_success.jsonl and the success / fail start coordinates of the
@@ -37,7 +37,7 @@ import torch
 sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
 from kinovagrasping_amd import scenarios                       # noqa: E402
 from kinovagrasping_amd.ddpgfd import DDPGfD                   # noqa: E402
-from kinovagrasping_amd.demonstrators import run_controller_episodes  # noqa: E402
+from kinovagrasping_amd.demonstrators import run_controller_episodes, run_controller_free_running  # noqa: E402
 from kinovagrasping_amd.evaluate import eval_policy, eval_policy_free_running  # noqa: E402
 from kinovagrasping_amd.metrics import EpisodeLedger, save_heatmap_coords      # noqa: E402
 from kinovagrasping_amd.replay import DeviceEpisodeReplay      # noqa: E402
@@ -61,6 +61,9 @@ def main():
     ap.add_argument("--seed", type=int, default=2)
     ap.add_argument("--expert-episodes", type=int, default=2048)
     ap.add_argument("--controller", default="combined", choices=["naive", "position-dependent", "combined"])
+    ap.add_argument("--demonstrations", default="loop", choices=["loop", "free-running"], help="how the expert replay is filled: the Python loop around "
+                    "ks_step, one episode per env and pass (loop), or the controller inside the persistent rollout kernel on an auto-reset context "
+                    "whose envs draw their starts from a pool (free-running: ks_set_rollout_controller; --starts-per-env sets the pool's size, default 8)")
     ap.add_argument("--expert-prob", type=float, default=0.3, help="share of expert episodes in a batch (DDPGfD.py:232-254); 0: plain DDPG, no demonstrations")
     ap.add_argument("--eval-every", type=int, default=600, help="env-steps between evaluations without exploration noise (0: none)")
     ap.add_argument("--free-running", action="store_true", help="the persistent rollout kernel (ks_rollout) instead of one launch per env-step")
@@ -88,9 +91,17 @@ def main():
 
     # 1. expert replay: the combined controller with the demonstration loop of expert_data.py:746-804
     expert = DeviceEpisodeReplay(n, capacity=args.expert_episodes, device=dev) if args.expert_prob > 0 else None
-    sim = KinovaSim(n, args.shape, auto_reset=False, horizon=30)
+    free_demos = args.demonstrations == "free-running"
+    sim = KinovaSim(n, args.shape, auto_reset=free_demos, horizon=30)
     succ = []
-    while expert is not None and expert.count < args.expert_episodes:
+    if expert is not None and free_demos:
+        kd = args.starts_per_env if args.starts_per_env > 0 else 8
+        qd, hqd, _ = scenarios.draw_start_pool([args.shape] * n, "normal", kd, rng)
+        sim.set_start_pool(torch.as_tensor(qd), torch.as_tensor(hqd), seed=args.seed)
+        out = run_controller_free_running(sim, expert, episodes_per_env=-(-args.expert_episodes // n), mode=args.controller, object_names=[args.shape])
+        succ.append(out["success"].float().mean().item())
+        print(f"demonstrations on the free-running path: {out['env_steps']} env-steps, {out['episodes_dropped']} episodes dropped")
+    while expert is not None and not free_demos and expert.count < args.expert_episodes:
         q0, hq = start_states(n, args.shape, rng)
         out = run_controller_episodes(sim, sim.reset(torch.as_tensor(q0), torch.as_tensor(hq)), expert, mode=args.controller)
         succ.append(out["success"].float().mean().item())

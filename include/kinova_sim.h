@@ -16,6 +16,8 @@
  *   ks_set_episode_log /
  *   ks_get_episode_log       <- the per-episode outcome eval_policy collects: success / fail start coordinates per orientation,
  *                               main_DDPGfD.py:130-272, 310-330 - for the episodes that end inside ks_step / ks_rollout
+ *   ks_set_rollout_controller<- the scripted demonstrators that act instead of the actor: expert_data.py:318-671 (get_action) with the
+ *                               lift rule of expert_data.py:746-804 or main_DDPGfD.py:418-439 - inside ks_rollout
  *   ks_step                  <- KinovaGripper_Env.step: action->ctrl, 15 x sim.step(),
  *                               _get_obs(), _get_reward()                           ENV:1495-1552
  *                               + gym TimeLimit (max_episode_steps)                 gym_kinova_gripper/__init__.py:3-7, main_DDPGfD.py:384
@@ -263,7 +265,14 @@ int ks_obs_from_snapshot(ks_ctx *ctx, const void *snap, const void *rays, void *
  *     rows are that same rounding, the reward is rounded once.  So per env the trajectory equals the lock-step
  *     kr_actor_select -> ks_step -> (sim outputs rounded to fp32) -> kr_store_transition, bit for bit.  One persistent workgroup
  *     per compute unit steps its 16-env groups in turn, barrier-joined (KS_PLAN_WORKGROUPS, or KS_PLAN_RUNS / KS_PLAN_ROUND_ROBIN
- *     with more groups than workgroups); no ready queue, no time budget (budget_ticks != 0: KS_ERR_STATE). */
+ *     with more groups than workgroups); no ready queue, no time budget (budget_ticks != 0: KS_ERR_STATE).
+ * Scripted demonstrators (ks_set_rollout_controller below): with a controller set, the policy phase of every env-step is the
+ * controller's rule instead of the actor forward and the check_grasp / scripted-lift rule - in every scheduling form, both
+ * precisions (the exact mode feeds it the fp32 rounding of the fp64 observation, as it feeds the actor), both libraries.  actor_pub,
+ * actor_ver, actor_stride, the offsets, h1 / h2, sigma and max_action are then ignored and the pointers may be NULL.  Everything behind
+ * the action is unchanged - lift steps are not stored, an episode that ends during the lift writes its outcome into the last stored
+ * transition (the demonstration loop's own storage rule, expert_data.py:789-793), the hand-over, the keep rule, counters, log and
+ * pool - so per env trajectory and stored transitions are those of kr_controller_select -> ks_step -> kr_store_transition. */
 typedef struct {
     const float *actor_pub;
     const int64_t *actor_ver;
@@ -302,6 +311,24 @@ typedef struct {
     int64_t *repeats;
 } ks_rollout_args;
 int ks_rollout(ks_ctx *ctx, int32_t n_iter, const ks_rollout_args *args_host, void *stream);
+
+/* The scripted demonstrators on the free-running path: the reference's naive, position-dependent and combined controllers
+ * (expert_data.py:318-671; main_DDPGfD.py --mode naive / combined) act in ks_rollout instead of the actor.  The context owns a small
+ * record in device memory (mode, lift rule, and a context-owned float [2][N] holding every env's (obs[21], obs[81]) of its episode's
+ * start) that `stream` writes - like the start pool's and the episode log's - so a ks_rollout captured BEFORE this call acts by the
+ * controller when the graph is replayed after it.  (The reverse needs care: a ks_rollout issued with NULL actor pointers must not
+ * run once the controller has been cleared.)  The call zeroes the [2][N] buffer: it is meant for episode boundaries - an env that is
+ * mid-episode (t > 0) when the controller is set uses (0, 0) as its start values until its next episode begins.
+ * lift_rule: KS_LIFT_RULE_TRAIN (ready |= check_grasp && has_prev && t + 1 >= skip_steps; lifting = ready) or KS_LIFT_RULE_EXPERT
+ * (ready |= check_grasp && has_prev && t >= 2; lifting = ready && t > 10) - kinova_rollout.h, kr_controller_select.
+ * KS_CONTROLLER_NONE clears the record: the actor path again (lift_rule is then ignored).  KS_ERR_STATE before ks_load_model,
+ * KS_ERR_INVALID for values out of range.  No host synchronisation.  Both precisions, both libraries.
+ * ks_get_rollout_controller: *mode / *lift_rule (host) as last set, and a device-to-device copy of the start values (init: device float
+ * [2, N]), asynchronous on `stream`; any pointer may be NULL.  KS_ERR_STATE before ks_load_model. */
+enum { KS_CONTROLLER_NONE = 0, KS_CONTROLLER_NAIVE = 1, KS_CONTROLLER_POSITION_DEPENDENT = 2, KS_CONTROLLER_COMBINED = 3 };
+enum { KS_LIFT_RULE_TRAIN = 0, KS_LIFT_RULE_EXPERT = 1 };
+int ks_set_rollout_controller(ks_ctx *ctx, int32_t mode, int32_t lift_rule, void *stream);
+int ks_get_rollout_controller(ks_ctx *ctx, int32_t *mode, int32_t *lift_rule, float *init, void *stream);
 
 /* How ks_rollout would schedule this context's env groups (16 envs sharing one object's hull tables) on the device it runs on - the library's
  * own decision, for callers that report or warn about it (bench.py, pipeline.AsyncTrainer; ADVICE r5: they used to re-derive it from environment

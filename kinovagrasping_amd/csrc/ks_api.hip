@@ -65,6 +65,14 @@ template <typename T> struct EpisodeLog {
     const StartPool<T> *pool;                   // the start pool's record: index[env] is the entry the finished episode started from
 };
 
+// The scripted controller of a context (ks_set_rollout_controller): which of the reference's demonstrators acts in ks_rollout instead
+// of the actor, and the per-env start values its rule latches - like the two records above, one record in device memory that the stream
+// writes (k_controller_set), so that a captured ks_rollout follows whatever the context holds when the graph is replayed.  mode = 0: none.
+struct RolloutController {
+    int32_t mode, lift_rule;
+    float *init;                                // [2][N] (obs[21], obs[81]) at the start of every env's running episode
+};
+
 template <typename T> struct Buffers {
     T *qpos, *qvel, *warm;        // [16|15|15][N]
     T *hand_quat, *qpos0;         // [4][N], [16][N]   stored initial state
@@ -94,6 +102,7 @@ template <typename T> struct Buffers {
     int32_t *rayq;
     StartPool<T> *pool;           // [1] the start pool's record (k = 0: none); read only where an episode restarts
     EpisodeLog<T> *elog;          // [1] the episode log's record (capacity = 0: none); read only where an episode restarts
+    RolloutController *ctl;       // [1] the scripted controller's record (mode = 0: none); read by the rollout kernels' policy phase
 };
 
 template <typename T> struct ColW {
@@ -828,6 +837,21 @@ __device__ __noinline__ void rollout_policy(const ks_rollout_args* __restrict__ 
     }
 }
 
+// The policy phase with a scripted controller set (ks_set_rollout_controller): one lane per env of the group (row_env < 0: not this
+// lane's), the rule of ks_controller.h on the engine's fp32 rows - no actor forward, no version counter, no staleness loop.  Out of line
+// like the phases around it, one copy for every rollout kernel: its registers are its own.
+__device__ __noinline__ void rollout_controller(const RolloutController* __restrict__ ctl, const ks_rollout_args* __restrict__ rap, int N, int row_env) {
+    if (row_env < 0) return;
+    const ks_rollout_args& ra = *rap;
+    krsel::controller_one(row_env, N, ctl->mode, ctl->lift_rule, ra.obs, ra.prev_obs, ra.has_prev, ra.t, ra.ready, ctl->init, ra.skip_steps, ra.action,
+                          ra.action_t, ra.lifting);
+}
+__global__ void k_controller_set(RolloutController* rec, RolloutController v, int N) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i == 0) *rec = v;
+    if (v.mode != 0 && i < 2 * N) v.init[i] = 0.0f;
+}
+
 // replay write + per-env bookkeeping of one env by its 16-lane team (k_store_transition of ks_rollout.hip + the episode hand-over).
 // R: the type of the context's outputs (sim_*): float, or double in the exact mode - rounded to float once, here, as the lock-step
 // RolloutEngine rounds them before kr_store_transition.
@@ -943,7 +967,8 @@ __device__ __forceinline__ void rollout_iter(const Model<float>& m, const Hulls<
     {
         const int nn = threadIdx.x & 15;
         const int row_env = nn < epw ? b.slot_env[grp * epw + nn] : -1;   // the policy row of this lane (the same in all four waves)
-        rollout_policy<NT1, NT2>(rap, N, row_env, blocks);
+        if (b.ctl->mode != 0) rollout_controller(b.ctl, rap, N, threadIdx.x < 16 ? row_env : -1);      // (uniform: a scripted controller acts)
+        else rollout_policy<NT1, NT2>(rap, N, row_env, blocks);
     }
     __threadfence_block();
     __syncthreads();
@@ -1077,7 +1102,8 @@ __device__ __forceinline__ void rollout_iter_wave(const Model<float>& m, const H
     {
         const int nn = lane & 15;
         const int row_env = nn < wepw ? b.slot_env[wslot0 + nn] : -1;
-        rollout_policy_wave<NT1, NT2>(rap, N, row_env, wblocks);
+        if (b.ctl->mode != 0) rollout_controller(b.ctl, rap, N, lane < 16 ? row_env : -1);
+        else rollout_policy_wave<NT1, NT2>(rap, N, row_env, wblocks);
     }
     C::sync();
     KS_RS(0)
@@ -1862,7 +1888,8 @@ __device__ __forceinline__ void rollout_iter_f64(const Model<double>* __restrict
     {
         const int nn = threadIdx.x & 15;
         const int row_env = nn < epw ? b.slot_env[grp * epw + nn] : -1;
-        rollout_policy<NT1, NT2, true>(rap, N, row_env, ws);
+        if (b.ctl->mode != 0) rollout_controller(b.ctl, rap, N, threadIdx.x < 16 ? row_env : -1);
+        else rollout_policy<NT1, NT2, true>(rap, N, row_env, ws);
     }
     __threadfence_block();
     __syncthreads();
@@ -1961,6 +1988,8 @@ struct CtxBase {
     virtual int get_start_index(int32_t* index, int64_t* episode, hipStream_t s) = 0;
     virtual int set_episode_log(int capacity, hipStream_t s) = 0;
     virtual int get_episode_log(ks_episode_record* ring_out, int64_t* written_out, hipStream_t s) = 0;
+    virtual int set_rollout_controller(int mode, int lift_rule, hipStream_t s) = 0;
+    virtual int get_rollout_controller(int32_t* mode, int32_t* lift_rule, float* init, hipStream_t s) = 0;
 };
 
 #define HIPCHK(expr)                                                                         \
@@ -2018,6 +2047,9 @@ template <typename T> struct Ctx : CtxBase {
     size_t elog_cap = 0;                  // records the ring's storage holds
     unsigned long long* elog_written = nullptr;
     int32_t* elog_ordinal = nullptr;
+    // the scripted controller (ks_set_rollout_controller): the mode as the host last set it, and the envs' start values
+    int ctl_mode = 0, ctl_lift_rule = 0;
+    float* ctl_init = nullptr;            // [2][N]
     int n_models = 0, n_wg = 0;
     int32_t n_groups = 0;                 // groups of the slot list that hold envs (<= n_wg): what ks_rollout deals
     std::map<std::pair<size_t, uint64_t>, void*> shared;      // uploaded arrays by (bytes, content hash): the hand's meshes are
@@ -2066,6 +2098,8 @@ template <typename T> struct Ctx : CtxBase {
         if ((r = alloc(&b.elog, (size_t)1))) return r;          // zeroed: capacity = 0, no log
         if ((r = alloc(&elog_written, (size_t)1))) return r;
         if ((r = alloc(&elog_ordinal, N))) return r;
+        if ((r = alloc(&b.ctl, (size_t)1))) return r;           // zeroed: mode = 0, no controller
+        if ((r = alloc(&ctl_init, 2 * N))) return r;
         ev0.resize(NEV); ev1.resize(NEV);
         for (int i = 0; i < NEV; i++) { HIPCHK(hipEventCreate(&ev0[i])); HIPCHK(hipEventCreate(&ev1[i])); }
         return KS_OK;
@@ -2308,7 +2342,7 @@ template <typename T> struct Ctx : CtxBase {
     }
     // the checks of ks_rollout's arguments that every form makes: the buffers ...
     int check_rollout_buffers(int n_iter, const ks_rollout_args* ra) {
-        if (!ra || n_iter <= 0 || !ra->actor_pub || !ra->actor_ver || !ra->obs || !ra->prev_obs || !ra->has_prev || !ra->ready || !ra->lifting ||
+        if (!ra || n_iter <= 0 || (ctl_mode == 0 && (!ra->actor_pub || !ra->actor_ver)) || !ra->obs || !ra->prev_obs || !ra->has_prev || !ra->ready || !ra->lifting ||
             !ra->t || !ra->steps_total || !ra->action || !ra->action_t || !ra->reward_out || !ra->done_out || !ra->sim_obs || !ra->sim_reward ||
             !ra->sim_done || !ra->sim_info || !ra->sim_final_obs || !ra->counters) { error = "ks_rollout: NULL argument"; return KS_ERR_INVALID; }
         if (ra->with_replay && (!ra->cur_state || !ra->cur_next || !ra->cur_action || !ra->cur_reward || !ra->cur_not_done || !ra->cur_len ||
@@ -2317,6 +2351,7 @@ template <typename T> struct Ctx : CtxBase {
     }
     // ... and the actor's layout
     int check_rollout_actor(const ks_rollout_args* ra) {
+        if (ctl_mode != 0) return KS_OK;                       // a scripted controller acts: the actor's fields are ignored
         if ((ra->off_w2 | ra->off_w3 | ra->actor_stride) & 3) { error = "ks_rollout: weight offsets must be multiples of 4 floats"; return KS_ERR_INVALID; }
         if ((ra->h1 | ra->h2) & 3) { error = "ks_rollout: hidden widths must be multiples of 4"; return KS_ERR_INVALID; }
         return KS_OK;
@@ -2355,8 +2390,10 @@ template <typename T> struct Ctx : CtxBase {
         if (lds > 160 * 1024) { error = "ks_rollout: no LDS for the policy beside this object's hull tables"; return KS_ERR_STATE; }
         if ((r = send_rollout_records(ra, s))) return r;
         const int N = cfg.n_envs;
+        const int t1 = (ra->h1 + 15) / 16, t2 = (ra->h2 + 15) / 16;
+        const bool no_actor = ctl_mode != 0 && !((t1 == 25 && t2 == 19) || (t1 == 8 && t2 == 8) || (t1 == 4 && t2 == 4));     // (any instantiation serves a controller)
 #define KS_ROLLOUT_F64_CASE(A, B)                                                                                                                     \
-    if ((ra->h1 + 15) / 16 == A && (ra->h2 + 15) / 16 == B) {                                                                                             \
+    if ((t1 == A && t2 == B) || (A == 16 && no_actor)) {                                                                                             \
         HIPCHK(hipFuncSetAttribute((const void*)k_rollout_f64<A, B>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                          \
         hipLaunchKernelGGL((k_rollout_f64<A, B>), dim3(n_groups < resident_wgs ? n_groups : resident_wgs), dim3(WG), lds, s, d_model, b,                  \
                            (const Buffers<T>*)d_b, N, cfg.frame_skip, cfg.solver_iterations, lpw, (const ObsOut<T>*)d_out, (const ks_rollout_args*)d_ra,    \
@@ -2398,8 +2435,10 @@ template <typename T> struct Ctx : CtxBase {
                 if (rollout_phase_deal == 2 && N <= PHASE_ENVS_MAX) hipLaunchKernelGGL(k_slots_by_phase, dim3(1), dim3(PHASE_THREADS), 0, s, (const int64_t*)ra->t, N, n_wg * lpw, b.slot_env);
                 else if (lpw <= 16) hipLaunchKernelGGL(k_slots_by_phase_in_groups, dim3((n_groups + 255) / 256), dim3(256), 0, s, (const int64_t*)ra->t, n_groups, lpw, b.slot_env);
             }
+            const int t1 = (ra->h1 + 15) / 16, t2 = (ra->h2 + 15) / 16;
+            const bool no_actor = ctl_mode != 0 && !((t1 == 25 && t2 == 19) || (t1 == 8 && t2 == 8) || (t1 == 4 && t2 == 4));     // (any instantiation serves a controller)
 #define KS_ROLLOUT_CASE(A, B)                                                                                                                         \
-    if ((ra->h1 + 15) / 16 == A && (ra->h2 + 15) / 16 == B) {                                                                                                 \
+    if ((t1 == A && t2 == B) || (A == 16 && no_actor)) {                                                                                                 \
         HIPCHK(hipFuncSetAttribute((const void*)k_rollout<A, B>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)step_lds));                        \
         hipLaunchKernelGGL((k_rollout<A, B>), dim3(n_groups < resident_wgs ? n_groups : resident_wgs), dim3(WG), step_lds, s, d_model, b, (const Buffers<T>*)d_b, N, cfg.frame_skip,              \
                            cfg.solver_iterations, lpw, (int)cfg.pair_memory, (const ObsOut<T>*)d_out, (const ks_rollout_args*)d_ra, n_iter,                                              \
@@ -2537,6 +2576,27 @@ template <typename T> struct Ctx : CtxBase {
         hipLaunchKernelGGL((k_elog_begin<T>), dim3((N + 255) / 256), dim3(256), 0, s, b, rec, N);
         HIPCHK(hipGetLastError());
         elog_capacity = capacity;
+        return KS_OK;
+    }
+    int set_rollout_controller(int mode, int lift_rule, hipStream_t s) override {
+        if (!model_loaded) { error = "ks_set_rollout_controller before ks_load_model"; return KS_ERR_STATE; }
+        if (mode != KS_CONTROLLER_NONE && !krsel::controller_args_ok(mode, lift_rule)) {
+            error = "ks_set_rollout_controller: mode 0 (none), 1 (naive), 2 (position-dependent) or 3 (combined); lift rule 0 (train) or 1 (expert)";
+            return KS_ERR_INVALID;
+        }
+        const int N = cfg.n_envs;
+        const RolloutController rec{mode, mode != KS_CONTROLLER_NONE ? lift_rule : 0, ctl_init};
+        hipLaunchKernelGGL(k_controller_set, dim3(mode != KS_CONTROLLER_NONE ? (2 * N + 255) / 256 : 1), dim3(256), 0, s, b.ctl, rec, N);
+        HIPCHK(hipGetLastError());
+        ctl_mode = mode;
+        ctl_lift_rule = rec.lift_rule;
+        return KS_OK;
+    }
+    int get_rollout_controller(int32_t* mode, int32_t* lift_rule, float* init, hipStream_t s) override {
+        if (!model_loaded) { error = "ks_get_rollout_controller before ks_load_model"; return KS_ERR_STATE; }
+        if (mode) *mode = ctl_mode;
+        if (lift_rule) *lift_rule = ctl_lift_rule;
+        if (init) HIPCHK(hipMemcpyAsync(init, ctl_init, (size_t)2 * cfg.n_envs * sizeof(float), hipMemcpyDeviceToDevice, s));
         return KS_OK;
     }
     int get_episode_log(ks_episode_record* ring_out, int64_t* written_out, hipStream_t s) override {
@@ -2711,6 +2771,14 @@ int ks_get_start_index(ks_ctx* ctx, int32_t* index, int64_t* episode, void* stre
 int ks_set_episode_log(ks_ctx* ctx, int32_t capacity, void* stream) {
     if (!ctx) return KS_ERR_INVALID;
     return ctx->impl->set_episode_log(capacity, (hipStream_t)stream);
+}
+int ks_set_rollout_controller(ks_ctx* ctx, int32_t mode, int32_t lift_rule, void* stream) {
+    if (!ctx) return KS_ERR_INVALID;
+    return ctx->impl->set_rollout_controller(mode, lift_rule, (hipStream_t)stream);
+}
+int ks_get_rollout_controller(ks_ctx* ctx, int32_t* mode, int32_t* lift_rule, float* init, void* stream) {
+    if (!ctx) return KS_ERR_INVALID;
+    return ctx->impl->get_rollout_controller(mode, lift_rule, init, (hipStream_t)stream);
 }
 int ks_get_episode_log(ks_ctx* ctx, ks_episode_record* ring_out, int64_t* written_out, void* stream) {
     if (!ctx) return KS_ERR_INVALID;

@@ -28,6 +28,16 @@ __global__ __launch_bounds__(256) void k_select_action(int n, const float* __res
     krsel::select_one(i, n, pi, nz, obs, prev_obs, has_prev, t, ready, sigma, max_action, skip_steps, action, action_t, lifting);
 }
 
+// the scripted demonstrators in k_select_action's place (ks_controller.h): one env per lane
+__global__ __launch_bounds__(256) void k_controller_select(int n, int mode, int lift_rule, const float* __restrict__ obs,
+                                                           const float* __restrict__ prev_obs, const uint8_t* __restrict__ has_prev,
+                                                           const int64_t* __restrict__ t, uint8_t* ready, float* init, int skip_steps,
+                                                           float* __restrict__ action, float* __restrict__ action_t, uint8_t* __restrict__ lifting) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    krsel::controller_one(i, n, mode, lift_rule, obs, prev_obs, has_prev, t, ready, init, skip_steps, action, action_t, lifting);
+}
+
 // one wave per env
 __global__ __launch_bounds__(WAVE) void k_store_transition(int n, int H, int n_steps, int auto_reset, int with_replay,
                                                            const float* __restrict__ sim_obs, const float* __restrict__ sim_final,
@@ -345,6 +355,15 @@ int kr_select_action(int32_t n, const float* obs, const float* prev_obs, const u
     if (n <= 0 || !obs || !prev_obs || !has_prev || !t || !ready || !actor_out || !noise || !action || !action_t || !lifting) return KS_ERR_INVALID;
     hipLaunchKernelGGL(k_select_action, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, n, obs, prev_obs, has_prev, t, ready, actor_out,
                        noise, sigma, max_action, skip_steps, action, action_t, lifting);
+    return launched();
+}
+
+int kr_controller_select(int32_t n, int32_t mode, int32_t lift_rule, const float* obs, const float* prev_obs, const uint8_t* has_prev, const int64_t* t,
+                         uint8_t* ready, float* init, int32_t skip_steps, float* action, float* action_t, uint8_t* lifting, void* stream) {
+    if (n <= 0 || !krsel::controller_args_ok(mode, lift_rule) || !obs || !prev_obs || !has_prev || !t || !ready || !init || !action || !action_t || !lifting)
+        return KS_ERR_INVALID;
+    hipLaunchKernelGGL(k_controller_select, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, n, mode, lift_rule, obs, prev_obs, has_prev, t, ready,
+                       init, skip_steps, action, action_t, lifting);
     return launched();
 }
 

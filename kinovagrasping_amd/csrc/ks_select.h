@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "ks_controller.h"      // krsel::controller_one: the scripted demonstrators' rule, reachable from the same three places
+
 namespace krsel {
 
 constexpr int S = 82, A = 4;

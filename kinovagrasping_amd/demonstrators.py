@@ -175,3 +175,82 @@ def run_naive_episodes(sim, obs0: torch.Tensor, replay=None, horizon: int = 30):
     if replay is not None:
         replay.end_episodes(torch.ones(n, dtype=torch.bool, device=dev))
     return {"success": success, "steps": steps, "total_reward": total}
+
+
+@torch.no_grad()
+def run_controller_free_running(sim, replay=None, episodes_per_env: int = 1, mode: str = "combined", lift_rule: str = "expert", classes="normal",
+                                chunk: int | None = None, object_names=None):
+    """run_controller_episodes on the free-running path (after evaluate.eval_policy_free_running): the scripted demonstrator acts inside
+    ks_rollout (sim.set_rollout_controller: csrc/ks_controller.h, the arithmetic of controller_action) on an AUTO-RESET context, whose
+    stepping kernel writes one record per finished episode into the context's episode log - until every env has logged
+    `episodes_per_env` episodes.  An env that is done early goes on with further episodes meanwhile (with a start pool: from further
+    starts); only each env's first `episodes_per_env` count in the result.
+    replay: a DeviceEpisodeReplay (the expert replay) that receives EVERY kept episode of the run, the uncounted ones too, by the
+    demonstration loop's storage rule (lift steps unstored, the outcome of an episode that ends during the lift in its last stored
+    transition) - handed over between the launches (replay.commit_published()).  An env has two open-episode buffers, so a launch
+    must be shorter than two episodes of an env: chunk defaults to the shortest episode the lift rule allows (12 env-steps for
+    "expert", 6 for "train"; the time limit if that is shorter) with a replay and to the time limit without one; `episodes_dropped`
+    counts the episodes that found no free buffer all the same.
+    The envs must stand at the start of an episode: call it behind sim.reset / sim.set_start_pool.  Sets a controller and an episode log
+    of its own on `sim` and clears both afterwards.  classes / object_names: as in eval_policy_free_running.
+    Returns `success` and `steps` ([N] tensors; [N, episodes_per_env] for more than one episode), `start_index`, `per_object`,
+    `success_coords` / `fail_coords`, `num_success`, `env_steps` and `episodes_dropped`."""
+    from .metrics import EpisodeLedger
+    from .pipeline import rollout_args
+    from .rollout import RolloutEngine
+    from .sim import EPISODE_LOG_CAPACITY_MAX, controller_codes
+    controller_codes(mode, lift_rule)
+    if mode is None:
+        raise ValueError("run_controller_free_running needs a controller mode")
+    n, dev, E = sim.n_envs, sim.device, int(episodes_per_env)
+    horizon = int(sim.cfg.horizon)
+    if not (sim.cfg.auto_reset and sim.obs_env_major) or horizon <= 0 or E < 1:
+        raise ValueError("run_controller_free_running needs an auto-reset context with env-major observations and a time limit, and episodes_per_env >= 1")
+    eng = RolloutEngine(sim, None, replay, controller=mode, lift_rule=lift_rule)
+    eng.start(sim.obs)
+    if replay is not None:
+        replay.enable_async()
+    steps_total, counters = torch.zeros(n, dtype=torch.long, device=dev), torch.zeros(8 + 4 * 512 + 8, dtype=torch.long, device=dev)
+    args = rollout_args(sim, None, eng, None, None, steps_total, counters, replay=replay)
+    if chunk is None:
+        shortest = MIN_LIFT_TIMESTEPS + 2 if lift_rule == "expert" else SKIP_NUM_TS
+        chunk = horizon if replay is None else min(horizon, shortest)
+    chunk = int(chunk)
+    n_obj = len(getattr(sim, "models", [None]))
+    ledger = EpisodeLedger(n, n_obj, None)
+    success = torch.zeros(n, E, dtype=torch.bool, device=dev)
+    steps = torch.zeros(n, E, dtype=torch.long, device=dev)
+    start = torch.full((n, E), -1, dtype=torch.long, device=dev)
+    have = torch.zeros(n, dtype=torch.long, device=dev)
+    launches, limit = 0, (E * horizon + chunk - 1) // chunk + 1
+    sim.set_rollout_controller(mode, lift_rule)
+    try:
+        # at most one record per env and env-step: a launch's records always fit, whatever the envs do
+        sim.set_episode_log(min(max(n * chunk, n), EPISODE_LOG_CAPACITY_MAX))
+        while int(have.min()) < E:
+            if launches >= limit:
+                raise RuntimeError(f"run_controller_free_running: {launches} launches of {chunk} env-steps and an env has logged {int(have.min())} of {E} episodes")
+            sim.rollout(chunk, args)
+            launches += 1
+            if replay is not None:
+                replay.commit_published()
+            rec = sim.episode_log()
+            if rec["lost"]:
+                raise RuntimeError(f"run_controller_free_running: the episode log lost {rec['lost']} records")
+            m = rec["episode"] < E
+            counted = {k: (v[m] if torch.is_tensor(v) else v) for k, v in rec.items()}
+            e, j = counted["env"].long(), counted["episode"].long()
+            success[e, j] = (counted["done"] & 1) != 0
+            steps[e, j] = counted["steps"].long()
+            start[e, j] = counted["start_index"].long()
+            have.index_add_(0, e, torch.ones_like(e))
+            ledger.add(counted)
+    finally:
+        sim.set_rollout_controller(None)
+        if sim.cfg.auto_reset:
+            sim.set_episode_log(0)
+    ok_coords, fail_coords = ledger.coords(classes)
+    sq = (lambda t: t[:, 0]) if E == 1 else (lambda t: t)
+    return {"num_success": int(success.sum()), "success_coords": ok_coords, "fail_coords": fail_coords, "success": sq(success), "steps": sq(steps),
+            "start_index": sq(start), "per_object": ledger.per_object(object_names), "env_steps": launches * chunk * n,
+            "episodes_dropped": int(counters[3].item())}

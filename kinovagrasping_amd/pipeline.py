@@ -338,17 +338,20 @@ def rollout_args(sim, policy, eng, pub, pub_ver, steps_total, counters, replay=N
     (pub [3, stride] with the layout of policy's flat actor parameters, pub_ver the version counter), the engine's state tensors,
     the context's output buffers and - with a replay in its asynchronous form - the open-episode buffers (with_replay = 1); without
     one nothing is stored (with_replay = 0).  sigma: the exploration noise's std, the engine's unless given.  Borrows every tensor:
-    the caller keeps them alive for as long as the record is used."""
+    the caller keeps them alive for as long as the record is used.
+    An engine with a scripted controller (RolloutEngine(controller=...)) needs no actor: policy, pub and pub_ver may be None and the
+    record's actor pointers stay NULL - ks_rollout accepts that only while the context's controller is set (sim.set_rollout_controller)."""
     from .rollout import SKIP_NUM_TS
     from .sim import KsRolloutArgs
-    flat, actor = policy._flat_params["actor"], policy.actor
-    off = lambda t: (t.data_ptr() - flat.data_ptr()) // 4
     P = lambda t: t.data_ptr()
     a = KsRolloutArgs()
-    a.actor_pub, a.actor_ver, a.actor_stride = P(pub), P(pub_ver), pub.shape[1]
-    a.off_w1, a.off_b1, a.off_w2, a.off_b2, a.off_w3, a.off_b3 = (off(actor.l1.weight), off(actor.l1.bias), off(actor.l2.weight), off(actor.l2.bias),
-                                                                  off(actor.l3.weight), off(actor.l3.bias))
-    a.h1, a.h2 = actor.l1.weight.shape[0], actor.l2.weight.shape[0]
+    if getattr(eng, "controller", None) is None or policy is not None:
+        flat, actor = policy._flat_params["actor"], policy.actor
+        off = lambda t: (t.data_ptr() - flat.data_ptr()) // 4
+        a.actor_pub, a.actor_ver, a.actor_stride = P(pub), P(pub_ver), pub.shape[1]
+        a.off_w1, a.off_b1, a.off_w2, a.off_b2, a.off_w3, a.off_b3 = (off(actor.l1.weight), off(actor.l1.bias), off(actor.l2.weight), off(actor.l2.bias),
+                                                                      off(actor.l3.weight), off(actor.l3.bias))
+        a.h1, a.h2 = actor.l1.weight.shape[0], actor.l2.weight.shape[0]
     a.sigma, a.max_action, a.skip_steps, a.with_replay, a.seed = (eng.sigma if sigma is None else sigma), eng.max_action, SKIP_NUM_TS, int(replay is not None), eng.noise_seed
     a.obs, a.prev_obs, a.has_prev, a.ready, a.lifting = P(eng.obs), P(eng.prev_obs), P(eng.has_prev), P(eng.ready), P(eng.lifting)
     a.t, a.steps_total, a.action, a.action_t = P(eng.t), P(steps_total), P(eng.action), P(eng.action_t)

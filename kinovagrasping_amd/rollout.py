@@ -34,8 +34,12 @@ class RolloutEngine:
     selection) and `post()` (replay + bookkeeping) can each be captured in a HIP graph (pipeline.GraphedTrainer);
     `step()` is the plain eager sequence pre -> sim -> post."""
 
-    def __init__(self, sim, policy, replay=None, expl_noise=0.1, max_action=0.8, generator=None, device_noise=None):
-        """device_noise: draw the exploration noise inside the fused actor kernel (counter-based Philox keyed by
+    def __init__(self, sim, policy, replay=None, expl_noise=0.1, max_action=0.8, generator=None, device_noise=None, controller=None,
+                 lift_rule="expert"):
+        """controller: "naive", "position-dependent" or "combined" - a scripted demonstrator (demonstrators.controller_action) selects the
+        actions instead of the actor, with lift rule "expert" or "train" (demonstrators.run_controller_episodes); `policy` may then be None.
+        pre() is then one launch of kr_controller_select; the engine owns the episode's start values `init` [2, n].
+        device_noise: draw the exploration noise inside the fused actor kernel (counter-based Philox keyed by
         torch.initial_seed(), a device step counter and the env index) instead of with torch.randn.  Default: on when no
         torch generator is given and the actor is a 3-layer MLP the fused kernel supports."""
         self.sim, self.policy, self.replay = sim, policy, replay
@@ -72,6 +76,12 @@ class RolloutEngine:
         self.device_noise = (generator is None) if device_noise is None else bool(device_noise)
         self.noise_seed = int(torch.initial_seed()) & 0xFFFFFFFFFFFFFFFF
         self.rng_state = torch.zeros(2, dtype=torch.long, device=dev)        # [launch counter, scratch] of kr_actor_select
+        from .sim import controller_codes
+        self.controller, self.lift_rule = controller, lift_rule
+        self._controller_codes = controller_codes(controller, lift_rule)
+        self.init = torch.zeros(2, self.n, device=dev)                       # (obs[21], obs[81]) at the start of the env's episode
+        if controller is None and policy is None:
+            raise ValueError("RolloutEngine needs a policy or a controller")
 
     def _stream(self):
         import ctypes
@@ -84,10 +94,36 @@ class RolloutEngine:
         self.has_prev.zero_()
         self.t.zero_()
         self.ready.zero_()
+        self.init.zero_()
+
+    def _controller_pre(self):
+        """pre() with a scripted controller: kr_controller_select, or the same rule in torch (its checker)"""
+        mode, rule = self._controller_codes
+        if self.native:
+            P = self._ptr
+            rc = self._lib.kr_controller_select(self.n, mode, rule, P(self.obs), P(self.prev_obs), P(self.has_prev), P(self.t), P(self.ready),
+                                                P(self.init), SKIP_NUM_TS, P(self.action), P(self.action_t), P(self.lifting), self._stream())
+            if rc != 0:
+                raise RuntimeError(f"kr_controller_select failed ({rc})")
+            return
+        from .demonstrators import MIN_LIFT_TIMESTEPS, controller_action
+        first = self.t == 0
+        self.init.copy_(torch.where(first.unsqueeze(0), torch.stack([self.obs[:, 21], self.obs[:, 81]]), self.init))
+        chk = check_grasp(self.prev_obs[:, 9:17], self.obs[:, 9:17]) & self.has_prev
+        if self.lift_rule == "expert":
+            self.ready |= chk & (self.t >= 2)
+            self.lifting.copy_(self.ready & (self.t > MIN_LIFT_TIMESTEPS))
+        else:
+            self.ready |= chk & (self.t + 1 >= SKIP_NUM_TS)
+            self.lifting.copy_(self.ready)
+        self.action.copy_(controller_action(self.controller, self.obs, self.init[0], self.init[1], self.lifting))
+        self.action_t.copy_(self.action.t())
 
     @torch.no_grad()
     def pre(self):
         """Action selection for every env -> self.action [N,4] / self.action_t [4,N]."""
+        if self.controller is not None:
+            return self._controller_pre()
         if self.native:
             layers = self._fused_actor_layers()
             if layers is not None:

@@ -52,6 +52,17 @@ class KsEpisodeRecord(C.Structure):
 
 
 EPISODE_RECORD_WORDS = 8
+# KS_CONTROLLER_* / KS_LIFT_RULE_* of include/kinova_sim.h: the scripted demonstrators of demonstrators.py by name
+CONTROLLER_MODES = {None: 0, "naive": 1, "position-dependent": 2, "combined": 3}
+LIFT_RULES = {"train": 0, "expert": 1}
+
+
+def controller_codes(mode, lift_rule):
+    """(KS_CONTROLLER_*, KS_LIFT_RULE_*) of a controller mode name (None: no controller) and a lift rule name; ValueError for others"""
+    if mode not in CONTROLLER_MODES or lift_rule not in LIFT_RULES:
+        raise ValueError(f"controller {mode!r} / lift rule {lift_rule!r}: one of {[m for m in CONTROLLER_MODES if m]} (or None) and one of {list(LIFT_RULES)}")
+    return CONTROLLER_MODES[mode], LIFT_RULES[lift_rule]
+
 EPISODE_LOG_CAPACITY_MAX = 1 << 24      # KS_EPISODE_LOG_CAPACITY_MAX of include/kinova_sim.h (tests/test_episode_log_cpu.py compares them)
 
 
@@ -81,13 +92,13 @@ def episode_records(words: torch.Tensor) -> dict:
 
 EXPORTS = ["ks_default_config", "ks_create", "ks_destroy", "ks_last_error", "ks_load_model", "ks_load_models", "ks_reset", "ks_reset_objects", "ks_step",
            "ks_get_state", "ks_set_state", "ks_set_env_params", "ks_substep", "ks_rollout", "ks_rollout_plan", "ks_obs_from_snapshot", "ks_kernel_time", "ks_version",
-           "ks_set_start_pool", "ks_get_start_index", "ks_set_episode_log", "ks_get_episode_log"]
+           "ks_set_start_pool", "ks_get_start_index", "ks_set_episode_log", "ks_get_episode_log", "ks_set_rollout_controller", "ks_get_rollout_controller"]
 # include/kinova_rollout.h
 ROLLOUT_EXPORTS = ["kr_select_action", "kr_store_transition", "kr_rank_episodes", "kr_wait_min", "kr_wait_min_counted", "kr_commit_episodes", "kr_advance_ring",
                    "kr_sample_windows", "kr_sample_windows_draw", "kr_sample_windows_mixed", "kr_xchg_create", "kr_xchg_connect", "kr_xchg_allreduce_mean", "kr_xchg_status",
                    "kr_xchg_destroy", "kr_critic_grad", "kr_update_prologue", "kr_relu_backward", "kr_sigmoid_scale_backward", "kr_adam_step", "kr_soft_update",
                    "kr_mlp3_forward", "kr_mlp3_forward_shadow", "kr_mlp3_forward_split", "kr_mlp3_backward_shadow", "kr_mlp3_backward_split", "kr_weight_grad_shadow",
-                   "kr_actor_select"]
+                   "kr_actor_select", "kr_controller_select"]
 
 _lib = None
 _lib_mg = None
@@ -154,8 +165,11 @@ def _bind(L):
     L.ks_get_start_index.argtypes = [vp, vp, vp, vp]
     L.ks_set_episode_log.argtypes = [vp, C.c_int32, vp]
     L.ks_get_episode_log.argtypes = [vp, vp, vp, vp]
+    L.ks_set_rollout_controller.argtypes = [vp, C.c_int32, C.c_int32, vp]
+    L.ks_get_rollout_controller.argtypes = [vp, vp, vp, vp, vp]
     i32, f32 = C.c_int32, C.c_float
     L.kr_select_action.argtypes = [i32] + [vp] * 7 + [f32, f32, i32] + [vp] * 4
+    L.kr_controller_select.argtypes = [i32] * 3 + [vp] * 6 + [i32] + [vp] * 4
     L.kr_store_transition.argtypes = [i32] * 5 + [vp] * 21
     L.kr_rank_episodes.argtypes = [i32, vp, vp, vp, vp]
     L.kr_wait_min.argtypes = [vp, i32, C.c_int64, C.c_double, vp]
@@ -327,6 +341,21 @@ class KinovaSim:
         out = episode_records(words)
         out["lost"], out["written"] = lost, total
         return out
+
+    def set_rollout_controller(self, mode: str | None, lift_rule: str = "expert"):
+        """A scripted demonstrator - "naive", "position-dependent" or "combined" (demonstrators.controller_action) with lift rule "expert" or
+        "train" (demonstrators.run_controller_episodes) - acts in ks_rollout instead of the actor, from the next launch on the current stream
+        (ks_set_rollout_controller).  Meant for episode boundaries: call it right after a reset.  None returns to the actor path."""
+        m, r = controller_codes(mode, lift_rule)
+        self._check(self.lib.ks_set_rollout_controller(self.ctx, m, r, self._stream()))
+        self.rollout_controller = mode
+
+    def rollout_controller_init(self):
+        """float32 [2, N]: the (obs[21], obs[81]) every env's running episode started with, as the in-kernel controller latched them
+        (ks_get_rollout_controller; a device copy behind the work queued on the current stream)"""
+        init = torch.empty((2, self.n_envs), dtype=torch.float32, device=self.device)
+        self._check(self.lib.ks_get_rollout_controller(self.ctx, None, None, _ptr(init), self._stream()))
+        return init
 
     def step(self, action: torch.Tensor):
         """action [4, N].  Returns (obs, reward, done, info) views of the context's output buffers."""

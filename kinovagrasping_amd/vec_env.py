@@ -330,6 +330,11 @@ class KinovaGripperVecEnv:
         self.orientation_idx[:] = -1
         return obs
 
+    def set_rollout_controller(self, mode, lift_rule="expert"):
+        """A scripted demonstrator ("naive", "position-dependent", "combined"; None: the actor again) acts on the free-running path
+        (KinovaSim.set_rollout_controller).  Call it at an episode boundary: behind reset() / set_start_pool()."""
+        return self.sim.set_rollout_controller(mode, lift_rule)
+
     # -- step -------------------------------------------------------------------------------------
     def step(self, action, graspnetwork=False):
         """action: [N,4] (wrist, finger1..3) torch tensor or array.  Returns (obs [N,82], reward [N],
