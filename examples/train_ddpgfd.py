@@ -12,7 +12,7 @@
      hand by ~5 mm per env-step on average while the fingers close - as in the reference, main_DDPGfD.py:443-446.)
 
     python examples/train_ddpgfd.py --envs 1024 --steps 600 --hidden 256 256 [--free-running] [--expert-prob 0] [--starts-per-env 64]
-                                    [--success-map DIR] [--demonstrations free-running]
+                                    [--success-map DIR] [--demonstrations free-running] [--randomize-params]
 
 --success-map DIR (with --free-running): the stepping kernel logs every finished training episode (ks_set_episode_log); at every report
 the script folds the log (metrics.EpisodeLedger) and writes DIR/per_shape_success.jsonl and the success / fail start coordinates of the
@@ -39,7 +39,7 @@ from kinovagrasping_amd import scenarios                       # noqa: E402
 from kinovagrasping_amd.ddpgfd import DDPGfD                   # noqa: E402
 from kinovagrasping_amd.demonstrators import run_controller_episodes, run_controller_free_running  # noqa: E402
 from kinovagrasping_amd.evaluate import eval_policy, eval_policy_free_running  # noqa: E402
-from kinovagrasping_amd.metrics import EpisodeLedger, save_heatmap_coords      # noqa: E402
+from kinovagrasping_amd.metrics import EpisodeLedger, param_success_table, save_heatmap_coords      # noqa: E402
 from kinovagrasping_amd.replay import DeviceEpisodeReplay      # noqa: E402
 from kinovagrasping_amd.rollout import RolloutEngine           # noqa: E402
 from kinovagrasping_amd.sim import EPISODE_LOG_CAPACITY_MAX, KinovaSim      # noqa: E402
@@ -69,6 +69,9 @@ def main():
     ap.add_argument("--free-running", action="store_true", help="the persistent rollout kernel (ks_rollout) instead of one launch per env-step")
     ap.add_argument("--starts-per-env", type=int, default=0, help="K > 0: every training env holds a pool of K start positions and each of its episodes starts from one "
                     "drawn inside the stepping kernel (ks_set_start_pool); 0: an env replays the one start it was reset to")
+    ap.add_argument("--randomize-params", action="store_true", help="every training episode draws its object mass (0.05-0.15 kg) and object-hand friction "
+                    "(0.5-1.0) inside the stepping kernel (ks_set_param_ranges: BASELINE config 5's ranges, per episode); with --success-map the "
+                    "success table per (mass, friction) bin is printed at every report")
     ap.add_argument("--success-map", default=None, help="with --free-running: keep the in-kernel episode log and write per-shape success and the success / fail "
                     "heatmap coordinates of the training episodes into this directory at every report; the evaluation runs through ks_rollout too")
     ap.add_argument("--batch-episodes", type=int, default=64, help="episodes per update (x 25 five-step windows each); the reference: 64")
@@ -130,6 +133,10 @@ def main():
         eng.start(sim.set_start_pool(torch.as_tensor(qp), torch.as_tensor(hqp), seed=args.seed))
     else:
         eng.start(sim.reset(torch.as_tensor(q0), torch.as_tensor(hq)))
+    param_ranges = None
+    if args.randomize_params:               # (behind the pool: an episode boundary; the ranges reset nothing)
+        param_ranges = sim.set_param_ranges(seed=args.seed, **scenarios.config5_param_ranges(n)).cpu().numpy()
+        print("per-episode parameters: object mass 0.05-0.15 kg, object-hand friction 0.5-1.0, drawn at every auto-reset")
     Trainer = AsyncTrainer if args.free_running else GraphedTrainer
     tr = Trainer(sim, policy, agent, eng, batch_episodes=args.batch_episodes, expert_replay=expert, expert_prob=args.expert_prob if expert is not None else 0.3,
                  updates_per_step=args.updates_per_step)
@@ -145,6 +152,11 @@ def main():
         map_dir.mkdir(parents=True, exist_ok=True)
         ledger = EpisodeLedger(n, 1, args.starts_per_env or None)
         sim.set_episode_log(min(n * 60, EPISODE_LOG_CAPACITY_MAX))           # a report's 60 env-steps: at most one record per env and env-step
+        if param_ranges is not None:
+            # the log starts here, the draws started behind the pool: the record of ordinal k of an env ran the env's draw number first_draw + k
+            first_draw = sim.env_params()[2].cpu().numpy()
+            mass_edges, mu_edges = np.linspace(0.05, 0.15, 5), np.linspace(0.5, 1.0, 5)
+            p_attempts, p_successes = np.zeros((4, 4), dtype=np.int64), np.zeros((4, 4), dtype=np.int64)
     sim_eval = KinovaSim(1024, args.shape, auto_reset=bool(args.success_map), horizon=30)
     qe, hqe = start_states(1024, args.shape, np.random.RandomState(args.seed + 1))
     qe, hqe = torch.as_tensor(qe), torch.as_tensor(hqe)
@@ -158,7 +170,17 @@ def main():
             d_ep, d_lift = c["episodes_finished"] - episodes, c["lifted"] - lifted
             episodes, lifted = c["episodes_finished"], c["lifted"]
             if ledger is not None:
-                ledger.add(sim.episode_log())
+                records = sim.episode_log()
+                ledger.add(records)
+                if param_ranges is not None:
+                    r_env, r_ep = records["env"].cpu().numpy(), records["episode"].cpu().numpy()
+                    r_mass, r_mu = scenarios.param_draw_reference(args.seed, r_env, first_draw[r_env] + r_ep, param_ranges, np.float32)
+                    a_, s_ = param_success_table(records, r_mass, r_mu, mass_edges, mu_edges)
+                    p_attempts += a_
+                    p_successes += s_
+                    print("lift success per (mass bin, mu bin), rows mass 0.05 .. 0.15 kg, columns mu 0.5 .. 1.0 (successes / attempts):")
+                    for i in range(4):
+                        print("   " + "  ".join(f"{p_successes[i, j]:6d}/{p_attempts[i, j]:<6d}" for j in range(4)))
                 with open(map_dir / "per_shape_success.jsonl", "a") as f:
                     f.write(json.dumps({"step": it + 60, "episodes": ledger.episodes, "lost": ledger.lost, "per_shape": ledger.per_object([args.shape])}) + "\n")
                 save_heatmap_coords(*ledger.coords(pool_classes if args.starts_per_env > 0 else "normal", clear=True), it + 60, map_dir / "train")

@@ -22,6 +22,8 @@
  *                               _get_obs(), _get_reward()                           ENV:1495-1552
  *                               + gym TimeLimit (max_episode_steps)                 gym_kinova_gripper/__init__.py:3-7, main_DDPGfD.py:384
  *   ks_set_env_params        <- (none: the reference edits geom mass / pair friction in the XML; config-5 extension)
+ *   ks_set_param_ranges /
+ *   ks_get_env_params        <- (none: config-5 extension, per episode)
  *   ks_obs_from_snapshot     <- _get_obs() + _get_reward() on a given engine state          ENV:438-534, 631-687
  *   ks_get_state/ks_set_state<- sim.data.qpos / qvel / qacc_warmstart, sim.data.ncon,
  *                               contact forces (parity taps)                        ENV:109, 347-353
@@ -220,6 +222,38 @@ int ks_set_state(ks_ctx *ctx, const void *qpos, const void *qvel, const void *qa
  * XML:153, and the object-hand friction at 1, XML:160-166).  obj_mass [N] (kg; the inertia scales with it), obj_mu [N]
  * (friction of the seven object-hand pairs); either pointer may be NULL = leave as is.  Defaults are the model's. */
 int ks_set_env_params(ks_ctx *ctx, const void *obj_mass, const void *obj_mu, void *stream);
+
+/* Per-EPISODE domain randomisation: ranges from which every AUTO-RESET of an env draws its object's mass and its object-hand friction
+ * inside the stepping kernels (ks_step and ks_rollout, both precisions, both libraries) - instead of keeping the one pair the host wrote
+ * for as long as the context lives.
+ * ranges: device [4][N], context precision: mass_lo, mass_hi, mu_lo, mu_hi per env (ranges[k * N + env]); copied into storage the context
+ * owns.  NULL clears the ranges (seed ignored): every env keeps the values of its running episode.
+ * The draw, for callers that want to reproduce any episode's parameters from (seed, env, episode) alone:
+ *     r    = Philox4x32-10(counter = (env, episode low word, episode high word, 0x4d46), key = (seed low word, seed high word))
+ *     mass = T( mass_lo + (mass_hi - mass_lo) * (r[0] * 2^-32) )        mu = T( mu_lo + (mu_hi - mu_lo) * (r[1] * 2^-32) )
+ * evaluated in fp64 - the bounds converted exactly, difference, product and sum each rounded to nearest (never contracted into a fused
+ * multiply-add) - and rounded ONCE to the context precision T: float64 arithmetic followed by one conversion (numpy: .astype)
+ * reproduces it bit for bit in both precisions; kinovagrasping_amd.scenarios.param_draw_reference does.  lo == hi gives the constant;
+ * every result lies in [lo, hi].  `episode` counts the env's auto-resets since the ranges were set (episode 0: the call's own draw) -
+ * with an episode log set at the same boundary it is the `episode` ordinal of the log's records.
+ * The call zeroes every env's counter, draws episode 0 and writes the pair of all N envs where the env-steps read them (what
+ * ks_set_env_params writes).  It resets nothing: it is meant for an episode boundary, behind ks_reset or ks_set_start_pool.  On an
+ * auto-reset the kernel bumps the env's counter, draws and stores the pair; the env-step that follows loads it.  With or without a
+ * start pool, with or without an episode log.
+ * ks_set_env_params after the call overrides the values of the running episodes until an env's next auto-reset draws again; ks_reset
+ * keeps the ranges; ks_reset_objects with object_id CLEARS them (a range belonged to the object the env held), with mass_friction only
+ * it behaves like ks_set_env_params.
+ * The record the kernels read lives in device memory and is written by the stream, so a ks_step / ks_rollout captured BEFORE the call
+ * draws when it is replayed after it.  Storage ([4][N] values, [N] int64 counters) is allocated by the first call that sets ranges and
+ * kept until ks_destroy; no host synchronisation otherwise.  Not for stream capture itself.
+ * KS_ERR_STATE on a context without auto_reset (nothing would ever be drawn) or before ks_load_model.  The library cannot see device
+ * values without a synchronisation: the CALLER is responsible for mass_lo > 0 and lo <= hi in every env (the Python layer checks host
+ * inputs).  A context that never sets ranges computes what it always did. */
+int ks_set_param_ranges(ks_ctx *ctx, const void *ranges, uint64_t seed, void *stream);
+/* mass, mu: [N], context precision - the object mass and object-hand friction every env's running episode uses (drawn, or written by
+ * ks_set_env_params / ks_reset_objects, or the model's); episode: int64 [N], the env's draws since the ranges were set (0 in a context
+ * that never set ranges).  Asynchronous copies on `stream`; any pointer may be NULL.  KS_ERR_STATE before ks_load_model. */
+int ks_get_env_params(ks_ctx *ctx, void *mass, void *mu, int64_t *episode, void *stream);
 
 /* Advance by ONE mj_step with explicit controls ctrl [9, N] (no observation); parity testing. */
 int ks_substep(ks_ctx *ctx, const void *ctrl, void *stream);

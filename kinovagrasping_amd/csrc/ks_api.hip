@@ -15,6 +15,9 @@
 //                start_pool_restart (out of line, called where obs_finish restarts an episode)
 //   k_elog_begin the episode log (ks_set_episode_log): its record and zeroed counters; a finished episode's record is written in
 //                episode_log_write (out of line, called at the same place, just before the next start is drawn)
+//   k_ranges_begin the per-episode parameter ranges (ks_set_param_ranges): their record, every env's object mass / object-hand friction at
+//                its draw for episode 0; an auto-reset draws the next pair in param_ranges_restart (out of line, called at the same
+//                place, right after the next start is drawn)
 // No CPU fallback exists in this library.
 #include <hip/hip_runtime.h>
 
@@ -65,6 +68,18 @@ template <typename T> struct EpisodeLog {
     const StartPool<T> *pool;                   // the start pool's record: index[env] is the entry the finished episode started from
 };
 
+// The per-episode parameter ranges of a context (ks_set_param_ranges): per env the interval its object's mass and its object-hand
+// friction are drawn from where an episode restarts - like the two records above, one record in device memory that the stream writes
+// (k_ranges_begin / k_ranges_clear), so that a captured ks_step / ks_rollout draws from whatever ranges the context holds when the
+// graph is replayed.  active = 0: none.
+template <typename T> struct ParamRanges {
+    int32_t active, pad;
+    uint64_t seed;
+    const T *ranges;                            // [4][N] mass_lo, mass_hi, mu_lo, mu_hi (the context's copy)
+    T *envp;                                    // [2][N] (Buffers): what every env-step loads - a restart stores the drawn pair there
+    int64_t *episode;                           // [N] draws (auto-resets) since the ranges were set
+};
+
 // The scripted controller of a context (ks_set_rollout_controller): which of the reference's demonstrators acts in ks_rollout instead
 // of the actor, and the per-env start values its rule latches - like the two records above, one record in device memory that the stream
 // writes (k_controller_set), so that a captured ks_rollout follows whatever the context holds when the graph is replayed.  mode = 0: none.
@@ -103,6 +118,10 @@ template <typename T> struct Buffers {
     StartPool<T> *pool;           // [1] the start pool's record (k = 0: none); read only where an episode restarts
     EpisodeLog<T> *elog;          // [1] the episode log's record (capacity = 0: none); read only where an episode restarts
     RolloutController *ctl;       // [1] the scripted controller's record (mode = 0: none); read by the rollout kernels' policy phase
+    // [1] the parameter ranges' record (active = 0: none); read only where an episode restarts.  It sits behind the start pool's record in
+    // one allocation, not behind a pointer of its own: this table is a kernel argument that the fp64 kernels copy to their stack to pass it
+    // on by reference, and its size is part of their scratch budget
+    __host__ __device__ ParamRanges<T>* dr() const { return (ParamRanges<T>*)(pool + 1); }
 };
 
 template <typename T> struct ColW {
@@ -1654,6 +1673,49 @@ template <typename T> __global__ void k_elog_begin(Buffers<T> b, EpisodeLog<T> l
 }
 template <typename T> __global__ void k_elog_clear(Buffers<T> b) { b.elog->capacity = 0; }
 
+// The parameter ranges' draw (include/kinova_sim.h, ks_set_param_ranges): object mass and object-hand friction of `env` for its episode
+// number `episode`, stored where the env-steps load them.  fp64 arithmetic, every operation rounded on its own (numpy's float64
+// arithmetic reproduces it), one rounding to the context precision at the end.
+template <typename T> __device__ __forceinline__ void param_ranges_draw(const ParamRanges<T>& p, uint64_t episode, int env, int N) {
+    // no fma contraction here: difference, product and sum are each rounded, as __dsub_rn / __dmul_rn / __dadd_rn round them (those are
+    // plain operators in the compiler's headers, which a caller's pragma does not reach: hence operators under the pragma)
+#pragma clang fp contract(off)
+    uint32_t r[4];
+    krsel::philox4x32((uint32_t)env, (uint32_t)episode, (uint32_t)(episode >> 32), 0x4d46u, (uint32_t)p.seed, (uint32_t)(p.seed >> 32), r);
+    const double u0 = (double)r[0] * 0x1p-32, u1 = (double)r[1] * 0x1p-32;      // (exact: 32-bit integers, a power of two)
+    const double lo_m = (double)p.ranges[env], hi_m = (double)p.ranges[(long)N + env];
+    const double lo_u = (double)p.ranges[2L * N + env], hi_u = (double)p.ranges[3L * N + env];
+    const double dm = hi_m - lo_m, du = hi_u - lo_u;
+    const double pm = dm * u0, pu = du * u1;
+    p.envp[env] = (T)(lo_m + pm);
+    p.envp[(long)N + env] = (T)(lo_u + pu);
+}
+
+// An episode of `env` restarts (obs_finish, after the next start is drawn): with parameter ranges, count the episode, draw its mass and
+// friction and store them into envp - the env-step that follows loads them (load_env_params) as it loads the state the restart wrote:
+// both are plain global stores of the lane that finishes the env, ahead of the same fence + barrier (rollout_iter, rollout_iter_f64:
+// __threadfence_block + __syncthreads; rollout_iter_wave: Crew::sync's workgroup fence + wave barrier; the queue form: the agent-scope
+// release before the group is handed on) that orders the restarted state and a pool's env_qpos0 before the team's next loads.  Out of
+// line for the reason start_pool_restart is: ONE copy per precision with registers of its own.  Without ranges: one load and back.
+template <typename T> __device__ __noinline__ void param_ranges_restart(const ParamRanges<T>* dr, int env, int N) {
+    if (dr->active <= 0) return;
+    const ParamRanges<T> p = *dr;
+    const int64_t ep = p.episode[env] + 1;
+    p.episode[env] = ep;
+    param_ranges_draw(p, (uint64_t)ep, env, N);
+}
+
+// ks_set_param_ranges: the ranges' record (thread 0), every env at episode 0 with its draw in envp.  k_ranges_clear: back to no ranges
+// (envp keeps the running episode's values).
+template <typename T> __global__ void k_ranges_begin(Buffers<T> b, ParamRanges<T> p, int N) {
+    const int env = blockIdx.x * blockDim.x + threadIdx.x;
+    if (env == 0) *b.dr() = p;
+    if (env >= N) return;
+    p.episode[env] = 0;
+    param_ranges_draw(p, 0, env, N);
+}
+template <typename T> __global__ void k_ranges_clear(Buffers<T> b) { b.dr()->active = 0; }
+
 // phase 1 (part = -1: all of it; 0..3: that quarter of the slots, see build_obs): the observation, straight to its destination
 template <typename T, typename SnapT>
 __device__ __forceinline__ void obs_write(const Model<T>& m, const Buffers<T>& b, int env, int N, int mode, const ObsOut<T>& o, SnapT snap,
@@ -1700,6 +1762,8 @@ __device__ __forceinline__ void obs_finish(const Model<T>& m, const Buffers<T>& 
         episode_log_write(b.elog, env, sc, (int)d);
         // ... and with a start pool (ks_set_start_pool) the next episode's start is drawn: its entry becomes the stored initial state
         start_pool_restart(b.pool, env, N);
+        // ... and with parameter ranges (ks_set_param_ranges) its object mass and object-hand friction: the next env-step loads them
+        param_ranges_restart(b.dr(), env, N);
         if (o.obs) {
             for (int j = 0; j < NOBS; j++) o.obs[base + j * stride] = b.obs0[(long)env * NOBS + j];
         }
@@ -1988,6 +2052,8 @@ struct CtxBase {
     virtual int get_start_index(int32_t* index, int64_t* episode, hipStream_t s) = 0;
     virtual int set_episode_log(int capacity, hipStream_t s) = 0;
     virtual int get_episode_log(ks_episode_record* ring_out, int64_t* written_out, hipStream_t s) = 0;
+    virtual int set_param_ranges(const void* ranges, uint64_t seed, hipStream_t s) = 0;
+    virtual int get_env_params(void* mass, void* mu, int64_t* episode, hipStream_t s) = 0;
     virtual int set_rollout_controller(int mode, int lift_rule, hipStream_t s) = 0;
     virtual int get_rollout_controller(int32_t* mode, int32_t* lift_rule, float* init, hipStream_t s) = 0;
 };
@@ -2050,6 +2116,11 @@ template <typename T> struct Ctx : CtxBase {
     // the scripted controller (ks_set_rollout_controller): the mode as the host last set it, and the envs' start values
     int ctl_mode = 0, ctl_lift_rule = 0;
     float* ctl_init = nullptr;            // [2][N]
+    // the parameter ranges (ks_set_param_ranges): the context's copy of the ranges and the per-env draw counters, allocated by the
+    // first call that sets ranges and kept until the context goes
+    bool dr_active = false;
+    T* dr_ranges = nullptr;               // [4][N]
+    int64_t* dr_episode = nullptr;        // [N]
     int n_models = 0, n_wg = 0;
     int32_t n_groups = 0;                 // groups of the slot list that hold envs (<= n_wg): what ks_rollout deals
     std::map<std::pair<size_t, uint64_t>, void*> shared;      // uploaded arrays by (bytes, content hash): the hand's meshes are
@@ -2092,7 +2163,12 @@ template <typename T> struct Ctx : CtxBase {
         if ((r = alloc(&b.step_count, N))) return r;
         if ((r = alloc(&b.flag, N))) return r;
         if ((r = alloc(&b.obj_id, N))) return r;
-        if ((r = alloc(&b.pool, (size_t)1))) return r;          // zeroed: k = 0, no pool
+        {
+            // the start pool's record and, behind it, the parameter ranges' (Buffers::dr).  zeroed: k = 0, no pool; active = 0, no ranges
+            unsigned char* recs = nullptr;
+            if ((r = alloc(&recs, sizeof(StartPool<T>) + sizeof(ParamRanges<T>)))) return r;
+            b.pool = (StartPool<T>*)recs;
+        }
         if ((r = alloc(&pool_episode, N))) return r;
         if ((r = alloc(&pool_index, N))) return r;
         if ((r = alloc(&b.elog, (size_t)1))) return r;          // zeroed: capacity = 0, no log
@@ -2286,6 +2362,11 @@ template <typename T> struct Ctx : CtxBase {
         if (object_id && pool_k > 0) {
             hipLaunchKernelGGL((k_pool_clear<T>), dim3(1), dim3(1), 0, s, b);
             pool_k = 0;
+        }
+        // ... and so are parameter ranges: a range belonged to the object the env held
+        if (object_id && dr_active) {
+            hipLaunchKernelGGL((k_ranges_clear<T>), dim3(1), dim3(1), 0, s, b);
+            dr_active = false;
         }
         // objects changed: regroup the stepping kernel's work list by object
         if (object_id && n_models > 1)
@@ -2578,6 +2659,41 @@ template <typename T> struct Ctx : CtxBase {
         elog_capacity = capacity;
         return KS_OK;
     }
+    int set_param_ranges(const void* ranges, uint64_t seed, hipStream_t s) override {
+        if (!model_loaded) { error = "ks_set_param_ranges before ks_load_model"; return KS_ERR_STATE; }
+        if (!cfg.auto_reset) { error = "ks_set_param_ranges: the parameters are drawn where an episode restarts inside the stepping kernels - the context needs auto_reset"; return KS_ERR_STATE; }
+        if (!ranges) {                                          // no ranges: every env keeps the values of its running episode
+            if (dr_active) hipLaunchKernelGGL((k_ranges_clear<T>), dim3(1), dim3(1), 0, s, b);
+            dr_active = false;
+            HIPCHK(hipGetLastError());
+            return KS_OK;
+        }
+        const size_t N = cfg.n_envs;
+        int r;
+        if (!dr_ranges || !dr_episode) {
+            // the first call allocates - and waits once, so that the allocation's zero fill is over before `s` (any stream) writes there
+            if (!dr_ranges && (r = alloc(&dr_ranges, 4 * N))) return r;
+            if (!dr_episode && (r = alloc(&dr_episode, N))) return r;
+            HIPCHK(hipDeviceSynchronize());
+        }
+        HIPCHK(hipMemcpyAsync(dr_ranges, ranges, 4 * N * sizeof(T), hipMemcpyDefault, s));
+        const ParamRanges<T> rec{1, 0, seed, dr_ranges, b.envp, dr_episode};
+        hipLaunchKernelGGL((k_ranges_begin<T>), dim3(((int)N + 255) / 256), dim3(256), 0, s, b, rec, (int)N);
+        HIPCHK(hipGetLastError());
+        dr_active = true;
+        return KS_OK;
+    }
+    int get_env_params(void* mass, void* mu, int64_t* episode, hipStream_t s) override {
+        if (!model_loaded) { error = "ks_get_env_params before ks_load_model"; return KS_ERR_STATE; }
+        const size_t N = cfg.n_envs;
+        if (mass) HIPCHK(hipMemcpyAsync(mass, b.envp, N * sizeof(T), hipMemcpyDefault, s));
+        if (mu) HIPCHK(hipMemcpyAsync(mu, b.envp + N, N * sizeof(T), hipMemcpyDefault, s));
+        if (episode) {
+            if (dr_episode) HIPCHK(hipMemcpyAsync(episode, dr_episode, N * sizeof(int64_t), hipMemcpyDefault, s));
+            else HIPCHK(hipMemsetAsync(episode, 0, N * sizeof(int64_t), s));      // (no ranges were ever set: no draws)
+        }
+        return KS_OK;
+    }
     int set_rollout_controller(int mode, int lift_rule, hipStream_t s) override {
         if (!model_loaded) { error = "ks_set_rollout_controller before ks_load_model"; return KS_ERR_STATE; }
         if (mode != KS_CONTROLLER_NONE && !krsel::controller_args_ok(mode, lift_rule)) {
@@ -2771,6 +2887,14 @@ int ks_get_start_index(ks_ctx* ctx, int32_t* index, int64_t* episode, void* stre
 int ks_set_episode_log(ks_ctx* ctx, int32_t capacity, void* stream) {
     if (!ctx) return KS_ERR_INVALID;
     return ctx->impl->set_episode_log(capacity, (hipStream_t)stream);
+}
+int ks_set_param_ranges(ks_ctx* ctx, const void* ranges, uint64_t seed, void* stream) {
+    if (!ctx) return KS_ERR_INVALID;
+    return ctx->impl->set_param_ranges(ranges, seed, (hipStream_t)stream);
+}
+int ks_get_env_params(ks_ctx* ctx, void* mass, void* mu, int64_t* episode, void* stream) {
+    if (!ctx) return KS_ERR_INVALID;
+    return ctx->impl->get_env_params(mass, mu, episode, (hipStream_t)stream);
 }
 int ks_set_rollout_controller(ks_ctx* ctx, int32_t mode, int32_t lift_rule, void* stream) {
     if (!ctx) return KS_ERR_INVALID;

@@ -95,7 +95,8 @@ def policy_basename(policy_dir) -> str:
 
 
 def run_stage(plan, policy, n_envs: int = 1024, rounds: int = 10, updates_per_round: int = 100, expert_prob: float = 0.3, seed: int = 2,
-              device: int = 0, load_previous: bool = True, save: bool = True, eval_envs: int | None = None, starts_per_env: int = 0):
+              device: int = 0, load_previous: bool = True, save: bool = True, eval_envs: int | None = None, starts_per_env: int = 0,
+              param_ranges=None):
     """One stage of the curriculum on the GPU simulator (the batched counterpart of rl_experiment + train_policy,
     main_DDPGfD.py:600-621, 776-800): start from the previous stage's policy and agent replay, mix in the expert
     replay of the stage's shapes at `expert_prob` (DDPGfD.py:232-254), train, evaluate, save policy + replay + info.
@@ -114,6 +115,12 @@ def run_stage(plan, policy, n_envs: int = 1024, rounds: int = 10, updates_per_ro
     over the rounds and returns its fold: `episodes` (episodes that ended in the rounds) and `per_shape_success` ({shape: attempts,
     successes, mean_steps}, by the object the record names; with several shapes every env is given its shape's object before the pool
     is set).  0: the host reset per round, as before (same draws from the same rng).
+    param_ranges = {"mass": (lo, hi), "mu": (lo, hi)} (scenarios.config5_param_ranges; honoured only with starts_per_env > 0, ValueError
+    otherwise): every episode also draws its object's mass and object-hand friction inside the stepping kernel (ks_set_param_ranges, set
+    behind the pool with the episode log, seed = `seed`) - the final evaluation's episodes included.  The result gains `param_success`:
+    {"mass_edges", "mu_edges", "attempts", "successes"}, the rounds' episodes per (mass bin, mu bin) in four bins each over the ranges
+    (metrics.param_success_table; every record's parameters from scenarios.param_draw_reference: the log's episode ordinal is the draw's
+    episode number).
     Returns a dict (num_success, num_total, paths, ...)."""
     import torch
 
@@ -122,6 +129,8 @@ def run_stage(plan, policy, n_envs: int = 1024, rounds: int = 10, updates_per_ro
     from .replay import DeviceEpisodeReplay
     from .rollout import RolloutEngine
 
+    if param_ranges is not None and starts_per_env <= 0:
+        raise ValueError("run_stage: param_ranges are drawn where an episode restarts inside the stepping kernel - they need starts_per_env > 0")
     dirs = plan["dirs"]
     known = scenarios.SHAPES + scenarios.MEDIUM_SHAPES + scenarios.EXTRA_SHAPES + scenarios.MULTI_GEOM_SHAPES
     shapes = [s for s in plan["requested_shapes"] if s in known]
@@ -187,6 +196,15 @@ def run_stage(plan, policy, n_envs: int = 1024, rounds: int = 10, updates_per_ro
         from .sim import EPISODE_LOG_CAPACITY_MAX
         ledger = EpisodeLedger(n_envs, len(shapes), starts_per_env, keep_coords=False)
         sim.set_episode_log(min(n_envs * 30, EPISODE_LOG_CAPACITY_MAX))
+        if param_ranges is not None:
+            from .metrics import param_success_table
+            ranges = sim.set_param_ranges(seed=seed, **param_ranges).cpu().numpy()
+            npdt = np.float32 if sim.dtype == torch.float32 else np.float64
+            edges = lambda lo, hi: np.linspace(float(ranges[lo].min()), float(ranges[hi].max()), 5) if ranges[hi].max() > ranges[lo].min() \
+                else np.array([float(ranges[lo].min()), float(np.nextafter(ranges[lo].min(), np.inf))])
+            mass_edges, mu_edges = edges(0, 1), edges(2, 3)
+            p_attempts = np.zeros((len(mass_edges) - 1, len(mu_edges) - 1), dtype=np.int64)
+            p_successes = np.zeros_like(p_attempts)
     for r in range(rounds):
         if starts_per_env <= 0:
             obs0, _ = reset_all(sim, n_envs)
@@ -196,7 +214,14 @@ def run_stage(plan, policy, n_envs: int = 1024, rounds: int = 10, updates_per_ro
                 seen[all_envs, sim.start_index()[0].long()] = True
             eng.step()
         if seen is not None:
-            ledger.add(sim.episode_log())
+            records = sim.episode_log()
+            ledger.add(records)
+            if param_ranges is not None:
+                r_env = records["env"].cpu().numpy()
+                r_mass, r_mu = scenarios.param_draw_reference(seed, r_env, records["episode"].cpu().numpy(), ranges, npdt)
+                a_, s_ = param_success_table(records, r_mass, r_mu, mass_edges, mu_edges)
+                p_attempts += a_
+                p_successes += s_
         if replay.count >= 2:
             for u in range(updates_per_round):
                 batch = replay.sample_mixed(expert, policy.batch_size, expert_prob) if mix else replay.sample_batch_nstep(policy.batch_size)
@@ -212,6 +237,9 @@ def run_stage(plan, policy, n_envs: int = 1024, rounds: int = 10, updates_per_ro
            "distinct_starts": n_envs * rounds if seen is None else int(seen.sum()), "orientation_counts": {c: classes.count(c) for c in sorted(set(classes))}}
     if seen is not None:
         out.update(episodes=ledger.episodes, per_shape_success=ledger.per_object(shapes))
+    if param_ranges is not None:
+        out["param_success"] = {"mass_edges": mass_edges.tolist(), "mu_edges": mu_edges.tolist(), "attempts": p_attempts.tolist(),
+                                "successes": p_successes.tolist()}
     if save:
         for k in ("policy_dir", "replay_dir", "output_dir"):
             Path(dirs[k]).mkdir(parents=True, exist_ok=True)

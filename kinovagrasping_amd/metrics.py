@@ -95,6 +95,35 @@ class ScalarLog:
         return [json.loads(l) for l in open(self.path)] if self.path.exists() else []
 
 
+def param_success_table(records, mass, mu, mass_edges, mu_edges):
+    """Which physical parameters succeeded: records (the in-kernel episode log's, sim.KinovaSim.episode_log(): `done` [m] is what is
+    read) with the object mass [m] and object-hand friction [m] each record's episode ran with -> (attempts, successes), int64
+    [len(mass_edges) - 1, len(mu_edges) - 1] per (mass bin, mu bin).  Bins are [edge_i, edge_i+1), the last one closed; a value outside
+    the edges is not counted.  An episode is a success when it ended lifted (done bit 0).
+    With per-episode ranges (sim.KinovaSim.set_param_ranges) set at the same boundary as the log, a record's `episode` ordinal IS the
+    draw's episode number: mass, mu = scenarios.param_draw_reference(seed, records["env"], records["episode"], ranges, dtype)."""
+    host = lambda v: np.asarray(v.detach().cpu().numpy() if hasattr(v, "detach") else v)
+    done, mass, mu = host(records["done"]).astype(np.int64).ravel(), host(mass).astype(np.float64).ravel(), host(mu).astype(np.float64).ravel()
+    me, ue = np.asarray(mass_edges, dtype=np.float64), np.asarray(mu_edges, dtype=np.float64)
+    if not (len(done) == len(mass) == len(mu)):
+        raise ValueError("param_success_table: one mass and one mu per record")
+    if len(me) < 2 or len(ue) < 2 or (np.diff(me) <= 0).any() or (np.diff(ue) <= 0).any():
+        raise ValueError("param_success_table: edges must be increasing, at least two")
+
+    def bins(v, edges):
+        i = np.searchsorted(edges, v, side="right") - 1
+        i[v == edges[-1]] = len(edges) - 2
+        return i, (i >= 0) & (i < len(edges) - 1)
+
+    (i, oki), (j, okj) = bins(mass, me), bins(mu, ue)
+    keep = oki & okj
+    attempts = np.zeros((len(me) - 1, len(ue) - 1), dtype=np.int64)
+    successes = np.zeros_like(attempts)
+    np.add.at(attempts, (i[keep], j[keep]), 1)
+    np.add.at(successes, (i[keep], j[keep]), (done[keep] & 1))
+    return attempts, successes
+
+
 class EpisodeLedger:
     """Which env, object and start succeeded: the fold of the in-kernel episode log's records (sim.KinovaSim.episode_log(); include/
     kinova_sim.h: ks_episode_record).  add(records) accumulates, as torch ops on the device the records live on:

@@ -31,6 +31,15 @@ class MultiShapeSim(KinovaSim):
         self.shape_of_env = torch.as_tensor(np.asarray(object_id), dtype=torch.int32, device=self.device)
         self._mass_friction = None
         self._pool_set = False
+        self._ranges_set = False
+
+    def set_param_ranges(self, mass=None, mu=None, seed: int = 0):
+        """KinovaSim.set_param_ranges; a range belongs to the object env e holds NOW - a later reset that passes object ids ends the
+        ranges (ks_reset_objects), as it ends a start pool.  While ranges are set, a reset that leaves the objects alone is the plain
+        ks_reset: the parameters are the draws', not what set_env_params stored."""
+        out = super().set_param_ranges(mass, mu, seed)
+        self._ranges_set = out is not None
+        return out
 
     def set_start_pool(self, qpos0, hand_quat=None, seed: int = 0):
         """KinovaSim.set_start_pool; entry j of env e is a start of the object env e holds NOW (scenarios.draw_start_pool(self.shapes[...]))
@@ -42,10 +51,12 @@ class MultiShapeSim(KinovaSim):
     def reset(self, qpos0: torch.Tensor, hand_quat: torch.Tensor, env_ids=None, object_id=None, mass_friction=None):
         """All envs (or env_ids): object ids default to the env's current shape; mass_friction [2, n] defaults to what
         set_env_params stored (else every object's compiled values)."""
-        if object_id is None and self._pool_set and mass_friction is None and self._mass_friction is None:
-            # objects stay and a start pool is set: the plain ks_reset, which keeps the pool (the envs run this start until their next auto-reset)
+        if object_id is None and mass_friction is None and (self._ranges_set or (self._pool_set and self._mass_friction is None)):
+            # objects stay and a start pool or parameter ranges are set: the plain ks_reset, which keeps both (the envs run this start
+            # until their next auto-reset)
             return super().reset(qpos0, hand_quat, env_ids)
         self._pool_set = False
+        self._ranges_set = False          # (ks_reset_objects with object ids clears the ranges, as it clears the pool)
         if object_id is None:
             object_id = self.shape_of_env if env_ids is None else self.shape_of_env[torch.as_tensor(env_ids).long()]
         else:

@@ -312,6 +312,42 @@ def config5_env_params(n_envs: int, seed: int = 5):
     return rng.uniform(0.05, 0.15, n_envs), rng.uniform(0.5, 1.0, n_envs)
 
 
+def config5_param_ranges(n_envs: int):
+    """The ranges config5_env_params draws from, as KinovaSim.set_param_ranges takes them: {"mass": (0.05, 0.15), "mu": (0.5, 1.0)},
+    every bound a float64 [N] (the same range for every env) - per-episode randomisation inside the stepping kernels."""
+    full = lambda v: np.full(int(n_envs), v)
+    return {"mass": (full(0.05), full(0.15)), "mu": (full(0.5), full(1.0))}
+
+
+def _philox4x32_10(c0, c1, c2, c3, k0, k1):
+    """Philox4x32-10 (Random123) on uint64 arrays holding 32-bit words: counter (c0..c3), key (k0, k1) -> four words"""
+    mask = np.uint64(0xFFFFFFFF)
+    for rnd in range(10):
+        p0, p1 = np.uint64(0xD2511F53) * c0, np.uint64(0xCD9E8D57) * c2         # 32 x 32 bits: exact in uint64
+        c0, c1, c2, c3 = (p1 >> np.uint64(32)) ^ c1 ^ k0, p1 & mask, (p0 >> np.uint64(32)) ^ c3 ^ k1, p0 & mask
+        k0, k1 = (k0 + np.uint64(0x9E3779B9)) & mask, (k1 + np.uint64(0xBB67AE85)) & mask
+    return c0, c1, c2, c3
+
+
+def param_draw_reference(seed, env, episode, ranges, dtype=np.float32):
+    """The stepping kernels' per-episode parameter draw (include/kinova_sim.h, ks_set_param_ranges) in numpy, bit for bit:
+        r    = Philox4x32-10(counter = (env, episode low word, episode high word, 0x4d46), key = (seed low word, seed high word))
+        mass = dtype(lo_m + (hi_m - lo_m) * (r[0] * 2^-32)),   mu = dtype(lo_u + (hi_u - lo_u) * (r[1] * 2^-32))
+    in float64 arithmetic, rounded once to `dtype` (the context precision).  env, episode: integer arrays that broadcast against each
+    other; ranges: [4, N] (mass_lo, mass_hi, mu_lo, mu_hi per env, as set_param_ranges returned them - the bounds in the context
+    precision), indexed by env.  `episode` is the env's draw number since the ranges were set - and, with an episode log set at the same
+    boundary, the `episode` ordinal of the log's records.  Returns (mass, mu) of the broadcast shape."""
+    mask = np.uint64(0xFFFFFFFF)
+    seed = np.uint64(int(seed) & (2 ** 64 - 1))
+    env, episode = np.broadcast_arrays(np.asarray(env, dtype=np.int64), np.asarray(episode, dtype=np.int64))
+    e64, ep = env.astype(np.uint64), episode.astype(np.uint64)
+    r = _philox4x32_10(e64 & mask, ep & mask, ep >> np.uint64(32), np.full_like(e64, 0x4D46), seed & mask, seed >> np.uint64(32))
+    rng = np.asarray(ranges.detach().cpu().numpy() if hasattr(ranges, "detach") else ranges).astype(dtype).astype(np.float64)
+    u0, u1 = r[0].astype(np.float64) * 2.0 ** -32, r[1].astype(np.float64) * 2.0 ** -32
+    lo_m, hi_m, lo_u, hi_u = (rng[k][env] for k in range(4))
+    return (lo_m + (hi_m - lo_m) * u0).astype(dtype), (lo_u + (hi_u - lo_u) * u1).astype(dtype)
+
+
 def config_actions(n_envs: int, n_steps: int = 30, base_seed: int = 1000) -> np.ndarray:
     """Per-env action streams Generator(PCG64(base_seed + i)).uniform(-0.8, 0.8, (n_steps, 4)) as
     float32; returns [n_steps, 4, N].  (Config 1 is base_seed=0 with one env.)"""

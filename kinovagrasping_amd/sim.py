@@ -92,7 +92,8 @@ def episode_records(words: torch.Tensor) -> dict:
 
 EXPORTS = ["ks_default_config", "ks_create", "ks_destroy", "ks_last_error", "ks_load_model", "ks_load_models", "ks_reset", "ks_reset_objects", "ks_step",
            "ks_get_state", "ks_set_state", "ks_set_env_params", "ks_substep", "ks_rollout", "ks_rollout_plan", "ks_obs_from_snapshot", "ks_kernel_time", "ks_version",
-           "ks_set_start_pool", "ks_get_start_index", "ks_set_episode_log", "ks_get_episode_log", "ks_set_rollout_controller", "ks_get_rollout_controller"]
+           "ks_set_start_pool", "ks_get_start_index", "ks_set_episode_log", "ks_get_episode_log", "ks_set_rollout_controller", "ks_get_rollout_controller",
+           "ks_set_param_ranges", "ks_get_env_params"]
 # include/kinova_rollout.h
 ROLLOUT_EXPORTS = ["kr_select_action", "kr_store_transition", "kr_rank_episodes", "kr_wait_min", "kr_wait_min_counted", "kr_commit_episodes", "kr_advance_ring",
                    "kr_sample_windows", "kr_sample_windows_draw", "kr_sample_windows_mixed", "kr_xchg_create", "kr_xchg_connect", "kr_xchg_allreduce_mean", "kr_xchg_status",
@@ -167,6 +168,8 @@ def _bind(L):
     L.ks_get_episode_log.argtypes = [vp, vp, vp, vp]
     L.ks_set_rollout_controller.argtypes = [vp, C.c_int32, C.c_int32, vp]
     L.ks_get_rollout_controller.argtypes = [vp, vp, vp, vp, vp]
+    L.ks_set_param_ranges.argtypes = [vp, vp, C.c_uint64, vp]
+    L.ks_get_env_params.argtypes = [vp, vp, vp, vp, vp]
     i32, f32 = C.c_int32, C.c_float
     L.kr_select_action.argtypes = [i32] + [vp] * 7 + [f32, f32, i32] + [vp] * 4
     L.kr_controller_select.argtypes = [i32] * 3 + [vp] * 6 + [i32] + [vp] * 4
@@ -204,6 +207,35 @@ def _bind(L):
 
 def _ptr(t):
     return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def param_range_rows(n_envs: int, mass=None, mu=None):
+    """The host side of set_param_ranges: mass / mu = (lo, hi), each a scalar or one value per env -> float64 [4, n_envs] rows mass_lo,
+    mass_hi, mu_lo, mu_hi; the rows of a parameter given as None are NaN (the caller fills them with the envs' current values).  Checks
+    what the library cannot see without a synchronisation: ValueError on a wrong length, lo > hi, a mass that is not positive, a
+    negative friction, or a value that is not finite."""
+    import numpy as np
+    rows = np.full((4, int(n_envs)), np.nan)
+    for k, (name, pair) in enumerate((("mass", mass), ("mu", mu))):
+        if pair is None:
+            continue
+        if not isinstance(pair, (tuple, list)) or len(pair) != 2:
+            raise ValueError(f"set_param_ranges: {name} = (lo, hi)")
+        for j, v in enumerate(pair):
+            v = np.asarray(v.detach().cpu().numpy() if hasattr(v, "detach") else v, dtype=np.float64)
+            if v.ndim > 1 or (v.ndim == 1 and v.shape[0] != n_envs):
+                raise ValueError(f"set_param_ranges: {name} bounds are scalars or one value per env ({n_envs})")
+            rows[2 * k + j] = v
+        lo, hi = rows[2 * k], rows[2 * k + 1]
+        if not (np.isfinite(lo).all() and np.isfinite(hi).all()):
+            raise ValueError(f"set_param_ranges: {name} bounds must be finite")
+        if (lo > hi).any():
+            raise ValueError(f"set_param_ranges: {name} lo > hi")
+        if name == "mass" and (lo <= 0).any():
+            raise ValueError("set_param_ranges: mass_lo must be positive")
+        if name == "mu" and (lo < 0).any():
+            raise ValueError("set_param_ranges: mu_lo must not be negative")
+    return rows
 
 
 class KinovaSim:
@@ -341,6 +373,38 @@ class KinovaSim:
         out = episode_records(words)
         out["lost"], out["written"] = lost, total
         return out
+
+    def set_param_ranges(self, mass=None, mu=None, seed: int = 0):
+        """Per-episode domain randomisation inside the stepping kernels (ks_set_param_ranges; the draw: include/kinova_sim.h,
+        scenarios.param_draw_reference): every AUTO-RESET of an env draws its object's mass from mass = (lo, hi) and its object-hand
+        friction from mu = (lo, hi) - scalars or [N], one range per env.  None for either keeps that parameter constant at every env's
+        current value; set_param_ranges(None) (both None) clears the ranges: the envs keep the values of their running episodes.  Draws
+        episode 0 for every env now and resets nothing: call it at an episode boundary, behind reset() / set_start_pool().  Set at the
+        same boundary as set_episode_log, a record's `episode` is the draw's episode number.  Returns the ranges [4, N] as sent."""
+        if mass is None and mu is None:
+            self._check(self.lib.ks_set_param_ranges(self.ctx, None, 0, self._stream()))
+            self._keep_ranges = None
+            return None
+        rows = param_range_rows(self.n_envs, mass, mu)            # (raises before any library call)
+        ranges = torch.as_tensor(rows).to(self.device, self.dtype)
+        if mass is None or mu is None:
+            cur_mass, cur_mu, _ = self.env_params()
+            k = 0 if mass is None else 2
+            ranges[k] = ranges[k + 1] = cur_mass if mass is None else cur_mu
+        ranges = ranges.contiguous()
+        self._check(self.lib.ks_set_param_ranges(self.ctx, _ptr(ranges), int(seed) & (2 ** 64 - 1), self._stream()))
+        self._keep_ranges = ranges
+        return ranges
+
+    def env_params(self):
+        """(mass [N], mu [N], episode int64 [N]): the object mass and object-hand friction every env's running episode uses, and the
+        env's draws since set_param_ranges (0 without ranges) - device copies behind the work queued on the current stream
+        (ks_get_env_params; no synchronisation)."""
+        mass = torch.empty(self.n_envs, dtype=self.dtype, device=self.device)
+        mu = torch.empty(self.n_envs, dtype=self.dtype, device=self.device)
+        episode = torch.empty(self.n_envs, dtype=torch.int64, device=self.device)
+        self._check(self.lib.ks_get_env_params(self.ctx, _ptr(mass), _ptr(mu), _ptr(episode), self._stream()))
+        return mass, mu, episode
 
     def set_rollout_controller(self, mode: str | None, lift_rule: str = "expert"):
         """A scripted demonstrator - "naive", "position-dependent" or "combined" (demonstrators.controller_action) with lift rule "expert" or

@@ -21,7 +21,7 @@ import torch
 
 from . import scenarios
 from .model_compiler import read_blob
-from .sim import NOBS, SOLVER_ITERATIONS, KinovaSim
+from .sim import NOBS, SOLVER_ITERATIONS, KinovaSim, param_range_rows
 
 COORDS_DIR = "gym_kinova_gripper/envs/kinova_description/obj_hand_coords/"     # ENV:1245
 
@@ -329,6 +329,17 @@ class KinovaGripperVecEnv:
         self.orientation = classes[idx, e].tolist()
         self.orientation_idx[:] = -1
         return obs
+
+    def set_param_ranges(self, mass=None, mu=None, seed: int = 0):
+        """Per-episode domain randomisation on the fast paths (KinovaSim.set_param_ranges): every auto-reset of an env draws its object's
+        mass from mass = (lo, hi) and its object-hand friction from mu = (lo, hi) inside the stepping kernels - scalars or one value per
+        env; None keeps a parameter at the envs' current values, both None clears the ranges.  Call it at an episode boundary: behind
+        reset() / set_start_pool().  The arguments are checked on the host first (ValueError); sim.env_params() says what an env runs."""
+        if mass is not None or mu is not None:
+            param_range_rows(self.n_envs, mass, mu)
+        if self.sim is None:
+            raise RuntimeError("set_param_ranges: a host_only env has no simulator to draw in")
+        return self.sim.set_param_ranges(mass, mu, seed)
 
     def set_rollout_controller(self, mode, lift_rule="expert"):
         """A scripted demonstrator ("naive", "position-dependent", "combined"; None: the actor again) acts on the free-running path
