@@ -11,7 +11,7 @@
      (The lift rate of the TRAINING rollouts is depressed by the exploration noise on the wrist channel: clip(pi + N(0, 0.08), 0, 0.8) lifts the
      hand by ~5 mm per env-step on average while the fingers close - as in the reference, main_DDPGfD.py:443-446.)
 
-    python examples/train_ddpgfd.py --envs 1024 --steps 600 --hidden 256 256 [--free-running] [--expert-prob 0] [--starts-per-env 64]
+    python examples/train_ddpgfd.py --envs 1024 --steps 600 --hidden 256 256 (or 400 300: the reference's widths, free-running too) [--free-running] [--expert-prob 0] [--starts-per-env 64]
                                     [--success-map DIR] [--demonstrations free-running] [--randomize-params]
 
 --success-map DIR (with --free-running): the stepping kernel logs every finished training episode (ks_set_episode_log); at every report

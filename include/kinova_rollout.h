@@ -204,6 +204,30 @@ int kr_mlp3_backward_split(int32_t n, int32_t in_dim, int32_t h1, int32_t h2, in
 int kr_weight_grad_shadow(int32_t n, int32_t M, int32_t Na, int32_t Nb, const float *dz, const float *ha, int32_t lda, const float *hb,
                           int32_t ldb, int32_t chunks, float *workspace, float *dW, float *db, void *stream);
 
+/* The LEAN LDS-free forward and backward: kr_mlp3_forward_shadow / kr_mlp3_backward_shadow (same operand layouts, optional
+ * outputs, act / scale handling and dx epilogue with the sigmoid backward) for the tile pair the one-wave kernels cannot take:
+ * (ceil(h1/16), ceil(h2/16)) == (25, 19) - the reference's 400-300 and partial last tiles in either layer, e.g. 392-292.
+ * Why they exist: the free-running rollout kernel at that width (k_rollout<25,19>) holds 416 of the 512 registers of every SIMD
+ * lane for a whole launch, so a learner wave is resident beside it only within the remaining 96.  Both kernels are capped at
+ * 96 registers per lane in the source (amdgpu_waves_per_eu(5, 5)) and use no scratch memory; tools/learner_budget.py reads the
+ * compiler's figures and fails when a pairing exceeds 512.  They keep no hidden layer in registers: the first product's output
+ * (h1 / dz2) goes through global memory - the caller's h1_out / dz2_out when given, else `scratch` - and is streamed back, with
+ * the weights, as the operands of the second product.
+ * Refused with KS_ERR_INVALID, nothing written: any other tile pair; h1 % 4 or h2 % 4 != 0; in_a + in_b > 96; out_dim > 4;
+ * W2, W3, h1_out, h2_out / h1a, h2a, dz1_out, dz2_out or scratch not 16-byte aligned; a NULL or short scratch when it is needed:
+ *   forward   scratch_floats >= (h1_out  ? 0 : ceil(n/16) * 16 * h1)
+ *   backward  scratch_floats >= (dz2_out ? 0 : ceil(n/16) * 16 * h2)
+ * (scratch may be NULL when that is 0); ceil(n/16) * 16 * max(h1, h2) * 4 bytes, n * lda * 4 and n * ldb * 4 must stay below 2^31.
+ * Elements at or beyond h1 / h2 of a partial last tile contribute zero to every reduction and are neither read nor stored. */
+int kr_mlp3_forward_lean(int32_t n, int32_t in_a, int32_t in_b, int32_t h1, int32_t h2, int32_t out_dim, const float *xa, int32_t lda,
+                         const float *xb, int32_t ldb, const float *W1, const float *b1, const float *W2, const float *b2,
+                         const float *W3, const float *b3, int32_t act, float scale, float *out, float *h1_out, float *h2_out,
+                         float *scratch, int64_t scratch_floats, void *stream);
+int kr_mlp3_backward_lean(int32_t n, int32_t in_dim, int32_t h1, int32_t h2, int32_t out_dim, const float *dz3, const float *W3,
+                          const float *h2a, const float *W2, const float *h1a, float *dz2_out, float *dz1_out, const float *W1, int32_t col0,
+                          int32_t ncol, const float *act_out, float scale, float *dx_out, float *scratch, int64_t scratch_floats,
+                          void *stream);
+
 /* Actor forward + exploration noise + kr_select_action in ONE launch (main_DDPGfD.py:424-451): the epilogue of the
  * fused MLP applies the selection rule to its own output.  obs .. ready and action .. lifting as in kr_select_action;
  * W1 .. b3 the actor (82 -> h1 -> h2 -> 4; any hidden widths kr_mlp3_forward accepts, partial last tiles included).

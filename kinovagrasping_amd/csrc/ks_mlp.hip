@@ -507,6 +507,236 @@ __global__ __launch_bounds__(64 * NWS) __attribute__((amdgpu_waves_per_eu(KS_SPL
     }
 }
 
+// ---- the LEAN LDS-free kernels: the same forward and backward for tile pairs too wide for k_mlp3_wave / k_mlp3_bwd_wave, which keep
+// a whole hidden layer in registers (at 25 tiles that alone is 100).  The free-running rollout kernel at the reference's 400-300
+// (k_rollout<25,19>) holds 416 of the 512 registers of every SIMD lane for a whole launch: a learner wave is resident beside it
+// only at <= 96, and these two kernels are capped there (amdgpu_waves_per_eu(5, 5): 512 / 5, rounded down to the allocation
+// granule of 8, is 96; tools/learner_budget.py checks the sums).  Data flow: one wave = 16 batch rows as before, but NO layer stays
+// in registers.  The first product's output quads go to global memory (the caller's h1_out / dz2_out, or scratch) and come back
+// as the B operands of the second product's k-loop, LEAN_KC k-steps per round, together with the weight quads; every quad is read
+// back by the lane that wrote it (the D layout of one MFMA is the B layout of the next), behind a fence and with glc loads.
+// A round's loads serve TWO output tiles (one B quad, two A quads per k-step: 12 registers instead of 16), which halves the
+// number of dependent load rounds - the kernels are bound by those, not by the matrix pipe.
+// Partial last tiles are right by construction: every element at or beyond h1 / h2 - a row of the A tile or a k of the
+// reduction - gets an out-of-range LANE offset, so it is read as zero and never touches memory (the tile and k steps sit in the
+// scalar offset, which the hardware's range check does not cover: the end of the buffer protects nothing), and is never stored.
+constexpr int LEAN_KC = 5;                   // k-steps per load round: 3 quads x 5 = 60 registers of operands in flight
+constexpr int LEAN_OOR = 0x7ffffff0;
+#define KS_LEAN_ATTR __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5)))
+#define KS_LDF(rsrc, voff, soff) __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsrc, voff, soff, 0))
+// all loads of a round are issued before its first MFMA: left alone, the scheduler interleaves them and waits for each in turn
+#define KS_LEAN_LOADS_FIRST() __builtin_amdgcn_sched_barrier(0)
+#define KS_LDQ(rsrc, voff, soff, aux) __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, soff, aux))
+
+template <int NT1, int NT2>
+__global__ KS_LEAN_ATTR void k_mlp3_lean(
+    int n, int in_a, int in_b, int h1, int h2, int out_dim, const float* __restrict__ xa, int lda, const float* __restrict__ xb, int ldb,
+    const float* __restrict__ W1, const float* __restrict__ b1, const float* __restrict__ W2, const float* __restrict__ b2,
+    const float* __restrict__ W3, const float* __restrict__ b3, int act, float scale, float* __restrict__ out, float* __restrict__ h1buf,
+    int h1_rows, float* __restrict__ h2_out) {
+    const int lane = threadIdx.x & 63, nn = lane & 15, q = lane >> 4;
+    const int row = blockIdx.x * ROWS + nn;
+    const bool row_ok = row < n;
+    const int in_dim = in_a + in_b;
+    constexpr int OOR = LEAN_OOR;
+    const auto rW1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(W1), 0, h1 * in_dim * 4, 0x00020000);
+    const auto rW2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(W2), 0, h2 * h1 * 4, 0x00020000);
+    const auto rW3 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(W3), 0, out_dim * h2 * 4, 0x00020000);
+    const auto rH1 = __builtin_amdgcn_make_buffer_rsrc(h1buf, 0, h1_rows * h1 * 4, 0x00020000);
+    {
+        const auto rXa = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(xa), 0, ((n - 1) * lda + in_a) * 4, 0x00020000);
+        const auto rXb = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(xb ? xb : xa), 0, xb ? ((n - 1) * ldb + in_b) * 4 : 0, 0x00020000);
+        // B operands of layer 1 (as k_mlp3_wave): the 16 input rows, k = 16 s + 4 q + j
+        f32x4 bx[KS_IN_MAX];
+        const int oa = row * lda * 4 + 16 * q, ob = (row * ldb + 4 * q - in_a) * 4;
+#pragma unroll
+        for (int s = 0; s < KS_IN_MAX; s++) {
+            float v[4];
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                const int k = 16 * s + 4 * q + j;
+                const float fa = KS_LDF(rXa, (row_ok && k < in_a) ? oa : OOR, (16 * s + j) * 4);
+                const float fb = KS_LDF(rXb, (row_ok && k >= in_a && k < in_dim) ? ob + (16 * s + j) * 4 : OOR, 0);
+                v[j] = k < in_a ? fa : fb;
+            }
+            bx[s] = f32x4{v[0], v[1], v[2], v[3]};
+        }
+        // layer 1, one tile per round: A = W1[16 t + nn][16 s + 4 q + j], zero beyond h1 rows / in_dim columns
+        const int o1 = (nn * in_dim + 4 * q) * 4;
+#pragma unroll 1
+        for (int t = 0; t < NT1; t++) {
+            const bool rok = 16 * t + nn < h1;
+            f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
+            f32x4 w[KS_IN_MAX];
+#pragma unroll
+            for (int s = 0; s < KS_IN_MAX; s++) {
+                const int so = (16 * t * in_dim + 16 * s) * 4, k0 = 16 * s + 4 * q;
+                w[s] = f32x4{KS_LDF(rW1, (rok && k0 < in_dim) ? o1 : OOR, so), KS_LDF(rW1, (rok && k0 + 1 < in_dim) ? o1 : OOR, so + 4),
+                             KS_LDF(rW1, (rok && k0 + 2 < in_dim) ? o1 : OOR, so + 8), KS_LDF(rW1, (rok && k0 + 3 < in_dim) ? o1 : OOR, so + 12)};
+            }
+            KS_LEAN_LOADS_FIRST();
+#pragma unroll
+            for (int s = 0; s < KS_IN_MAX; s++) {
+                if (s & 1) acc1 = mfma4(w[s], bx[s], acc1);
+                else acc0 = mfma4(w[s], bx[s], acc0);
+            }
+            const int f4 = t * 16 + 4 * q;
+            const f32x4 hq = bias_relu(acc0 + acc1, b1, f4, h1);
+            if (f4 < h1 && row < h1_rows) *(f32x4*)(h1buf + (long)row * h1 + f4) = hq;
+        }
+    }
+    __threadfence_block();          // the quads above are read back below, each by the lane that stored it (glc loads)
+    f32x4 acc3 = {0.f, 0.f, 0.f, 0.f};
+    const int o2 = (nn * h1 + 4 * q) * 4;                       // W2[16 t + nn][16 s + 4 q ..]: 16-byte reads (h1 % 4 == 0)
+    const int o3 = (nn * h2 + 4 * q) * 4;                       // W3[nn][16 t + 4 q ..]
+    const int oh = row < h1_rows ? (row * h1 + 4 * q) * 4 : OOR;
+    constexpr int NC = (NT1 + LEAN_KC - 1) / LEAN_KC;
+#pragma unroll 1
+    for (int t = 0; t < NT2; t += 2) {                          // tiles t and t + 1 (a tile at or beyond NT2: every row masked)
+        f32x4 acca = {0.f, 0.f, 0.f, 0.f}, accb = {0.f, 0.f, 0.f, 0.f};
+        const int oa = 16 * t + nn < h2 ? o2 : OOR, ob = 16 * (t + 1) + nn < h2 ? o2 : OOR;
+#pragma unroll 1
+        for (int c = 0; c < NC; c++) {
+            f32x4 wa[LEAN_KC], wb[LEAN_KC], hb[LEAN_KC];
+#pragma unroll
+            for (int u = 0; u < LEAN_KC; u++) {
+                const int s = c * LEAN_KC + u;
+                const bool kok = (NT1 % LEAN_KC == 0 || s < NT1) && 16 * s + 4 * q < h1;
+                hb[u] = KS_LDQ(rH1, kok ? oh : OOR, 16 * s * 4, 1);
+                wa[u] = KS_LDQ(rW2, kok ? oa : OOR, (16 * t * h1 + 16 * s) * 4, 0);
+                wb[u] = KS_LDQ(rW2, kok ? ob : OOR, (16 * (t + 1) * h1 + 16 * s) * 4, 0);
+            }
+            KS_LEAN_LOADS_FIRST();
+#pragma unroll
+            for (int u = 0; u < LEAN_KC; u++) {
+                acca = mfma4(wa[u], hb[u], acca);
+                accb = mfma4(wb[u], hb[u], accb);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < 2; u++) {
+            const int f4 = (t + u) * 16 + 4 * q;
+            const f32x4 hq = bias_relu(u ? accb : acca, b2, f4, h2);
+            if (h2_out && row_ok && f4 < h2) *(f32x4*)(h2_out + (long)row * h2 + f4) = hq;
+            const f32x4 w3 = KS_LDQ(rW3, (nn < out_dim && f4 < h2) ? o3 : OOR, 16 * (t + u) * 4, 0);
+            acc3 = mfma4(w3, hq, acc3);
+        }
+    }
+    if (q == 0 && row_ok) {
+        const float z[4] = {acc3.x, acc3.y, acc3.z, acc3.w};
+        for (int i = 0; i < out_dim; i++) {
+            float y = z[i] + b3[i];
+            if (act == KR_ACT_SIGMOID) y = scale / (1.f + __expf(-y));
+            out[(long)row * out_dim + i] = y;
+        }
+    }
+}
+
+// backward (the arithmetic of k_mlp3_bwd_wave): the masked dz2 quads (one MFMA each) go to dz2buf, then every pair of dz1 tiles
+// streams them back with the W2^T quads; dx accumulates in four registers.
+template <int NT1, int NT2>
+__global__ KS_LEAN_ATTR void k_mlp3_bwd_lean(
+    int n, int in_dim, int h1, int h2, int out_dim, const float* __restrict__ dz3, const float* __restrict__ W3, const float* __restrict__ h2a,
+    const float* __restrict__ W2, const float* __restrict__ h1a, float* __restrict__ dz2buf, int dz2_rows, float* __restrict__ dz1_out,
+    const float* __restrict__ W1, int col0, int ncol, const float* __restrict__ act_out, float scale, float* __restrict__ dx_out) {
+    const int lane = threadIdx.x & 63, nn = lane & 15, q = lane >> 4;
+    const int row = blockIdx.x * ROWS + nn;
+    const bool row_ok = row < n;
+    constexpr int OOR = LEAN_OOR;
+    const auto rW3 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(W3), 0, out_dim * h2 * 4, 0x00020000);
+    const auto rW2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(W2), 0, h2 * h1 * 4, 0x00020000);
+    const auto rH2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(h2a), 0, n * h2 * 4, 0x00020000);
+    const auto rH1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(h1a), 0, n * h1 * 4, 0x00020000);
+    const auto rD2 = __builtin_amdgcn_make_buffer_rsrc(dz2buf, 0, dz2_rows * h2 * 4, 0x00020000);
+    // B operand of the first product: dz3^T, k = output index = q
+    const float b3 = (row_ok && q < out_dim) ? dz3[(long)row * out_dim + q] : 0.f;
+    {
+        const int o3 = (q * h2 + nn) * 4;                                   // A: W3^T[f][k = q] = W3[q][f], f = 16 t + nn
+        const int oh2 = row_ok ? (row * h2 + 4 * q) * 4 : OOR;
+#pragma unroll 1
+        for (int t0 = 0; t0 < NT2; t0 += 4) {
+            float a3[4];
+            f32x4 hv[4];
+#pragma unroll
+            for (int u = 0; u < 4; u++) {
+                const int t = t0 + u;
+                a3[u] = KS_LDF(rW3, (q < out_dim && 16 * t + nn < h2) ? o3 : OOR, 16 * t * 4);
+                hv[u] = KS_LDQ(rH2, 16 * t + 4 * q < h2 ? oh2 : OOR, 16 * t * 4, 0);
+            }
+            KS_LEAN_LOADS_FIRST();
+#pragma unroll
+            for (int u = 0; u < 4; u++) {
+                const int f4 = (t0 + u) * 16 + 4 * q;
+                f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+                acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a3[u], b3, acc, 0, 0, 0);
+                f32x4 dz;
+                dz.x = hv[u].x > 0.f ? acc.x : 0.f; dz.y = hv[u].y > 0.f ? acc.y : 0.f; dz.z = hv[u].z > 0.f ? acc.z : 0.f; dz.w = hv[u].w > 0.f ? acc.w : 0.f;
+                if (f4 < h2 && row < dz2_rows) *(f32x4*)(dz2buf + (long)row * h2 + f4) = dz;
+            }
+        }
+    }
+    __threadfence_block();          // read back below by the lane that stored them (glc loads)
+    f32x4 accx = {0.f, 0.f, 0.f, 0.f};
+    const auto rW1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(W1 ? W1 : W2), 0, W1 ? h1 * in_dim * 4 : 0, 0x00020000);
+    const int od = row < dz2_rows ? (row * h2 + 4 * q) * 4 : OOR;
+    const int oh1 = row_ok ? (row * h1 + 4 * q) * 4 : OOR;
+    constexpr int NC = (NT2 + LEAN_KC - 1) / LEAN_KC;
+#pragma unroll 1
+    for (int t = 0; t < NT1; t += 2) {                          // tiles t and t + 1 (a tile at or beyond NT1: every row masked)
+        // A: W2^T[f][k] = W2[k][f], k = 16 s + 4 q + j (rows of W2, stride h1: the steps (16 s + j) h1 are scalar), f = 16 t + nn
+        f32x4 acca = {0.f, 0.f, 0.f, 0.f}, accb = {0.f, 0.f, 0.f, 0.f};
+        const int va = 16 * t + nn < h1 ? (4 * q * h1 + 16 * t + nn) * 4 : OOR, vb = 16 * (t + 1) + nn < h1 ? (4 * q * h1 + 16 * (t + 1) + nn) * 4 : OOR;
+#pragma unroll 1
+        for (int c = 0; c < NC; c++) {
+            f32x4 wa[LEAN_KC], wb[LEAN_KC], db[LEAN_KC];
+#pragma unroll
+            for (int u = 0; u < LEAN_KC; u++) {
+                const int s = c * LEAN_KC + u;
+                const bool kok = (NT2 % LEAN_KC == 0 || s < NT2) && 16 * s + 4 * q < h2;       // h2 % 4 == 0: a quad exists as a whole
+                const int ka = kok ? va : OOR, kb = kok ? vb : OOR;
+                db[u] = KS_LDQ(rD2, kok ? od : OOR, 16 * s * 4, 1);
+                wa[u] = f32x4{KS_LDF(rW2, ka, (16 * s + 0) * h1 * 4), KS_LDF(rW2, ka, (16 * s + 1) * h1 * 4), KS_LDF(rW2, ka, (16 * s + 2) * h1 * 4),
+                              KS_LDF(rW2, ka, (16 * s + 3) * h1 * 4)};
+                wb[u] = f32x4{KS_LDF(rW2, kb, (16 * s + 0) * h1 * 4), KS_LDF(rW2, kb, (16 * s + 1) * h1 * 4), KS_LDF(rW2, kb, (16 * s + 2) * h1 * 4),
+                              KS_LDF(rW2, kb, (16 * s + 3) * h1 * 4)};
+            }
+            KS_LEAN_LOADS_FIRST();
+#pragma unroll
+            for (int u = 0; u < LEAN_KC; u++) {
+                acca = mfma4(wa[u], db[u], acca);
+                accb = mfma4(wb[u], db[u], accb);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < 2; u++) {
+            const int f4 = (t + u) * 16 + 4 * q;
+            const f32x4 acc = u ? accb : acca;
+            const f32x4 hv = KS_LDQ(rH1, f4 < h1 ? oh1 : OOR, 16 * (t + u) * 4, 0);
+            f32x4 dz;
+            dz.x = hv.x > 0.f ? acc.x : 0.f; dz.y = hv.y > 0.f ? acc.y : 0.f; dz.z = hv.z > 0.f ? acc.z : 0.f; dz.w = hv.w > 0.f ? acc.w : 0.f;
+            if (dz1_out && row_ok && f4 < h1) *(f32x4*)(dz1_out + (long)row * h1 + f4) = dz;
+            if (dx_out) {
+                // A: W1[:, col0 + m]^T: [m][k] = W1[k][col0 + m], k = 16 t + 4 q + j (rows of W1, stride in_dim), m = nn < ncol
+                const int vx = (nn < ncol && f4 < h1) ? ((4 * q * in_dim) + col0 + nn) * 4 : OOR;
+                const int sx = 16 * (t + u) * in_dim * 4;
+                const f32x4 v = {KS_LDF(rW1, vx, sx), KS_LDF(rW1, vx, sx + in_dim * 4), KS_LDF(rW1, vx, sx + 2 * in_dim * 4), KS_LDF(rW1, vx, sx + 3 * in_dim * 4)};
+                accx = mfma4(v, dz, accx);
+            }
+        }
+    }
+    if (dx_out && q == 0 && row_ok) {
+        const float g[4] = {accx.x, accx.y, accx.z, accx.w};
+        for (int i = 0; i < ncol; i++) {
+            float v = g[i];
+            if (act_out) { const float a = act_out[(long)row * ncol + i]; v *= a * (1.f - a / scale); }
+            dx_out[(long)row * ncol + i] = v;
+        }
+    }
+}
+#undef KS_LDF
+#undef KS_LDQ
+#undef KS_LEAN_LOADS_FIRST
+
 // Weight gradients  dW[M][N] = dz^T h  (dz [n][M], h = [ha | hb] [n][N]) and the bias gradient  db[M] = column sums of dz,
 // without LDS: a wave owns one 16-row tile of dW and TN 16-column tiles, and one chunk of the batch rows; A = dz^T
 // (lane: feature m, row k), B = h (lane: row k, column).  The chunk partials go to a workspace [chunk][M * N + M] that
@@ -751,6 +981,75 @@ int kr_mlp3_backward_split(int32_t n, int32_t in_dim, int32_t h1, int32_t h2, in
     KR_BWDS_CASE(8, 8, 4) KR_BWDS_CASE(8, 8, 2)
     KR_BWDS_CASE(4, 4, 4) KR_BWDS_CASE(4, 4, 2)
 #undef KR_BWDS_CASE
+    return KS_ERR_INVALID;
+}
+
+// tile pairs of the lean kernels (mlp.py: LEAN_TILES); every lane offset is a 32-bit byte offset: rows * width * 4 must stay below LEAN_OOR
+#define KR_LEAN_PAIRS(CASE) CASE(25, 19)       /* 400-300 (reference, DDPGfD.py:19-23) and its partial tiles, e.g. 392-292 */
+static bool lean_widths_ok(int h1, int h2) {
+    if (h1 < 1 || h2 < 1 || h1 % 4 || h2 % 4) return false;
+    const int nt1 = (h1 + 15) / 16, nt2 = (h2 + 15) / 16;
+#define KR_LEAN_IS(A, B) if (nt1 == A && nt2 == B) return true;
+    KR_LEAN_PAIRS(KR_LEAN_IS)
+#undef KR_LEAN_IS
+    return false;
+}
+static bool lean_fits32(int64_t rows, int64_t width) { return rows * width * 4 < (int64_t)LEAN_OOR; }
+
+int kr_mlp3_forward_lean(int32_t n, int32_t in_a, int32_t in_b, int32_t h1, int32_t h2, int32_t out_dim, const float* xa, int32_t lda,
+                         const float* xb, int32_t ldb, const float* W1, const float* b1, const float* W2, const float* b2,
+                         const float* W3, const float* b3, int32_t act, float scale, float* out, float* h1_out, float* h2_out,
+                         float* scratch, int64_t scratch_floats, void* stream) {
+    if (n <= 0) return KS_OK;
+    if (!xa || !W1 || !b1 || !W2 || !b2 || !W3 || !b3 || !out || in_a <= 0 || in_b < 0 || (in_b > 0 && !xb)) return KS_ERR_INVALID;
+    if (in_a + in_b > 16 * KS_IN_MAX || out_dim < 1 || out_dim > 4 || !lean_widths_ok(h1, h2)) return KS_ERR_INVALID;
+    if (act != KR_ACT_NONE && act != KR_ACT_SIGMOID) return KS_ERR_INVALID;
+    if ((uintptr_t)W2 % 16 || (uintptr_t)W3 % 16 || (h1_out && (uintptr_t)h1_out % 16) || (h2_out && (uintptr_t)h2_out % 16)) return KS_ERR_INVALID;
+    if (lda < in_a || (in_b > 0 && ldb < in_b)) return KS_ERR_INVALID;
+    const int blocks = (n + ROWS - 1) / ROWS;
+    // scratch: layer 1's output quads of every wave's 16 rows, unless the caller keeps h1 itself
+    const int64_t need = h1_out ? 0 : (int64_t)blocks * ROWS * h1;
+    if (need && (!scratch || (uintptr_t)scratch % 16 || scratch_floats < need)) return KS_ERR_INVALID;
+    if (!lean_fits32((int64_t)blocks * ROWS, h1 > h2 ? h1 : h2) || !lean_fits32(n, lda) || !lean_fits32(n, in_b > 0 ? ldb : 1)) return KS_ERR_INVALID;
+    float* h1buf = h1_out ? h1_out : scratch;
+    const int h1_rows = h1_out ? n : blocks * ROWS;
+    const int nt1 = (h1 + 15) / 16, nt2 = (h2 + 15) / 16;
+    hipStream_t s = (hipStream_t)stream;
+#define KR_LEAN_CASE(A, B)                                                                                                                    \
+    if (nt1 == A && nt2 == B) {                                                                                                               \
+        hipLaunchKernelGGL((k_mlp3_lean<A, B>), dim3(blocks), dim3(64), 0, s, n, in_a, in_b, h1, h2, out_dim, xa, lda, xb, ldb, W1, b1, W2, b2,  \
+                           W3, b3, act, scale, out, h1buf, h1_rows, h2_out);                                                                  \
+        return hipGetLastError() == hipSuccess ? KS_OK : KS_ERR_HIP;                                                                          \
+    }
+    KR_LEAN_PAIRS(KR_LEAN_CASE)
+#undef KR_LEAN_CASE
+    return KS_ERR_INVALID;
+}
+
+int kr_mlp3_backward_lean(int32_t n, int32_t in_dim, int32_t h1, int32_t h2, int32_t out_dim, const float* dz3, const float* W3,
+                          const float* h2a, const float* W2, const float* h1a, float* dz2_out, float* dz1_out, const float* W1, int32_t col0,
+                          int32_t ncol, const float* act_out, float scale, float* dx_out, float* scratch, int64_t scratch_floats, void* stream) {
+    if (n <= 0) return KS_OK;
+    if (!dz3 || !W3 || !h2a || !W2 || !h1a || out_dim < 1 || out_dim > 4 || !lean_widths_ok(h1, h2)) return KS_ERR_INVALID;
+    if (dx_out && (!W1 || ncol < 1 || ncol > 4 || col0 < 0 || col0 + ncol > in_dim)) return KS_ERR_INVALID;
+    if ((uintptr_t)h1a % 16 || (uintptr_t)h2a % 16 || (dz1_out && (uintptr_t)dz1_out % 16) || (dz2_out && (uintptr_t)dz2_out % 16)) return KS_ERR_INVALID;
+    const int blocks = (n + ROWS - 1) / ROWS;
+    // scratch: the masked dz2 quads of every wave's 16 rows, unless the caller keeps dz2 itself
+    const int64_t need = dz2_out ? 0 : (int64_t)blocks * ROWS * h2;
+    if (need && (!scratch || (uintptr_t)scratch % 16 || scratch_floats < need)) return KS_ERR_INVALID;
+    if (!lean_fits32((int64_t)blocks * ROWS, h1 > h2 ? h1 : h2) || (dx_out && !lean_fits32(h1, in_dim))) return KS_ERR_INVALID;
+    float* dz2buf = dz2_out ? dz2_out : scratch;
+    const int dz2_rows = dz2_out ? n : blocks * ROWS;
+    const int nt1 = (h1 + 15) / 16, nt2 = (h2 + 15) / 16;
+    hipStream_t s = (hipStream_t)stream;
+#define KR_LEAN_CASE(A, B)                                                                                                                    \
+    if (nt1 == A && nt2 == B) {                                                                                                               \
+        hipLaunchKernelGGL((k_mlp3_bwd_lean<A, B>), dim3(blocks), dim3(64), 0, s, n, in_dim, h1, h2, out_dim, dz3, W3, h2a, W2, h1a, dz2buf,    \
+                           dz2_rows, dz1_out, W1, col0, ncol, act_out, scale, dx_out);                                                        \
+        return hipGetLastError() == hipSuccess ? KS_OK : KS_ERR_HIP;                                                                          \
+    }
+    KR_LEAN_PAIRS(KR_LEAN_CASE)
+#undef KR_LEAN_CASE
     return KS_ERR_INVALID;
 }
 

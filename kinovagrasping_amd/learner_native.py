@@ -1,4 +1,4 @@
-"""DDPGfD update without autograd (DDPGfD.train_batch, DDPGfD.py:219-367 of the reference), in two forms:
+"""DDPGfD update without autograd (DDPGfD.train_batch, DDPGfD.py:219-367 of the reference), in three forms:
 
 * **LDS-free MFMA kernels** (widths 256-256 / 128-128 / 64-64; `lds_free`): every forward, data-gradient and
   weight-gradient pass is a hand-written fp32-MFMA launch of libkinova_sim.so (csrc/ks_mlp.hip, mlp.py) that keeps its
@@ -7,7 +7,12 @@
   whole update runs in the stepping kernel's shadow on the matrix pipes and issue slots it leaves idle
   (pipeline.GraphedTrainer launches it on a second stream), instead of waiting for its workgroups to retire as the
   library GEMMs (which need LDS) must.  ~35 launches per update.
-* **library GEMMs** (any width, e.g. the reference's 400-300): explicit forward / backward GEMMs (PyTorch -> hipBLASLt)
+* **lean LDS-free MFMA kernels** (the reference's 400-300 and its partial tiles; `NativeDDPGfDUpdate(policy, lean=True)`, `lean_kernels`):
+  the same passes on kr_mlp3_forward_lean / kr_mlp3_backward_lean + the generic kr_weight_grad_shadow.  The free-running rollout
+  kernel at that width (k_rollout<25,19>) leaves 96 registers per SIMD lane, too few to keep a hidden layer in registers: these
+  kernels write the first product's output (h1 / dz2) to global memory and stream it back with the weights, <= 96 registers, no
+  scratch.  Opt-in: what pipeline.AsyncTrainer builds at 400-300; the default at that width stays the next form.
+* **library GEMMs** (any width; the default at the reference's 400-300): explicit forward / backward GEMMs (PyTorch -> hipBLASLt)
   with the elementwise steps between them as single kernels (kr_relu_backward, ...), weight gradients written by the
   GEMMs straight into one flat gradient buffer per network; the forward-only target networks and the critic forward
   still go through the fused LDS kernel (kr_mlp3_forward) when the width has an instantiation.  ~75 launches.
@@ -52,7 +57,10 @@ class _Net:
 
 
 class NativeDDPGfDUpdate:
-    def __init__(self, policy):
+    def __init__(self, policy, lean=None):
+        """lean: None keeps the form the width has by default (LDS-free kernels at 256-256 / 128-128 / 64-64, library GEMMs otherwise);
+        True asks for an update without a single launch that needs LDS - the default LDS-free kernels where the width has them, the
+        lean ones (mlp.LEAN_TILES: 400-300) where it does not, ValueError when it has neither."""
         assert policy.device.type == "cuda", "the learner glue kernels are GPU only"
         self.p = policy
         self.lib = _sim.load_library()
@@ -88,6 +96,19 @@ class NativeDDPGfDUpdate:
         self.fused_targets = mult(4) and all(_mlp.supported(layers, d) for layers, d in zip(tl, ins))
         self.shadow = self.fused_targets and all(_mlp.supported(layers, d, shadow=True) for layers, d in zip(tl, ins))
         self.lds_free = self.shadow and mult(16) and os.environ.get("KS_EXP_LDSFREE", "1") == "1"
+        # lean=True: no launch of the update may need LDS.  A width without the kernels above runs every pass - the 8000-row forwards
+        # of the actor phase included - on the lean kernels (kr_mlp3_forward_lean / kr_mlp3_backward_lean: <= 96 registers per lane,
+        # which is what k_rollout<25,19> leaves on a SIMD) and the generic kr_weight_grad_shadow.
+        self.lean = bool(lean)
+        self.lean_kernels = False
+        if self.lean and not self.lds_free:
+            nets = (self.actor, self.critic, self.actor_t, self.critic_t)
+            if not all(_mlp.supported(list(zip(net.W, net.b)), net.W[0].shape[1], lean=True) for net in nets):
+                raise ValueError("NativeDDPGfDUpdate(lean=True): hidden widths %s have neither the LDS-free learner kernels (256-256 / 128-128 / "
+                                 "64-64) nor the lean ones (400-300)" % (tuple(w.shape[0] for w in self.actor.W[:2]),))
+            self.lean_kernels = self.fused_targets = self.lds_free = True
+        self._form = dict(lean=True) if self.lean_kernels else dict(shadow=True)      # the LDS-free passes of mlp.py
+        self._targets_form = self._form if self.lds_free else dict(shadow=self.shadow)
         # The 8000-row forwards of the actor phase stay on the library GEMMs unless the update is LDS-free: at that size
         # three large-tile GEMMs beat the 16-row-tile LDS kernel (measured 1.48 vs 1.44 ms per env-step in bench.py).
         self.fuse_critic_fwd, self.fuse_actor_fwd = True, False
@@ -231,17 +252,17 @@ class NativeDDPGfDUpdate:
             s0, a0 = state[:, 0], action[:, 0]
             reward = reward.contiguous()
             with self._branch(0):
-                ta = _mlp.mlp3_forward(list(zip(self.actor_t.W, self.actor_t.b)), nx, act=_mlp.ACT_SIGMOID, scale=pol.max_action, shadow=True)
-                tq = _mlp.mlp3_forward(list(zip(self.critic_t.W, self.critic_t.b)), nx, ta, act=_mlp.ACT_NONE, shadow=True)
+                ta = _mlp.mlp3_forward(list(zip(self.actor_t.W, self.actor_t.b)), nx, act=_mlp.ACT_SIGMOID, scale=pol.max_action, **self._form)
+                tq = _mlp.mlp3_forward(list(zip(self.critic_t.W, self.critic_t.b)), nx, ta, act=_mlp.ACT_NONE, **self._form)
             h1, h2 = s0.new_empty(R, c.W[0].shape[0]), s0.new_empty(R, c.W[1].shape[0])
-            q = _mlp.mlp3_forward(cl, s0, a0, act=_mlp.ACT_NONE, h1_out=h1, h2_out=h2, shadow=True)
+            q = _mlp.mlp3_forward(cl, s0, a0, act=_mlp.ACT_NONE, h1_out=h1, h2_out=h2, **self._form)
             dq = torch.empty_like(q)
             self._join(0)
             self._chk(self.lib.kr_critic_grad(R, pol.n, P(q), P(tq), P(tq[R:]), P(reward), P(weight), P(self.wsum), pol.discount, P(dq), P(self.losses),
                                               self._st()), "kr_critic_grad")
             with self._branch(0):                              # the last layer's weight gradient needs dq only: beside the data-gradient pass
                 _mlp.weight_grad(dq, h2, None, c.gW[2], c.gb[2])
-            dz2, dz1, _ = _mlp.mlp3_backward(cl, dq, h1, h2)
+            dz2, dz1, _ = _mlp.mlp3_backward(cl, dq, h1, h2, lean=self.lean_kernels)
             with self._branch(1):
                 _mlp.weight_grad(dz2, h1, None, c.gW[1], c.gb[1])
             _mlp.weight_grad(dz1, s0, a0, c.gW[0], c.gb[0])
@@ -249,8 +270,8 @@ class NativeDDPGfDUpdate:
             return self.losses[0], self.losses[1], self.losses[2]
         if self.fused_targets:
             # forward-only networks: one fused fp32-MFMA launch each (mlp.mlp3_forward) instead of 3 GEMMs + glue
-            ta = _mlp.mlp3_forward(list(zip(self.actor_t.W, self.actor_t.b)), nx, act=_mlp.ACT_SIGMOID, scale=pol.max_action, shadow=self.shadow)
-            tq = _mlp.mlp3_forward(list(zip(self.critic_t.W, self.critic_t.b)), nx, ta, act=_mlp.ACT_NONE, shadow=self.shadow)
+            ta = _mlp.mlp3_forward(list(zip(self.actor_t.W, self.actor_t.b)), nx, act=_mlp.ACT_SIGMOID, scale=pol.max_action, **self._targets_form)
+            tq = _mlp.mlp3_forward(list(zip(self.critic_t.W, self.critic_t.b)), nx, ta, act=_mlp.ACT_NONE, **self._targets_form)
         else:
             _, _, ta = self._actor_forward(self.actor_t, nx)
             ct = self.critic_t
@@ -261,12 +282,12 @@ class NativeDDPGfDUpdate:
             cl = list(zip(c.W, c.b))
             s0, a0 = state[:, 0], action[:, 0]
             h1, h2 = s0.new_empty(R, c.W[0].shape[0]), s0.new_empty(R, c.W[1].shape[0])
-            q = _mlp.mlp3_forward(cl, s0, a0, act=_mlp.ACT_NONE, h1_out=h1, h2_out=h2, shadow=True)
+            q = _mlp.mlp3_forward(cl, s0, a0, act=_mlp.ACT_NONE, h1_out=h1, h2_out=h2, **self._form)
             dq = torch.empty_like(q)
             reward = reward.contiguous()
             self._chk(self.lib.kr_critic_grad(R, pol.n, P(q), P(tq), P(tq[R:]), P(reward), P(weight), P(self.wsum), pol.discount, P(dq), P(self.losses),
                                               self._st()), "kr_critic_grad")
-            dz2, dz1, _ = _mlp.mlp3_backward(cl, dq, h1, h2)
+            dz2, dz1, _ = _mlp.mlp3_backward(cl, dq, h1, h2, lean=self.lean_kernels)
             _mlp.weight_grad(dq, h2, None, c.gW[2], c.gb[2])
             _mlp.weight_grad(dz2, h1, None, c.gW[1], c.gb[1])
             _mlp.weight_grad(dz1, s0, a0, c.gW[0], c.gb[0])
@@ -274,7 +295,7 @@ class NativeDDPGfDUpdate:
         x0 = torch.cat([state[:, 0], action[:, 0]], 1)
         if self.fused_targets and self.fuse_critic_fwd:
             h1, h2 = x0.new_empty(R, c.W[0].shape[0]), x0.new_empty(R, c.W[1].shape[0])
-            q = _mlp.mlp3_forward(list(zip(c.W, c.b)), state[:, 0], action[:, 0], act=_mlp.ACT_NONE, h1_out=h1, h2_out=h2, shadow=self.shadow)
+            q = _mlp.mlp3_forward(list(zip(c.W, c.b)), state[:, 0], action[:, 0], act=_mlp.ACT_NONE, h1_out=h1, h2_out=h2, **self._targets_form)
         else:
             h1 = self._lin_relu(c, 0, x0)
             h2 = self._lin_relu(c, 1, h1)
@@ -298,24 +319,24 @@ class NativeDDPGfDUpdate:
             rows = sa.shape[0]
             al, cl = list(zip(a_.W, a_.b)), list(zip(c.W, c.b))
             ha1, ha2 = sa.new_empty(rows, a_.W[0].shape[0]), sa.new_empty(rows, a_.W[1].shape[0])
-            a = _mlp.mlp3_forward(al, sa, act=_mlp.ACT_SIGMOID, scale=pol.max_action, h1_out=ha1, h2_out=ha2, shadow=True)
+            a = _mlp.mlp3_forward(al, sa, act=_mlp.ACT_SIGMOID, scale=pol.max_action, h1_out=ha1, h2_out=ha2, **self._form)
             hc1, hc2 = sa.new_empty(rows, c.W[0].shape[0]), sa.new_empty(rows, c.W[1].shape[0])
-            q = _mlp.mlp3_forward(cl, sa, a, act=_mlp.ACT_NONE, h1_out=hc1, h2_out=hc2, shadow=True)       # Q itself is not needed
+            q = _mlp.mlp3_forward(cl, sa, a, act=_mlp.ACT_NONE, h1_out=hc1, h2_out=hc2, **self._form)       # Q itself is not needed
             if self.track_actor_loss:
                 self._set_actor_loss(q, n)
             dq = self.dq_actor
             # dLoss/d(actor pre-activation): through the critic to its action inputs, then through 0.8 * sigmoid
-            _, _, dz3 = _mlp.mlp3_backward(cl, dq, hc1, hc2, want_dz=False, dx_cols=(sa.shape[1], a.shape[1]), act_out=a, scale=pol.max_action)
+            _, _, dz3 = _mlp.mlp3_backward(cl, dq, hc1, hc2, want_dz=False, dx_cols=(sa.shape[1], a.shape[1]), act_out=a, scale=pol.max_action, lean=self.lean_kernels)
             if self.fork:
                 with self._branch(0):
                     _mlp.weight_grad(dz3, ha2, None, a_.gW[2], a_.gb[2])
-                dz2, dz1, _ = _mlp.mlp3_backward(al, dz3, ha1, ha2)
+                dz2, dz1, _ = _mlp.mlp3_backward(al, dz3, ha1, ha2, lean=self.lean_kernels)
                 with self._branch(1):
                     _mlp.weight_grad(dz2, ha1, None, a_.gW[1], a_.gb[1])
                 _mlp.weight_grad(dz1, sa, None, a_.gW[0], a_.gb[0])
                 self._join(0, 1)
                 return None
-            dz2, dz1, _ = _mlp.mlp3_backward(al, dz3, ha1, ha2)
+            dz2, dz1, _ = _mlp.mlp3_backward(al, dz3, ha1, ha2, lean=self.lean_kernels)
             _mlp.weight_grad(dz3, ha2, None, a_.gW[2], a_.gb[2])
             _mlp.weight_grad(dz2, ha1, None, a_.gW[1], a_.gb[1])
             _mlp.weight_grad(dz1, sa, None, a_.gW[0], a_.gb[0])

@@ -11,6 +11,7 @@ from . import sim as _sim
 ACT_NONE, ACT_SIGMOID = 0, 1
 SUPPORTED_TILES = {(16, 16), (25, 19), (8, 8), (4, 4)}      # ceil(hidden / 16) of the two hidden layers (ks_mlp.hip)
 SHADOW_TILES = {(16, 16), (8, 8), (4, 4)}                   # ... of the LDS-free variant (kr_mlp3_forward_shadow)
+LEAN_TILES = {(25, 19)}                                     # ... of the lean LDS-free variant (kr_mlp3_forward_lean): <= 96 registers per lane
 
 
 def layers_of(module):
@@ -18,14 +19,17 @@ def layers_of(module):
     return [(getattr(module, k).weight.data, getattr(module, k).bias.data) for k in ("l1", "l2", "l3")]
 
 
-def supported(layers, in_dim: int, shadow: bool = False) -> bool:
-    """True when the fused forward (shadow: its LDS-free form) runs these layers: the tile pair has an instantiation and,
-    for the LDS-free form, both hidden widths are whole tiles (kr_mlp3_forward_shadow refuses h % 16 != 0)"""
+def supported(layers, in_dim: int, shadow: bool = False, lean: bool = False) -> bool:
+    """True when the fused forward (shadow: its LDS-free form, lean: its lean LDS-free form) runs these layers: the tile pair has an
+    instantiation and, for the LDS-free form, both hidden widths are whole tiles (kr_mlp3_forward_shadow refuses h % 16 != 0); the
+    lean form takes partial last tiles of whole quads (kr_mlp3_forward_lean refuses h % 4 != 0)"""
     (w1, _), (w2, _), (w3, _) = layers
     tiles = ((w1.shape[0] + 15) // 16, (w2.shape[0] + 15) // 16)
+    ok = (w1.is_cuda and w1.dtype == torch.float32 and in_dim <= 96 and w3.shape[0] <= 4 and all(w.is_contiguous() and b.is_contiguous() for w, b in layers))
+    if lean:
+        return ok and tiles in LEAN_TILES and w1.shape[0] % 4 == 0 and w2.shape[0] % 4 == 0
     whole = not shadow or (w1.shape[0] % 16 == 0 and w2.shape[0] % 16 == 0)
-    return (w1.is_cuda and w1.dtype == torch.float32 and tiles in (SHADOW_TILES if shadow else SUPPORTED_TILES) and whole and in_dim <= 96
-            and w3.shape[0] <= 4 and all(w.is_contiguous() and b.is_contiguous() for w, b in layers))
+    return ok and tiles in (SHADOW_TILES if shadow else SUPPORTED_TILES) and whole
 
 
 def _split_waves(n: int) -> int:
@@ -40,11 +44,12 @@ def _split_waves(n: int) -> int:
 
 def mlp3_forward(layers, xa: torch.Tensor, xb: torch.Tensor | None = None, act: int = ACT_NONE, scale: float = 1.0,
                  out: torch.Tensor | None = None, h1_out: torch.Tensor | None = None, h2_out: torch.Tensor | None = None,
-                 shadow: bool = False) -> torch.Tensor:
+                 shadow: bool = False, lean: bool = False) -> torch.Tensor:
     """out[n, out_dim] = f(W3 relu(W2 relu(W1 [xa | xb] + b1) + b2) + b3) on the current stream.  xa / xb: fp32 [n, *]
     with unit column stride (row stride free: slices of wider tensors are fine).  h1_out [n, h1] / h2_out [n, h2]
     (contiguous, optional) receive the hidden activations for a backward pass.  shadow=True: the LDS-free kernel whose
-    waves fit beside the resident simulator kernel (include/kinova_rollout.h: kr_mlp3_forward_shadow)."""
+    waves fit beside the resident simulator kernel (include/kinova_rollout.h: kr_mlp3_forward_shadow).  lean=True: the lean
+    LDS-free kernel (kr_mlp3_forward_lean, tile pairs LEAN_TILES), whose waves fit beside the free-running rollout kernel at 400-300."""
     (w1, b1), (w2, b2), (w3, b3) = layers
     n, in_a = xa.shape
     in_b = 0 if xb is None else xb.shape[1]
@@ -56,6 +61,16 @@ def mlp3_forward(layers, xa: torch.Tensor, xb: torch.Tensor | None = None, act: 
     for h, w in ((h1_out, w1), (h2_out, w2)):
         assert h is None or (h.is_contiguous() and tuple(h.shape) == (n, w.shape[0]) and h.dtype == torch.float32)
     lib, P = _sim.load_library(), _sim._ptr
+    if lean:
+        # layer 1's output goes through global memory: the caller's h1_out, or scratch
+        need = 0 if h1_out is not None else (n + 15) // 16 * 16 * w1.shape[0]
+        scratch = torch.empty(need, device=xa.device, dtype=torch.float32) if need else None
+        rc = lib.kr_mlp3_forward_lean(n, in_a, in_b, w1.shape[0], w2.shape[0], w3.shape[0], P(xa), xa.stride(0), P(xb) if xb is not None else None,
+                                      xb.stride(0) if xb is not None else 0, P(w1), P(b1), P(w2), P(b2), P(w3), P(b3), act, float(scale), P(out),
+                                      P(h1_out), P(h2_out), P(scratch), need, _stream(xa))
+        if rc != 0:
+            raise RuntimeError(f"kr_mlp3_forward_lean failed ({rc}): unsupported layer widths or bad arguments")
+        return out
     waves = _split_waves(n) if shadow and w1.shape[0] % 16 == 0 and w2.shape[0] % 16 == 0 and w1.shape[0] // 16 in (4, 8, 16) and w1.shape[0] == w2.shape[0] else 0
     if waves:
         # the LDS-free launch with each layer's tiles split over 2 / 4 waves of a workgroup (kr_mlp3_forward_split)
@@ -81,11 +96,11 @@ def _stream(t):
 
 
 def mlp3_backward(layers, dz3: torch.Tensor, h1: torch.Tensor, h2: torch.Tensor, want_dz: bool = True, dx_cols: tuple[int, int] | None = None,
-                  act_out: torch.Tensor | None = None, scale: float = 1.0):
+                  act_out: torch.Tensor | None = None, scale: float = 1.0, lean: bool = False):
     """Data gradients of the 3-layer MLP without LDS (kr_mlp3_backward_shadow).  dz3 [n, out_dim] = dLoss/d(last
     pre-activation); h1 / h2 the activations of the forward pass.  Returns (dz2, dz1, dx): dz2 / dz1 None unless want_dz;
     dx [n, ncol] = dLoss/d(input columns col0..col0+ncol) for dx_cols = (col0, ncol), None otherwise - multiplied by the
-    derivative of scale * sigmoid when act_out (that sigmoid's output) is given."""
+    derivative of scale * sigmoid when act_out (that sigmoid's output) is given.  lean=True: kr_mlp3_backward_lean (LEAN_TILES)."""
     (w1, _), (w2, _), (w3, _) = layers
     n = dz3.shape[0]
     assert dz3.is_contiguous() and h1.is_contiguous() and h2.is_contiguous() and tuple(h1.shape) == (n, w1.shape[0]) and tuple(h2.shape) == (n, w2.shape[0])
@@ -97,6 +112,15 @@ def mlp3_backward(layers, dz3: torch.Tensor, h1: torch.Tensor, h2: torch.Tensor,
         dx = torch.empty(n, ncol, device=dz3.device, dtype=torch.float32)
         assert act_out is None or (act_out.is_contiguous() and tuple(act_out.shape) == (n, ncol))
     lib, P = _sim.load_library(), _sim._ptr
+    if lean:
+        # dz2 goes through global memory: the returned dz2, or scratch
+        need = 0 if dz2 is not None else (n + 15) // 16 * 16 * w2.shape[0]
+        scratch = torch.empty(need, device=dz3.device, dtype=torch.float32) if need else None
+        rc = lib.kr_mlp3_backward_lean(n, w1.shape[1], w1.shape[0], w2.shape[0], w3.shape[0], P(dz3), P(w3), P(h2), P(w2), P(h1), P(dz2), P(dz1), P(w1),
+                                       col0, ncol, P(act_out), float(scale), P(dx), P(scratch), need, _stream(dz3))
+        if rc != 0:
+            raise RuntimeError(f"kr_mlp3_backward_lean failed ({rc})")
+        return dz2, dz1, dx
     waves = _split_waves(n) if w1.shape[0] == w2.shape[0] and w1.shape[0] % 16 == 0 and w1.shape[0] // 16 in (4, 8, 16) else 0
     if waves:
         need = (n + 15) // 16 * waves * 64 if dx is not None else 0

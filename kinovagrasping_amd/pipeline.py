@@ -73,7 +73,7 @@ def _concurrent_stream(main, dev, tries=8):
 
 class GraphedTrainer:
     def __init__(self, sim, policy, replay, engine, batch_episodes=64, overlap=True, learn_after=31, expert_replay=None, expert_prob=0.3,
-                 updates_per_step=1):
+                 updates_per_step=1, lean_learner=False):
         """updates_per_step U / batch_episodes: the update-to-data knobs.  The reference makes 100 updates per 30-step episode of ONE
         env (main_DDPGfD.py:474-486: ~3 per stored transition); BASELINE config 3 - bench.py's workload - is ONE update on 64 episodes
         per env-step of 4096 envs.  U > 1 replays the captured update U times per env-step (the step becomes learner-bound beyond
@@ -82,7 +82,11 @@ class GraphedTrainer:
         hardly grows with the rows.
         expert_replay (a DeviceEpisodeReplay filled by demonstrators.run_controller_episodes or loaded from a reference replay
         bundle) turns the update into DDPGfD proper: every batch is int(batch_episodes * (1 - expert_prob)) agent episodes + the rest
-        expert episodes (DDPGfD.train_batch, DDPGfD.py:232-254), sampled by ONE launch inside the captured update."""
+        expert episodes (DDPGfD.train_batch, DDPGfD.py:232-254), sampled by ONE launch inside the captured update.
+        lean_learner: build the learner with NativeDDPGfDUpdate(policy, lean=True) - no launch of the update needs LDS at any width
+        that has LDS-free kernels of either kind (400-300: the lean ones) - so that the overlapped lock-step form can be measured on
+        the kernels AsyncTrainer uses at that width.  "auto" (AsyncTrainer's choice): only when the default form is not LDS-free and
+        the lean kernels take the width."""
         assert engine.gen is None, "graph capture uses the default CUDA generator"
         self.sim, self.policy, self.replay, self.eng = sim, policy, replay, engine
         self.expert_replay, self.expert_prob = expert_replay, float(expert_prob)
@@ -110,7 +114,12 @@ class GraphedTrainer:
         self.losses = None
         # the update itself: explicit GEMMs + fused glue kernels (learner_native), same arithmetic as policy.train_on_batch
         from .learner_native import NativeDDPGfDUpdate
-        self.native = NativeDDPGfDUpdate(policy)
+        self.native = NativeDDPGfDUpdate(policy, lean=True if (lean_learner and lean_learner != "auto") else None)
+        if lean_learner == "auto" and not self.native.lds_free:
+            try:
+                self.native = NativeDDPGfDUpdate(policy, lean=True)
+            except ValueError:
+                pass                     # neither form: the caller decides (AsyncTrainer raises)
         self.native.pipelined = True
         # the gradient exchange between the ranks: an LDS-free all-reduce over peer-mapped memory where the ranks can map each
         # other's buffers (one process per GPU on a node) - it runs beside the stepping kernel, which a library collective
@@ -395,7 +404,7 @@ class AsyncTrainer(GraphedTrainer):
         (run(budget_ms=...)).  max_launch_steps sizes the staging ring: one finished episode per 10 env-steps of the longest launch
         and env, plus two; what does not fit is kept waiting in the env's buffers, never overwritten."""
         super().__init__(sim, policy, replay, engine, batch_episodes=batch_episodes, overlap=True, expert_replay=expert_replay, expert_prob=expert_prob,
-                         updates_per_step=updates_per_step)
+                         updates_per_step=updates_per_step, lean_learner="auto")
         self.launch_synchronous = bool(launch_synchronous)
         if self.launch_synchronous:
             from .replay import DeviceEpisodeReplay
@@ -408,7 +417,7 @@ class AsyncTrainer(GraphedTrainer):
                            torch.rand(replay.ep_state.shape[2], generator=g, dtype=torch.float64).to(replay.device))
         eng, dev = engine, self.dev
         if not self.native.lds_free:
-            raise ValueError("AsyncTrainer needs the LDS-free learner kernels (hidden widths 256-256 / 128-128 / 64-64): the persistent rollout kernel "
+            raise ValueError("AsyncTrainer needs the LDS-free learner kernels (hidden widths 256-256 / 128-128 / 64-64, or the lean ones: 400-300): the persistent rollout kernel "
                              "holds every CU's LDS for the whole launch, a learner built on library GEMMs could only run behind it")
         # How the replicas are kept together:
         #   "per-update"         every update's two gradient buffers are averaged over the ranks before Adam (north_star's scheme).  Beside the
@@ -538,6 +547,7 @@ class AsyncTrainer(GraphedTrainer):
         # (mlp._split_waves reads KS_MLP_SPLIT at every call) is baked into the captured graphs
         before = os.environ.get("KS_MLP_SPLIT")
         os.environ["KS_MLP_SPLIT"] = os.environ.get("KS_ASYNC_MLP_SPLIT", "0")      # (experiment: a build whose split kernels fit in 128 registers)
+        # (the lean kernels of 400-300 have no split form: mlp.py takes the lean path before it looks at KS_MLP_SPLIT)
         try:
             self._capture(warmup_updates)
         finally:
