@@ -800,6 +800,10 @@ __global__ __launch_bounds__(WG) KS_STEP_REGS void k_env_step_f32(const Model<fl
 // the 512 registers per lane) is what lets the learner's LDS-free waves run beside this kernel for its whole life.
 // (EXACT: the exact-mode kernel's own instantiation of the same body - one out-of-line callee shared with k_rollout_f64, which has no register
 // cap, changes the callee's frame and so k_rollout's scratch size)
+__device__ __forceinline__ long long uniform64(long long v) {      // lane 0's value, in scalar registers
+    const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)v), hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)((unsigned long long)v >> 32));
+    return (long long)(((unsigned long long)hi << 32) | lo);
+}
 template <int NT1, int NT2, bool EXACT = false>
 __device__ __noinline__ void rollout_policy(const ks_rollout_args* __restrict__ rap, int N, int row_env, KS_LDS float* blocks) {
     const ks_rollout_args& ra = *rap;
@@ -815,13 +819,13 @@ __device__ __noinline__ void rollout_policy(const ks_rollout_args* __restrict__ 
     for (;;) {
         if (threadIdx.x == 0) vbox[0] = (long long)__hip_atomic_load(ra.actor_ver, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         __syncthreads();
-        const long long ver = vbox[0];
+        const long long ver = uniform64(vbox[0]);                               // (in scalar registers: the weights' buffer resources are built from it)
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");                      // the newest complete weight buffer, as written
         const float* pw = ra.actor_pub + (ver % 3) * ra.actor_stride;
         kmlp::f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
-        const bool mine = kmlp::mlp3_rows16<NT1, NT2, true>(wave, lane, (long)row_env, S, 0, ra.h1, ra.h2, A, ra.obs, S, nullptr, 0, pw + ra.off_w1,
-                                                            pw + ra.off_b1, pw + ra.off_w2, pw + ra.off_b2, pw + ra.off_w3, nullptr, nullptr, H1, H2, Pp,
-                                                            z4);
+        const bool mine = kmlp::mlp3_rows16<NT1, NT2, true>(wave, lane, (long)row_env, S, 0, ra.h1, ra.h2, A, ra.obs, S, kmlp::x_bytes(N, 0, S, S), nullptr, 0,
+                                                            0u, pw + ra.off_w1, pw + ra.off_b1, pw + ra.off_w2, pw + ra.off_b2, pw + ra.off_w3, nullptr,
+                                                            nullptr, H1, H2, Pp, z4);
         // the last words read from buffer ver % 3 - the layer-3 bias - are taken BEFORE the staleness check below, and a fence keeps
         // the check's load behind them: everything the action is computed from has then been read when the counter is looked at
         float y[4] = {0.f, 0.f, 0.f, 0.f};
@@ -1051,10 +1055,6 @@ __device__ __forceinline__ void rollout_iter(const Model<float>& m, const Hulls<
 // tile a quarter full, bit-equal per row to the 4-wave tile), its own rays (the same work-sharing queue among 64 lanes), its own
 // observation and replay rows - and no s_barrier between kernel entry and exit.  Scratch of the tails: the wave's own four (then
 // dead) env blocks.
-__device__ __forceinline__ long long uniform64(long long v) {      // lane 0's value, in scalar registers
-    const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)v), hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)((unsigned long long)v >> 32));
-    return (long long)(((unsigned long long)hi << 32) | lo);
-}
 template <int NT1, int NT2>
 __device__ __noinline__ void rollout_policy_wave(const ks_rollout_args* __restrict__ rap, int N, int row_env, KS_LDS float* wblocks) {
     const ks_rollout_args& ra = *rap;
@@ -1069,8 +1069,8 @@ __device__ __noinline__ void rollout_policy_wave(const ks_rollout_args* __restri
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
         const float* pw = ra.actor_pub + (ver % 3) * ra.actor_stride;
         kmlp::f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
-        const bool mine = kmlp::mlp3_rows_wave<NT1, NT2, true, NR>(lane, (long)row_env, S, ra.h1, ra.h2, A, ra.obs, S, pw + ra.off_w1, pw + ra.off_b1,
-                                                                     pw + ra.off_w2, pw + ra.off_b2, pw + ra.off_w3, H1, H2, z4);
+        const bool mine = kmlp::mlp3_rows_wave<NT1, NT2, true, NR>(lane, (long)row_env, S, ra.h1, ra.h2, A, ra.obs, S, kmlp::x_bytes(N, 0, S, S), pw + ra.off_w1,
+                                                                     pw + ra.off_b1, pw + ra.off_w2, pw + ra.off_b2, pw + ra.off_w3, H1, H2, z4);
         float y[4] = {0.f, 0.f, 0.f, 0.f};
         if (mine) {
             const float z[4] = {z4.x, z4.y, z4.z, z4.w};
@@ -2435,6 +2435,7 @@ template <typename T> struct Ctx : CtxBase {
         if (ctl_mode != 0) return KS_OK;                       // a scripted controller acts: the actor's fields are ignored
         if ((ra->off_w2 | ra->off_w3 | ra->actor_stride) & 3) { error = "ks_rollout: weight offsets must be multiples of 4 floats"; return KS_ERR_INVALID; }
         if ((ra->h1 | ra->h2) & 3) { error = "ks_rollout: hidden widths must be multiples of 4"; return KS_ERR_INVALID; }
+        if ((int64_t)cfg.n_envs * krsel::S * 4 >= (int64_t)kmlp::OOR) { error = "ks_rollout: the observation rows exceed the actor's 32-bit lane offsets"; return KS_ERR_INVALID; }
         return KS_OK;
     }
     // the launch's output record (the context's sim_* buffers) and argument record -> device memory

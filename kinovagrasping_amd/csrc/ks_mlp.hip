@@ -62,8 +62,12 @@ __global__ __launch_bounds__(64 * NW) void k_mlp3(int n, int in_a, int in_b, int
     unsigned long long rng_step = 0;
     if (SEL && sel.rng_state) rng_step = (unsigned long long)sel.rng_state[0];      // read by every workgroup before any of them finishes
     f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
-    if (mlp3_rows16<NT1, NT2, VEC>(wave, lane, row_ok ? (long)row : -1L, in_a, in_b, h1, h2, out_dim, xa, lda, xb, ldb, W1, b1, W2, b2, W3, h1_out, h2_out,
-                                   H1, H2, P, z4)) {
+    // (the tile body addresses the workgroup's own rows 0 .. 15 of blocks that begin at its first row: 32-bit offsets at any n)
+    const long r0 = (long)blockIdx.x * ROWS;
+    const long nr = n - r0 < ROWS ? n - r0 : ROWS;
+    if (mlp3_rows16<NT1, NT2, VEC>(wave, lane, row_ok ? (long)nn : -1L, in_a, in_b, h1, h2, out_dim, xa + r0 * lda, lda, x_bytes(nr, 0, in_a, lda),
+                                   xb ? xb + r0 * ldb : nullptr, ldb, x_bytes(nr, in_a, in_a + in_b, ldb), W1, b1, W2, b2, W3,
+                                   h1_out ? h1_out + r0 * h1 : nullptr, h2_out ? h2_out + r0 * h2 : nullptr, H1, H2, P, z4)) {
         const float z[4] = {z4.x, z4.y, z4.z, z4.w};
         float y[4] = {0.f, 0.f, 0.f, 0.f};
         for (int i = 0; i < out_dim; i++) {

@@ -1,33 +1,114 @@
 // ks_mlp_tile.h -- the 3-layer MLP forward of ONE 16-row tile on the matrix cores, as a device function: the body of k_mlp3
 // (ks_mlp.hip: kr_mlp3_forward / kr_actor_select) and of the in-kernel actor of the free-running rollout kernel (ks_api.hip:
 // k_rollout), so that both are the same k-ordered fp32 fma chains bit for bit.  See ks_mlp.hip for the layout.
+//
+// How the operands arrive.  Every matrix, bias vector and input block is read through a raw buffer resource of exactly its own
+// bytes, with the addressing rule of the section below: the tile and k steps go into the (wave-uniform) scalar offset, the lane
+// adds its row and quarter, and a lane whose element does not exist - a row of a partial last tile, the prefetch behind the last
+// tile, a k beyond the row, a batch row that is not there - gets the out-of-range lane offset OOR instead: the hardware returns
+// +0.0f for it and touches no memory.  No load sits in a branch, so all loads of a tile (its weight quads, the words of a row's
+// tail when rows are no multiple of 4 floats, its bias quad) leave as ONE batch, the batch of the next tile before the MFMAs of
+// the current one, and the first wait on them is the next tile's first MFMA: the two register sets take turns (Tile a / b below),
+// nothing is copied.  sched_barrier(0) behind every batch keeps the scheduler from pulling it apart.
 #pragma once
-#include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+#define KS_MLP_HD __host__ __device__
+#else
+#define KS_MLP_HD
+#endif
 
 namespace kmlp {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int ROWS = 16;        // batch rows per workgroup (the N of the MFMA)
 constexpr int KS_IN_MAX = 6;    // input k-steps: in_dim <= 96
+
+// ---- the addressing rule (host / device, no intrinsics: tests/native/ks_mlp_offsets.cpp walks it over every lane, tile and k-step).
+// A load's byte address is  base + scalar offset + lane offset;  the hardware's range check covers the LANE offset only (lane offset
+// + size of the load <= bytes of the resource, else the load returns 0), so every guard is in the lane offset.
+constexpr uint32_t OOR = 0x7ffffff0u;          // beyond every resource (whose sizes are < 2^31)
+
+// scalar offset of tile row row0, k-step k0 of a row-major [.][K] float matrix
+KS_MLP_HD inline uint32_t tile_soff(int row0, int k0, int K) { return (uint32_t)(row0 * K + k0) * 4u; }
+// lane offset of the 16-byte load of W[row0 + nn][k0 + 4 q .. + 3], W = [nrow][K]: the row must exist and the quad lie in it as a whole
+KS_MLP_HD inline uint32_t quad_off(int nn, int q, int row0, int nrow, int k0, int K) {
+    const int row = row0 + nn, k = k0 + 4 * q;
+    return (row >= 0 && row < nrow && k + 3 < K) ? (uint32_t)(nn * K + 4 * q) * 4u : OOR;
+}
+// A row of K % 4 != 0 floats ends in a tail of K % 4 words at k = tail_k(K), which no 16-byte load may touch (its last words are the
+// next row's, or lie behind the matrix).  The tail's words j = 0 .. 2 are 4-byte loads of the tile's batch - lane offset tail_off
+// beside the scalar offset tile_soff(row0, 0, K) - and replace the quad of the k-step and quarter that tail_here names.
+KS_MLP_HD inline int tail_k(int K) { return K & ~3; }
+KS_MLP_HD inline uint32_t tail_off(int nn, int row0, int nrow, int K, int j) {
+    const int row = row0 + nn;
+    return (row >= 0 && row < nrow && j < (K & 3)) ? (uint32_t)(nn * K + tail_k(K) + j) * 4u : OOR;
+}
+KS_MLP_HD inline bool tail_here(int q, int k0, int K) { return k0 + 4 * q == tail_k(K); }
+// lane offset (scalar offset 0) of word k of batch row `row` of an input block x[.][ld] that holds the columns lo <= k < hi
+KS_MLP_HD inline uint32_t x_off(long row, int k, int lo, int hi, int ld) {
+    return (row >= 0 && k >= lo && k < hi) ? (uint32_t)(row * ld + (k - lo)) * 4u : OOR;
+}
+// bytes of such a block of `rows` rows (the last row ends with its own columns, not with the stride)
+KS_MLP_HD inline uint32_t x_bytes(long rows, int lo, int hi, int ld) { return rows > 0 ? (uint32_t)((rows - 1) * ld + (hi - lo)) * 4u : 0u; }
+
+}  // namespace kmlp
+
+#if defined(__HIPCC__)
+namespace kmlp {
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef __amdgpu_buffer_rsrc_t rsrc_t;
+
 #ifndef KS_MLP_WAVES
 #define KS_MLP_WAVES 4
 #endif
 constexpr int NW = KS_MLP_WAVES;   // waves per workgroup
 
-// 4 consecutive weights W[row][k .. k+3] (zero beyond the matrix): one 16-byte load when the row is 16-byte aligned
-template <bool VEC> __device__ __forceinline__ f32x4 load_w4(const float* __restrict__ W, int row, int nrow, int k, int K) {
-    f32x4 v = {0.f, 0.f, 0.f, 0.f};
-    if (row >= nrow) return v;
-    const float* p = W + (long)row * K + k;
-    if (VEC && k + 3 < K) return *(const f32x4*)p;
-    if (k < K) v.x = p[0];
-    if (k + 1 < K) v.y = p[1];
-    if (k + 2 < K) v.z = p[2];
-    if (k + 3 < K) v.w = p[3];
-    return v;
+// A wave-uniform value into scalar registers.  What a resource or a scalar offset is made of must be there: an out-of-line device function gets
+// its arguments in vector registers, and a resource the compiler takes for divergent is loaded through in a loop over its distinct values.
+__device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
+__device__ __forceinline__ const float* uni(const float* p) {
+    const unsigned long long v = (unsigned long long)p;
+    const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)v), hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(v >> 32));
+    return (const float*)(((unsigned long long)hi << 32) | lo);
 }
+// a resource over `bytes` bytes at p (both the same in all lanes); 4- and 16-byte loads through it (any 4-byte-aligned address)
+__device__ __forceinline__ rsrc_t rsrc(const float* p, uint32_t bytes) {
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(uni(p)), 0, uni((int)bytes), 0x00020000);
+}
+__device__ __forceinline__ float ldf(rsrc_t r, uint32_t voff, uint32_t soff) { return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, (int)voff, (int)soff, 0)); }
+__device__ __forceinline__ f32x4 ldq(rsrc_t r, uint32_t voff, uint32_t soff) { return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, (int)soff, 0)); }
+
+// The operands of one output tile - rows row0 .. row0 + 15 of W = [nrow][K] over NS k-steps, and the tile's bias quad - as ONE batch of
+// loads (issue) whose values are touched only by quad() / bias(), at the MFMAs.  TAIL: K % 4 may be nonzero (W1 always; W2 / W3 and the
+// biases in the VEC = false instantiation); without it a row is whole quads.
+template <int NS, bool TAIL> struct Tile {
+    f32x4 w[NS], bq;
+    float wt[3], bt[3];
+    __device__ __forceinline__ void issue(rsrc_t rW, rsrc_t rB, int nn, int q, int row0, int nrow, int K) {
+#pragma unroll
+        for (int s = 0; s < NS; s++) w[s] = ldq(rW, quad_off(nn, q, row0, nrow, 16 * s, K), tile_soff(row0, 16 * s, K));
+        bq = ldq(rB, quad_off(0, q, 0, 1, row0, nrow), tile_soff(0, row0, nrow));
+        if (TAIL) {
+#pragma unroll
+            for (int j = 0; j < 3; j++) {
+                wt[j] = ldf(rW, tail_off(nn, row0, nrow, K, j), tile_soff(row0, 0, K));
+                bt[j] = ldf(rB, tail_off(0, 0, 1, nrow, j), 0);
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    __device__ __forceinline__ f32x4 quad(int s, int q, int K) const {
+        if (TAIL && tail_here(q, 16 * s, K)) return f32x4{wt[0], wt[1], wt[2], 0.f};
+        return w[s];
+    }
+    __device__ __forceinline__ f32x4 bias(int q, int row0, int nrow) const {
+        if (TAIL && tail_here(q, row0, nrow)) return f32x4{bt[0], bt[1], bt[2], 0.f};
+        return bq;
+    }
+};
 
 __device__ __forceinline__ f32x4 mfma4(f32x4 a, f32x4 b, f32x4 c) {
     c = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, b.x, c, 0, 0, 0);
@@ -37,7 +118,7 @@ __device__ __forceinline__ f32x4 mfma4(f32x4 a, f32x4 b, f32x4 c) {
     return c;
 }
 
-// bias + ReLU on an output quad (features f .. f+3, zero beyond nfeat)
+// bias + ReLU on an output quad (features f .. f+3, zero beyond nfeat), the biases read where they are used (the learner's kernels)
 __device__ __forceinline__ f32x4 bias_relu(f32x4 acc, const float* __restrict__ bias, int f, int nfeat) {
     f32x4 r;
     r.x = f < nfeat ? fmaxf(acc.x + bias[f], 0.f) : 0.f;
@@ -47,81 +128,113 @@ __device__ __forceinline__ f32x4 bias_relu(f32x4 acc, const float* __restrict__ 
     return r;
 }
 
+// the same with the bias quad in registers (features f .. f+3 with their bias quad b, zero beyond nfeat)
+__device__ __forceinline__ f32x4 bias_relu(f32x4 acc, f32x4 b, int f, int nfeat) {
+    f32x4 r;
+    r.x = f < nfeat ? fmaxf(acc.x + b.x, 0.f) : 0.f;
+    r.y = f + 1 < nfeat ? fmaxf(acc.y + b.y, 0.f) : 0.f;
+    r.z = f + 2 < nfeat ? fmaxf(acc.z + b.z, 0.f) : 0.f;
+    r.w = f + 3 < nfeat ? fmaxf(acc.w + b.w, 0.f) : 0.f;
+    return r;
+}
+
 // All three layers for the 16 rows of a workgroup of NW waves (every thread of the workgroup must call this: two barriers inside).
-// `row` = this lane's batch row (lane & 15 selects it; the same in all waves), < 0: no such row.  H1 / H2 / P: workgroup-shared
-// scratch, [NT1 * 4][ROWS], [NT2 * 4][ROWS], [NW][ROWS] float4.  Returns true on the lanes that hold a row's layer-3 sums z4
-// (wave 0, first quarter, row valid): the caller adds b3 and applies the output activation.
+// `row` = this lane's batch row (lane & 15 selects it; the same in all waves), < 0: no such row.  xa / xb: the input blocks,
+// xa_bytes / xb_bytes what x_bytes() gives for the rows `row` can name (xb == nullptr: none); all pointers wave-uniform.  H1 / H2 / P:
+// workgroup-shared scratch, [NT1 * 4][ROWS], [NT2 * 4][ROWS], [NW][ROWS] float4.  Returns true on the lanes that hold a row's layer-3
+// sums z4 (wave 0, first quarter, row valid): the caller adds b3 and applies the output activation.
 template <int NT1, int NT2, bool VEC>
-__device__ __forceinline__ bool mlp3_rows16(const int wave, const int lane, const long row, int in_a, int in_b, int h1, int h2, int out_dim,
-                                            const float* __restrict__ xa, int lda, const float* __restrict__ xb, int ldb,
-                                            const float* __restrict__ W1, const float* __restrict__ b1, const float* __restrict__ W2,
-                                            const float* __restrict__ b2, const float* __restrict__ W3, float* __restrict__ h1_out,
-                                            float* __restrict__ h2_out, f32x4 (*H1)[ROWS], f32x4 (*H2)[ROWS], f32x4 (*P)[ROWS], f32x4& z4) {
+__device__ __forceinline__ bool mlp3_rows16(const int wave_id, const int lane, const long row, int in_a, int in_b, int h1, int h2, int out_dim,
+                                            const float* __restrict__ xa, int lda, uint32_t xa_bytes, const float* __restrict__ xb, int ldb,
+                                            uint32_t xb_bytes, const float* __restrict__ W1, const float* __restrict__ b1,
+                                            const float* __restrict__ W2, const float* __restrict__ b2, const float* __restrict__ W3,
+                                            float* __restrict__ h1_out, float* __restrict__ h2_out, f32x4 (*H1)[ROWS], f32x4 (*H2)[ROWS],
+                                            f32x4 (*P)[ROWS], f32x4& z4) {
     const int nn = lane & 15, q = lane >> 4;
+    const int wave = uni(wave_id);          // (threadIdx.x >> 6 is the same in all lanes, but the compiler does not know: it goes into scalar offsets)
     const bool row_ok = row >= 0;
+    in_a = uni(in_a), in_b = uni(in_b), h1 = uni(h1), h2 = uni(h2), out_dim = uni(out_dim), lda = uni(lda), ldb = uni(ldb);
     const int in_dim = in_a + in_b;
-    // layer 1: the wave's copy of the 16 input rows as B operands (k = 16 s + 4 q + j)
+    const rsrc_t rW1 = rsrc(W1, (uint32_t)(h1 * in_dim) * 4u), rB1 = rsrc(b1, (uint32_t)h1 * 4u), rW2 = rsrc(W2, (uint32_t)(h2 * h1) * 4u),
+                 rB2 = rsrc(b2, (uint32_t)h2 * 4u), rW3 = rsrc(W3, (uint32_t)(out_dim * h2) * 4u);
+    // the first batch: the wave's copy of the 16 input rows as B operands of layer 1 (k = 16 s + 4 q + j), its first tile of W1, and its
+    // first tile of W2, which arrives while layer 1 computes
     f32x4 bx[KS_IN_MAX];
-#pragma unroll
-    for (int s = 0; s < KS_IN_MAX; s++) {
-        float v[4];
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const int k = 16 * s + 4 * q + j;
-            float x = 0.f;
-            if (row_ok && k < in_a) x = xa[(long)row * lda + k];
-            else if (row_ok && k < in_dim) x = xb[(long)row * ldb + (k - in_a)];
-            v[j] = x;
-        }
-        bx[s] = f32x4{v[0], v[1], v[2], v[3]};
-    }
-    // Weights stream from L2 (~1.5 us per dependent read at one wave per SIMD): every tile's weights are requested one
-    // tile ahead of the MFMAs that use them, and the first tile of a layer while the previous layer is still computing.
-    f32x4 w2[NT1];
-#pragma unroll
-    for (int s = 0; s < NT1; s++) w2[s] = load_w4<VEC>(W2, wave * 16 + nn, wave < NT2 ? h2 : 0, 16 * s + 4 * q, h1);
     {
-        f32x4 w1[KS_IN_MAX];
+        const rsrc_t rXa = rsrc(xa, xa_bytes);
+        float fa[KS_IN_MAX][4];
 #pragma unroll
-        for (int s = 0; s < KS_IN_MAX; s++) w1[s] = load_w4<false>(W1, wave * 16 + nn, wave < NT1 ? h1 : 0, 16 * s + 4 * q, in_dim);
-        for (int t = wave; t < NT1; t += NW) {
-            f32x4 wn[KS_IN_MAX];
+        for (int s = 0; s < KS_IN_MAX; s++)
 #pragma unroll
-            for (int s = 0; s < KS_IN_MAX; s++) wn[s] = load_w4<false>(W1, (t + NW) * 16 + nn, t + NW < NT1 ? h1 : 0, 16 * s + 4 * q, in_dim);
-            f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};  // two chains: the MFMA's dependent latency is 40 cycles, its issue 32
+            for (int j = 0; j < 4; j++) fa[s][j] = ldf(rXa, x_off(row, 16 * s + 4 * q + j, 0, in_a, lda), 0);
+        if (xb) {       // (the same for the whole launch; nullptr at compile time in the rollout kernels)
+            const rsrc_t rXb = rsrc(xb, xb_bytes);
+#pragma unroll
+            for (int s = 0; s < KS_IN_MAX; s++)
+#pragma unroll
+                for (int j = 0; j < 4; j++) {
+                    const float fb = ldf(rXb, x_off(row, 16 * s + 4 * q + j, in_a, in_dim, ldb), 0);
+                    fa[s][j] = 16 * s + 4 * q + j < in_a ? fa[s][j] : fb;
+                }
+        }
+#pragma unroll
+        for (int s = 0; s < KS_IN_MAX; s++) bx[s] = f32x4{fa[s][0], fa[s][1], fa[s][2], fa[s][3]};
+    }
+    Tile<NT1, !VEC> a2, b2t;
+    {
+        Tile<KS_IN_MAX, true> a1, b1t;
+        a1.issue(rW1, rB1, nn, q, 16 * wave, h1, in_dim);
+        a2.issue(rW2, rB2, nn, q, 16 * wave, h2, h1);
+        // one output tile of layer 1 (two chains: the MFMA's dependent latency is 40 cycles, its issue 32)
+        auto tile1 = [&](const Tile<KS_IN_MAX, true>& w, int t) {
+            f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int s = 0; s < KS_IN_MAX; s++) {       // k beyond in_dim: both operands are zero
-                if (s & 1) acc1 = mfma4(w1[s], bx[s], acc1);
-                else acc0 = mfma4(w1[s], bx[s], acc0);
+                if (s & 1) acc1 = mfma4(w.quad(s, q, in_dim), bx[s], acc1);
+                else acc0 = mfma4(w.quad(s, q, in_dim), bx[s], acc0);
             }
-            const f32x4 hq = bias_relu(acc0 + acc1, b1, t * 16 + 4 * q, h1);
+            const f32x4 hq = bias_relu(acc0 + acc1, w.bias(q, 16 * t, h1), t * 16 + 4 * q, h1);
             H1[t * 4 + q][nn] = hq;
             if (h1_out && row_ok && t * 16 + 4 * q < h1) *(f32x4*)(h1_out + (long)row * h1 + t * 16 + 4 * q) = hq;   // h1 % 4 == 0 (checked by the host)
-#pragma unroll
-            for (int s = 0; s < KS_IN_MAX; s++) w1[s] = wn[s];
+        };
+#pragma unroll 1
+        for (int t = wave; t < NT1; t += 2 * NW) {
+            if (NT1 > NW) b1t.issue(rW1, rB1, nn, q, 16 * (t + NW), h1, in_dim);          // (a wave with one tile, or two: no batch for a tile nobody has)
+            tile1(a1, t);
+            if (NT1 > 2 * NW) a1.issue(rW1, rB1, nn, q, 16 * (t + 2 * NW), h1, in_dim);
+            if (NT1 > NW && t + NW < NT1) tile1(b1t, t + NW);
         }
     }
     __syncthreads();
 
-    // layer 2: K = h1, one k-step per tile of H1
-    f32x4 w3[(NT2 + NW - 1) / NW];
+    // layer 2: K = h1, one k-step per tile of H1.  The wave's quads of W3 leave ahead of the loop and are used behind it.
+    constexpr int NJ = (NT2 + NW - 1) / NW;
+    f32x4 w3[NJ];
+    float w3t[3];
 #pragma unroll
-    for (int j = 0; j < (NT2 + NW - 1) / NW; j++) w3[j] = load_w4<VEC>(W3, nn, out_dim, 16 * (wave + NW * j) + 4 * q, h2);
-    for (int t = wave; t < NT2; t += NW) {
-        f32x4 wn[NT1];
+    for (int j = 0; j < NJ; j++) w3[j] = ldq(rW3, quad_off(nn, q, 0, out_dim, 16 * (wave + NW * j), h2), tile_soff(0, 16 * (wave + NW * j), h2));
+    if (!VEC) {
 #pragma unroll
-        for (int s = 0; s < NT1; s++) wn[s] = load_w4<VEC>(W2, (t + NW) * 16 + nn, t + NW < NT2 ? h2 : 0, 16 * s + 4 * q, h1);
+        for (int j = 0; j < 3; j++) w3t[j] = ldf(rW3, tail_off(nn, 0, out_dim, h2, j), 0);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    auto tile2 = [&](const Tile<NT1, !VEC>& w, int t) {
         f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int s = 0; s < NT1; s++) {
-            if (s & 1) acc1 = mfma4(w2[s], H1[s * 4 + q][nn], acc1);
-            else acc0 = mfma4(w2[s], H1[s * 4 + q][nn], acc0);
+            if (s & 1) acc1 = mfma4(w.quad(s, q, h1), H1[s * 4 + q][nn], acc1);
+            else acc0 = mfma4(w.quad(s, q, h1), H1[s * 4 + q][nn], acc0);
         }
-        const f32x4 hq = bias_relu(acc0 + acc1, b2, t * 16 + 4 * q, h2);
+        const f32x4 hq = bias_relu(acc0 + acc1, w.bias(q, 16 * t, h2), t * 16 + 4 * q, h2);
         H2[t * 4 + q][nn] = hq;
         if (h2_out && row_ok && t * 16 + 4 * q < h2) *(f32x4*)(h2_out + (long)row * h2 + t * 16 + 4 * q) = hq;
-#pragma unroll
-        for (int s = 0; s < NT1; s++) w2[s] = wn[s];
+    };
+#pragma unroll 1
+    for (int t = wave; t < NT2; t += 2 * NW) {
+        if (NT2 > NW) b2t.issue(rW2, rB2, nn, q, 16 * (t + NW), h2, h1);
+        tile2(a2, t);
+        if (NT2 > 2 * NW) a2.issue(rW2, rB2, nn, q, 16 * (t + 2 * NW), h2, h1);
+        if (NT2 > NW && t + NW < NT2) tile2(b2t, t + NW);
     }
     __syncthreads();
 
@@ -129,8 +242,11 @@ __device__ __forceinline__ bool mlp3_rows16(const int wave, const int lane, cons
     {
         f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int j = 0; j < (NT2 + NW - 1) / NW; j++)
-            if (wave + NW * j < NT2) acc = mfma4(w3[j], H2[(wave + NW * j) * 4 + q][nn], acc);
+        for (int j = 0; j < NJ; j++)
+            if (wave + NW * j < NT2) {
+                const f32x4 wq = (!VEC && tail_here(q, 16 * (wave + NW * j), h2)) ? f32x4{w3t[0], w3t[1], w3t[2], 0.f} : w3[j];
+                acc = mfma4(wq, H2[(wave + NW * j) * 4 + q][nn], acc);
+            }
         if (q == 0) P[wave][nn] = acc;
     }
     __syncthreads();
@@ -146,72 +262,96 @@ __device__ __forceinline__ bool mlp3_rows16(const int wave, const int lane, cons
 // The same three layers by ONE wave for the first NR rows of a tile (the free-running rollout kernel's waves each own four envs and
 // never meet a barrier): every output element is the chain of MFMAs mlp3_rows16 runs for it - same k order, the same two accumulators
 // per tile, layer 3 as NW partial sums added in wave order - so a row's result is the 4-wave kernel's bit for bit (an MFMA's output
-// column depends on its own B column only; columns >= NR read zeros and are discarded).  H1 / H2: the wave's own scratch,
-// [NT1 * 4][NR], [NT2 * 4][NR] float4.  Returns true on the lanes that hold a row's layer-3 sums (first quarter, row valid).
+// column depends on its own B column only; columns >= NR read zeros and are discarded).  xa: [.][lda] rows of in_dim columns, xa_bytes
+// as x_bytes() gives them.  H1 / H2: the wave's own scratch, [NT1 * 4][NR], [NT2 * 4][NR] float4.  Returns true on the lanes that hold
+// a row's layer-3 sums (first quarter, row valid).  W3's quads are not held across layer 2 (its two register sets of NT1 quads and the
+// NT1 B quads leave no room): they leave as one batch behind its loop.
 template <int NT1, int NT2, bool VEC, int NR>
 __device__ __forceinline__ bool mlp3_rows_wave(const int lane, const long row, int in_dim, int h1, int h2, int out_dim, const float* __restrict__ xa, int lda,
-                                               const float* __restrict__ W1, const float* __restrict__ b1, const float* __restrict__ W2,
-                                               const float* __restrict__ b2, const float* __restrict__ W3, f32x4 (*H1)[NR], f32x4 (*H2)[NR], f32x4& z4) {
+                                               uint32_t xa_bytes, const float* __restrict__ W1, const float* __restrict__ b1,
+                                               const float* __restrict__ W2, const float* __restrict__ b2, const float* __restrict__ W3,
+                                               f32x4 (*H1)[NR], f32x4 (*H2)[NR], f32x4& z4) {
     const int nn = lane & 15, q = lane >> 4;
     const bool row_ok = row >= 0, col_ok = nn < NR;
     const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+    in_dim = uni(in_dim), h1 = uni(h1), h2 = uni(h2), out_dim = uni(out_dim), lda = uni(lda);
+    const rsrc_t rW1 = rsrc(W1, (uint32_t)(h1 * in_dim) * 4u), rB1 = rsrc(b1, (uint32_t)h1 * 4u), rW2 = rsrc(W2, (uint32_t)(h2 * h1) * 4u),
+                 rB2 = rsrc(b2, (uint32_t)h2 * 4u), rW3 = rsrc(W3, (uint32_t)(out_dim * h2) * 4u);
+    // the first batch: the input rows, the first tile of W1, and the first tile of W2, which arrives while layer 1 computes
     f32x4 bx[KS_IN_MAX];
-#pragma unroll
-    for (int s = 0; s < KS_IN_MAX; s++) {
-        float v[4];
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const int k = 16 * s + 4 * q + j;
-            v[j] = (row_ok && k < in_dim) ? xa[(long)row * lda + k] : 0.f;
-        }
-        bx[s] = f32x4{v[0], v[1], v[2], v[3]};
-    }
-    f32x4 w2[NT1];
-#pragma unroll
-    for (int s = 0; s < NT1; s++) w2[s] = load_w4<VEC>(W2, nn, h2, 16 * s + 4 * q, h1);
     {
-        f32x4 w1[KS_IN_MAX];
+        const rsrc_t rXa = rsrc(xa, xa_bytes);
 #pragma unroll
-        for (int s = 0; s < KS_IN_MAX; s++) w1[s] = load_w4<false>(W1, nn, h1, 16 * s + 4 * q, in_dim);
-        for (int t = 0; t < NT1; t++) {
-            f32x4 wn[KS_IN_MAX];
+        for (int s = 0; s < KS_IN_MAX; s++) {
+            float v[4];
 #pragma unroll
-            for (int s = 0; s < KS_IN_MAX; s++) wn[s] = load_w4<false>(W1, (t + 1) * 16 + nn, t + 1 < NT1 ? h1 : 0, 16 * s + 4 * q, in_dim);
+            for (int j = 0; j < 4; j++) v[j] = ldf(rXa, x_off(row, 16 * s + 4 * q + j, 0, in_dim, lda), 0);
+            bx[s] = f32x4{v[0], v[1], v[2], v[3]};
+        }
+    }
+    Tile<NT1, !VEC> a2, b2t;
+    {
+        Tile<KS_IN_MAX, true> a1, b1t;
+        a1.issue(rW1, rB1, nn, q, 0, h1, in_dim);
+        a2.issue(rW2, rB2, nn, q, 0, h2, h1);
+        auto tile1 = [&](const Tile<KS_IN_MAX, true>& w, int t) {
             f32x4 acc0 = zero, acc1 = zero;
 #pragma unroll
             for (int s = 0; s < KS_IN_MAX; s++) {
-                if (s & 1) acc1 = mfma4(w1[s], bx[s], acc1);
-                else acc0 = mfma4(w1[s], bx[s], acc0);
+                if (s & 1) acc1 = mfma4(w.quad(s, q, in_dim), bx[s], acc1);
+                else acc0 = mfma4(w.quad(s, q, in_dim), bx[s], acc0);
             }
-            const f32x4 hq = bias_relu(acc0 + acc1, b1, t * 16 + 4 * q, h1);
+            const f32x4 hq = bias_relu(acc0 + acc1, w.bias(q, 16 * t, h1), t * 16 + 4 * q, h1);
             if (col_ok) H1[t * 4 + q][nn] = hq;
-#pragma unroll
-            for (int s = 0; s < KS_IN_MAX; s++) w1[s] = wn[s];
+        };
+#pragma unroll 1
+        for (int t = 0; t < NT1; t += 2) {
+            b1t.issue(rW1, rB1, nn, q, 16 * (t + 1), h1, in_dim);
+            tile1(a1, t);
+            a1.issue(rW1, rB1, nn, q, 16 * (t + 2), h1, in_dim);
+            if (t + 1 < NT1) tile1(b1t, t + 1);
         }
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 
-    // layer 2: the B operands are the same for every tile - read once
-    f32x4 hb[NT1];
+    // layer 2: the B operands are the same for every tile - read once and held where that leaves room for two tiles of weights (up to
+    // 16 k-steps: 64 registers), else read again for every tile (400-300: 100 registers, which the kernel's budget does not have)
+    constexpr bool HOLD_B = NT1 <= 16;
+    f32x4 hb[HOLD_B ? NT1 : 1];
+    if (HOLD_B) {
 #pragma unroll
-    for (int s = 0; s < NT1; s++) hb[s] = col_ok ? H1[s * 4 + q][nn] : zero;
-    for (int t = 0; t < NT2; t++) {
-        f32x4 wn[NT1];
-#pragma unroll
-        for (int s = 0; s < NT1; s++) wn[s] = load_w4<VEC>(W2, (t + 1) * 16 + nn, t + 1 < NT2 ? h2 : 0, 16 * s + 4 * q, h1);
+        for (int s = 0; s < NT1; s++) hb[s] = col_ok ? H1[s * 4 + q][nn] : zero;
+    }
+    auto tile2 = [&](const Tile<NT1, !VEC>& w, int t) {
         f32x4 acc0 = zero, acc1 = zero;
 #pragma unroll
         for (int s = 0; s < NT1; s++) {
-            if (s & 1) acc1 = mfma4(w2[s], hb[s], acc1);
-            else acc0 = mfma4(w2[s], hb[s], acc0);
+            const f32x4 b = HOLD_B ? hb[HOLD_B ? s : 0] : (col_ok ? H1[s * 4 + q][nn] : zero);
+            if (s & 1) acc1 = mfma4(w.quad(s, q, h1), b, acc1);
+            else acc0 = mfma4(w.quad(s, q, h1), b, acc0);
         }
-        const f32x4 hq = bias_relu(acc0 + acc1, b2, t * 16 + 4 * q, h2);
+        const f32x4 hq = bias_relu(acc0 + acc1, w.bias(q, 16 * t, h2), t * 16 + 4 * q, h2);
         if (col_ok) H2[t * 4 + q][nn] = hq;
-#pragma unroll
-        for (int s = 0; s < NT1; s++) w2[s] = wn[s];
+    };
+#pragma unroll 1
+    for (int t = 0; t < NT2; t += 2) {
+        b2t.issue(rW2, rB2, nn, q, 16 * (t + 1), h2, h1);
+        tile2(a2, t);
+        a2.issue(rW2, rB2, nn, q, 16 * (t + 2), h2, h1);
+        if (t + 1 < NT2) tile2(b2t, t + 1);
     }
+    // layer 3's operands: all of W3 as one batch
+    f32x4 w3[NT2];
+    float w3t[3];
+#pragma unroll
+    for (int s = 0; s < NT2; s++) w3[s] = ldq(rW3, quad_off(nn, q, 0, out_dim, 16 * s, h2), tile_soff(0, 16 * s, h2));
+    if (!VEC) {
+#pragma unroll
+        for (int j = 0; j < 3; j++) w3t[j] = ldf(rW3, tail_off(nn, 0, out_dim, h2, j), 0);
+    }
+    __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -223,7 +363,11 @@ __device__ __forceinline__ bool mlp3_rows_wave(const int lane, const long row, i
         f32x4 acc = zero;
 #pragma unroll
         for (int j = 0; j < (NT2 + NW - 1) / NW; j++)
-            if (w + NW * j < NT2) acc = mfma4(load_w4<VEC>(W3, nn, out_dim, 16 * (w + NW * j) + 4 * q, h2), col_ok ? H2[(w + NW * j) * 4 + q][nn] : zero, acc);
+            if (w + NW * j < NT2) {
+                const int s = w + NW * j;
+                const f32x4 wq = (!VEC && tail_here(q, 16 * s, h2)) ? f32x4{w3t[0], w3t[1], w3t[2], 0.f} : w3[s];
+                acc = mfma4(wq, col_ok ? H2[s * 4 + q][nn] : zero, acc);
+            }
         part[w] = acc;
     }
     if (q == 0 && row_ok && col_ok) {
@@ -236,3 +380,4 @@ __device__ __forceinline__ bool mlp3_rows_wave(const int lane, const long row, i
 }
 
 }  // namespace kmlp
+#endif  // __HIPCC__
