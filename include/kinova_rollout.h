@@ -16,6 +16,8 @@
  *   kr_advance_ring     utils.py:66-90          ring head / count, open-episode lengths of finished envs
  *   kr_sample_windows   utils.py:240-306        sample_batch_nstep: per sampled episode, ceiling-1 uniform window
  *                                               starts + the final window, as ONE fixed-shape padded batch
+ *   kr_commit_classes / kr_sample_windows_balanced   (none: main_DDPGfD.py balances objects while collecting)  the same batch with
+ *                                               every episode drawn from one class of its ring, the classes in cyclic rotation
  *
  * Conventions: all pointers are DEVICE pointers owned by the caller (PyTorch tensors); bool arrays are one byte per
  * element; counters are int64; float data is fp32, row-major; every call is asynchronous on `stream` (hipStream_t
@@ -118,6 +120,42 @@ typedef struct {
 int kr_sample_windows_mixed(int32_t batch, int32_t batch_agent, int32_t horizon, int32_t n_steps, const kr_ring *agent, const kr_ring *expert,
                             const float *u_ep, const float *u_start, uint64_t seed, const int64_t *draw, float *state, float *action,
                             float *next_state, float *reward, float *not_done, float *weight, float *next_ends, void *stream);
+
+/* ---- replay batches balanced over the episodes' classes (no reference counterpart as a sampler: main_DDPGfD.py takes the stage's objects
+ * in Latin-square order while COLLECTING, so that every object contributes the same number of episodes; a free-running or time-budgeted
+ * rollout fills the ring at each object's own pace instead, and the balance is restored where the batch is drawn).
+ *
+ * kr_commit_classes: the per-episode class column of a ring.  keep uint8 [n], rank int64 [n] (kr_rank_episodes), head int64 [1], env_class
+ * int32 [n] (the class of whatever env i collects), ep_class int32 [capacity (+ trash row)]: for every env i with keep[i] != 0
+ *     ep_class[(head[0] + rank[i] - 1) % capacity] = env_class[i]
+ * - kr_commit_episodes' slot rule; issued between kr_rank_episodes and kr_advance_ring.  Nothing else is written. */
+int kr_commit_classes(int32_t n, int32_t capacity, const uint8_t *keep, const int64_t *rank, const int64_t *head, const int32_t *env_class,
+                      int32_t *ep_class, void *stream);
+
+/* kr_sample_windows_mixed with the episode of every batch slot drawn from ONE class of its ring.  agent_class / expert_class int32: one tag
+ * per slot of that ring (expert_class may be NULL only when batch_agent == batch, agent_class only when batch_agent == 0); n_classes in
+ * 1 .. 64; picked (optional, may be NULL) int32 [batch]: the ring slot each batch episode was read from.
+ * Per ring segment of the batch - agent: slots [0, batch_agent), expert: [batch_agent, batch); b0 its first slot:
+ *   eligible   the count - 1 oldest episodes of the ring, age a = 0 .. count - 2 in slot (head - count + a) mod capacity (the newest is
+ *              never sampled, as in kr_sample_windows);
+ *   m_c        the eligible episodes whose tag is c; a tag outside [0, n_classes) - -1: unknown - counts for no class;
+ *   slot b     wants class c = (b - b0 + rotation + (draw ? draw[0] : 0)) mod n_classes (non-negative), and takes the j-th OLDEST eligible
+ *              episode of that class, j = (long)(ue * (float)m_c) capped at m_c - 1; where m_c == 0 it falls back to kr_sample_windows'
+ *              rule, k = (long)(ue * (float)hi) capped at hi - 1 over all eligible episodes.
+ * A ring with fewer than two episodes: as kr_sample_windows (weight-0 rows).  Window starts, the final window, weights, the output layout
+ * and next_ends are kr_sample_windows'; the uniforms are the caller's u_ep / u_start or Philox with kr_sample_windows_draw's key, counters
+ * and tags.  Hence: with n_classes == 1 and every tag 0 the batch equals kr_sample_windows_mixed's in every bit; within a segment the
+ * classes' slot counts differ by at most one, and over n_classes consecutive values of draw[0] every class gets exactly the segment's
+ * length in slots.
+ * Two launches of one-wave, LDS-free workgroups: the pick (`batch` waves, each walks its ring's tag table twice - count, locate - and
+ * touches no episode data) and the gather (batch * W waves, kr_sample_windows' rows with the episode supplied).  Without `picked` the
+ * slots travel between the two in `weight`, which needs no more than the [batch * W] floats it has.
+ * KS_ERR_INVALID, nothing launched or written: what kr_sample_windows_mixed refuses; n_classes < 1 or > 64; a NULL class array for a ring
+ * that has batch slots. */
+int kr_sample_windows_balanced(int32_t batch, int32_t batch_agent, int32_t horizon, int32_t n_steps, const kr_ring *agent, const kr_ring *expert,
+                               const int32_t *agent_class, const int32_t *expert_class, int32_t n_classes, int32_t rotation, const float *u_ep,
+                               const float *u_start, uint64_t seed, const int64_t *draw, float *state, float *action, float *next_state,
+                               float *reward, float *not_done, float *weight, float *next_ends, int32_t *picked, void *stream);
 
 /* ---- learner glue (DDPGfD.train_batch, DDPGfD.py:219-367): the elementwise steps between the GEMMs, one launch each
  *

@@ -168,45 +168,38 @@ struct Ring {                      // one episode ring of DeviceEpisodeReplay (k
     const float *ep_state, *ep_next, *ep_action, *ep_reward, *ep_not_done;
 };
 
-// one wave per window row (b, w); episodes b < B_agent are drawn from ring `ra`, the others from ring `re` (the expert
-// demonstrations DDPGfD mixes into every batch, DDPGfD.py:232-254; B_agent = B: one ring)
-__global__ __launch_bounds__(WAVE) void k_sample_windows(int B, int B_agent, int H, int n_steps, Ring ra, Ring re, const float* __restrict__ u_ep,
-                                                         const float* __restrict__ u_start, unsigned long long seed,
-                                                         const int64_t* __restrict__ draw, float* __restrict__ next_ends,
-                                                         float* __restrict__ state, float* __restrict__ action, float* __restrict__ next_state,
-                                                         float* __restrict__ reward, float* __restrict__ not_done, float* __restrict__ weight) {
-    const int W = H - n_steps;
-    const int r = blockIdx.x, lane = threadIdx.x;
-    if (r >= B * W) return;
-    const int b = r / W, w = r % W;
-    const Ring& g = b < B_agent ? ra : re;
-    const int64_t *count = g.count, *head = g.head, *ep_len = g.ep_len;
-    const int capacity = g.capacity;
-    const float *ep_state = g.ep_state, *ep_next = g.ep_next, *ep_action = g.ep_action, *ep_reward = g.ep_reward, *ep_not_done = g.ep_not_done;
-    // np.random.randint(replay_ep_num - 1): the k-th OLDEST episode, k in [0, count - 1) - the newest one is never sampled
-    // (utils.py:259).  In the ring the oldest episode sits at head - count, so after the first wrap the excluded slot is
-    // head - 1, wherever that is.  With fewer than two episodes there is nothing to sample: every row gets weight 0.
-    const long cnt = count[0];
-    const bool none = cnt < 2;
+// the sampler's uniforms: the caller's, or (u == nullptr) Philox4x32-10 keyed by the seed at counter (draw[0], index, tag) - `draw` is a
+// device counter that does not change while the kernel runs (the learner's update count).  tag 0x5a4d with the batch episode b: which
+// episode; tag 0x5a4e with the row r: where its window starts.
+__device__ __forceinline__ float sample_uniform(const float* __restrict__ u, long index, uint32_t tag, unsigned long long seed,
+                                                const int64_t* __restrict__ draw) {
+    if (u != nullptr) return u[index];
+    const unsigned long long d = (unsigned long long)draw[0];
+    uint32_t r4[4];
+    krsel::philox4x32((uint32_t)index, (uint32_t)d, (uint32_t)(d >> 32), tag, (uint32_t)seed, (uint32_t)(seed >> 32), r4);
+    return (float)(r4[0] >> 8) * (1.0f / 16777216.0f);
+}
+
+// np.random.randint(replay_ep_num - 1): the k-th OLDEST episode, k in [0, count - 1) - the newest one is never sampled
+// (utils.py:259).  In the ring the oldest episode sits at head - count, so after the first wrap the excluded slot is
+// head - 1, wherever that is.  (Fewer than two episodes: slot head - count, and every row of it gets weight 0.)
+__device__ __forceinline__ long uniform_episode(float ue, long cnt, long head, int capacity) {
     long hi = cnt - 1;
     hi = hi > 1 ? hi : 1;
-    // the uniforms: the caller's, or (u_ep == nullptr) Philox4x32-10 keyed by the seed at counter (draw[0], b | row, tag) -
-    // `draw` is a device counter that does not change while this kernel runs (the learner's update count)
-    float ue, us;
-    if (u_ep != nullptr) { ue = u_ep[b]; us = u_start[(long)b * W + w]; }
-    else {
-        const unsigned long long d = (unsigned long long)draw[0];
-        uint32_t r4[4];
-        krsel::philox4x32((uint32_t)b, (uint32_t)d, (uint32_t)(d >> 32), 0x5a4du, (uint32_t)seed, (uint32_t)(seed >> 32), r4);
-        ue = (float)(r4[0] >> 8) * (1.0f / 16777216.0f);
-        krsel::philox4x32((uint32_t)r, (uint32_t)d, (uint32_t)(d >> 32), 0x5a4eu, (uint32_t)seed, (uint32_t)(seed >> 32), r4);
-        us = (float)(r4[0] >> 8) * (1.0f / 16777216.0f);
-    }
     long k = (long)(ue * (float)hi);
     k = k < hi - 1 ? k : hi - 1;
-    long ep = (head[0] - cnt + k) % capacity;
-    ep = ep < 0 ? ep + capacity : ep;
-    long ceiling = ep_len[ep] - n_steps;
+    long ep = (head - cnt + k) % capacity;
+    return ep < 0 ? ep + capacity : ep;
+}
+
+// window row r = (b, w) of the batch, read from ring slot `ep`: the body k_sample_windows and k_gather_windows share
+__device__ __forceinline__ void window_row(const Ring& g, long ep, float us, bool none, int B, int H, int n_steps, int r, int w, int lane,
+                                           float* __restrict__ next_ends, float* __restrict__ state, float* __restrict__ action,
+                                           float* __restrict__ next_state, float* __restrict__ reward, float* __restrict__ not_done,
+                                           float* weight) {
+    const int W = H - n_steps;
+    const float *ep_state = g.ep_state, *ep_next = g.ep_next, *ep_action = g.ep_action, *ep_reward = g.ep_reward, *ep_not_done = g.ep_not_done;
+    long ceiling = g.ep_len[ep] - n_steps;
     ceiling = ceiling > 1 ? ceiling : 1;
     long start = (long)(us * (float)ceiling);
     start = start < H - n_steps ? start : H - n_steps;
@@ -230,6 +223,169 @@ __global__ __launch_bounds__(WAVE) void k_sample_windows(int B, int B_agent, int
         not_done[dst + lane] = ep_not_done[src + lane];
     }
     if (lane == 0) weight[r] = (!none && w < ceiling) ? 1.0f : 0.0f;
+}
+
+// one wave per window row (b, w); episodes b < B_agent are drawn from ring `ra`, the others from ring `re` (the expert
+// demonstrations DDPGfD mixes into every batch, DDPGfD.py:232-254; B_agent = B: one ring)
+__global__ __launch_bounds__(WAVE) void k_sample_windows(int B, int B_agent, int H, int n_steps, Ring ra, Ring re, const float* __restrict__ u_ep,
+                                                         const float* __restrict__ u_start, unsigned long long seed,
+                                                         const int64_t* __restrict__ draw, float* __restrict__ next_ends,
+                                                         float* __restrict__ state, float* __restrict__ action, float* __restrict__ next_state,
+                                                         float* __restrict__ reward, float* __restrict__ not_done, float* __restrict__ weight) {
+    const int W = H - n_steps;
+    const int r = blockIdx.x, lane = threadIdx.x;
+    if (r >= B * W) return;
+    const int b = r / W, w = r % W;
+    const Ring& g = b < B_agent ? ra : re;
+    const long cnt = g.count[0];
+    const float ue = sample_uniform(u_ep, b, 0x5a4du, seed, draw);
+    const float us = sample_uniform(u_start, r, 0x5a4eu, seed, draw);
+    const long ep = uniform_episode(ue, cnt, g.head[0], g.capacity);
+    window_row(g, ep, us, cnt < 2, B, H, n_steps, r, w, lane, next_ends, state, action, next_state, reward, not_done, weight);
+}
+
+// ---- replay batches balanced over the episodes' classes (kr_sample_windows_balanced): the pick and the gather.
+// One wave per workgroup and no LDS, as everything on the learner's stream (see wave_sum below).
+//
+// scan_tags walks tags[s0, s1) - one contiguous piece of a ring's eligible range, in age order - for the tag `c`.  A trip is 64 lanes x 4
+// consecutive tags, one 16-byte load per lane where the four lie inside the piece (the first and last vector of a piece, and a table that
+// is not 16-byte aligned, are covered by per-tag loads of the elements inside it: nothing outside [s0, s1) is read); the match flags become
+// counts through four 64-bit ballots per trip.  The loads of the next SCAN_TRIPS trips are issued before the ballots of the current
+// ones: a table of 16 384 tags is 64 KB in L2, what costs is the number of dependent round trips - 8 for it.
+//   LOCATE = false: returns how many tags equal c.
+//   LOCATE = true:  returns the index of the target-th (0-based, age order) tag that equals c, -1 if there are not that many.
+// The result is the same in every lane.
+constexpr int SCAN_TRIPS = 8;
+typedef int v4i __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ v4i load_tags(const int* __restrict__ tags, long q, long mis, long s0, long s1, long q1) {
+    v4i v = {-1, -1, -1, -1};                        // (-1 equals no wanted class: 0 <= c)
+    if (q >= q1) return v;
+    const long e0 = 4 * q - mis;
+    if (e0 >= s0 && e0 + 4 <= s1) return *(const v4i*)(tags + e0);
+    if (e0 + 0 >= s0 && e0 + 0 < s1) v.x = tags[e0 + 0];
+    if (e0 + 1 >= s0 && e0 + 1 < s1) v.y = tags[e0 + 1];
+    if (e0 + 2 >= s0 && e0 + 2 < s1) v.z = tags[e0 + 2];
+    if (e0 + 3 >= s0 && e0 + 3 < s1) v.w = tags[e0 + 3];
+    return v;
+}
+
+template <bool LOCATE>
+__device__ __forceinline__ long scan_tags(const int* __restrict__ tags, long s0, long s1, int c, long target, int lane) {
+    if (s1 <= s0) return LOCATE ? -1 : 0;
+    const long mis = (long)(((uintptr_t)tags >> 2) & 3);            // tags + e is 16-byte aligned where (e + mis) % 4 == 0
+    const long q0 = (s0 + mis) >> 2, q1 = (s1 + mis + 3) >> 2;      // the 16-byte vectors [q0, q1) cover the piece
+    constexpr long GROUP = (long)SCAN_TRIPS * WAVE;
+    v4i cur[SCAN_TRIPS], nxt[SCAN_TRIPS];
+#pragma unroll
+    for (int u = 0; u < SCAN_TRIPS; u++) cur[u] = load_tags(tags, q0 + u * WAVE + lane, mis, s0, s1, q1);
+    long seen = 0;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    for (long g0 = q0; g0 < q1; g0 += GROUP) {
+        const bool more = g0 + GROUP < q1;
+        if (more) {
+#pragma unroll
+            for (int u = 0; u < SCAN_TRIPS; u++) nxt[u] = load_tags(tags, g0 + GROUP + u * WAVE + lane, mis, s0, s1, q1);
+        }
+#pragma unroll
+        for (int u = 0; u < SCAN_TRIPS; u++) {
+            const bool m0 = cur[u].x == c, m1 = cur[u].y == c, m2 = cur[u].z == c, m3 = cur[u].w == c;
+            const unsigned long long b0 = __ballot(m0), b1 = __ballot(m1), b2 = __ballot(m2), b3 = __ballot(m3);
+            const long tot = __popcll(b0) + __popcll(b1) + __popcll(b2) + __popcll(b3);
+            if (LOCATE && target < seen + tot) {
+                // age order within a trip: lane by lane, the lane's four tags in turn
+                long rest = target - seen - (__popcll(b0 & below) + __popcll(b1 & below) + __popcll(b2 & below) + __popcll(b3 & below));
+                const int mine = (int)m0 + (int)m1 + (int)m2 + (int)m3;
+                const bool owner = rest >= 0 && rest < mine;
+                int k = 0;
+                if (owner) {
+                    if (m0) { if (rest == 0) k = 0; rest--; }
+                    if (m1) { if (rest == 0) k = 1; rest--; }
+                    if (m2) { if (rest == 0) k = 2; rest--; }
+                    if (m3) { if (rest == 0) k = 3; rest--; }
+                }
+                const int at = (int)(4 * (g0 + u * WAVE + lane) - mis) + k;
+                const unsigned long long who = __ballot(owner);          // exactly one lane
+                return (long)__shfl(at, __ffsll((long long)who) - 1);
+            }
+            seen += tot;
+        }
+        if (more) {
+#pragma unroll
+            for (int u = 0; u < SCAN_TRIPS; u++) cur[u] = nxt[u];
+        }
+    }
+    return LOCATE ? -1 : seen;
+}
+
+// The pick: one wave per batch episode b.  Its class is c = (i + rotation + draw) mod n_classes for its index i within its ring's segment
+// of the batch (the Latin square's cyclic rotation, moved from collection to sampling); among the m_c eligible episodes of that class -
+// the count - 1 oldest of the ring, ages 0 .. count - 2 in slots head - count + age mod capacity: one or two contiguous pieces of the tag
+// table - it takes the floor(ue * m_c)-th oldest, and where the class has none the slot k_sample_windows would take.  Writes the slot
+// to picked[b] (row_major == 0) or to picked[b * W + w] for every row w of the episode (row_major != 0: the scratch form, see
+// kr_sample_windows_balanced); never touches episode data.
+__global__ __launch_bounds__(WAVE) void k_pick_balanced(int B, int B_agent, int W, Ring ra, Ring re, const int* __restrict__ agent_class,
+                                                        const int* __restrict__ expert_class, int n_classes, int rotation,
+                                                        const float* __restrict__ u_ep, unsigned long long seed,
+                                                        const int64_t* __restrict__ draw, int* __restrict__ picked, int row_major) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    if (b >= B) return;
+    const bool is_agent = b < B_agent;
+    const Ring& g = is_agent ? ra : re;
+    const int* tags = is_agent ? agent_class : expert_class;
+    const long cnt = g.count[0], head = g.head[0];
+    const int capacity = g.capacity;
+    const float ue = sample_uniform(u_ep, b, 0x5a4du, seed, draw);
+    long want = (long)(b - (is_agent ? 0 : B_agent)) + rotation + (draw != nullptr ? draw[0] : 0);
+    want %= n_classes;
+    const int c = (int)(want < 0 ? want + n_classes : want);
+    long first = (head - cnt) % capacity;
+    first = first < 0 ? first + capacity : first;
+    const long eligible = cnt - 1 > 0 ? cnt - 1 : 0;                            // <= capacity - 1
+    const long end_a = first + eligible < capacity ? first + eligible : capacity;   // piece A: slots [first, end_a), the older ones
+    const long end_b = first + eligible - end_a;                                // piece B: slots [0, end_b) behind the wrap
+    const long m_a = scan_tags<false>(tags, first, end_a, c, 0, lane);
+    const long m_c = m_a + scan_tags<false>(tags, 0, end_b, c, 0, lane);
+    long ep;
+    if (m_c > 0) {
+        long j = (long)(ue * (float)m_c);
+        j = j < m_c - 1 ? j : m_c - 1;
+        ep = j < m_a ? scan_tags<true>(tags, first, end_a, c, j, lane) : scan_tags<true>(tags, 0, end_b, c, j - m_a, lane);
+    } else {
+        ep = uniform_episode(ue, cnt, head, capacity);
+    }
+    if (row_major == 0) {
+        if (lane == 0) picked[b] = (int)ep;
+    } else {
+        for (int w = lane; w < W; w += WAVE) picked[(long)b * W + w] = (int)ep;
+    }
+}
+
+// The gather: k_sample_windows' rows with the episode supplied - picked[b], or (row_major != 0) picked[r], which may be the weight
+// output itself: every wave reads its own element before it writes it and touches no other (hence no __restrict__ on the two).
+__global__ __launch_bounds__(WAVE) void k_gather_windows(int B, int B_agent, int H, int n_steps, Ring ra, Ring re, const int* picked,
+                                                         int row_major, const float* __restrict__ u_start, unsigned long long seed,
+                                                         const int64_t* __restrict__ draw, float* __restrict__ next_ends,
+                                                         float* __restrict__ state, float* __restrict__ action, float* __restrict__ next_state,
+                                                         float* __restrict__ reward, float* __restrict__ not_done, float* weight) {
+    const int W = H - n_steps;
+    const int r = blockIdx.x, lane = threadIdx.x;
+    if (r >= B * W) return;
+    const int b = r / W, w = r % W;
+    const Ring& g = b < B_agent ? ra : re;
+    long ep = picked[row_major != 0 ? r : b];
+    ep = ep < 0 ? 0 : (ep < g.capacity ? ep : g.capacity - 1);      // (the pick launch wrote a slot of this ring)
+    const float us = sample_uniform(u_start, r, 0x5a4eu, seed, draw);
+    window_row(g, ep, us, g.count[0] < 2, B, H, n_steps, r, w, lane, next_ends, state, action, next_state, reward, not_done, weight);
+}
+
+// kr_commit_classes: the class tag of every kept env into kr_commit_episodes' slot
+__global__ __launch_bounds__(WAVE) void k_commit_classes(int n, int capacity, const uint8_t* __restrict__ keep, const int64_t* __restrict__ rank,
+                                                         const int64_t* __restrict__ head, const int* __restrict__ env_class,
+                                                         int* __restrict__ ep_class) {
+    const int i = blockIdx.x * WAVE + threadIdx.x;
+    if (i >= n || keep[i] == 0) return;
+    ep_class[(head[0] + rank[i] - 1) % capacity] = env_class[i];
 }
 
 // ---- learner glue: plain grid-stride elementwise kernels, no fma contraction where the torch expression has none
@@ -460,6 +616,39 @@ int kr_sample_windows_mixed(int32_t batch, int32_t batch_agent, int32_t horizon,
                   expert->ep_reward, expert->ep_not_done};
     hipLaunchKernelGGL(k_sample_windows, dim3(batch * (horizon - n_steps)), dim3(WAVE), 0, (hipStream_t)stream, batch, batch_agent, horizon, n_steps, ga,
                        ge, u_ep, u_start, (unsigned long long)seed, draw, next_ends, state, action, next_state, reward, not_done, weight);
+    return launched();
+}
+
+int kr_commit_classes(int32_t n, int32_t capacity, const uint8_t* keep, const int64_t* rank, const int64_t* head, const int32_t* env_class,
+                      int32_t* ep_class, void* stream) {
+    if (n <= 0 || capacity <= 0 || !keep || !rank || !head || !env_class || !ep_class) return KS_ERR_INVALID;
+    hipLaunchKernelGGL(k_commit_classes, dim3((n + WAVE - 1) / WAVE), dim3(WAVE), 0, (hipStream_t)stream, n, capacity, keep, rank, head, env_class,
+                       ep_class);
+    return launched();
+}
+
+int kr_sample_windows_balanced(int32_t batch, int32_t batch_agent, int32_t horizon, int32_t n_steps, const kr_ring* agent, const kr_ring* expert,
+                               const int32_t* agent_class, const int32_t* expert_class, int32_t n_classes, int32_t rotation, const float* u_ep,
+                               const float* u_start, uint64_t seed, const int64_t* draw, float* state, float* action, float* next_state,
+                               float* reward, float* not_done, float* weight, float* next_ends, int32_t* picked, void* stream) {
+    if (batch <= 0 || batch_agent < 0 || batch_agent > batch || horizon <= n_steps || n_steps <= 0 || n_steps > WAVE || !ring_ok(agent) || !ring_ok(expert) ||
+        ((u_ep == nullptr) != (u_start == nullptr)) || (!u_ep && !draw) || !state || !action || !next_state || !reward || !not_done || !weight ||
+        n_classes < 1 || n_classes > 64 || (batch_agent > 0 && !agent_class) || (batch_agent < batch && !expert_class))
+        return KS_ERR_INVALID;
+    const Ring ga{agent->count, agent->head, agent->capacity, agent->ep_len, agent->ep_state, agent->ep_next, agent->ep_action, agent->ep_reward,
+                  agent->ep_not_done};
+    const Ring ge{expert->count, expert->head, expert->capacity, expert->ep_len, expert->ep_state, expert->ep_next, expert->ep_action,
+                  expert->ep_reward, expert->ep_not_done};
+    // without `picked` the slots travel from the pick to the gather in the weight output, one copy per window row: the gather wave of a row
+    // reads its own element and then writes its weight there - no scratch buffer to own, nothing allocated on a captured stream
+    const int W = horizon - n_steps, row_major = picked == nullptr;
+    int* slots = picked != nullptr ? picked : (int*)weight;
+    hipLaunchKernelGGL(k_pick_balanced, dim3(batch), dim3(WAVE), 0, (hipStream_t)stream, batch, batch_agent, W, ga, ge, agent_class, expert_class,
+                       n_classes, rotation, u_ep, (unsigned long long)seed, draw, slots, row_major);
+    if (launched() != KS_OK) return KS_ERR_HIP;
+    hipLaunchKernelGGL(k_gather_windows, dim3(batch * W), dim3(WAVE), 0, (hipStream_t)stream, batch, batch_agent, horizon, n_steps, ga, ge,
+                       (const int*)slots, row_major, u_start, (unsigned long long)seed, draw, next_ends, state, action, next_state, reward, not_done,
+                       weight);
     return launched();
 }
 

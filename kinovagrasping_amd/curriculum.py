@@ -96,7 +96,7 @@ def policy_basename(policy_dir) -> str:
 
 def run_stage(plan, policy, n_envs: int = 1024, rounds: int = 10, updates_per_round: int = 100, expert_prob: float = 0.3, seed: int = 2,
               device: int = 0, load_previous: bool = True, save: bool = True, eval_envs: int | None = None, starts_per_env: int = 0,
-              param_ranges=None):
+              param_ranges=None, free_running: bool = False, balanced: bool | None = None, budget_ms: float | None = None):
     """One stage of the curriculum on the GPU simulator (the batched counterpart of rl_experiment + train_policy,
     main_DDPGfD.py:600-621, 776-800): start from the previous stage's policy and agent replay, mix in the expert
     replay of the stage's shapes at `expert_prob` (DDPGfD.py:232-254), train, evaluate, save policy + replay + info.
@@ -121,6 +121,22 @@ def run_stage(plan, policy, n_envs: int = 1024, rounds: int = 10, updates_per_ro
     {"mass_edges", "mu_edges", "attempts", "successes"}, the rounds' episodes per (mass bin, mu bin) in four bins each over the ranges
     (metrics.param_success_table; every record's parameters from scenarios.param_draw_reference: the log's episode ordinal is the draw's
     episode number).
+    free_running=True (needs starts_per_env > 0, ValueError otherwise): the stage trains through pipeline.AsyncTrainer - capture, then one
+    run per round, then flush - instead of eng.step() plus serial updates: a round is ONE persistent launch of 30 env-steps (ks_rollout)
+    with the learner's captured updates beside it on a second stream.  updates_per_round maps to the trainer's updates_per_step =
+    max(1, round(updates_per_round / 30)): that many updates per env-step of the launch, so 100 becomes 3 per step = 90 per round, and
+    anything below 45 one per step = 30 per round.  The batch is policy.batch_size episodes.  budget_ms: every round is one TIME-budgeted
+    launch (AsyncTrainer.run(30, budget_ms=...): each wave steps its envs until the budget has passed, at most 30 env-steps) - cheap
+    objects then finish several times the episodes of expensive ones; only on a context whose rollout plan is "waves" (KS_PLAN_WAVES:
+    asked once the envs hold their shapes' objects, since the plan follows the objects' 16-env groups), ValueError before the trainer is
+    built or a rollout launched otherwise.  balanced (None: true when the stage has more than one shape): the agent ring's
+    episodes carry their shape as a class (DeviceEpisodeReplay.set_env_classes(sim.shape_of_env, shapes)), every shape's expert bundle
+    is loaded with its shape's class, and each batch is drawn balanced over the shapes (sample_balanced) whatever the ring holds - the
+    Latin square's equal shares, kept at the sampler instead of at collection.  The episode-log fold, per_shape_success, param_success,
+    the final evaluation and the saved files are the lock-step stage's; `distinct_starts` is counted from the log's records (the starts
+    of the episodes that ended in the rounds) and the starts running when the rounds end.  The result gains `env_steps` (the sum of the
+    envs' step counters), `replay_class_counts` ({shape: episodes in the agent ring}) and `batch_class_slots` ({shape: slots of the
+    last update's agent segment}, from the sampler's `picked`; empty without balanced).
     Returns a dict (num_success, num_total, paths, ...)."""
     import torch
 
@@ -131,6 +147,10 @@ def run_stage(plan, policy, n_envs: int = 1024, rounds: int = 10, updates_per_ro
 
     if param_ranges is not None and starts_per_env <= 0:
         raise ValueError("run_stage: param_ranges are drawn where an episode restarts inside the stepping kernel - they need starts_per_env > 0")
+    if free_running and starts_per_env <= 0:
+        raise ValueError("run_stage: free_running episodes restart inside the rollout kernel - they need starts_per_env > 0")
+    if not free_running and (balanced or budget_ms is not None):
+        raise ValueError("run_stage: balanced / budget_ms belong to free_running=True")
     dirs = plan["dirs"]
     known = scenarios.SHAPES + scenarios.MEDIUM_SHAPES + scenarios.EXTRA_SHAPES + scenarios.MULTI_GEOM_SHAPES
     shapes = [s for s in plan["requested_shapes"] if s in known]
@@ -143,6 +163,9 @@ def run_stage(plan, policy, n_envs: int = 1024, rounds: int = 10, updates_per_ro
         policy.load(str(dirs["prev_policy_dir"] / policy_basename(dirs["prev_policy_dir"])))
     sim = MultiShapeSim(n_envs, shapes, device=device, auto_reset=starts_per_env > 0, horizon=30)
     replay = DeviceEpisodeReplay(n_envs, capacity=max(4 * n_envs, 1024), horizon=30, device=dev)
+    if free_running:
+        balanced = len(shapes) > 1 if balanced is None else bool(balanced)
+        replay.set_env_classes(sim.shape_of_env, shapes)          # (before the load: a previous stage's sidecar names its episodes' shapes)
     if load_previous and dirs["prev_replay_dir"].is_dir():
         replay.load(dirs["prev_replay_dir"])
     expert = None
@@ -151,7 +174,12 @@ def run_stage(plan, policy, n_envs: int = 1024, rounds: int = 10, updates_per_ro
         if p.is_dir():
             if expert is None:
                 expert = DeviceEpisodeReplay(n_envs, capacity=max(4 * n_envs, 1024), horizon=30, device=dev)
-            expert.load(p)
+                if free_running:
+                    expert.set_env_classes(None, shapes)
+            if free_running:
+                expert.load(p, class_id=shapes.index(s))
+            else:
+                expert.load(p)
 
     def reset_all(the_sim, count):
         """per env: orientation class by the reference's rule, start row from that class's table of the env's shape"""
@@ -176,7 +204,7 @@ def run_stage(plan, policy, n_envs: int = 1024, rounds: int = 10, updates_per_ro
     # int(batch_size * (1 - expert_prob)) agent + the rest expert episodes sampled by ONE launch (kr_sample_windows_mixed,
     # DDPGfD.train_batch's mix, DDPGfD.py:232-254); without expert data every episode comes from the agent ring
     from .learner_native import NativeDDPGfDUpdate
-    native = NativeDDPGfDUpdate(policy)
+    native = None if free_running else NativeDDPGfDUpdate(policy)
     mix = expert is not None and expert.count >= 2
     losses = []
     seen = None
@@ -205,7 +233,45 @@ def run_stage(plan, policy, n_envs: int = 1024, rounds: int = 10, updates_per_ro
             mass_edges, mu_edges = edges(0, 1), edges(2, 3)
             p_attempts = np.zeros((len(mass_edges) - 1, len(mu_edges) - 1), dtype=np.int64)
             p_successes = np.zeros_like(p_attempts)
-    for r in range(rounds):
+    trainer = None
+    if budget_ms is not None and sim.rollout_plan()[0] != "waves":
+        # (asked here, with every env on its shape's object: the plan follows the objects' 16-env groups - 14 shapes over 4096 envs leave partly
+        # filled groups, more than there are workgroups; 4032 = 14 x 18 whole groups is the wave form)
+        plan_name = sim.rollout_plan()[0]
+        sim.close()
+        raise ValueError(f"run_stage: budget_ms needs the wave form of the rollout kernel (KS_PLAN_WAVES); this context's plan is {plan_name!r}")
+    if free_running:
+        from .pipeline import AsyncTrainer
+        trainer = AsyncTrainer(sim, policy, replay, eng, batch_episodes=policy.batch_size, expert_replay=expert if mix else None, expert_prob=expert_prob,
+                               updates_per_step=max(1, round(updates_per_round / 30)), balanced=balanced)
+        trainer.capture()
+    for r in range(rounds if free_running else 0):             # a round = one launch, the updates beside it
+        trainer.run(30, budget_ms=budget_ms)
+        trainer.flush()
+        torch.cuda.synchronize(dev)
+        records = sim.episode_log()
+        ledger.add(records)
+        seen[records["env"].long(), records["start_index"].long()] = True
+        if param_ranges is not None:
+            r_env = records["env"].cpu().numpy()
+            r_mass, r_mu = scenarios.param_draw_reference(seed, r_env, records["episode"].cpu().numpy(), ranges, npdt)
+            a_, s_ = param_success_table(records, r_mass, r_mu, mass_edges, mu_edges)
+            p_attempts += a_
+            p_successes += s_
+    if trainer is not None:
+        trainer.flush(finish_update=True)
+        torch.cuda.synchronize(dev)
+        seen[all_envs, sim.start_index()[0].long()] = True
+        cnt, head = replay.count, replay.head
+        tags = replay.ep_class[(head - cnt + torch.arange(cnt, device=dev)) % replay.capacity].cpu().numpy()
+        free_out = {"env_steps": int(trainer.steps_total.sum()), "replay_class_counts": {s: int((tags == i).sum()) for i, s in enumerate(shapes)},
+                    "batch_class_slots": {}}
+        if balanced and trainer.picked is not None and trainer.updates > 0:
+            b_agent = int(trainer.batch_episodes * (1 - expert_prob)) if mix else trainer.batch_episodes
+            got = replay.ep_class[trainer.picked[:b_agent].long()].cpu().numpy()
+            free_out["batch_class_slots"] = {s: int((got == i).sum()) for i, s in enumerate(shapes)}
+        n_updates = trainer.updates
+    for r in range(0 if free_running else rounds):             # lock step: a round = 30 eng.step() calls, then the updates
         if starts_per_env <= 0:
             obs0, _ = reset_all(sim, n_envs)
             eng.start(obs0)
@@ -233,10 +299,12 @@ def run_stage(plan, policy, n_envs: int = 1024, rounds: int = 10, updates_per_ro
     obs0, classes = reset_all(sim, n_envs)
     res = eval_policy(sim, policy, obs0, horizon=30, orientation=plan["requested_orientation"])
     out = {"expert_episodes": 0 if expert is None else int(expert.count), "num_success": res["num_success"], "num_total": n_envs, "avg_reward": res["avg_reward"], "skipped_shapes": skipped, "shapes": shapes,
-           "updates": len(losses),
+           "updates": len(losses) if trainer is None else n_updates,
            "distinct_starts": n_envs * rounds if seen is None else int(seen.sum()), "orientation_counts": {c: classes.count(c) for c in sorted(set(classes))}}
     if seen is not None:
         out.update(episodes=ledger.episodes, per_shape_success=ledger.per_object(shapes))
+    if trainer is not None:
+        out.update(free_out)
     if param_ranges is not None:
         out["param_success"] = {"mass_edges": mass_edges.tolist(), "mu_edges": mu_edges.tolist(), "attempts": p_attempts.tolist(),
                                 "successes": p_successes.tolist()}

@@ -73,7 +73,7 @@ def _concurrent_stream(main, dev, tries=8):
 
 class GraphedTrainer:
     def __init__(self, sim, policy, replay, engine, batch_episodes=64, overlap=True, learn_after=31, expert_replay=None, expert_prob=0.3,
-                 updates_per_step=1, lean_learner=False):
+                 updates_per_step=1, lean_learner=False, balanced=False):
         """updates_per_step U / batch_episodes: the update-to-data knobs.  The reference makes 100 updates per 30-step episode of ONE
         env (main_DDPGfD.py:474-486: ~3 per stored transition); BASELINE config 3 - bench.py's workload - is ONE update on 64 episodes
         per env-step of 4096 envs.  U > 1 replays the captured update U times per env-step (the step becomes learner-bound beyond
@@ -86,10 +86,19 @@ class GraphedTrainer:
         lean_learner: build the learner with NativeDDPGfDUpdate(policy, lean=True) - no launch of the update needs LDS at any width
         that has LDS-free kernels of either kind (400-300: the lean ones) - so that the overlapped lock-step form can be measured on
         the kernels AsyncTrainer uses at that width.  "auto" (AsyncTrainer's choice): only when the default form is not LDS-free and
-        the lean kernels take the width."""
+        the lean kernels take the width.
+        balanced: every batch is drawn with replay.sample_balanced - the episodes of each ring's share of the batch spread evenly over the
+        ring's classes, whatever it holds - instead of uniformly over its episodes.  The replay (and the expert replay, if there is one)
+        must have classes set (DeviceEpisodeReplay.set_env_classes), else ValueError.  self.picked: the ring slot of every batch episode
+        of the last update (readable after flush())."""
         assert engine.gen is None, "graph capture uses the default CUDA generator"
         self.sim, self.policy, self.replay, self.eng = sim, policy, replay, engine
         self.expert_replay, self.expert_prob = expert_replay, float(expert_prob)
+        self.balanced, self.picked = bool(balanced), None
+        if self.balanced and (getattr(replay, "ep_class", None) is None or (expert_replay is not None and getattr(expert_replay, "ep_class", None) is None)):
+            raise ValueError("balanced=True: the replay (and the expert replay) must have classes set (DeviceEpisodeReplay.set_env_classes)")
+        if self.balanced and not replay.native:
+            raise ValueError("balanced=True needs a device ring (DeviceEpisodeReplay on the GPU)")
         if expert_replay is not None and not (replay.native and expert_replay.native):
             raise ValueError("GraphedTrainer: the expert mix needs device rings (DeviceEpisodeReplay on the GPU)")
         self.batch_episodes, self.overlap, self.learn_after = batch_episodes, overlap, learn_after
@@ -148,7 +157,12 @@ class GraphedTrainer:
     # -- learner phases on the static batch -------------------------------------------------------------
     def _sample(self):
         # (uniforms drawn in the sampling kernel, keyed by the update count: no generator-state launches in the graph)
-        if self.expert_replay is not None and self.expert_prob > 0:
+        if self.balanced:
+            mix = self.expert_replay is not None and self.expert_prob > 0
+            out = self.replay.sample_balanced(self.expert_replay if mix else None, self.batch_episodes, self.expert_prob, draw=self.native.it,
+                                              seed=self.sample_seed)
+            self.batch, self.picked = out[:-1], out[-1]
+        elif self.expert_replay is not None and self.expert_prob > 0:
             self.batch = self.replay.sample_mixed(self.expert_replay, self.batch_episodes, self.expert_prob, draw=self.native.it, seed=self.sample_seed)
         else:
             self.batch = self.replay.sample_batch_nstep(self.batch_episodes, draw=self.native.it if self.replay.native else None, seed=self.sample_seed)
@@ -393,8 +407,10 @@ class AsyncTrainer(GraphedTrainer):
     for fixed weights).  The reference's own loop acts with a policy that is a whole episode old (main_DDPGfD.py:466-486)."""
 
     def __init__(self, sim, policy, replay, engine, batch_episodes=64, expert_replay=None, expert_prob=0.3, updates_per_step=1,
-                 launch_synchronous=False, max_launch_steps=60):
-        """launch_synchronous (opt-in): what one stream hands the other changes only at launch boundaries, so that the same inputs give the
+                 launch_synchronous=False, max_launch_steps=60, balanced=False):
+        """balanced: as GraphedTrainer's (class-balanced batches: what lets a ring that a time-budgeted or free-running rollout fills at each
+        object's own pace train every object alike); not with launch_synchronous, whose staging ring carries no classes.
+        launch_synchronous (opt-in): what one stream hands the other changes only at launch boundaries, so that the same inputs give the
         same results in every run (the default form acts with whatever was published last and fills the ring in arrival order).  The
         actor is published once, before a launch starts: every env of a launch acts with the same weights.  The learner keeps collecting
         finished episodes beside the launch (paced as in the default form), but into a staging ring; before the next launch they enter
@@ -404,8 +420,10 @@ class AsyncTrainer(GraphedTrainer):
         (run(budget_ms=...)).  max_launch_steps sizes the staging ring: one finished episode per 10 env-steps of the longest launch
         and env, plus two; what does not fit is kept waiting in the env's buffers, never overwritten."""
         super().__init__(sim, policy, replay, engine, batch_episodes=batch_episodes, overlap=True, expert_replay=expert_replay, expert_prob=expert_prob,
-                         updates_per_step=updates_per_step, lean_learner="auto")
+                         updates_per_step=updates_per_step, lean_learner="auto", balanced=balanced)
         self.launch_synchronous = bool(launch_synchronous)
+        if self.launch_synchronous and getattr(replay, "ep_class", None) is not None:
+            raise ValueError("AsyncTrainer: launch_synchronous stages episodes in a ring without classes - not with a replay that has classes set")
         if self.launch_synchronous:
             from .replay import DeviceEpisodeReplay
             self.stage = DeviceEpisodeReplay(replay.n_envs, capacity=(max(1, int(max_launch_steps)) // 10 + 2) * replay.n_envs, horizon=replay.horizon, state_dim=replay.ep_state.shape[2],

@@ -115,6 +115,9 @@ class HostEpisodeReplay:
         return pick(self.state), pick(self.action), pick(self.next_state), pick(self.reward), pick(self.not_done)
 
 
+CLASS_SIDECAR = "episode_classes.json"      # beside the reference bundle's files: DeviceEpisodeReplay.save / load
+
+
 class DeviceEpisodeReplay:
     """Fixed-shape episode ring on the GPU: [capacity, horizon, ...] plus per-episode lengths.
     Envs append to their own open episode; a finished episode is committed to the ring (FIFO).
@@ -140,6 +143,7 @@ class DeviceEpisodeReplay:
         self._all = torch.ones(n_envs, dtype=torch.bool, device=self.device)
         self._row = torch.arange(horizon - n_steps, device=self.device).unsqueeze(0)
         self._win = torch.arange(n_steps, device=self.device)
+        self.env_class = self.ep_class = self.class_names = None          # per-episode class column: set_env_classes
         # on a GPU the bookkeeping runs as the kr_* kernels of libkinova_sim.so (include/kinova_rollout.h), one launch
         # per method instead of a dozen torch ops; the torch code below is the same arithmetic (and their checker)
         self.native = self.device.type == "cuda"
@@ -199,6 +203,8 @@ class DeviceEpisodeReplay:
         self.ep_reward.index_copy_(0, slots, self.cur_reward)
         self.ep_not_done.index_copy_(0, slots, self.cur_not_done)
         self.ep_len.index_copy_(0, slots, self.cur_len)
+        if self.ep_class is not None:
+            self.ep_class.index_copy_(0, slots, self.env_class)
         k = keep.sum()
         self._head.copy_((self._head + k) % self.capacity)
         self._count.copy_((self._count + k).clamp(max=self.capacity))
@@ -219,21 +225,75 @@ class DeviceEpisodeReplay:
         return out
 
     def save(self, dirpath, max_episode=None):
-        """the reference's replay bundle (utils.py:345-365)"""
+        """the reference's replay bundle (utils.py:345-365).  With classes set (set_env_classes) the directory also gets the sidecar
+        CLASS_SIDECAR - the class names and the class index of every saved episode, oldest first -, which the reference's loader, reading
+        its files by name, never opens; the bundle's own files are what they are without classes."""
         save_reference_bundle(dirpath, self.host_episodes(), self.capacity if max_episode is None else max_episode)
+        if self.ep_class is not None:
+            import json
+            from pathlib import Path
+            cnt, head = self.count, self.head
+            slots = (head - cnt + torch.arange(cnt, device=self.device)) % self.capacity
+            (Path(dirpath) / CLASS_SIDECAR).write_text(json.dumps({"class_names": list(self.class_names),
+                                                                   "episode_class": [int(c) for c in self.ep_class[slots].tolist()]}))
 
-    def load(self, dirpath):
-        """append the episodes of a reference replay bundle to the ring (episodes longer than the horizon are cut)"""
+    def load(self, dirpath, class_id=None):
+        """append the episodes of a reference replay bundle to the ring (episodes longer than the horizon are cut).  On a ring with classes
+        every loaded episode is tagged `class_id` when one is given; else by the bundle's sidecar (save), its class NAMES mapped onto this
+        ring's - a name this ring does not know, like a bundle without a sidecar, gives -1: the episode belongs to no class."""
         eps, info = load_reference_bundle(dirpath)
-        for ep in eps:
+        tags = None
+        if self.ep_class is not None:
+            tags = [-1 if class_id is None else int(class_id)] * len(eps)
+            if class_id is not None and not -1 <= int(class_id) < len(self.class_names):
+                raise ValueError(f"load: class_id {class_id} is not one of the ring's {len(self.class_names)} classes")
+            from pathlib import Path
+            side = Path(dirpath) / CLASS_SIDECAR
+            if class_id is None and side.is_file():
+                import json
+                rec = json.loads(side.read_text())
+                known = {name: i for i, name in enumerate(self.class_names)}
+                if len(rec["episode_class"]) == len(eps):            # (a sidecar of another bundle's length says nothing about this one)
+                    tags = [known.get(rec["class_names"][c], -1) if 0 <= c < len(rec["class_names"]) else -1 for c in rec["episode_class"]]
+        for i, ep in enumerate(eps):
             L = min(len(ep["reward"]), self.horizon)
             s = int(self._head)
             for name, key in (("ep_state", "state"), ("ep_next", "next_state"), ("ep_action", "action"), ("ep_reward", "reward"), ("ep_not_done", "not_done")):
                 getattr(self, name)[s, :L] = torch.as_tensor(ep[key][:L]).to(self.device)
             self.ep_len[s] = L
+            if tags is not None:
+                self.ep_class[s] = tags[i]
             self._head.copy_((self._head + 1) % self.capacity)
             self._count.copy_((self._count + 1).clamp(max=self.capacity))
         return info
+
+    def set_env_classes(self, env_class, class_names):
+        """Give the ring a per-episode class column: env_class int [n_envs] - the class of whatever env i collects (an index into
+        class_names; None: -1 for every env, a ring that is only loaded into, such as an expert ring) -, class_names the classes' names
+        (1 .. 64 of them).  Allocates ep_class int32 [capacity + 1] filled with -1 (the episodes the ring already holds belong to no
+        class); from here on every commit - commit_native, both buffers of commit_published, the torch path of end_episodes - tags
+        the slots it fills (kr_commit_classes between the rank and the advance), load / save carry the tags and sample_balanced can
+        draw by them.  Without this call nothing about the ring changes."""
+        names = [str(c) for c in class_names]
+        if not 1 <= len(names) <= 64 or len(set(names)) != len(names):
+            raise ValueError("set_env_classes: 1 .. 64 distinct class names")
+        if env_class is None:
+            env_class = torch.full((self.n_envs,), -1, dtype=torch.int32)
+        env_class = torch.as_tensor(env_class)
+        if env_class.shape != (self.n_envs,) or env_class.dtype.is_floating_point or env_class.dtype == torch.bool:
+            raise ValueError("set_env_classes: env_class is an int tensor [n_envs]")
+        if env_class.numel() and not (-1 <= int(env_class.min()) and int(env_class.max()) < len(names)):
+            raise ValueError("set_env_classes: env_class values are indices into class_names (or -1)")
+        self.env_class = env_class.to(device=self.device, dtype=torch.int32).contiguous()
+        self.class_names = names
+        self.ep_class = torch.full((self.capacity + 1,), -1, dtype=torch.int32, device=self.device)
+
+    def _commit_classes(self, keep, st):
+        """kr_commit_classes behind a kr_rank_episodes on the same keep (a ring without classes: nothing)"""
+        if self.ep_class is not None:
+            P = self._ptr
+            self._check(self._lib.kr_commit_classes(self.n_envs, self.capacity, P(keep), P(self._rank), P(self._head), P(self.env_class),
+                                                    P(self.ep_class), st), "kr_commit_classes")
 
     def enable_async(self):
         """Open-episode buffers of the free-running rollout kernel (ks_rollout): TWO per env, so that an env can start its next
@@ -263,6 +323,7 @@ class DeviceEpisodeReplay:
                                              P(self.a_next[b]), P(self.a_action[b]), P(self.a_reward[b]), P(self.a_not_done[b]), P(self.pub_len[b]),
                                              P(self.ep_state), P(self.ep_next), P(self.ep_action), P(self.ep_reward), P(self.ep_not_done),
                                              P(self.ep_len), st), "kr_commit_episodes")
+            self._commit_classes(keep, st)
             self._check(L.kr_advance_ring(self.n_envs, self.capacity, P(self._total), P(self._head), P(self._count), P(keep), P(self.pub_len[b]), st),
                         "kr_advance_ring")
 
@@ -274,6 +335,7 @@ class DeviceEpisodeReplay:
                                          P(self.cur_next), P(self.cur_action), P(self.cur_reward), P(self.cur_not_done), P(self.cur_len),
                                          P(self.ep_state), P(self.ep_next), P(self.ep_action), P(self.ep_reward), P(self.ep_not_done),
                                          P(self.ep_len), st), "kr_commit_episodes")
+        self._commit_classes(keep, st)
         self._check(L.kr_advance_ring(self.n_envs, self.capacity, P(self._total), P(self._head), P(self._count), P(ended), P(self.cur_len), st),
                     "kr_advance_ring")
         return self._total[0]
@@ -355,9 +417,14 @@ class DeviceEpisodeReplay:
         ue = torch.rand(batch_size, device=self.device, generator=generator) if uniforms is None else uniforms[:batch_size]
         k = torch.minimum((ue * hi).long(), hi - 1)
         ep = (self._head - self._count + k) % self.capacity
+        u = torch.rand(batch_size, W, device=self.device, generator=generator) if uniforms is None else uniforms[batch_size:].view(batch_size, W)
+        return self._windows_of(ep, u)
+
+    def _windows_of(self, ep, u):
+        """the window rows of the episodes in ring slots ep [B] with the start uniforms u [B, W] (torch path)"""
+        n, W, batch_size = self.n_steps, self.horizon - self.n_steps, ep.shape[0]
         ceiling = (self.ep_len[ep] - n).clamp(min=1)       # [B]
         row = self._row                                                      # [1,W]
-        u = torch.rand(batch_size, W, device=self.device, generator=generator) if uniforms is None else uniforms[batch_size:].view(batch_size, W)
         start = (u * ceiling.unsqueeze(1)).long().clamp(max=self.horizon - n)
         start = torch.where(row == (ceiling.unsqueeze(1) - 1), ceiling.unsqueeze(1).expand(-1, W), start)
         start = start.clamp(max=self.horizon - n)
@@ -366,3 +433,67 @@ class DeviceEpisodeReplay:
         e = ep.view(-1, 1, 1).expand(-1, W, n)
         g = lambda x: x[e, t].reshape(batch_size * W, n, *x.shape[2:])
         return g(self.ep_state), g(self.ep_action), g(self.ep_next), g(self.ep_reward), g(self.ep_not_done), weight
+
+    def _pick_balanced(self, ue, rotation, d):
+        """sample_balanced's pick on this ring (torch path, the checker of k_pick_balanced): the ring slot of every batch slot of the
+        ring's segment, ue [nb] its episode uniforms"""
+        nb, cap, nc = ue.shape[0], self.capacity, len(self.class_names)
+        cnt, head = self._count, self._head
+        ages = torch.arange(cap - 1, device=self.device)                     # eligible: ages 0 .. count - 2
+        slots = (head - cnt + ages) % cap
+        tags = torch.where(ages < cnt - 1, self.ep_class[slots].long(), torch.full_like(ages, -1))
+        want = (torch.arange(nb, device=self.device) + int(rotation) + d) % nc           # (non-negative: the divisor's sign)
+        match = tags.unsqueeze(0) == want.unsqueeze(1)                       # [nb, cap - 1]
+        m = match.sum(1)
+        j = torch.minimum((ue * m.float()).long(), m - 1)
+        at = (match & (match.cumsum(1) == (j + 1).unsqueeze(1))).long().argmax(1) if cap > 1 else torch.zeros_like(m)
+        hi = (cnt - 1).clamp(min=1)
+        k = torch.minimum((ue * hi).long(), hi - 1)
+        return torch.where(m > 0, (head - cnt + at) % cap, (head - cnt + k) % cap)
+
+    def sample_balanced(self, expert, batch_size, prob=0.3, uniforms=None, draw=None, seed=0, rotation=0, generator=None):
+        """sample_mixed with every batch episode drawn from ONE class of its ring (set_env_classes), the classes in cyclic rotation: slot i
+        of a ring's segment of the batch - agent [0, b_agent), expert [b_agent, batch_size); expert=None: one ring, the whole batch - wants
+        class (i + rotation + draw) mod n_classes and takes the floor(u * m)-th oldest of that class's m eligible episodes (the newest
+        episode of the ring is never eligible); a class without eligible episodes falls back to sample_batch_nstep's draw over all of
+        them.  So whatever the ring holds, the classes' shares of a segment differ by one slot at most, and over n_classes consecutive
+        draws each class gets exactly the segment's length.  Return layout of sample_mixed, then `picked` int32 [batch_size]: the ring
+        slot every batch episode was read from.  On the GPU two launches (kr_sample_windows_balanced: the pick, the gather); the torch
+        path below is the same rule and their checker."""
+        n, W = self.n_steps, self.horizon - self.n_steps
+        if self.ep_class is None or (expert is not None and expert.ep_class is None):
+            raise ValueError("sample_balanced: the ring has no classes (set_env_classes)")
+        if expert is not None and (expert.horizon != self.horizon or expert.n_steps != n or expert.class_names != self.class_names):
+            raise ValueError("sample_balanced: the expert ring must have the agent ring's horizon, n_steps and class names")
+        b_agent = batch_size if expert is None else int(batch_size * (1 - prob))
+        nc = len(self.class_names)
+        if self.native and (expert is None or expert.native):
+            import ctypes
+            R, dev = batch_size * W, self.device
+            S, A = self.ep_state.shape[2], self.ep_action.shape[2]
+            out = (torch.empty(R, n, S, device=dev), torch.empty(R, n, A, device=dev), torch.empty(R, n, S, device=dev),
+                   torch.empty(R, n, device=dev), torch.empty(R, n, device=dev), torch.empty(R, device=dev))
+            picked = torch.empty(batch_size, dtype=torch.int32, device=dev)
+            P = self._ptr
+            ends = torch.empty(2 * R, S, device=dev) if (draw is not None and uniforms is None) else None
+            if uniforms is None and draw is None:
+                uniforms = torch.rand(batch_size * (W + 1), device=dev, generator=generator)
+            u = None if uniforms is None else uniforms.contiguous()
+            ra = self._ring()
+            re = ra if expert is None else expert._ring()
+            self._check(self._lib.kr_sample_windows_balanced(batch_size, b_agent, self.horizon, n, ctypes.byref(ra), ctypes.byref(re), P(self.ep_class),
+                                                             None if expert is None else P(expert.ep_class), nc, int(rotation), P(u),
+                                                             P(u[batch_size:]) if u is not None else None, int(seed) & (2 ** 64 - 1), P(draw),
+                                                             P(out[0]), P(out[1]), P(out[2]), P(out[3]), P(out[4]), P(out[5]), P(ends), P(picked),
+                                                             self._stream()), "kr_sample_windows_balanced")
+            return (out if ends is None else out + (ends,)) + (picked,)
+        if uniforms is None:
+            uniforms = torch.rand(batch_size * (W + 1), device=self.device, generator=generator)
+        ue, us = uniforms[:batch_size], uniforms[batch_size:].view(batch_size, W)
+        d = 0 if draw is None else int(draw)
+        parts, picks = [], []
+        for ring, lo, hi in ((self, 0, b_agent), (expert, b_agent, batch_size)):
+            if hi > lo:
+                picks.append(ring._pick_balanced(ue[lo:hi], rotation, d))
+                parts.append(ring._windows_of(picks[-1], us[lo:hi]))
+        return tuple(torch.cat([p[k] for p in parts], 0) for k in range(6)) + (torch.cat(picks).to(torch.int32),)
