@@ -12,7 +12,7 @@
      hand by ~5 mm per env-step on average while the fingers close - as in the reference, main_DDPGfD.py:443-446.)
 
     python examples/train_ddpgfd.py --envs 1024 --steps 600 --hidden 256 256 (or 400 300: the reference's widths, free-running too) [--free-running] [--expert-prob 0] [--starts-per-env 64]
-                                    [--success-map DIR] [--demonstrations free-running] [--randomize-params]
+                                    [--success-map DIR] [--demonstrations free-running] [--randomize-params] [--prioritized]
 
 --success-map DIR (with --free-running): the stepping kernel logs every finished training episode (ks_set_episode_log); at every report
 the script folds the log (metrics.EpisodeLedger) and writes DIR/per_shape_success.jsonl and the success / fail start coordinates of the
@@ -76,6 +76,11 @@ def main():
                     "heatmap coordinates of the training episodes into this directory at every report; the evaluation runs through ks_rollout too")
     ap.add_argument("--batch-episodes", type=int, default=64, help="episodes per update (x 25 five-step windows each); the reference: 64")
     ap.add_argument("--updates-per-step", type=int, default=1, help="learner updates per env-step of the whole batch of envs")
+    ap.add_argument("--prioritized", action="store_true", help="prioritized episode replay: episodes are drawn in proportion to (last TD error + eps)^alpha, "
+                    "demonstrations with a priority bonus, importance weights (p_min / p)^beta in the losses (DeviceEpisodeReplay.sample_prioritized)")
+    ap.add_argument("--per-alpha", type=float, default=0.3, help="with --prioritized: the priorities' exponent")
+    ap.add_argument("--per-beta0", type=float, default=0.4, help="with --prioritized: the importance weights' exponent at the start; annealed linearly to 1 over --steps")
+    ap.add_argument("--per-eps-expert", type=float, default=1.0, help="with --prioritized: the constant added to a demonstration's TD error (the agent's: 1e-3)")
     ap.add_argument("--actor-lr", type=float, default=1e-4, help="reference: 1e-4 (DDPGfD.py:57)")
     ap.add_argument("--critic-lr", type=float, default=1e-3, help="reference: Adam's default 1e-3 (DDPGfD.py:61)")
     ap.add_argument("--tau", type=float, default=0.001, help="soft target update rate (reference: 0.0005, main_DDPGfD.py:894 - for 100 updates per episode of one env)")
@@ -139,7 +144,8 @@ def main():
         print("per-episode parameters: object mass 0.05-0.15 kg, object-hand friction 0.5-1.0, drawn at every auto-reset")
     Trainer = AsyncTrainer if args.free_running else GraphedTrainer
     tr = Trainer(sim, policy, agent, eng, batch_episodes=args.batch_episodes, expert_replay=expert, expert_prob=args.expert_prob if expert is not None else 0.3,
-                 updates_per_step=args.updates_per_step)
+                 updates_per_step=args.updates_per_step, prioritized=args.prioritized, per_alpha=args.per_alpha, per_beta=args.per_beta0,
+                 per_eps_expert=args.per_eps_expert)
     tr.capture()
     if args.free_running:
         tr.run(36, learn=False)
@@ -163,6 +169,8 @@ def main():
     t0 = time.perf_counter()
     t_eval = 0.0
     for it in range(0, args.steps, 60):
+        if args.prioritized:                # beta from --per-beta0 to 1 over the run (a fill of the device scalar the captured sampler reads)
+            tr.set_per_beta(args.per_beta0 + (1.0 - args.per_beta0) * min(1.0, it / max(args.steps - 60, 1)))
         if args.free_running:
             tr.run(60)                      # one persistent launch of 60 env-steps (+ 60 updates beside it): long launches keep the launch tail small
             tr.flush()

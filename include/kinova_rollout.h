@@ -157,6 +157,71 @@ int kr_sample_windows_balanced(int32_t batch, int32_t batch_agent, int32_t horiz
                                const float *u_start, uint64_t seed, const int64_t *draw, float *state, float *action, float *next_state,
                                float *reward, float *not_done, float *weight, float *next_ends, int32_t *picked, void *stream);
 
+/* ---- prioritized episode replay (DDPGfD's sampling, Vecerik et al. 2017, per episode: an episode is drawn in proportion to the last TD error
+ * seen on it, demonstrations carry a priority bonus so that they stay sampled, and importance weights correct the bias).  The reference
+ * samples uniformly (utils.py:259); this is an option beside it, not a restatement.
+ *
+ * A ring may carry ep_prio uint32 [capacity (+ trash row)], one priority per slot in units of 1 / 65536 (65536 is priority 1.0; a committed
+ * slot holds 1 .. 2^32 - 1, a stored 0 is read as 1 everywhere), and prio_max uint32 [1], the largest priority any update has written to
+ * the ring (initialised to 65536 by the caller).  Priorities are integers, their sums 64-bit and the draw an integer comparison: which
+ * episode a uniform takes is exact and independent of any order of evaluation.  The two powf calls below are the only inexact steps.
+ * All kernels: one wave per workgroup, no LDS, vector loads / stores and one vector atomic (they run on the learner's stream beside a
+ * stepping kernel that holds the CUs' LDS).
+ *
+ * kr_commit_priorities: keep uint8 [n], rank int64 [n] (kr_rank_episodes), head int64 [1]: for every env i with keep[i] != 0
+ *     ep_prio[(head[0] + rank[i] - 1) % capacity] = max(prio_max[0], 1)
+ * - kr_commit_episodes' slot rule; a new episode enters at the largest priority seen so far, so it is sampled soon.  Issued between
+ * kr_rank_episodes and kr_advance_ring, where kr_commit_classes is.  Nothing else is written. */
+int kr_commit_priorities(int32_t n, int32_t capacity, const uint8_t *keep, const int64_t *rank, const int64_t *head, const uint32_t *prio_max,
+                         uint32_t *ep_prio, void *stream);
+
+/* kr_sample_windows_mixed with the episode of every batch slot drawn in proportion to its priority within its ring.  agent_prio / expert_prio:
+ * the rings' ep_prio (expert_prio may be NULL only when batch_agent == batch, agent_prio only when batch_agent == 0); beta: a device float
+ * (a captured graph is annealed by a fill between replays); picked (optional, may be NULL) int32 [batch]: the ring slot each batch episode
+ * was read from.  Per ring segment of the batch - agent: slots [0, batch_agent), expert: [batch_agent, batch):
+ *   eligible   the count - 1 oldest episodes of the ring, age a = 0 .. count - 2 in slot (head - count + a) mod capacity (the newest is never
+ *              sampled, as in kr_sample_windows); p_a = max(ep_prio[slot], 1);
+ *   T, p_min   the sum (uint64) and the minimum of the p_a;
+ *   slot b     with its episode uniform ue:  t = min(T - 1, (uint64)((double)ue * (double)T))  - one IEEE double product, (double)T exact
+ *              because T < 2^52 -, and it takes the episode at the SMALLEST age whose inclusive prefix sum p_0 + .. + p_a exceeds t;
+ *   weight     every real window row of the episode gets  w_b = powf((float)p_min / (float)p_b, beta[0])  - the usual (N P(b))^-beta over
+ *              its maximum over the ring - in (0, 1]; padding rows get 0.
+ * A ring with fewer than two episodes: as kr_sample_windows (slot head - count, weight-0 rows).  Window starts, the final window, the output
+ * layout and next_ends are kr_sample_windows'; the uniforms are the caller's u_ep / u_start or Philox with kr_sample_windows_draw's key,
+ * counters and tags.  Hence with equal priorities slot b takes age min(count - 2, floor((double)ue * (count - 1))) and every weight is 1.
+ * Two launches: the pick (`batch` waves; each walks its ring's one or two contiguous pieces of the table twice - sum and minimum, then
+ * locate - with 16-byte loads where aligned, per-element loads at the pieces' ends, nothing outside them read; touches no episode data)
+ * and the gather (batch * W waves, kr_sample_windows' rows with the episode supplied).  Between the two w_b travels in `weight`, one copy
+ * per row, and without `picked` the slot travels in the first reward of each row: the gather wave of a row reads both before it writes
+ * the row.
+ * KS_ERR_INVALID, nothing launched or written: what kr_sample_windows_mixed refuses; a NULL beta; for a ring that has batch slots, a NULL
+ * priority table or capacity > 2^20. */
+int kr_sample_windows_prioritized(int32_t batch, int32_t batch_agent, int32_t horizon, int32_t n_steps, const kr_ring *agent, const kr_ring *expert,
+                                  const uint32_t *agent_prio, const uint32_t *expert_prio, const float *beta, const float *u_ep,
+                                  const float *u_start, uint64_t seed, const int64_t *draw, float *state, float *action, float *next_state,
+                                  float *reward, float *not_done, float *weight, float *next_ends, int32_t *picked, void *stream);
+
+/* The priorities of the episodes a batch was read from, from the critic's errors on it: issued after kr_critic_grad on the same q, tq1
+ * [batch * W], reward [batch * W, n_steps], weight [batch * W] and on the sampler's picked [batch]; W = horizon - n_steps.
+ *   real row   r = b W + w is real iff weight[r] > 0;
+ *   e_r        |q[r] - (reward[r n_steps] + discount * tq1[r])|, kr_critic_grad's own target_Q, fp32 without contraction;
+ *   delta_b    the maximum of e_r over the real rows of batch episode b; NaN if one of them is NaN; -1 without a real row;
+ *   v_b        clamp(floor(powf(delta_b + eps, alpha) * 65536), 1, 2^32 - 1) in fp32, the conversion saturating; eps = eps_agent for
+ *              b < batch_agent, eps_expert otherwise (eps_expert > eps_agent is the demonstration bonus);
+ *   table      for every slot s that a segment picked:  ep_prio[s] = max{ v_b : b in the segment, picked[b] == s, delta_b finite and >= 0 }
+ *              - the same episode picked twice has two sets of rows; the maximum is taken inside one wave, no result depends on which wave
+ *              runs last -, and the ring's prio_max[0] = max(prio_max[0], that value) (an atomic maximum).  A slot none of whose batch
+ *              episodes has a finite delta >= 0 stays as it is: a diverged critic does not reach the table.
+ * delta_out (optional) float [batch] receives delta_b (tests, logging).  picked[b] < 0 is skipped; the call has no capacity to check the
+ * slots against - they are the sampler's.  Nothing else is written.
+ * KS_ERR_INVALID, nothing launched or written: batch <= 0, batch_agent outside [0, batch], horizon <= n_steps, n_steps <= 0; a NULL q, tq1,
+ * reward, weight or picked; alpha, eps_agent or eps_expert negative or NaN, discount NaN; for a segment that has batch slots, a NULL table
+ * or prio_max. */
+int kr_update_priorities(int32_t batch, int32_t batch_agent, int32_t horizon, int32_t n_steps, const float *q, const float *tq1,
+                         const float *reward, const float *weight, float discount, const int32_t *picked, float alpha, float eps_agent,
+                         float eps_expert, uint32_t *agent_prio, uint32_t *expert_prio, uint32_t *agent_prio_max, uint32_t *expert_prio_max,
+                         float *delta_out, void *stream);
+
 /* ---- learner glue (DDPGfD.train_batch, DDPGfD.py:219-367): the elementwise steps between the GEMMs, one launch each
  *
  *   kr_critic_grad   targets + dLoss/dQ of the critic loss L1 + 0.5 LN with masked row means (DDPGfD.py:256-330):

@@ -196,7 +196,7 @@ __device__ __forceinline__ long uniform_episode(float ue, long cnt, long head, i
 __device__ __forceinline__ void window_row(const Ring& g, long ep, float us, bool none, int B, int H, int n_steps, int r, int w, int lane,
                                            float* __restrict__ next_ends, float* __restrict__ state, float* __restrict__ action,
                                            float* __restrict__ next_state, float* __restrict__ reward, float* __restrict__ not_done,
-                                           float* weight) {
+                                           float* weight, float real_weight = 1.0f) {
     const int W = H - n_steps;
     const float *ep_state = g.ep_state, *ep_next = g.ep_next, *ep_action = g.ep_action, *ep_reward = g.ep_reward, *ep_not_done = g.ep_not_done;
     long ceiling = g.ep_len[ep] - n_steps;
@@ -222,7 +222,7 @@ __device__ __forceinline__ void window_row(const Ring& g, long ep, float us, boo
         reward[dst + lane] = ep_reward[src + lane];
         not_done[dst + lane] = ep_not_done[src + lane];
     }
-    if (lane == 0) weight[r] = (!none && w < ceiling) ? 1.0f : 0.0f;
+    if (lane == 0) weight[r] = (!none && w < ceiling) ? real_weight : 0.0f;
 }
 
 // one wave per window row (b, w); episodes b < B_agent are drawn from ring `ra`, the others from ring `re` (the expert
@@ -361,22 +361,25 @@ __global__ __launch_bounds__(WAVE) void k_pick_balanced(int B, int B_agent, int 
     }
 }
 
-// The gather: k_sample_windows' rows with the episode supplied - picked[b], or (row_major != 0) picked[r], which may be the weight
-// output itself: every wave reads its own element before it writes it and touches no other (hence no __restrict__ on the two).
+// The gather: k_sample_windows' rows with the episode supplied - picked[b], or (row_major != 0) picked[r * row_major], which may lie in
+// an output of the call itself - the weight column (row_major 1) or, for the prioritized sampler, the first reward of the row (row_major
+// n_steps): every wave reads its own element before it writes it and touches no other (hence no __restrict__ on these).  row_weight (NULL:
+// 1, the other samplers' path) holds, per window row, the weight a real row gets; it may be the weight column itself, read the same way.
 __global__ __launch_bounds__(WAVE) void k_gather_windows(int B, int B_agent, int H, int n_steps, Ring ra, Ring re, const int* picked,
                                                          int row_major, const float* __restrict__ u_start, unsigned long long seed,
                                                          const int64_t* __restrict__ draw, float* __restrict__ next_ends,
                                                          float* __restrict__ state, float* __restrict__ action, float* __restrict__ next_state,
-                                                         float* __restrict__ reward, float* __restrict__ not_done, float* weight) {
+                                                         float* reward, float* __restrict__ not_done, float* weight, const float* row_weight) {
     const int W = H - n_steps;
     const int r = blockIdx.x, lane = threadIdx.x;
     if (r >= B * W) return;
     const int b = r / W, w = r % W;
     const Ring& g = b < B_agent ? ra : re;
-    long ep = picked[row_major != 0 ? r : b];
+    long ep = picked[row_major != 0 ? (long)r * row_major : (long)b];
     ep = ep < 0 ? 0 : (ep < g.capacity ? ep : g.capacity - 1);      // (the pick launch wrote a slot of this ring)
+    const float real_weight = row_weight != nullptr ? row_weight[r] : 1.0f;
     const float us = sample_uniform(u_start, r, 0x5a4eu, seed, draw);
-    window_row(g, ep, us, g.count[0] < 2, B, H, n_steps, r, w, lane, next_ends, state, action, next_state, reward, not_done, weight);
+    window_row(g, ep, us, g.count[0] < 2, B, H, n_steps, r, w, lane, next_ends, state, action, next_state, reward, not_done, weight, real_weight);
 }
 
 // kr_commit_classes: the class tag of every kept env into kr_commit_episodes' slot
@@ -386,6 +389,311 @@ __global__ __launch_bounds__(WAVE) void k_commit_classes(int n, int capacity, co
     const int i = blockIdx.x * WAVE + threadIdx.x;
     if (i >= n || keep[i] == 0) return;
     ep_class[(head[0] + rank[i] - 1) % capacity] = env_class[i];
+}
+
+// ---- prioritized episode replay (kr_commit_priorities, kr_sample_windows_prioritized, kr_update_priorities).  One wave per workgroup, no
+// LDS, vector loads / stores and one vector atomic only, as everything on the learner's stream (see wave_sum below).  A priority is a
+// uint32 in units of 1 / 65536; a stored 0 reads as 1, so every eligible episode has a positive share and sums of at most 2^20 of them
+// stay below 2^52: exact as uint64 and as double.
+//
+// The table walk has scan_tags' shape with the ragged ends taken out of the loop.  A piece [s0, s1) of the table is a head of up to three
+// priorities in front of the first 16-byte boundary, whole 16-byte vectors, and a tail of up to three; head and tail are read element
+// by element, the same elements in every lane.  A trip is 64 lanes x one vector, a group PRIO_TRIPS trips (1536 priorities); the loads of
+// the next group are issued before the current one is reduced.  Six trips, not scan_tags' eight: two groups of vectors, their addresses and
+// the 64-bit sums fit the 96 registers a learner wave has beside the 400-300 rollout kernel, with eight they do not.  Nothing outside the
+// piece is read.  Indices are ints: a table has at most 2^20 slots.
+constexpr int PRIO_TRIPS = 6;
+typedef unsigned int v4u __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ uint32_t at_least_one(uint32_t p) { return p > 1u ? p : 1u; }
+
+struct PrioPiece { int s0, ha, hb, s1, qa, qb, mis; };      // head [s0, ha), vectors [qa, qb) = elements [ha, hb), tail [hb, s1)
+
+__device__ __forceinline__ PrioPiece prio_piece(const uint32_t* tab, int s0, int s1) {
+    PrioPiece p;
+    p.mis = (int)(((uintptr_t)tab >> 2) & 3);                       // tab + e is 16-byte aligned where (e + mis) % 4 == 0
+    p.s0 = s0; p.s1 = s1;
+    p.qa = (s0 + p.mis + 3) >> 2; p.qb = (s1 + p.mis) >> 2;
+    p.ha = min(s1, 4 * p.qa - p.mis);
+    p.hb = max(p.ha, 4 * p.qb - p.mis);
+    p.qb = max(p.qa, p.qb);
+    return p;
+}
+
+// element e if it lies in [lo, hi), else 0 (a priority inside reads as at least 1)
+__device__ __forceinline__ uint32_t prio_at(const uint32_t* __restrict__ tab, int e, int lo, int hi) {
+    return e >= lo && e < hi ? at_least_one(tab[e]) : 0u;
+}
+
+// vector q of a piece that has one (qa < qb), in two steps so that a group's loads can be issued back to back: the load itself is
+// unconditional - beyond the piece's last vector, of that one - and what it brought is put right afterwards, 0 beyond the last vector
+__device__ __forceinline__ v4u prio_raw(const uint32_t* __restrict__ tab, int q, const PrioPiece& p) {
+    const uint32_t e = (uint32_t)(4 * (q < p.qb ? q : p.qb - 1) - p.mis);      // (>= s0 >= 0; unsigned: a 32-bit offset to a uniform base)
+    return *(const v4u*)(tab + e);
+}
+
+__device__ __forceinline__ v4u prio_fix(v4u v, int q, const PrioPiece& p) {
+    const bool inside = q < p.qb;
+    v.x = inside ? at_least_one(v.x) : 0u; v.y = inside ? at_least_one(v.y) : 0u;
+    v.z = inside ? at_least_one(v.z) : 0u; v.w = inside ? at_least_one(v.w) : 0u;
+    return v;
+}
+
+__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long x) {
+#pragma unroll
+    for (int o = WAVE / 2; o > 0; o >>= 1) x += __shfl_xor(x, o);
+    return x;
+}
+
+__device__ __forceinline__ unsigned long long sum4(v4u v) {
+    return (unsigned long long)v.x + (unsigned long long)v.y + (unsigned long long)v.z + (unsigned long long)v.w;
+}
+
+__device__ __forceinline__ uint32_t min_inside(uint32_t m, uint32_t p) { return p != 0u && p < m ? p : m; }
+
+// the sum and the minimum of the piece's priorities: lane partials only (integers: exact in any order), the caller reduces over the wave
+__device__ __forceinline__ void prio_total(const uint32_t* __restrict__ tab, int s0, int s1, int lane, unsigned long long& sum, uint32_t& least) {
+    if (s1 <= s0) return;
+    const PrioPiece p = prio_piece(tab, s0, s1);
+    const uint32_t edge = lane < 3 ? prio_at(tab, p.s0 + lane, p.s0, p.ha) : (lane < 6 ? prio_at(tab, p.hb + lane - 3, p.hb, p.s1) : 0u);
+    sum += edge;
+    least = min_inside(least, edge);
+    if (p.qa >= p.qb) return;
+    constexpr int GROUP = PRIO_TRIPS * WAVE;
+    v4u cur[PRIO_TRIPS], nxt[PRIO_TRIPS];
+#pragma unroll
+    for (int u = 0; u < PRIO_TRIPS; u++) cur[u] = prio_raw(tab, p.qa + u * WAVE + lane, p);
+    for (int g0 = p.qa; g0 < p.qb; g0 += GROUP) {
+#pragma unroll
+        for (int u = 0; u < PRIO_TRIPS; u++) nxt[u] = prio_raw(tab, g0 + GROUP + u * WAVE + lane, p);
+#pragma unroll
+        for (int u = 0; u < PRIO_TRIPS; u++) {
+            const v4u v = prio_fix(cur[u], g0 + u * WAVE + lane, p);
+            sum += sum4(v);
+            least = min_inside(min_inside(min_inside(min_inside(least, v.x), v.y), v.z), v.w);
+        }
+#pragma unroll
+        for (int u = 0; u < PRIO_TRIPS; u++) cur[u] = nxt[u];
+    }
+}
+
+// the index, within the table, of the piece's first element - age order: the head, then trip by trip, lane by lane, the lane's four in turn,
+// then the tail - whose inclusive prefix sum over the piece exceeds `target` (< the piece's sum, so there is one; -1 otherwise), and its
+// priority.  One wave sum per group; the group that holds the target is then read once more and taken apart trip by trip, and its one trip
+// lane by lane.  The same in every lane.
+__device__ __forceinline__ int prio_locate(const uint32_t* __restrict__ tab, int s0, int s1, unsigned long long target, int lane, uint32_t& prio) {
+    if (s1 <= s0) return -1;
+    const PrioPiece p = prio_piece(tab, s0, s1);
+    unsigned long long seen = 0;
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+        const uint32_t x = prio_at(tab, p.s0 + i, p.s0, p.ha);
+        if (x != 0u && target < seen + x) { prio = x; return p.s0 + i; }
+        seen += x;
+    }
+    constexpr int GROUP = PRIO_TRIPS * WAVE;
+    int hit_group = -1;
+    if (p.qa < p.qb) {
+        v4u cur[PRIO_TRIPS], nxt[PRIO_TRIPS];
+#pragma unroll
+        for (int u = 0; u < PRIO_TRIPS; u++) cur[u] = prio_raw(tab, p.qa + u * WAVE + lane, p);
+        for (int g0 = p.qa; g0 < p.qb; g0 += GROUP) {
+#pragma unroll
+            for (int u = 0; u < PRIO_TRIPS; u++) nxt[u] = prio_raw(tab, g0 + GROUP + u * WAVE + lane, p);
+            unsigned long long mine = 0;
+#pragma unroll
+            for (int u = 0; u < PRIO_TRIPS; u++) mine += sum4(prio_fix(cur[u], g0 + u * WAVE + lane, p));
+            const unsigned long long group = wave_sum_u64(mine);
+            if (target < seen + group) { hit_group = g0; break; }             // (wave-uniform)
+            seen += group;
+#pragma unroll
+            for (int u = 0; u < PRIO_TRIPS; u++) cur[u] = nxt[u];
+        }
+    }
+    if (hit_group >= 0) {
+        v4u grp[PRIO_TRIPS];
+#pragma unroll
+        for (int u = 0; u < PRIO_TRIPS; u++) grp[u] = prio_raw(tab, hit_group + u * WAVE + lane, p);
+        v4u hit = {0u, 0u, 0u, 0u};
+        int trip = 0;
+        bool found = false;
+#pragma unroll
+        for (int u = 0; u < PRIO_TRIPS; u++) {
+            const v4u v = prio_fix(grp[u], hit_group + u * WAVE + lane, p);
+            const unsigned long long tot = wave_sum_u64(sum4(v));
+            if (!found && target < seen + tot) { hit = v; trip = hit_group + u * WAVE; found = true; }
+            if (!found) seen += tot;
+        }
+        const unsigned long long own = sum4(hit);
+        unsigned long long incl = own;
+#pragma unroll
+        for (int d = 1; d < WAVE; d <<= 1) {
+            const unsigned long long up = __shfl_up(incl, d);
+            if (lane >= d) incl += up;
+        }
+        unsigned long long rest = target - seen;                         // < the trip's sum
+        const bool owner = rest >= incl - own && rest < incl;             // exactly one lane
+        rest -= incl - own;
+        int k = 3;
+        if (owner) {
+            if (rest < hit.x) k = 0;
+            else if (rest < (unsigned long long)hit.x + hit.y) k = 1;
+            else if (rest < (unsigned long long)hit.x + hit.y + hit.z) k = 2;
+        }
+        const uint32_t x = k == 0 ? hit.x : (k == 1 ? hit.y : (k == 2 ? hit.z : hit.w));
+        const int at = 4 * (trip + lane) - p.mis + k;
+        const int src = __ffsll((long long)__ballot(owner)) - 1;
+        prio = (uint32_t)__shfl((int)x, src);
+        return __shfl(at, src);
+    }
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+        const uint32_t x = prio_at(tab, p.hb + i, p.hb, p.s1);
+        if (x != 0u && target < seen + x) { prio = x; return p.hb + i; }
+        seen += x;
+    }
+    return -1;
+}
+
+// The pick: one wave per batch episode b.  Over the eligible episodes of its ring - the count - 1 oldest, one or two contiguous pieces of the
+// priority table in age order - T is the sum of the priorities and the target t = min(T - 1, (uint64)((double)ue * (double)T)); the episode
+// taken is the one at the smallest age whose inclusive prefix sum exceeds t.  Its importance weight powf(p_min / p_b, beta) goes to EVERY
+// row of the episode in `weight`, where the gather finds it; the slot to picked[b], or (picked NULL) into the first reward of every row of
+// the episode, as an int.  Never touches episode data.
+__global__ __launch_bounds__(WAVE) void k_pick_prioritized(int B, int B_agent, int W, int n_steps, Ring ra, Ring re, const uint32_t* __restrict__ agent_prio,
+                                                           const uint32_t* __restrict__ expert_prio, const float* __restrict__ beta,
+                                                           const float* __restrict__ u_ep, unsigned long long seed,
+                                                           const int64_t* __restrict__ draw, int* __restrict__ picked, float* __restrict__ reward,
+                                                           float* __restrict__ weight) {
+#pragma clang fp contract(off)
+    const int b = blockIdx.x, lane = threadIdx.x;
+    if (b >= B) return;
+    const bool is_agent = b < B_agent;
+    const Ring& g = is_agent ? ra : re;
+    const uint32_t* tab = is_agent ? agent_prio : expert_prio;
+    const long cnt = g.count[0], head = g.head[0];
+    const int capacity = g.capacity;
+    const float ue = sample_uniform(u_ep, b, 0x5a4du, seed, draw);
+    long first = (head - cnt) % capacity;
+    first = first < 0 ? first + capacity : first;
+    long eligible = cnt - 1 > 0 ? cnt - 1 : 0;
+    eligible = eligible < capacity ? eligible : capacity - 1;                   // (count <= capacity)
+    const long end_a = first + eligible < capacity ? first + eligible : capacity;   // piece A: slots [first, end_a), the older ones
+    const long end_b = first + eligible - end_a;                                // piece B: slots [0, end_b) behind the wrap
+    long ep = -1;
+    float wb = 1.0f;
+    if (eligible > 0) {
+        unsigned long long sa = 0, sb = 0;
+        uint32_t least = 0xffffffffu;
+#pragma nounroll
+        for (int piece = 0; piece < 2; piece++) {                                   // (one copy of the walk's code and of its registers)
+            unsigned long long sum = 0;
+            prio_total(tab, piece ? 0 : (int)first, (int)(piece ? end_b : end_a), lane, sum, least);
+            if (piece) sb = sum; else sa = sum;
+        }
+        const unsigned long long t_a = wave_sum_u64(sa), total = t_a + wave_sum_u64(sb);
+#pragma unroll
+        for (int o = WAVE / 2; o > 0; o >>= 1) {
+            const uint32_t other = (uint32_t)__shfl_xor((int)least, o);
+            least = other < least ? other : least;
+        }
+        unsigned long long t = (unsigned long long)__dmul_rn((double)ue, (double)total);
+        t = t < total - 1 ? t : total - 1;
+        uint32_t p = least;
+        const bool older = t < t_a;
+        ep = prio_locate(tab, older ? (int)first : 0, (int)(older ? end_a : end_b), older ? t : t - t_a, lane, p);
+        wb = powf((float)least / (float)p, beta[0]);
+    }
+    if (ep < 0) ep = uniform_episode(ue, cnt, head, capacity);
+    for (int w = lane; w < W; w += WAVE) {
+        weight[(long)b * W + w] = wb;
+        if (picked == nullptr) ((int*)reward)[((long)b * W + w) * n_steps] = (int)ep;
+    }
+    if (picked != nullptr && lane == 0) picked[b] = (int)ep;
+}
+
+// kr_commit_priorities: a new episode enters its slot at the largest priority any update has written
+__global__ __launch_bounds__(WAVE) void k_commit_priorities(int n, int capacity, const uint8_t* __restrict__ keep, const int64_t* __restrict__ rank,
+                                                            const int64_t* __restrict__ head, const uint32_t* __restrict__ prio_max,
+                                                            uint32_t* __restrict__ ep_prio) {
+    const int i = blockIdx.x * WAVE + threadIdx.x;
+    if (i >= n || keep[i] == 0) return;
+    ep_prio[(head[0] + rank[i] - 1) % capacity] = at_least_one(prio_max[0]);
+}
+
+// delta_b of kr_update_priorities: the largest 1-step TD error over the real rows of batch episode b (k_critic_grad's t1 and e1), -1 without
+// a real row, NaN where a real row's error is NaN.  The same in every lane.
+__device__ __forceinline__ float episode_delta(int b, int W, int n, const float* __restrict__ q, const float* __restrict__ tq1,
+                                               const float* __restrict__ reward, const float* __restrict__ weight, float discount, int lane) {
+#pragma clang fp contract(off)
+    float m = -1.0f;
+    bool bad = false;
+    for (int w = lane; w < W; w += WAVE) {
+        const long r = (long)b * W + w;
+        if (weight[r] > 0.0f) {
+            const float t1 = reward[r * n] + discount * tq1[r];
+            const float e = fabsf(q[r] - t1);
+            if (e != e) bad = true;
+            else m = e > m ? e : m;
+        }
+    }
+#pragma unroll
+    for (int o = WAVE / 2; o > 0; o >>= 1) {
+        const float other = __shfl_xor(m, o);
+        m = other > m ? other : m;
+    }
+    return __ballot(bad) != 0ull ? __builtin_nanf("") : m;
+}
+
+// clamp(floor(powf(delta + eps, alpha) * 65536), 1, 2^32 - 1) in fp32, the conversion saturating
+__device__ __forceinline__ uint32_t quantise_priority(float delta, float eps, float alpha) {
+#pragma clang fp contract(off)
+    const float x = floorf(powf(delta + eps, alpha) * 65536.0f);
+    return !(x >= 1.0f) ? 1u : (x >= 4294967296.0f ? 0xffffffffu : (uint32_t)x);
+}
+
+// One wave per batch episode b: its delta to delta_out; then, unless an earlier batch episode of the segment was read from the same slot
+// (that wave writes for both), the largest quantised priority over b and the later batch episodes of the segment with b's slot - their
+// deltas recomputed here, duplicates are few - is stored to the slot and offered to the ring's prio_max.  Every slot has one writer and one
+// value: nothing depends on the order the waves run in.
+__global__ __launch_bounds__(WAVE) void k_update_priorities(int B, int B_agent, int W, int n, const float* __restrict__ q, const float* __restrict__ tq1,
+                                                            const float* __restrict__ reward, const float* __restrict__ weight, float discount,
+                                                            const int* __restrict__ picked, float alpha, float eps_agent, float eps_expert,
+                                                            uint32_t* __restrict__ agent_prio, uint32_t* __restrict__ expert_prio,
+                                                            uint32_t* agent_max, uint32_t* expert_max, float* __restrict__ delta_out) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    if (b >= B) return;
+    const bool is_agent = b < B_agent;
+    const int b0 = is_agent ? 0 : B_agent, b1 = is_agent ? B_agent : B;
+    uint32_t* tab = is_agent ? agent_prio : expert_prio;
+    uint32_t* top = is_agent ? agent_max : expert_max;
+    const float eps = is_agent ? eps_agent : eps_expert;
+    const float d = episode_delta(b, W, n, q, tq1, reward, weight, discount, lane);
+    if (delta_out != nullptr && lane == 0) delta_out[b] = d;
+    const int s = picked[b];
+    if (s < 0) return;
+    for (int j0 = b0; j0 < b; j0 += WAVE) {
+        const int j = j0 + lane;
+        if (__ballot(j < b && picked[j] == s) != 0ull) return;
+    }
+    uint32_t v = (d >= 0.0f && d < __builtin_inff()) ? quantise_priority(d, eps, alpha) : 0u;       // 0: nothing to write
+    for (int j0 = b + 1; j0 < b1; j0 += WAVE) {
+        const int j = j0 + lane;
+        unsigned long long same = __ballot(j < b1 && picked[j] == s);
+        while (same != 0ull) {
+            const int k = __ffsll((long long)same) - 1;
+            same &= same - 1ull;
+            const float dj = episode_delta(j0 + k, W, n, q, tq1, reward, weight, discount, lane);
+            if (dj >= 0.0f && dj < __builtin_inff()) {
+                const uint32_t vj = quantise_priority(dj, eps, alpha);
+                v = vj > v ? vj : v;
+            }
+        }
+    }
+    if (v != 0u && lane == 0) {
+        tab[s] = v;
+        atomicMax(top, v);
+    }
 }
 
 // ---- learner glue: plain grid-stride elementwise kernels, no fma contraction where the torch expression has none
@@ -648,7 +956,52 @@ int kr_sample_windows_balanced(int32_t batch, int32_t batch_agent, int32_t horiz
     if (launched() != KS_OK) return KS_ERR_HIP;
     hipLaunchKernelGGL(k_gather_windows, dim3(batch * W), dim3(WAVE), 0, (hipStream_t)stream, batch, batch_agent, horizon, n_steps, ga, ge,
                        (const int*)slots, row_major, u_start, (unsigned long long)seed, draw, next_ends, state, action, next_state, reward, not_done,
-                       weight);
+                       weight, (const float*)nullptr);
+    return launched();
+}
+
+int kr_commit_priorities(int32_t n, int32_t capacity, const uint8_t* keep, const int64_t* rank, const int64_t* head, const uint32_t* prio_max,
+                         uint32_t* ep_prio, void* stream) {
+    if (n <= 0 || capacity <= 0 || !keep || !rank || !head || !prio_max || !ep_prio) return KS_ERR_INVALID;
+    hipLaunchKernelGGL(k_commit_priorities, dim3((n + WAVE - 1) / WAVE), dim3(WAVE), 0, (hipStream_t)stream, n, capacity, keep, rank, head, prio_max,
+                       ep_prio);
+    return launched();
+}
+
+int kr_sample_windows_prioritized(int32_t batch, int32_t batch_agent, int32_t horizon, int32_t n_steps, const kr_ring* agent, const kr_ring* expert,
+                                  const uint32_t* agent_prio, const uint32_t* expert_prio, const float* beta, const float* u_ep, const float* u_start,
+                                  uint64_t seed, const int64_t* draw, float* state, float* action, float* next_state, float* reward, float* not_done,
+                                  float* weight, float* next_ends, int32_t* picked, void* stream) {
+    if (batch <= 0 || batch_agent < 0 || batch_agent > batch || horizon <= n_steps || n_steps <= 0 || n_steps > WAVE || !ring_ok(agent) || !ring_ok(expert) ||
+        ((u_ep == nullptr) != (u_start == nullptr)) || (!u_ep && !draw) || !state || !action || !next_state || !reward || !not_done || !weight ||
+        !beta || (batch_agent > 0 && (!agent_prio || agent->capacity > (1 << 20))) || (batch_agent < batch && (!expert_prio || expert->capacity > (1 << 20))))
+        return KS_ERR_INVALID;
+    const Ring ga{agent->count, agent->head, agent->capacity, agent->ep_len, agent->ep_state, agent->ep_next, agent->ep_action, agent->ep_reward,
+                  agent->ep_not_done};
+    const Ring ge{expert->count, expert->head, expert->capacity, expert->ep_len, expert->ep_state, expert->ep_next, expert->ep_action,
+                  expert->ep_reward, expert->ep_not_done};
+    // the pick hands every row its episode's importance weight in the weight output and, without `picked`, the slot in the row's first reward:
+    // the gather wave of a row reads its own two elements and then writes the row there - no scratch buffer, nothing allocated on a captured stream
+    const int W = horizon - n_steps, row_major = picked == nullptr ? n_steps : 0;
+    const int* slots = picked != nullptr ? picked : (const int*)reward;
+    hipLaunchKernelGGL(k_pick_prioritized, dim3(batch), dim3(WAVE), 0, (hipStream_t)stream, batch, batch_agent, W, n_steps, ga, ge, agent_prio, expert_prio,
+                       beta, u_ep, (unsigned long long)seed, draw, picked, reward, weight);
+    if (launched() != KS_OK) return KS_ERR_HIP;
+    hipLaunchKernelGGL(k_gather_windows, dim3(batch * W), dim3(WAVE), 0, (hipStream_t)stream, batch, batch_agent, horizon, n_steps, ga, ge, slots,
+                       row_major, u_start, (unsigned long long)seed, draw, next_ends, state, action, next_state, reward, not_done, weight,
+                       (const float*)weight);
+    return launched();
+}
+
+int kr_update_priorities(int32_t batch, int32_t batch_agent, int32_t horizon, int32_t n_steps, const float* q, const float* tq1, const float* reward,
+                         const float* weight, float discount, const int32_t* picked, float alpha, float eps_agent, float eps_expert, uint32_t* agent_prio,
+                         uint32_t* expert_prio, uint32_t* agent_prio_max, uint32_t* expert_prio_max, float* delta_out, void* stream) {
+    if (batch <= 0 || batch_agent < 0 || batch_agent > batch || horizon <= n_steps || n_steps <= 0 || !q || !tq1 || !reward || !weight || !picked ||
+        !(alpha >= 0.0f) || !(eps_agent >= 0.0f) || !(eps_expert >= 0.0f) || !(discount == discount) ||
+        (batch_agent > 0 && (!agent_prio || !agent_prio_max)) || (batch_agent < batch && (!expert_prio || !expert_prio_max)))
+        return KS_ERR_INVALID;
+    hipLaunchKernelGGL(k_update_priorities, dim3(batch), dim3(WAVE), 0, (hipStream_t)stream, batch, batch_agent, horizon - n_steps, n_steps, q, tq1, reward,
+                       weight, discount, picked, alpha, eps_agent, eps_expert, agent_prio, expert_prio, agent_prio_max, expert_prio_max, delta_out);
     return launched();
 }
 

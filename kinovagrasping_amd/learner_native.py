@@ -231,8 +231,10 @@ class NativeDDPGfDUpdate:
 
     # -- the three phases ---------------------------------------------------------------------------------------------
     @torch.no_grad()
-    def phase_critic(self, state, action, next_state, reward, weight=None, next_ends=None):
-        """targets, critic forward, loss gradient, critic weight gradients -> self.critic.grad"""
+    def phase_critic(self, state, action, next_state, reward, weight=None, next_ends=None, priorities=None):
+        """targets, critic forward, loss gradient, critic weight gradients -> self.critic.grad.  priorities (prioritized replay): a callable
+        (q, tq1, reward, weight) issued right after kr_critic_grad on that kernel's own operands - DeviceEpisodeReplay.update_priorities with
+        the batch's `picked` bound; None: the launch sequence has no such step."""
         pol, P = self.p, _sim._ptr
         R = reward.shape[0]
         if weight is None:
@@ -260,6 +262,8 @@ class NativeDDPGfDUpdate:
             self._join(0)
             self._chk(self.lib.kr_critic_grad(R, pol.n, P(q), P(tq), P(tq[R:]), P(reward), P(weight), P(self.wsum), pol.discount, P(dq), P(self.losses),
                                               self._st()), "kr_critic_grad")
+            if priorities is not None:
+                priorities(q, tq, reward, weight)
             with self._branch(0):                              # the last layer's weight gradient needs dq only: beside the data-gradient pass
                 _mlp.weight_grad(dq, h2, None, c.gW[2], c.gb[2])
             dz2, dz1, _ = _mlp.mlp3_backward(cl, dq, h1, h2, lean=self.lean_kernels)
@@ -287,6 +291,8 @@ class NativeDDPGfDUpdate:
             reward = reward.contiguous()
             self._chk(self.lib.kr_critic_grad(R, pol.n, P(q), P(tq), P(tq[R:]), P(reward), P(weight), P(self.wsum), pol.discount, P(dq), P(self.losses),
                                               self._st()), "kr_critic_grad")
+            if priorities is not None:
+                priorities(q, tq, reward, weight)
             dz2, dz1, _ = _mlp.mlp3_backward(cl, dq, h1, h2, lean=self.lean_kernels)
             _mlp.weight_grad(dq, h2, None, c.gW[2], c.gb[2])
             _mlp.weight_grad(dz2, h1, None, c.gW[1], c.gb[1])
@@ -304,6 +310,8 @@ class NativeDDPGfDUpdate:
         reward = reward.contiguous()
         self._chk(self.lib.kr_critic_grad(R, pol.n, P(q), P(tq), P(tq[R:]), P(reward), P(weight), P(self.wsum), pol.discount, P(dq), P(self.losses),
                                           self._st()), "kr_critic_grad")
+        if priorities is not None:
+            priorities(q, tq, reward, weight)
         self._weight_grads(c, x0, h1, h2, dq)
         return self.losses[0], self.losses[1], self.losses[2]
 

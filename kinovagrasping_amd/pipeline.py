@@ -73,7 +73,8 @@ def _concurrent_stream(main, dev, tries=8):
 
 class GraphedTrainer:
     def __init__(self, sim, policy, replay, engine, batch_episodes=64, overlap=True, learn_after=31, expert_replay=None, expert_prob=0.3,
-                 updates_per_step=1, lean_learner=False, balanced=False):
+                 updates_per_step=1, lean_learner=False, balanced=False, prioritized=False, per_alpha=0.3, per_beta=1.0, per_eps=1e-3,
+                 per_eps_expert=1.0):
         """updates_per_step U / batch_episodes: the update-to-data knobs.  The reference makes 100 updates per 30-step episode of ONE
         env (main_DDPGfD.py:474-486: ~3 per stored transition); BASELINE config 3 - bench.py's workload - is ONE update on 64 episodes
         per env-step of 4096 envs.  U > 1 replays the captured update U times per env-step (the step becomes learner-bound beyond
@@ -90,11 +91,29 @@ class GraphedTrainer:
         balanced: every batch is drawn with replay.sample_balanced - the episodes of each ring's share of the batch spread evenly over the
         ring's classes, whatever it holds - instead of uniformly over its episodes.  The replay (and the expert replay, if there is one)
         must have classes set (DeviceEpisodeReplay.set_env_classes), else ValueError.  self.picked: the ring slot of every batch episode
-        of the last update (readable after flush())."""
+        of the last update (readable after flush()).
+        prioritized: every batch is drawn with replay.sample_prioritized - an episode in proportion to (its last TD error + eps)^per_alpha,
+        per_eps for the agent's episodes and per_eps_expert, the demonstration bonus, for the expert's; importance weights
+        (p_min / p)^per_beta in the batch's weight column - and every update writes the priorities of the episodes it saw
+        (kr_update_priorities after kr_critic_grad).  Calls enable_priorities() on the ring(s); self.picked as with balanced;
+        set_per_beta anneals beta, also under captured graphs.  Priorities are per rank: nothing about them is exchanged.  Not together
+        with balanced (ValueError)."""
+        if prioritized and balanced:
+            raise ValueError("prioritized=True and balanced=True: one sampler draws a batch; combining the two is not implemented")
         assert engine.gen is None, "graph capture uses the default CUDA generator"
         self.sim, self.policy, self.replay, self.eng = sim, policy, replay, engine
         self.expert_replay, self.expert_prob = expert_replay, float(expert_prob)
         self.balanced, self.picked = bool(balanced), None
+        self.prioritized = bool(prioritized)
+        self.per_alpha, self.per_eps, self.per_eps_expert = float(per_alpha), float(per_eps), float(per_eps_expert)
+        if self.prioritized:
+            if not replay.native:
+                raise ValueError("prioritized=True needs a device ring (DeviceEpisodeReplay on the GPU)")
+            replay.enable_priorities()
+            if expert_replay is not None:
+                expert_replay.enable_priorities()
+            self.per_beta = torch.full((1,), float(per_beta), device=replay.device)
+            self.per_delta = torch.zeros(batch_episodes, device=replay.device)      # the last update's delta per batch episode (logging, tests)
         if self.balanced and (getattr(replay, "ep_class", None) is None or (expert_replay is not None and getattr(expert_replay, "ep_class", None) is None)):
             raise ValueError("balanced=True: the replay (and the expert replay) must have classes set (DeviceEpisodeReplay.set_env_classes)")
         if self.balanced and not replay.native:
@@ -157,7 +176,11 @@ class GraphedTrainer:
     # -- learner phases on the static batch -------------------------------------------------------------
     def _sample(self):
         # (uniforms drawn in the sampling kernel, keyed by the update count: no generator-state launches in the graph)
-        if self.balanced:
+        if self.prioritized:
+            out = self.replay.sample_prioritized(self._per_expert(), self.batch_episodes, self.expert_prob, self.per_beta, draw=self.native.it,
+                                                 seed=self.sample_seed)
+            self.batch, self.picked = out[:-1], out[-1]
+        elif self.balanced:
             mix = self.expert_replay is not None and self.expert_prob > 0
             out = self.replay.sample_balanced(self.expert_replay if mix else None, self.batch_episodes, self.expert_prob, draw=self.native.it,
                                               seed=self.sample_seed)
@@ -167,13 +190,32 @@ class GraphedTrainer:
         else:
             self.batch = self.replay.sample_batch_nstep(self.batch_episodes, draw=self.native.it if self.replay.native else None, seed=self.sample_seed)
 
+    def _per_expert(self):
+        return self.expert_replay if (self.expert_replay is not None and self.expert_prob > 0) else None
+
+    def set_per_beta(self, beta: float):
+        """the importance weights' exponent from the next update on (a fill of the device scalar the sampler reads: fine between graph replays)"""
+        if not self.prioritized:
+            raise ValueError("set_per_beta: the trainer was built without prioritized=True")
+        self.per_beta.fill_(float(beta))
+
+    def _update_priorities(self, q, tq1, reward, weight):
+        self.replay.update_priorities(self._per_expert(), q, tq1, reward, weight, self.picked, prob=self.expert_prob, discount=self.policy.discount,
+                                      alpha=self.per_alpha, eps=self.per_eps, eps_expert=self.per_eps_expert, delta_out=self.per_delta)
+
+    def _priority_state(self):
+        """both rings' priority tables and maxima (capture()'s warm-up updates are undone on them as on the learner's state)"""
+        rings = [r for r in (self.replay, self.expert_replay) if r is not None and getattr(r, "ep_prio", None) is not None] if self.prioritized else []
+        return [(t, t.clone()) for r in rings for t in (r.ep_prio, r.prio_max)]
+
     def _head(self):
         self.native.phase_head()
         self._sample()
 
     def _phase1(self):
         st, ac, ns, rw, nd, w = self.batch[:6]
-        self.loss_c = self.native.phase_critic(st, ac, ns, rw, w, next_ends=self.batch[6] if len(self.batch) > 6 else None)
+        self.loss_c = self.native.phase_critic(st, ac, ns, rw, w, next_ends=self.batch[6] if len(self.batch) > 6 else None,
+                                               priorities=self._update_priorities if self.prioritized else None)
 
     def _phase2(self):
         self.native.phase_actor(self.batch[0], self.batch[5])     # (its actor Adam step runs in the next update's head: native.pipelined)
@@ -205,6 +247,7 @@ class GraphedTrainer:
         saved = {k: v.clone() for k, v in pol._flat_params.items()}
         saved_opt = [(net, net.grad.clone(), net.exp_avg.clone(), net.exp_avg_sq.clone()) for net in (nat.actor, nat.critic)]
         saved_it, saved_head, saved_total = nat.it.clone(), nat.it_head.clone(), pol.total_it
+        saved_prio = self._priority_state()
         s = torch.cuda.Stream(self.dev)
         s.wait_stream(self.main)
         with torch.cuda.stream(s):
@@ -222,6 +265,8 @@ class GraphedTrainer:
             net.grad.copy_(g); net.exp_avg.copy_(m); net.exp_avg_sq.copy_(v)
         nat.it.copy_(saved_it); nat.it_head.copy_(saved_head)
         pol.total_it = saved_total
+        for t, v in saved_prio:
+            t.copy_(v)
         if tune:
             torch.cuda.tunable.tuning_enable(False)
         # thread_local: other threads (the RCCL watchdog of torch.distributed) keep issuing HIP calls during a capture
@@ -407,8 +452,11 @@ class AsyncTrainer(GraphedTrainer):
     for fixed weights).  The reference's own loop acts with a policy that is a whole episode old (main_DDPGfD.py:466-486)."""
 
     def __init__(self, sim, policy, replay, engine, batch_episodes=64, expert_replay=None, expert_prob=0.3, updates_per_step=1,
-                 launch_synchronous=False, max_launch_steps=60, balanced=False):
-        """balanced: as GraphedTrainer's (class-balanced batches: what lets a ring that a time-budgeted or free-running rollout fills at each
+                 launch_synchronous=False, max_launch_steps=60, balanced=False, prioritized=False, per_alpha=0.3, per_beta=1.0, per_eps=1e-3,
+                 per_eps_expert=1.0):
+        """prioritized, per_*: as GraphedTrainer's (prioritized replay; commit_published gives the episodes it collects the ring's prio_max);
+        not with launch_synchronous, whose staging ring carries no priorities.
+        balanced: as GraphedTrainer's (class-balanced batches: what lets a ring that a time-budgeted or free-running rollout fills at each
         object's own pace train every object alike); not with launch_synchronous, whose staging ring carries no classes.
         launch_synchronous (opt-in): what one stream hands the other changes only at launch boundaries, so that the same inputs give the
         same results in every run (the default form acts with whatever was published last and fills the ring in arrival order).  The
@@ -419,8 +467,11 @@ class AsyncTrainer(GraphedTrainer):
         env whose two open-episode buffers both wait for the learner drops, and when depends on timing) and no launch is time-budgeted
         (run(budget_ms=...)).  max_launch_steps sizes the staging ring: one finished episode per 10 env-steps of the longest launch
         and env, plus two; what does not fit is kept waiting in the env's buffers, never overwritten."""
+        if prioritized and launch_synchronous:
+            raise ValueError("AsyncTrainer: launch_synchronous stages episodes in a ring without priorities - not with prioritized=True")
         super().__init__(sim, policy, replay, engine, batch_episodes=batch_episodes, overlap=True, expert_replay=expert_replay, expert_prob=expert_prob,
-                         updates_per_step=updates_per_step, lean_learner="auto", balanced=balanced)
+                         updates_per_step=updates_per_step, lean_learner="auto", balanced=balanced, prioritized=prioritized, per_alpha=per_alpha,
+                         per_beta=per_beta, per_eps=per_eps, per_eps_expert=per_eps_expert)
         self.launch_synchronous = bool(launch_synchronous)
         if self.launch_synchronous and getattr(replay, "ep_class", None) is not None:
             raise ValueError("AsyncTrainer: launch_synchronous stages episodes in a ring without classes - not with a replay that has classes set")
@@ -579,6 +630,7 @@ class AsyncTrainer(GraphedTrainer):
         saved = {k: v.clone() for k, v in pol._flat_params.items()}
         saved_opt = [(net, net.grad.clone(), net.exp_avg.clone(), net.exp_avg_sq.clone()) for net in (nat.actor, nat.critic)]
         saved_it, saved_head, saved_total = nat.it.clone(), nat.it_head.clone(), pol.total_it
+        saved_prio = self._priority_state()
         s = torch.cuda.Stream(self.dev)
         s.wait_stream(self.main)
         with torch.cuda.stream(s):
@@ -593,6 +645,8 @@ class AsyncTrainer(GraphedTrainer):
             net.grad.copy_(g); net.exp_avg.copy_(m); net.exp_avg_sq.copy_(v)
         nat.it.copy_(saved_it); nat.it_head.copy_(saved_head)
         pol.total_it = saved_total
+        for t, v in saved_prio:
+            t.copy_(v)
         mode = dict(capture_error_mode="thread_local")
         self.g_commit = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.g_commit, **mode):

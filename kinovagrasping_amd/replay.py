@@ -116,6 +116,14 @@ class HostEpisodeReplay:
 
 
 CLASS_SIDECAR = "episode_classes.json"      # beside the reference bundle's files: DeviceEpisodeReplay.save / load
+PRIO_ONE = 65536                            # priority 1.0 in ep_prio's unit of 1 / 65536 (include/kinova_rollout.h)
+PRIO_MAX_CAPACITY = 1 << 20                 # the largest ring kr_sample_windows_prioritized takes: sums of priorities stay exact as double
+
+
+def _i32_bits(value: int) -> int:
+    """the int32 with the bit pattern of the uint32 `value` (torch's uint32 has few kernels: tables are written through an int32 view)"""
+    value = int(value) & 0xFFFFFFFF
+    return value - (1 << 32) if value >= (1 << 31) else value
 
 
 class DeviceEpisodeReplay:
@@ -144,6 +152,7 @@ class DeviceEpisodeReplay:
         self._row = torch.arange(horizon - n_steps, device=self.device).unsqueeze(0)
         self._win = torch.arange(n_steps, device=self.device)
         self.env_class = self.ep_class = self.class_names = None          # per-episode class column: set_env_classes
+        self.ep_prio = self.prio_max = None                                # per-episode priority column: enable_priorities
         # on a GPU the bookkeeping runs as the kr_* kernels of libkinova_sim.so (include/kinova_rollout.h), one launch
         # per method instead of a dozen torch ops; the torch code below is the same arithmetic (and their checker)
         self.native = self.device.type == "cuda"
@@ -205,6 +214,10 @@ class DeviceEpisodeReplay:
         self.ep_len.index_copy_(0, slots, self.cur_len)
         if self.ep_class is not None:
             self.ep_class.index_copy_(0, slots, self.env_class)
+        if self.ep_prio is not None:                       # (kr_commit_priorities; an env that is not kept rewrites the trash row with itself)
+            table, top = self.ep_prio.view(torch.int32), self.prio_max.view(torch.int32)
+            enter = torch.where(top == 0, torch.ones_like(top), top).expand(self.n_envs)
+            table.index_copy_(0, slots, torch.where(keep, enter, table[slots]))
         k = keep.sum()
         self._head.copy_((self._head + k) % self.capacity)
         self._count.copy_((self._count + k).clamp(max=self.capacity))
@@ -240,7 +253,8 @@ class DeviceEpisodeReplay:
     def load(self, dirpath, class_id=None):
         """append the episodes of a reference replay bundle to the ring (episodes longer than the horizon are cut).  On a ring with classes
         every loaded episode is tagged `class_id` when one is given; else by the bundle's sidecar (save), its class NAMES mapped onto this
-        ring's - a name this ring does not know, like a bundle without a sidecar, gives -1: the episode belongs to no class."""
+        ring's - a name this ring does not know, like a bundle without a sidecar, gives -1: the episode belongs to no class.  On a ring with
+        priorities (enable_priorities) every loaded episode enters at the ring's current prio_max, as a committed one does."""
         eps, info = load_reference_bundle(dirpath)
         tags = None
         if self.ep_class is not None:
@@ -263,6 +277,8 @@ class DeviceEpisodeReplay:
             self.ep_len[s] = L
             if tags is not None:
                 self.ep_class[s] = tags[i]
+            if self.ep_prio is not None:
+                self.ep_prio.view(torch.int32)[s] = _i32_bits(max(self.priority_max(), 1))
             self._head.copy_((self._head + 1) % self.capacity)
             self._count.copy_((self._count + 1).clamp(max=self.capacity))
         return info
@@ -287,6 +303,35 @@ class DeviceEpisodeReplay:
         self.env_class = env_class.to(device=self.device, dtype=torch.int32).contiguous()
         self.class_names = names
         self.ep_class = torch.full((self.capacity + 1,), -1, dtype=torch.int32, device=self.device)
+
+    def enable_priorities(self):
+        """Give the ring a per-episode priority column for prioritized replay (sample_prioritized / update_priorities): ep_prio uint32
+        [capacity + 1] in units of 1 / PRIO_ONE - the episodes the ring already holds get PRIO_ONE, priority 1.0 - and prio_max uint32 [1],
+        the largest priority an update has written, PRIO_ONE at first.  From here on every commit - commit_native, both buffers of
+        commit_published, the torch path of end_episodes - gives the slots it fills the current prio_max (kr_commit_priorities beside
+        kr_commit_classes), and load does the same: a new episode is sampled soon.  Priorities are transient: save writes the reference
+        bundle (and the class sidecar) and nothing about them, a loaded ring starts over.  Without this call nothing about the ring changes."""
+        if self.ep_prio is not None:
+            return
+        if self.capacity > PRIO_MAX_CAPACITY:
+            raise ValueError(f"enable_priorities: a ring of at most {PRIO_MAX_CAPACITY} episodes (the sum of the priorities must stay exact as a double)")
+        self.ep_prio = torch.full((self.capacity + 1,), PRIO_ONE, dtype=torch.uint32, device=self.device)
+        self.prio_max = torch.full((1,), PRIO_ONE, dtype=torch.uint32, device=self.device)
+
+    def priorities(self):
+        """ep_prio as int64 [capacity + 1] (a copy; torch's uint32 has few kernels)"""
+        return self.ep_prio.view(torch.int32).long() & 0xFFFFFFFF
+
+    def priority_max(self) -> int:
+        """prio_max (host read: synchronises)"""
+        return int(self.prio_max.view(torch.int32).item()) & 0xFFFFFFFF
+
+    def _commit_priorities(self, keep, st):
+        """kr_commit_priorities behind a kr_rank_episodes on the same keep (a ring without priorities: nothing)"""
+        if self.ep_prio is not None:
+            P = self._ptr
+            self._check(self._lib.kr_commit_priorities(self.n_envs, self.capacity, P(keep), P(self._rank), P(self._head), P(self.prio_max),
+                                                       P(self.ep_prio), st), "kr_commit_priorities")
 
     def _commit_classes(self, keep, st):
         """kr_commit_classes behind a kr_rank_episodes on the same keep (a ring without classes: nothing)"""
@@ -324,6 +369,7 @@ class DeviceEpisodeReplay:
                                              P(self.ep_state), P(self.ep_next), P(self.ep_action), P(self.ep_reward), P(self.ep_not_done),
                                              P(self.ep_len), st), "kr_commit_episodes")
             self._commit_classes(keep, st)
+            self._commit_priorities(keep, st)
             self._check(L.kr_advance_ring(self.n_envs, self.capacity, P(self._total), P(self._head), P(self._count), P(keep), P(self.pub_len[b]), st),
                         "kr_advance_ring")
 
@@ -336,6 +382,7 @@ class DeviceEpisodeReplay:
                                          P(self.ep_state), P(self.ep_next), P(self.ep_action), P(self.ep_reward), P(self.ep_not_done),
                                          P(self.ep_len), st), "kr_commit_episodes")
         self._commit_classes(keep, st)
+        self._commit_priorities(keep, st)
         self._check(L.kr_advance_ring(self.n_envs, self.capacity, P(self._total), P(self._head), P(self._count), P(ended), P(self.cur_len), st),
                     "kr_advance_ring")
         return self._total[0]
@@ -497,3 +544,95 @@ class DeviceEpisodeReplay:
                 picks.append(ring._pick_balanced(ue[lo:hi], rotation, d))
                 parts.append(ring._windows_of(picks[-1], us[lo:hi]))
         return tuple(torch.cat([p[k] for p in parts], 0) for k in range(6)) + (torch.cat(picks).to(torch.int32),)
+
+    def _pick_prioritized(self, ue, beta):
+        """sample_prioritized's pick on this ring (torch path, the checker of k_pick_prioritized): the ring slot of every batch slot of the
+        ring's segment, ue [nb] its episode uniforms, and the episodes' importance weights.  Integer arithmetic up to the two fp32
+        conversions of the weight; the power itself is taken in fp64 and rounded once."""
+        cap, cnt, head = self.capacity, self._count, self._head
+        ages = torch.arange(max(cap - 1, 1), device=self.device)            # eligible: ages 0 .. count - 2
+        slots = (head - cnt + ages) % cap
+        prio = self.priorities()[slots].clamp(min=1)
+        inside = ages < cnt - 1
+        prio = torch.where(inside, prio, torch.zeros_like(prio))
+        csum = prio.cumsum(0)                                                # int64: below 2^52
+        total = csum[-1]
+        t = torch.minimum((ue.double() * total.double()).long(), (total - 1).clamp(min=0))
+        at = (csum.unsqueeze(0) > t.unsqueeze(1)).long().argmax(1)          # the smallest age whose inclusive prefix sum exceeds t
+        least = torch.where(inside, prio, torch.full_like(prio, 1 << 32)).min()
+        ratio = least.float() / prio[at].clamp(min=1).float()
+        weight = torch.pow(ratio.double(), beta.to(self.device).float().double()).float()
+        hi = (cnt - 1).clamp(min=1)
+        k = torch.minimum((ue * hi).long(), hi - 1)
+        some = total > 0
+        return torch.where(some, (head - cnt + at) % cap, (head - cnt + k) % cap), torch.where(some, weight, torch.ones_like(weight))
+
+    def sample_prioritized(self, expert, batch_size, prob=0.3, beta=1.0, uniforms=None, draw=None, seed=0, generator=None):
+        """sample_mixed with every batch episode drawn in proportion to its priority within its ring (enable_priorities): with T the sum of
+        the priorities of the ring's eligible episodes - the count - 1 oldest - and u the slot's episode uniform, the episode at the
+        smallest age whose inclusive prefix sum exceeds min(T - 1, floor((double)u * T)).  Its real window rows carry the importance weight
+        (p_min / p)^beta in the weight column - 1 for the ring's least likely episode, smaller for the others -, padding rows 0; the
+        learner's weighted means (kr_update_prologue, kr_critic_grad, phase_actor) take it from there.  expert=None: one ring, the whole
+        batch.  beta: a float, or a device float tensor [1] that a captured graph reads at every replay.  Return layout of sample_balanced,
+        ending in `picked` int32 [batch_size]: the ring slot every batch episode was read from, which update_priorities needs.  On the GPU
+        two launches (kr_sample_windows_prioritized: the pick, the gather); the torch path below is the same rule and their checker."""
+        n, W = self.n_steps, self.horizon - self.n_steps
+        if self.ep_prio is None or (expert is not None and expert.ep_prio is None):
+            raise ValueError("sample_prioritized: the ring has no priorities (enable_priorities)")
+        if expert is not None and (expert.horizon != self.horizon or expert.n_steps != n):
+            raise ValueError("sample_prioritized: the expert ring must have the agent ring's horizon and n_steps")
+        b_agent = batch_size if expert is None else int(batch_size * (1 - prob))
+        if not torch.is_tensor(beta):
+            beta = torch.full((1,), float(beta), device=self.device)
+        if beta.dtype != torch.float32 or beta.numel() != 1:
+            raise ValueError("sample_prioritized: beta is a float or a float32 tensor with one element")
+        if self.native and (expert is None or expert.native):
+            import ctypes
+            R, dev = batch_size * W, self.device
+            S, A = self.ep_state.shape[2], self.ep_action.shape[2]
+            out = (torch.empty(R, n, S, device=dev), torch.empty(R, n, A, device=dev), torch.empty(R, n, S, device=dev),
+                   torch.empty(R, n, device=dev), torch.empty(R, n, device=dev), torch.empty(R, device=dev))
+            picked = torch.empty(batch_size, dtype=torch.int32, device=dev)
+            P = self._ptr
+            ends = torch.empty(2 * R, S, device=dev) if (draw is not None and uniforms is None) else None
+            if uniforms is None and draw is None:
+                uniforms = torch.rand(batch_size * (W + 1), device=dev, generator=generator)
+            u = None if uniforms is None else uniforms.contiguous()
+            ra = self._ring()
+            re = ra if expert is None else expert._ring()
+            self._check(self._lib.kr_sample_windows_prioritized(batch_size, b_agent, self.horizon, n, ctypes.byref(ra), ctypes.byref(re), P(self.ep_prio),
+                                                                None if expert is None else P(expert.ep_prio), P(beta), P(u),
+                                                                P(u[batch_size:]) if u is not None else None, int(seed) & (2 ** 64 - 1), P(draw),
+                                                                P(out[0]), P(out[1]), P(out[2]), P(out[3]), P(out[4]), P(out[5]), P(ends), P(picked),
+                                                                self._stream()), "kr_sample_windows_prioritized")
+            return (out if ends is None else out + (ends,)) + (picked,)
+        if uniforms is None:
+            uniforms = torch.rand(batch_size * (W + 1), device=self.device, generator=generator)
+        ue, us = uniforms[:batch_size], uniforms[batch_size:].view(batch_size, W)
+        parts, picks = [], []
+        for ring, lo, hi in ((self, 0, b_agent), (expert, b_agent, batch_size)):
+            if hi > lo:
+                slot, w_ep = ring._pick_prioritized(ue[lo:hi], beta)
+                rows = list(ring._windows_of(slot, us[lo:hi]))
+                rows[5] = rows[5] * w_ep.repeat_interleave(W)               # (0 / 1 times the episode's weight)
+                picks.append(slot)
+                parts.append(rows)
+        return tuple(torch.cat([p[k] for p in parts], 0) for k in range(6)) + (torch.cat(picks).to(torch.int32),)
+
+    def update_priorities(self, expert, q, tq1, reward, weight, picked, prob=0.3, discount=0.995, alpha=0.3, eps=1e-3, eps_expert=1.0, delta_out=None):
+        """kr_update_priorities: after the critic's forward on a batch of sample_prioritized - q [R], tq1 [R] (the 1-step target critic's
+        values), reward [R, n], weight [R], picked [batch] - every picked episode's priority becomes (delta + eps)^alpha in ep_prio's unit,
+        delta its largest 1-step TD error over its real rows; expert episodes (batch slots from int(batch * (1 - prob)) on; expert=None:
+        none) use eps_expert, the demonstration bonus, and the expert ring's table and prio_max.  An episode picked twice gets the larger
+        value, one without a finite error stays as it is.  delta_out (optional) float [batch].  GPU only: it has no torch path."""
+        if self.ep_prio is None or (expert is not None and expert.ep_prio is None):
+            raise ValueError("update_priorities: the ring has no priorities (enable_priorities)")
+        if not self.native or (expert is not None and not expert.native):
+            raise ValueError("update_priorities needs device rings (DeviceEpisodeReplay on the GPU)")
+        batch = picked.shape[0]
+        b_agent = batch if expert is None else int(batch * (1 - prob))
+        P = self._ptr
+        self._check(self._lib.kr_update_priorities(batch, b_agent, self.horizon, self.n_steps, P(q), P(tq1), P(reward), P(weight), float(discount), P(picked),
+                                                   float(alpha), float(eps), float(eps_expert), P(self.ep_prio), None if expert is None else P(expert.ep_prio),
+                                                   P(self.prio_max), None if expert is None else P(expert.prio_max), P(delta_out), self._stream()),
+                    "kr_update_priorities")
