@@ -881,49 +881,60 @@ int kr_advance_ring(int32_t n, int32_t capacity, const int64_t* total, int64_t* 
     return launched();
 }
 
+static bool ring_ok(const kr_ring* r) {
+    return r && r->count && r->head && r->capacity > 0 && r->ep_len && r->ep_state && r->ep_next && r->ep_action && r->ep_reward && r->ep_not_done;
+}
+
+static Ring to_ring(const kr_ring* r) {
+    return Ring{r->count, r->head, r->capacity, r->ep_len, r->ep_state, r->ep_next, r->ep_action, r->ep_reward, r->ep_not_done};
+}
+
+// what kr_sample_windows_mixed requires of its arguments; _balanced and _prioritized require it too and add their own terms behind it
+static bool sample_args_ok(int32_t batch, int32_t batch_agent, int32_t horizon, int32_t n_steps, const kr_ring* agent, const kr_ring* expert,
+                           const float* u_ep, const float* u_start, const int64_t* draw, const float* state, const float* action,
+                           const float* next_state, const float* reward, const float* not_done, const float* weight) {
+    return batch > 0 && batch_agent >= 0 && batch_agent <= batch && horizon > n_steps && n_steps > 0 && n_steps <= WAVE && ring_ok(agent) && ring_ok(expert) &&
+           ((u_ep == nullptr) == (u_start == nullptr)) && (u_ep || draw) && state && action && next_state && reward && not_done && weight;
+}
+
+// the gather behind a pick (kr_sample_windows_balanced, _prioritized): kr_sample_windows' rows with the episode supplied
+static int gather_windows(int32_t batch, int32_t batch_agent, int32_t horizon, int32_t n_steps, const kr_ring* agent, const kr_ring* expert,
+                          const int* slots, int row_major, const float* u_start, uint64_t seed, const int64_t* draw, float* next_ends, float* state,
+                          float* action, float* next_state, float* reward, float* not_done, float* weight, const float* row_weight, void* stream) {
+    hipLaunchKernelGGL(k_gather_windows, dim3(batch * (horizon - n_steps)), dim3(WAVE), 0, (hipStream_t)stream, batch, batch_agent, horizon, n_steps,
+                       to_ring(agent), to_ring(expert), slots, row_major, u_start, (unsigned long long)seed, draw, next_ends, state, action, next_state,
+                       reward, not_done, weight, row_weight);
+    return launched();
+}
+
 int kr_sample_windows(int32_t batch, int32_t horizon, int32_t n_steps, const int64_t* count, const int64_t* head, int32_t capacity,
                       const int64_t* ep_len, const float* u_ep, const float* u_start, const float* ep_state, const float* ep_next, const float* ep_action, const float* ep_reward,
                       const float* ep_not_done, float* state, float* action, float* next_state, float* reward, float* not_done, float* weight,
                       void* stream) {
-    if (batch <= 0 || horizon <= n_steps || n_steps <= 0 || n_steps > WAVE || capacity <= 0 || !count || !head || !ep_len || !u_ep || !u_start || !ep_state || !ep_next ||
-        !ep_action || !ep_reward || !ep_not_done || !state || !action || !next_state || !reward || !not_done || !weight)
-        return KS_ERR_INVALID;
-    const Ring g{count, head, capacity, ep_len, ep_state, ep_next, ep_action, ep_reward, ep_not_done};
-    hipLaunchKernelGGL(k_sample_windows, dim3(batch * (horizon - n_steps)), dim3(WAVE), 0, (hipStream_t)stream, batch, batch, horizon, n_steps, g, g,
-                       u_ep, u_start, 0ull, (const int64_t*)nullptr, (float*)nullptr, state, action, next_state, reward, not_done, weight);
-    return launched();
+    if (!u_ep || !u_start) return KS_ERR_INVALID;
+    const kr_ring g{count, head, capacity, ep_len, ep_state, ep_next, ep_action, ep_reward, ep_not_done};
+    return kr_sample_windows_mixed(batch, batch, horizon, n_steps, &g, &g, u_ep, u_start, 0, nullptr, state, action, next_state, reward, not_done, weight,
+                                   nullptr, stream);
 }
 
 int kr_sample_windows_draw(int32_t batch, int32_t horizon, int32_t n_steps, const int64_t* count, const int64_t* head, int32_t capacity,
                            const int64_t* ep_len, uint64_t seed, const int64_t* draw, const float* ep_state, const float* ep_next,
                            const float* ep_action, const float* ep_reward, const float* ep_not_done, float* state, float* action, float* next_state,
                            float* reward, float* not_done, float* weight, float* next_ends, void* stream) {
-    if (batch <= 0 || horizon <= n_steps || n_steps <= 0 || n_steps > WAVE || capacity <= 0 || !count || !head || !ep_len || !draw || !ep_state ||
-        !ep_next || !ep_action || !ep_reward || !ep_not_done || !state || !action || !next_state || !reward || !not_done || !weight)
-        return KS_ERR_INVALID;
-    const Ring g{count, head, capacity, ep_len, ep_state, ep_next, ep_action, ep_reward, ep_not_done};
-    hipLaunchKernelGGL(k_sample_windows, dim3(batch * (horizon - n_steps)), dim3(WAVE), 0, (hipStream_t)stream, batch, batch, horizon, n_steps, g, g,
-                       (const float*)nullptr, (const float*)nullptr, (unsigned long long)seed, draw, next_ends, state, action, next_state, reward,
-                       not_done, weight);
-    return launched();
-}
-
-static bool ring_ok(const kr_ring* r) {
-    return r && r->count && r->head && r->capacity > 0 && r->ep_len && r->ep_state && r->ep_next && r->ep_action && r->ep_reward && r->ep_not_done;
+    if (!draw) return KS_ERR_INVALID;
+    const kr_ring g{count, head, capacity, ep_len, ep_state, ep_next, ep_action, ep_reward, ep_not_done};
+    return kr_sample_windows_mixed(batch, batch, horizon, n_steps, &g, &g, nullptr, nullptr, seed, draw, state, action, next_state, reward, not_done, weight,
+                                   next_ends, stream);
 }
 
 int kr_sample_windows_mixed(int32_t batch, int32_t batch_agent, int32_t horizon, int32_t n_steps, const kr_ring* agent, const kr_ring* expert,
                             const float* u_ep, const float* u_start, uint64_t seed, const int64_t* draw, float* state, float* action,
                             float* next_state, float* reward, float* not_done, float* weight, float* next_ends, void* stream) {
-    if (batch <= 0 || batch_agent < 0 || batch_agent > batch || horizon <= n_steps || n_steps <= 0 || n_steps > WAVE || !ring_ok(agent) || !ring_ok(expert) ||
-        ((u_ep == nullptr) != (u_start == nullptr)) || (!u_ep && !draw) || !state || !action || !next_state || !reward || !not_done || !weight)
+    if (!sample_args_ok(batch, batch_agent, horizon, n_steps, agent, expert, u_ep, u_start, draw, state, action, next_state, reward, not_done, weight))
         return KS_ERR_INVALID;
-    const Ring ga{agent->count, agent->head, agent->capacity, agent->ep_len, agent->ep_state, agent->ep_next, agent->ep_action, agent->ep_reward,
-                  agent->ep_not_done};
-    const Ring ge{expert->count, expert->head, expert->capacity, expert->ep_len, expert->ep_state, expert->ep_next, expert->ep_action,
-                  expert->ep_reward, expert->ep_not_done};
-    hipLaunchKernelGGL(k_sample_windows, dim3(batch * (horizon - n_steps)), dim3(WAVE), 0, (hipStream_t)stream, batch, batch_agent, horizon, n_steps, ga,
-                       ge, u_ep, u_start, (unsigned long long)seed, draw, next_ends, state, action, next_state, reward, not_done, weight);
+    hipLaunchKernelGGL(k_sample_windows, dim3(batch * (horizon - n_steps)), dim3(WAVE), 0, (hipStream_t)stream, batch, batch_agent, horizon, n_steps,
+                       to_ring(agent), to_ring(expert), u_ep, u_start, (unsigned long long)seed, draw, next_ends, state, action, next_state, reward, not_done,
+                       weight);
     return launched();
 }
 
@@ -939,25 +950,18 @@ int kr_sample_windows_balanced(int32_t batch, int32_t batch_agent, int32_t horiz
                                const int32_t* agent_class, const int32_t* expert_class, int32_t n_classes, int32_t rotation, const float* u_ep,
                                const float* u_start, uint64_t seed, const int64_t* draw, float* state, float* action, float* next_state,
                                float* reward, float* not_done, float* weight, float* next_ends, int32_t* picked, void* stream) {
-    if (batch <= 0 || batch_agent < 0 || batch_agent > batch || horizon <= n_steps || n_steps <= 0 || n_steps > WAVE || !ring_ok(agent) || !ring_ok(expert) ||
-        ((u_ep == nullptr) != (u_start == nullptr)) || (!u_ep && !draw) || !state || !action || !next_state || !reward || !not_done || !weight ||
+    if (!sample_args_ok(batch, batch_agent, horizon, n_steps, agent, expert, u_ep, u_start, draw, state, action, next_state, reward, not_done, weight) ||
         n_classes < 1 || n_classes > 64 || (batch_agent > 0 && !agent_class) || (batch_agent < batch && !expert_class))
         return KS_ERR_INVALID;
-    const Ring ga{agent->count, agent->head, agent->capacity, agent->ep_len, agent->ep_state, agent->ep_next, agent->ep_action, agent->ep_reward,
-                  agent->ep_not_done};
-    const Ring ge{expert->count, expert->head, expert->capacity, expert->ep_len, expert->ep_state, expert->ep_next, expert->ep_action,
-                  expert->ep_reward, expert->ep_not_done};
     // without `picked` the slots travel from the pick to the gather in the weight output, one copy per window row: the gather wave of a row
     // reads its own element and then writes its weight there - no scratch buffer to own, nothing allocated on a captured stream
-    const int W = horizon - n_steps, row_major = picked == nullptr;
+    const int row_major = picked == nullptr;
     int* slots = picked != nullptr ? picked : (int*)weight;
-    hipLaunchKernelGGL(k_pick_balanced, dim3(batch), dim3(WAVE), 0, (hipStream_t)stream, batch, batch_agent, W, ga, ge, agent_class, expert_class,
-                       n_classes, rotation, u_ep, (unsigned long long)seed, draw, slots, row_major);
+    hipLaunchKernelGGL(k_pick_balanced, dim3(batch), dim3(WAVE), 0, (hipStream_t)stream, batch, batch_agent, horizon - n_steps, to_ring(agent),
+                       to_ring(expert), agent_class, expert_class, n_classes, rotation, u_ep, (unsigned long long)seed, draw, slots, row_major);
     if (launched() != KS_OK) return KS_ERR_HIP;
-    hipLaunchKernelGGL(k_gather_windows, dim3(batch * W), dim3(WAVE), 0, (hipStream_t)stream, batch, batch_agent, horizon, n_steps, ga, ge,
-                       (const int*)slots, row_major, u_start, (unsigned long long)seed, draw, next_ends, state, action, next_state, reward, not_done,
-                       weight, (const float*)nullptr);
-    return launched();
+    return gather_windows(batch, batch_agent, horizon, n_steps, agent, expert, slots, row_major, u_start, seed, draw, next_ends, state, action, next_state,
+                          reward, not_done, weight, nullptr, stream);
 }
 
 int kr_commit_priorities(int32_t n, int32_t capacity, const uint8_t* keep, const int64_t* rank, const int64_t* head, const uint32_t* prio_max,
@@ -972,25 +976,18 @@ int kr_sample_windows_prioritized(int32_t batch, int32_t batch_agent, int32_t ho
                                   const uint32_t* agent_prio, const uint32_t* expert_prio, const float* beta, const float* u_ep, const float* u_start,
                                   uint64_t seed, const int64_t* draw, float* state, float* action, float* next_state, float* reward, float* not_done,
                                   float* weight, float* next_ends, int32_t* picked, void* stream) {
-    if (batch <= 0 || batch_agent < 0 || batch_agent > batch || horizon <= n_steps || n_steps <= 0 || n_steps > WAVE || !ring_ok(agent) || !ring_ok(expert) ||
-        ((u_ep == nullptr) != (u_start == nullptr)) || (!u_ep && !draw) || !state || !action || !next_state || !reward || !not_done || !weight ||
+    if (!sample_args_ok(batch, batch_agent, horizon, n_steps, agent, expert, u_ep, u_start, draw, state, action, next_state, reward, not_done, weight) ||
         !beta || (batch_agent > 0 && (!agent_prio || agent->capacity > (1 << 20))) || (batch_agent < batch && (!expert_prio || expert->capacity > (1 << 20))))
         return KS_ERR_INVALID;
-    const Ring ga{agent->count, agent->head, agent->capacity, agent->ep_len, agent->ep_state, agent->ep_next, agent->ep_action, agent->ep_reward,
-                  agent->ep_not_done};
-    const Ring ge{expert->count, expert->head, expert->capacity, expert->ep_len, expert->ep_state, expert->ep_next, expert->ep_action,
-                  expert->ep_reward, expert->ep_not_done};
     // the pick hands every row its episode's importance weight in the weight output and, without `picked`, the slot in the row's first reward:
     // the gather wave of a row reads its own two elements and then writes the row there - no scratch buffer, nothing allocated on a captured stream
-    const int W = horizon - n_steps, row_major = picked == nullptr ? n_steps : 0;
+    const int row_major = picked == nullptr ? n_steps : 0;
     const int* slots = picked != nullptr ? picked : (const int*)reward;
-    hipLaunchKernelGGL(k_pick_prioritized, dim3(batch), dim3(WAVE), 0, (hipStream_t)stream, batch, batch_agent, W, n_steps, ga, ge, agent_prio, expert_prio,
-                       beta, u_ep, (unsigned long long)seed, draw, picked, reward, weight);
+    hipLaunchKernelGGL(k_pick_prioritized, dim3(batch), dim3(WAVE), 0, (hipStream_t)stream, batch, batch_agent, horizon - n_steps, n_steps, to_ring(agent),
+                       to_ring(expert), agent_prio, expert_prio, beta, u_ep, (unsigned long long)seed, draw, picked, reward, weight);
     if (launched() != KS_OK) return KS_ERR_HIP;
-    hipLaunchKernelGGL(k_gather_windows, dim3(batch * W), dim3(WAVE), 0, (hipStream_t)stream, batch, batch_agent, horizon, n_steps, ga, ge, slots,
-                       row_major, u_start, (unsigned long long)seed, draw, next_ends, state, action, next_state, reward, not_done, weight,
-                       (const float*)weight);
-    return launched();
+    return gather_windows(batch, batch_agent, horizon, n_steps, agent, expert, slots, row_major, u_start, seed, draw, next_ends, state, action, next_state,
+                          reward, not_done, weight, weight, stream);
 }
 
 int kr_update_priorities(int32_t batch, int32_t batch_agent, int32_t horizon, int32_t n_steps, const float* q, const float* tq1, const float* reward,

@@ -28,6 +28,7 @@ that is a whole episode old (100 updates at the end of each episode, main_DDPGfD
 from __future__ import annotations
 
 import os
+from functools import partial
 
 import torch
 
@@ -120,6 +121,16 @@ class GraphedTrainer:
             raise ValueError("balanced=True needs a device ring (DeviceEpisodeReplay on the GPU)")
         if expert_replay is not None and not (replay.native and expert_replay.native):
             raise ValueError("GraphedTrainer: the expert mix needs device rings (DeviceEpisodeReplay on the GPU)")
+        # the sampler of every update, chosen once; self.mix: the expert ring when batches mix its episodes in, else None
+        self.mix = expert_replay if (expert_replay is not None and self.expert_prob > 0) else None
+        if self.prioritized:
+            self._sampler = partial(replay.sample_prioritized, self.mix, batch_episodes, self.expert_prob, self.per_beta)
+        elif self.balanced:
+            self._sampler = partial(replay.sample_balanced, self.mix, batch_episodes, self.expert_prob)
+        elif self.mix is not None:
+            self._sampler = partial(replay.sample_mixed, self.mix, batch_episodes, self.expert_prob)
+        else:
+            self._sampler = partial(replay.sample_batch_nstep, batch_episodes)
         self.batch_episodes, self.overlap, self.learn_after = batch_episodes, overlap, learn_after
         self.updates_per_step = max(1, int(updates_per_step))
         self.dev = sim.device
@@ -176,22 +187,8 @@ class GraphedTrainer:
     # -- learner phases on the static batch -------------------------------------------------------------
     def _sample(self):
         # (uniforms drawn in the sampling kernel, keyed by the update count: no generator-state launches in the graph)
-        if self.prioritized:
-            out = self.replay.sample_prioritized(self._per_expert(), self.batch_episodes, self.expert_prob, self.per_beta, draw=self.native.it,
-                                                 seed=self.sample_seed)
-            self.batch, self.picked = out[:-1], out[-1]
-        elif self.balanced:
-            mix = self.expert_replay is not None and self.expert_prob > 0
-            out = self.replay.sample_balanced(self.expert_replay if mix else None, self.batch_episodes, self.expert_prob, draw=self.native.it,
-                                              seed=self.sample_seed)
-            self.batch, self.picked = out[:-1], out[-1]
-        elif self.expert_replay is not None and self.expert_prob > 0:
-            self.batch = self.replay.sample_mixed(self.expert_replay, self.batch_episodes, self.expert_prob, draw=self.native.it, seed=self.sample_seed)
-        else:
-            self.batch = self.replay.sample_batch_nstep(self.batch_episodes, draw=self.native.it if self.replay.native else None, seed=self.sample_seed)
-
-    def _per_expert(self):
-        return self.expert_replay if (self.expert_replay is not None and self.expert_prob > 0) else None
+        out = self._sampler(draw=self.native.it if self.replay.native else None, seed=self.sample_seed)
+        self.batch, self.picked = (out[:-1], out[-1]) if (self.prioritized or self.balanced) else (out, None)
 
     def set_per_beta(self, beta: float):
         """the importance weights' exponent from the next update on (a fill of the device scalar the sampler reads: fine between graph replays)"""
@@ -200,7 +197,7 @@ class GraphedTrainer:
         self.per_beta.fill_(float(beta))
 
     def _update_priorities(self, q, tq1, reward, weight):
-        self.replay.update_priorities(self._per_expert(), q, tq1, reward, weight, self.picked, prob=self.expert_prob, discount=self.policy.discount,
+        self.replay.update_priorities(self.mix, q, tq1, reward, weight, self.picked, prob=self.expert_prob, discount=self.policy.discount,
                                       alpha=self.per_alpha, eps=self.per_eps, eps_expert=self.per_eps_expert, delta_out=self.per_delta)
 
     def _priority_state(self):
@@ -555,19 +552,7 @@ class AsyncTrainer(GraphedTrainer):
         """launch-synchronous form, beside a launch: published episodes (buffer 0 first, env order) -> the staging ring, their buffers freed.
         A staged episode is never overwritten: what does not fit stays published in its buffer (its env drops further episodes -
         counts()["episodes_dropped"] - until a collection finds room)."""
-        r, st_ = self.replay, self.stage
-        L, P, s = r._lib, r._ptr, r._stream()
-        for b in (0, 1):
-            keep = r._keep2[b]
-            torch.gt(r.pub_len[b], 0, out=keep)
-            r._check(L.kr_rank_episodes(r.n_envs, P(keep), P(st_._rank), P(st_._total), s), "kr_rank_episodes")
-            torch.logical_and(keep, st_._rank + st_._count <= st_.capacity, out=keep)
-            r._check(L.kr_rank_episodes(r.n_envs, P(keep), P(st_._rank), P(st_._total), s), "kr_rank_episodes")
-            r._check(L.kr_commit_episodes(r.n_envs, r.horizon, st_.capacity, P(keep), P(st_._rank), P(st_._head), P(r.a_state[b]), P(r.a_next[b]),
-                                          P(r.a_action[b]), P(r.a_reward[b]), P(r.a_not_done[b]), P(r.pub_len[b]), P(st_.ep_state), P(st_.ep_next),
-                                          P(st_.ep_action), P(st_.ep_reward), P(st_.ep_not_done), P(st_.ep_len), s), "kr_commit_episodes")
-            r._check(L.kr_advance_ring(r.n_envs, st_.capacity, P(st_._total), P(st_._head), P(st_._count), P(keep), P(r.pub_len[b]), s),
-                     "kr_advance_ring")
+        self.replay.commit_published(into=self.stage)
 
     def _launch_boundary(self):
         """between launches: the staged episodes -> the ring (one graph), then the actor is published for the next launch"""
@@ -591,12 +576,8 @@ class AsyncTrainer(GraphedTrainer):
         skip = (st_._count - r.capacity).clamp(min=0)
         keep = valid & (self._stage_rank > skip)
         self._stage_rank.sub_(skip)                                               # kept rows: 1 .. min(count, ring capacity) -> slot head + rank - 1
-        r._total.copy_(torch.clamp(st_._count, max=r.capacity).view(1))
-        L, P, s = r._lib, r._ptr, r._stream()
-        r._check(L.kr_commit_episodes(cap, r.horizon, r.capacity, P(keep), P(self._stage_rank), P(r._head), P(st_.ep_state), P(st_.ep_next),
-                                      P(st_.ep_action), P(st_.ep_reward), P(st_.ep_not_done), P(st_.ep_len), P(r.ep_state), P(r.ep_next),
-                                      P(r.ep_action), P(r.ep_reward), P(r.ep_not_done), P(r.ep_len), s), "kr_commit_episodes")
-        r._check(L.kr_advance_ring(cap, r.capacity, P(r._total), P(r._head), P(r._count), P(keep), P(st_.ep_len), s), "kr_advance_ring")
+        r.commit_ranked((st_.ep_state, st_.ep_next, st_.ep_action, st_.ep_reward, st_.ep_not_done), st_.ep_len, keep, self._stage_rank,
+                        torch.clamp(st_._count, max=r.capacity).view(1))
         st_._head.zero_()
         st_._count.zero_()
         self._stage_published()                      # (episodes a full stage left in their buffers)

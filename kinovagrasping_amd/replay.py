@@ -8,6 +8,10 @@ ceiling - 1 uniform random starts in [0, ceiling) plus the final window starting
 """
 from __future__ import annotations
 
+import ctypes
+import json
+from pathlib import Path
+
 import numpy as np
 import torch
 
@@ -43,7 +47,6 @@ def _object_rows(rows):
 def save_reference_bundle(dirpath, episodes, max_episode=10000, orientation_indexes=None):
     """Write episodes (list of dicts with the five _BUNDLE_FIELDS, each [L, ...] array) in the layout
     ReplayBuffer_Queue.save_replay_buffer produces, readable by store_saved_data_into_replay (utils.py:367-400)."""
-    from pathlib import Path
     d = Path(dirpath)
     d.mkdir(parents=True, exist_ok=True)
     for f in _BUNDLE_FIELDS:
@@ -62,7 +65,6 @@ def save_reference_bundle(dirpath, episodes, max_episode=10000, orientation_inde
 def load_reference_bundle(dirpath):
     """Read a bundle written by the reference (or by save_reference_bundle): list of episode dicts of float32 arrays
     (empty trailing episodes dropped) + the episodes_info vector."""
-    from pathlib import Path
     d = Path(dirpath)
     cols = {f: np.load(d / (f + ".npy"), allow_pickle=True) for f in _BUNDLE_FIELDS}
     n = len(cols["reward"])
@@ -163,7 +165,6 @@ class DeviceEpisodeReplay:
             self._total = torch.zeros(1, dtype=torch.long, device=self.device)
 
     def _stream(self):
-        import ctypes
         return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
     def _check(self, rc, what):
@@ -243,8 +244,6 @@ class DeviceEpisodeReplay:
         its files by name, never opens; the bundle's own files are what they are without classes."""
         save_reference_bundle(dirpath, self.host_episodes(), self.capacity if max_episode is None else max_episode)
         if self.ep_class is not None:
-            import json
-            from pathlib import Path
             cnt, head = self.count, self.head
             slots = (head - cnt + torch.arange(cnt, device=self.device)) % self.capacity
             (Path(dirpath) / CLASS_SIDECAR).write_text(json.dumps({"class_names": list(self.class_names),
@@ -261,10 +260,8 @@ class DeviceEpisodeReplay:
             tags = [-1 if class_id is None else int(class_id)] * len(eps)
             if class_id is not None and not -1 <= int(class_id) < len(self.class_names):
                 raise ValueError(f"load: class_id {class_id} is not one of the ring's {len(self.class_names)} classes")
-            from pathlib import Path
             side = Path(dirpath) / CLASS_SIDECAR
             if class_id is None and side.is_file():
-                import json
                 rec = json.loads(side.read_text())
                 known = {name: i for i, name in enumerate(self.class_names)}
                 if len(rec["episode_class"]) == len(eps):            # (a sidecar of another bundle's length says nothing about this one)
@@ -355,37 +352,62 @@ class DeviceEpisodeReplay:
         self.a_sel = z(n, dtype=torch.uint8)
         self._keep2 = torch.zeros(2, n, dtype=torch.bool, device=dev)
 
-    def commit_published(self):
+    def commit_published(self, into=None):
         """Move every published episode (pub_len > 0) of both buffers into the ring, buffer 0 first, env order within a buffer,
-        and free the buffers (kr_rank_episodes / kr_commit_episodes / kr_advance_ring with the published lengths as cur_len).
+        and free the buffers (commit_episodes with the published lengths as cur_len).
+        into: another ring that takes the episodes instead (AsyncTrainer's staging ring), and only as many as it has free rows - a row
+        it holds is never overwritten: what does not fit stays published in its buffer (a rank, the clip, then commit_episodes' own rank).
         Fixed-shape device ops: capturable; runs on the learner's stream ahead of the window sampling."""
-        L, P, st = self._lib, self._ptr, self._stream()
         for b in (0, 1):
             keep = self._keep2[b]
             torch.gt(self.pub_len[b], 0, out=keep)
-            self._check(L.kr_rank_episodes(self.n_envs, P(keep), P(self._rank), P(self._total), st), "kr_rank_episodes")
-            self._check(L.kr_commit_episodes(self.n_envs, self.horizon, self.capacity, P(keep), P(self._rank), P(self._head), P(self.a_state[b]),
-                                             P(self.a_next[b]), P(self.a_action[b]), P(self.a_reward[b]), P(self.a_not_done[b]), P(self.pub_len[b]),
-                                             P(self.ep_state), P(self.ep_next), P(self.ep_action), P(self.ep_reward), P(self.ep_not_done),
-                                             P(self.ep_len), st), "kr_commit_episodes")
-            self._commit_classes(keep, st)
-            self._commit_priorities(keep, st)
-            self._check(L.kr_advance_ring(self.n_envs, self.capacity, P(self._total), P(self._head), P(self._count), P(keep), P(self.pub_len[b]), st),
-                        "kr_advance_ring")
+            if into is not None:
+                into._rank_episodes(keep, into._stream())
+                torch.logical_and(keep, into._rank + into._count <= into.capacity, out=keep)
+            (self if into is None else into).commit_episodes((self.a_state[b], self.a_next[b], self.a_action[b], self.a_reward[b], self.a_not_done[b]),
+                                                             self.pub_len[b], keep, keep)
 
     def commit_native(self, keep, ended):
         """rank -> commit -> advance with the kr_* kernels; keep / ended: bool [n_envs]"""
-        L, P, st = self._lib, self._ptr, self._stream()
-        self._check(L.kr_rank_episodes(self.n_envs, P(keep), P(self._rank), P(self._total), st), "kr_rank_episodes")
-        self._check(L.kr_commit_episodes(self.n_envs, self.horizon, self.capacity, P(keep), P(self._rank), P(self._head), P(self.cur_state),
-                                         P(self.cur_next), P(self.cur_action), P(self.cur_reward), P(self.cur_not_done), P(self.cur_len),
-                                         P(self.ep_state), P(self.ep_next), P(self.ep_action), P(self.ep_reward), P(self.ep_not_done),
-                                         P(self.ep_len), st), "kr_commit_episodes")
+        self.commit_episodes((self.cur_state, self.cur_next, self.cur_action, self.cur_reward, self.cur_not_done), self.cur_len, keep, ended)
+        return self._total[0]
+
+    def _rank_episodes(self, keep, st):
+        self._check(self._lib.kr_rank_episodes(keep.shape[0], self._ptr(keep), self._ptr(self._rank), self._ptr(self._total), st), "kr_rank_episodes")
+
+    def _commit_rows(self, src, src_len, keep, rank, st):
+        """kr_commit_episodes: row i of src (state, next_state, action, reward, not_done) with keep[i] -> ring slot head + rank[i], the others -> the trash row"""
+        P = self._ptr
+        self._check(self._lib.kr_commit_episodes(keep.shape[0], self.horizon, self.capacity, P(keep), P(rank), P(self._head), *[P(x) for x in src], P(src_len),
+                                                 P(self.ep_state), P(self.ep_next), P(self.ep_action), P(self.ep_reward), P(self.ep_not_done),
+                                                 P(self.ep_len), st), "kr_commit_episodes")
+
+    def _advance_ring(self, ended, src_len, st):
+        """kr_advance_ring: head and count move by the ranked total, src_len[i] = 0 where ended[i]"""
+        P = self._ptr
+        self._check(self._lib.kr_advance_ring(ended.shape[0], self.capacity, P(self._total), P(self._head), P(self._count), P(ended), P(src_len), st),
+                    "kr_advance_ring")
+
+    def commit_episodes(self, src, src_len, keep, ended):
+        """How an episode enters the ring on the GPU: rank -> commit -> classes -> priorities -> advance, one kr_* launch each (the last two only on
+        a ring that has the column).  src: the open-episode buffers (state, next_state, action, reward, not_done), [n_envs, horizon, ...] each, and
+        src_len int64 [n_envs] their lengths; keep bool [n_envs]: the rows that enter, in env order; ended bool [n_envs]: the rows whose src_len
+        is reset to 0.  Fixed-shape device ops: capturable."""
+        st = self._stream()
+        self._rank_episodes(keep, st)
+        self._commit_rows(src, src_len, keep, self._rank, st)
         self._commit_classes(keep, st)
         self._commit_priorities(keep, st)
-        self._check(L.kr_advance_ring(self.n_envs, self.capacity, P(self._total), P(self._head), P(self._count), P(ended), P(self.cur_len), st),
-                    "kr_advance_ring")
-        return self._total[0]
+        self._advance_ring(ended, src_len, st)
+
+    def commit_ranked(self, src, src_len, keep, rank, total):
+        """commit_episodes for rows the caller has ranked itself: row i of src ([n, horizon, ...] each, any n) with keep[i] enters at slot
+        head + rank[i]; total int64 [1]: how many enter; the kept rows' src_len is reset.  No rank launch, and nothing is tagged: for a ring
+        without classes and priorities (AsyncTrainer's launch boundary, staged rows in key order)."""
+        st = self._stream()
+        self._total.copy_(total)
+        self._commit_rows(src, src_len, keep, rank, st)
+        self._advance_ring(keep, src_len, st)
 
     def _ring(self):
         from .sim import KrRing
@@ -393,42 +415,61 @@ class DeviceEpisodeReplay:
         return KrRing(P(self._count), P(self._head), self.capacity, P(self.ep_len), P(self.ep_state), P(self.ep_next), P(self.ep_action),
                       P(self.ep_reward), P(self.ep_not_done))
 
+    def _sample_native(self, entry, expert, batch_size, b_agent, pick_args, uniforms, draw, seed, generator, with_picked):
+        """The native front end of every sampler: one call of libkinova_sim's `entry` (kr_sample_windows_mixed, or an entry point with its
+        argument list plus pick_args - what only its pick needs - behind the rings and `picked` behind next_ends).  Allocates the batch, the
+        7th tensor exactly when `draw` is given without `uniforms`, and `picked` on request; the uniforms are the caller's, torch.rand's
+        (neither uniforms nor draw) or the kernel's own (draw).  expert=None: this ring serves as both."""
+        n, W = self.n_steps, self.horizon - self.n_steps
+        R, dev = batch_size * W, self.device
+        S, A = self.ep_state.shape[2], self.ep_action.shape[2]
+        out = (torch.empty(R, n, S, device=dev), torch.empty(R, n, A, device=dev), torch.empty(R, n, S, device=dev),
+               torch.empty(R, n, device=dev), torch.empty(R, n, device=dev), torch.empty(R, device=dev))
+        picked = (torch.empty(batch_size, dtype=torch.int32, device=dev),) if with_picked else ()
+        P = self._ptr
+        ends = (torch.empty(2 * R, S, device=dev),) if (draw is not None and uniforms is None) else ()
+        if uniforms is None and draw is None:
+            uniforms = torch.rand(batch_size * (W + 1), device=dev, generator=generator)
+        u = None if uniforms is None else uniforms.contiguous()
+        ra = self._ring()
+        re = ra if expert is None else expert._ring()
+        self._check(getattr(self._lib, entry)(batch_size, b_agent, self.horizon, n, ctypes.byref(ra), ctypes.byref(re), *pick_args, P(u),
+                                              P(u[batch_size:]) if u is not None else None, int(seed) & (2 ** 64 - 1), P(draw),
+                                              P(out[0]), P(out[1]), P(out[2]), P(out[3]), P(out[4]), P(out[5]), P(ends[0]) if ends else None,
+                                              *[P(t) for t in picked], self._stream()), entry)
+        return out + ends + picked
+
+    def _sample_torch(self, expert, batch_size, b_agent, uniforms, generator, pick):
+        """The torch front end of the two-ring samplers (the checker of the kernels): batch slots [0, b_agent) from this ring, the others from
+        `expert`.  pick(ring, ue) -> (the ring slot of every batch slot of the ring's segment, ue [nb] its episode uniforms; the episodes'
+        weights or None).  Returns the six batch tensors and the picked slots int32 [batch_size]."""
+        W = self.horizon - self.n_steps
+        if uniforms is None:
+            uniforms = torch.rand(batch_size * (W + 1), device=self.device, generator=generator)
+        ue, us = uniforms[:batch_size], uniforms[batch_size:].view(batch_size, W)
+        parts, picks = [], []
+        for ring, lo, hi in ((self, 0, b_agent), (expert, b_agent, batch_size)):
+            if hi > lo:
+                slot, w_ep = pick(ring, ue[lo:hi])
+                rows = list(ring._windows_of(slot, us[lo:hi]))
+                if w_ep is not None:
+                    rows[5] = rows[5] * w_ep.repeat_interleave(W)               # (0 / 1 times the episode's weight)
+                picks.append(slot)
+                parts.append(rows)
+        return tuple(torch.cat([p[k] for p in parts], 0) for k in range(6)) + (torch.cat(picks).to(torch.int32),)
+
     def sample_mixed(self, expert: "DeviceEpisodeReplay", batch_size, prob=0.3, uniforms=None, draw=None, seed=0, generator=None):
         """DDPGfD's batch (DDPGfD.train_batch, DDPGfD.py:232-254): agent_batch_size = int(batch_size * (1 - prob)) episodes from THIS
         ring followed by batch_size - agent_batch_size episodes from `expert`, each sampled with sample_batch_nstep's rule on its own
         ring.  Same return layout as sample_batch_nstep (incl. the 7th tensor when `draw` is given).  One kernel launch on the GPU
         (kr_sample_windows_mixed); the torch path below - the concatenation of two sample_batch_nstep calls - is its checker."""
-        n, W = self.n_steps, self.horizon - self.n_steps
-        if expert.horizon != self.horizon or expert.n_steps != n:
+        if expert.horizon != self.horizon or expert.n_steps != self.n_steps:
             raise ValueError("sample_mixed: the expert ring must have the agent ring's horizon and n_steps")
         b_agent = int(batch_size * (1 - prob))
-        b_exp = batch_size - b_agent
         if self.native and expert.native:
-            import ctypes
-            R, dev = batch_size * W, self.device
-            S, A = self.ep_state.shape[2], self.ep_action.shape[2]
-            out = (torch.empty(R, n, S, device=dev), torch.empty(R, n, A, device=dev), torch.empty(R, n, S, device=dev),
-                   torch.empty(R, n, device=dev), torch.empty(R, n, device=dev), torch.empty(R, device=dev))
-            P = self._ptr
-            ends = torch.empty(2 * R, S, device=dev) if (draw is not None and uniforms is None) else None
-            if uniforms is None and draw is None:
-                uniforms = torch.rand(batch_size * (W + 1), device=dev, generator=generator)
-            u = None if uniforms is None else uniforms.contiguous()
-            ra, re = self._ring(), expert._ring()
-            self._check(self._lib.kr_sample_windows_mixed(batch_size, b_agent, self.horizon, n, ctypes.byref(ra), ctypes.byref(re),
-                                                          P(u), P(u[batch_size:]) if u is not None else None, int(seed) & (2 ** 64 - 1),
-                                                          P(draw) if u is None else None, P(out[0]), P(out[1]), P(out[2]), P(out[3]), P(out[4]),
-                                                          P(out[5]), P(ends), self._stream()), "kr_sample_windows_mixed")
-            return out if ends is None else out + (ends,)
-        if uniforms is None:
-            uniforms = torch.rand(batch_size * (W + 1), device=self.device, generator=generator)
-        ue, us = uniforms[:batch_size], uniforms[batch_size:].view(batch_size, W)
-        parts = []
-        if b_agent:
-            parts.append(self.sample_batch_nstep(b_agent, uniforms=torch.cat([ue[:b_agent], us[:b_agent].reshape(-1)])))
-        if b_exp:
-            parts.append(expert.sample_batch_nstep(b_exp, uniforms=torch.cat([ue[b_agent:], us[b_agent:].reshape(-1)])))
-        return tuple(torch.cat([p[k] for p in parts], 0) for k in range(6))
+            return self._sample_native("kr_sample_windows_mixed", expert, batch_size, b_agent, (), uniforms, draw if uniforms is None else None, seed,
+                                       generator, False)
+        return self._sample_torch(expert, batch_size, b_agent, uniforms, generator, lambda ring, ue: (ring._pick_uniform(ue), None))[:6]
 
     def sample_batch_nstep(self, batch_size, generator=None, uniforms=None, draw=None, seed=0):
         """Fixed-shape batch: batch_size episodes x (horizon - n) window rows, padding rows have weight 0.
@@ -438,34 +479,21 @@ class DeviceEpisodeReplay:
         uniforms are then drawn inside the kernel (Philox keyed by `seed`; no torch generator, hence none of its state
         launches in a captured graph) and a 7th tensor is returned: next_state[:, 0] and next_state[:, -1] stacked
         [2R, S], the rows the target networks evaluate."""
-        n, W = self.n_steps, self.horizon - self.n_steps
-        if self.native:
-            R, dev = batch_size * W, self.device
-            S, A = self.ep_state.shape[2], self.ep_action.shape[2]
-            out = (torch.empty(R, n, S, device=dev), torch.empty(R, n, A, device=dev), torch.empty(R, n, S, device=dev),
-                   torch.empty(R, n, device=dev), torch.empty(R, n, device=dev), torch.empty(R, device=dev))
-            P = self._ptr
-            if draw is not None and uniforms is None:
-                ends = torch.empty(2 * R, S, device=dev)
-                self._check(self._lib.kr_sample_windows_draw(batch_size, self.horizon, n, P(self._count), P(self._head), self.capacity, P(self.ep_len),
-                                                             int(seed) & (2 ** 64 - 1), P(draw), P(self.ep_state), P(self.ep_next), P(self.ep_action),
-                                                             P(self.ep_reward), P(self.ep_not_done), P(out[0]), P(out[1]), P(out[2]), P(out[3]),
-                                                             P(out[4]), P(out[5]), P(ends), self._stream()), "kr_sample_windows_draw")
-                return out + (ends,)
-            u = torch.rand(batch_size * (W + 1), device=self.device, generator=generator) if uniforms is None else uniforms.contiguous()
-            self._check(self._lib.kr_sample_windows(batch_size, self.horizon, n, P(self._count), P(self._head), self.capacity, P(self.ep_len), P(u),
-                                                    P(u[batch_size:]),
-                                                    P(self.ep_state), P(self.ep_next), P(self.ep_action), P(self.ep_reward),
-                                                    P(self.ep_not_done), P(out[0]), P(out[1]), P(out[2]), P(out[3]), P(out[4]), P(out[5]),
-                                                    self._stream()), "kr_sample_windows")
-            return out
-        # the k-th oldest episode, k in [0, count - 1): the newest one (ring slot head - 1) is never sampled (utils.py:259)
-        hi = (self._count - 1).clamp(min=1)
+        W = self.horizon - self.n_steps
+        if self.native:                                    # (kr_sample_windows_mixed with this ring as both: kr_sample_windows' launch, or _draw's)
+            return self._sample_native("kr_sample_windows_mixed", None, batch_size, batch_size, (), uniforms, draw if uniforms is None else None, seed,
+                                       generator, False)
         ue = torch.rand(batch_size, device=self.device, generator=generator) if uniforms is None else uniforms[:batch_size]
-        k = torch.minimum((ue * hi).long(), hi - 1)
-        ep = (self._head - self._count + k) % self.capacity
+        ep = self._pick_uniform(ue)
         u = torch.rand(batch_size, W, device=self.device, generator=generator) if uniforms is None else uniforms[batch_size:].view(batch_size, W)
         return self._windows_of(ep, u)
+
+    def _pick_uniform(self, ue):
+        """sample_batch_nstep's pick (torch path): the k-th oldest episode, k in [0, count - 1) - the newest one (ring slot head - 1) is never
+        sampled (utils.py:259) -, ue [nb] the episode uniforms"""
+        hi = (self._count - 1).clamp(min=1)
+        k = torch.minimum((ue * hi).long(), hi - 1)
+        return (self._head - self._count + k) % self.capacity
 
     def _windows_of(self, ep, u):
         """the window rows of the episodes in ring slots ep [B] with the start uniforms u [B, W] (torch path)"""
@@ -494,9 +522,7 @@ class DeviceEpisodeReplay:
         m = match.sum(1)
         j = torch.minimum((ue * m.float()).long(), m - 1)
         at = (match & (match.cumsum(1) == (j + 1).unsqueeze(1))).long().argmax(1) if cap > 1 else torch.zeros_like(m)
-        hi = (cnt - 1).clamp(min=1)
-        k = torch.minimum((ue * hi).long(), hi - 1)
-        return torch.where(m > 0, (head - cnt + at) % cap, (head - cnt + k) % cap)
+        return torch.where(m > 0, (head - cnt + at) % cap, self._pick_uniform(ue))
 
     def sample_balanced(self, expert, batch_size, prob=0.3, uniforms=None, draw=None, seed=0, rotation=0, generator=None):
         """sample_mixed with every batch episode drawn from ONE class of its ring (set_env_classes), the classes in cyclic rotation: slot i
@@ -507,43 +533,16 @@ class DeviceEpisodeReplay:
         draws each class gets exactly the segment's length.  Return layout of sample_mixed, then `picked` int32 [batch_size]: the ring
         slot every batch episode was read from.  On the GPU two launches (kr_sample_windows_balanced: the pick, the gather); the torch
         path below is the same rule and their checker."""
-        n, W = self.n_steps, self.horizon - self.n_steps
         if self.ep_class is None or (expert is not None and expert.ep_class is None):
             raise ValueError("sample_balanced: the ring has no classes (set_env_classes)")
-        if expert is not None and (expert.horizon != self.horizon or expert.n_steps != n or expert.class_names != self.class_names):
+        if expert is not None and (expert.horizon != self.horizon or expert.n_steps != self.n_steps or expert.class_names != self.class_names):
             raise ValueError("sample_balanced: the expert ring must have the agent ring's horizon, n_steps and class names")
         b_agent = batch_size if expert is None else int(batch_size * (1 - prob))
-        nc = len(self.class_names)
         if self.native and (expert is None or expert.native):
-            import ctypes
-            R, dev = batch_size * W, self.device
-            S, A = self.ep_state.shape[2], self.ep_action.shape[2]
-            out = (torch.empty(R, n, S, device=dev), torch.empty(R, n, A, device=dev), torch.empty(R, n, S, device=dev),
-                   torch.empty(R, n, device=dev), torch.empty(R, n, device=dev), torch.empty(R, device=dev))
-            picked = torch.empty(batch_size, dtype=torch.int32, device=dev)
-            P = self._ptr
-            ends = torch.empty(2 * R, S, device=dev) if (draw is not None and uniforms is None) else None
-            if uniforms is None and draw is None:
-                uniforms = torch.rand(batch_size * (W + 1), device=dev, generator=generator)
-            u = None if uniforms is None else uniforms.contiguous()
-            ra = self._ring()
-            re = ra if expert is None else expert._ring()
-            self._check(self._lib.kr_sample_windows_balanced(batch_size, b_agent, self.horizon, n, ctypes.byref(ra), ctypes.byref(re), P(self.ep_class),
-                                                             None if expert is None else P(expert.ep_class), nc, int(rotation), P(u),
-                                                             P(u[batch_size:]) if u is not None else None, int(seed) & (2 ** 64 - 1), P(draw),
-                                                             P(out[0]), P(out[1]), P(out[2]), P(out[3]), P(out[4]), P(out[5]), P(ends), P(picked),
-                                                             self._stream()), "kr_sample_windows_balanced")
-            return (out if ends is None else out + (ends,)) + (picked,)
-        if uniforms is None:
-            uniforms = torch.rand(batch_size * (W + 1), device=self.device, generator=generator)
-        ue, us = uniforms[:batch_size], uniforms[batch_size:].view(batch_size, W)
+            tables = (self._ptr(self.ep_class), None if expert is None else self._ptr(expert.ep_class), len(self.class_names), int(rotation))
+            return self._sample_native("kr_sample_windows_balanced", expert, batch_size, b_agent, tables, uniforms, draw, seed, generator, True)
         d = 0 if draw is None else int(draw)
-        parts, picks = [], []
-        for ring, lo, hi in ((self, 0, b_agent), (expert, b_agent, batch_size)):
-            if hi > lo:
-                picks.append(ring._pick_balanced(ue[lo:hi], rotation, d))
-                parts.append(ring._windows_of(picks[-1], us[lo:hi]))
-        return tuple(torch.cat([p[k] for p in parts], 0) for k in range(6)) + (torch.cat(picks).to(torch.int32),)
+        return self._sample_torch(expert, batch_size, b_agent, uniforms, generator, lambda ring, ue: (ring._pick_balanced(ue, rotation, d), None))
 
     def _pick_prioritized(self, ue, beta):
         """sample_prioritized's pick on this ring (torch path, the checker of k_pick_prioritized): the ring slot of every batch slot of the
@@ -562,10 +561,8 @@ class DeviceEpisodeReplay:
         least = torch.where(inside, prio, torch.full_like(prio, 1 << 32)).min()
         ratio = least.float() / prio[at].clamp(min=1).float()
         weight = torch.pow(ratio.double(), beta.to(self.device).float().double()).float()
-        hi = (cnt - 1).clamp(min=1)
-        k = torch.minimum((ue * hi).long(), hi - 1)
         some = total > 0
-        return torch.where(some, (head - cnt + at) % cap, (head - cnt + k) % cap), torch.where(some, weight, torch.ones_like(weight))
+        return torch.where(some, (head - cnt + at) % cap, self._pick_uniform(ue)), torch.where(some, weight, torch.ones_like(weight))
 
     def sample_prioritized(self, expert, batch_size, prob=0.3, beta=1.0, uniforms=None, draw=None, seed=0, generator=None):
         """sample_mixed with every batch episode drawn in proportion to its priority within its ring (enable_priorities): with T the sum of
@@ -576,10 +573,9 @@ class DeviceEpisodeReplay:
         batch.  beta: a float, or a device float tensor [1] that a captured graph reads at every replay.  Return layout of sample_balanced,
         ending in `picked` int32 [batch_size]: the ring slot every batch episode was read from, which update_priorities needs.  On the GPU
         two launches (kr_sample_windows_prioritized: the pick, the gather); the torch path below is the same rule and their checker."""
-        n, W = self.n_steps, self.horizon - self.n_steps
         if self.ep_prio is None or (expert is not None and expert.ep_prio is None):
             raise ValueError("sample_prioritized: the ring has no priorities (enable_priorities)")
-        if expert is not None and (expert.horizon != self.horizon or expert.n_steps != n):
+        if expert is not None and (expert.horizon != self.horizon or expert.n_steps != self.n_steps):
             raise ValueError("sample_prioritized: the expert ring must have the agent ring's horizon and n_steps")
         b_agent = batch_size if expert is None else int(batch_size * (1 - prob))
         if not torch.is_tensor(beta):
@@ -587,37 +583,9 @@ class DeviceEpisodeReplay:
         if beta.dtype != torch.float32 or beta.numel() != 1:
             raise ValueError("sample_prioritized: beta is a float or a float32 tensor with one element")
         if self.native and (expert is None or expert.native):
-            import ctypes
-            R, dev = batch_size * W, self.device
-            S, A = self.ep_state.shape[2], self.ep_action.shape[2]
-            out = (torch.empty(R, n, S, device=dev), torch.empty(R, n, A, device=dev), torch.empty(R, n, S, device=dev),
-                   torch.empty(R, n, device=dev), torch.empty(R, n, device=dev), torch.empty(R, device=dev))
-            picked = torch.empty(batch_size, dtype=torch.int32, device=dev)
-            P = self._ptr
-            ends = torch.empty(2 * R, S, device=dev) if (draw is not None and uniforms is None) else None
-            if uniforms is None and draw is None:
-                uniforms = torch.rand(batch_size * (W + 1), device=dev, generator=generator)
-            u = None if uniforms is None else uniforms.contiguous()
-            ra = self._ring()
-            re = ra if expert is None else expert._ring()
-            self._check(self._lib.kr_sample_windows_prioritized(batch_size, b_agent, self.horizon, n, ctypes.byref(ra), ctypes.byref(re), P(self.ep_prio),
-                                                                None if expert is None else P(expert.ep_prio), P(beta), P(u),
-                                                                P(u[batch_size:]) if u is not None else None, int(seed) & (2 ** 64 - 1), P(draw),
-                                                                P(out[0]), P(out[1]), P(out[2]), P(out[3]), P(out[4]), P(out[5]), P(ends), P(picked),
-                                                                self._stream()), "kr_sample_windows_prioritized")
-            return (out if ends is None else out + (ends,)) + (picked,)
-        if uniforms is None:
-            uniforms = torch.rand(batch_size * (W + 1), device=self.device, generator=generator)
-        ue, us = uniforms[:batch_size], uniforms[batch_size:].view(batch_size, W)
-        parts, picks = [], []
-        for ring, lo, hi in ((self, 0, b_agent), (expert, b_agent, batch_size)):
-            if hi > lo:
-                slot, w_ep = ring._pick_prioritized(ue[lo:hi], beta)
-                rows = list(ring._windows_of(slot, us[lo:hi]))
-                rows[5] = rows[5] * w_ep.repeat_interleave(W)               # (0 / 1 times the episode's weight)
-                picks.append(slot)
-                parts.append(rows)
-        return tuple(torch.cat([p[k] for p in parts], 0) for k in range(6)) + (torch.cat(picks).to(torch.int32),)
+            tables = (self._ptr(self.ep_prio), None if expert is None else self._ptr(expert.ep_prio), self._ptr(beta))
+            return self._sample_native("kr_sample_windows_prioritized", expert, batch_size, b_agent, tables, uniforms, draw, seed, generator, True)
+        return self._sample_torch(expert, batch_size, b_agent, uniforms, generator, lambda ring, ue: ring._pick_prioritized(ue, beta))
 
     def update_priorities(self, expert, q, tq1, reward, weight, picked, prob=0.3, discount=0.995, alpha=0.3, eps=1e-3, eps_expert=1.0, delta_out=None):
         """kr_update_priorities: after the critic's forward on a batch of sample_prioritized - q [R], tq1 [R] (the 1-step target critic's
