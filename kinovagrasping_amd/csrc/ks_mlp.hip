@@ -101,14 +101,95 @@ __global__ __launch_bounds__(64 * NW) void k_mlp3(int n, int in_a, int in_b, int
     }
 }
 
-// ---- the same network WITHOUT LDS: one wave = 16 batch rows, all layers in registers.  Layer 1's output quads (NT1
-// float4 registers) are the B operands of layer 2; every layer-2 output quad feeds layer 3's MFMAs right away, so h2
-// is never stored.  The kernel is capped at 168 registers per lane (3 waves per SIMD): k_env_step holds all of a
+// ---- the LDS-FREE forms of the same network (the learner's passes, which run in the shadow of the stepping kernel) and what
+// they share.  One wave = 16 batch rows with all layers in registers (k_mlp3_wave / k_mlp3_bwd_wave), the tiles of a layer split
+// over 2 / 4 waves of a workgroup (k_mlp3_split / k_mlp3_bwd_split), or no layer in registers at all (k_mlp3_lean /
+// k_mlp3_bwd_lean).  The helpers from here to k_mlp3_wave are the one copy of the blocks the forms have in common; a block that stays
+// written out in a kernel does so because the compiler allocates or schedules that kernel worse through a helper (profiles/mlp_front_end.txt).
+//
+// All operand reads are raw buffer loads (kmlp::rsrc / ldf / ldq): ONE 32-bit lane offset per matrix, the tile / k-step advance
+// in the wave-uniform scalar offset, out-of-range reads return 0 in hardware.  The flat-load version spent 5 VALU + 7 SALU
+// instructions (address arithmetic, bounds branches) per MFMA - issue slots these kernels share with the stepping kernel's wave
+// on the same SIMD.  The range check covers the LANE offset only, not the scalar offset: an element that does not exist gets the
+// out-of-range lane offset OOR instead of relying on the sum (the rule of ks_mlp_tile.h).
+
+// a 16-byte load that sees what another lane or wave of this workgroup stored behind a fence (glc)
+__device__ __forceinline__ f32x4 ldq_glc(rsrc_t r, uint32_t voff, uint32_t soff) {
+    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, (int)soff, 1));
+}
+
+// B operands of layer 1: the 16 input rows, k = 16 s + 4 q + j, columns < in_a from xa and the rest from xb.  A row beyond n gets OOR (0).
+__device__ __forceinline__ void input_quads(f32x4 (&bx)[KS_IN_MAX], int n, int row, int q, int in_a, int in_b, const float* __restrict__ xa, int lda,
+                                            const float* __restrict__ xb, int ldb) {
+    const bool row_ok = row < n;
+    const int in_dim = in_a + in_b;
+    const rsrc_t rXa = rsrc(xa, ((n - 1) * lda + in_a) * 4), rXb = rsrc(xb ? xb : xa, xb ? ((n - 1) * ldb + in_b) * 4 : 0);
+    const int oa = row * lda * 4 + 16 * q, ob = (row * ldb + 4 * q - in_a) * 4;
+#pragma unroll
+    for (int s = 0; s < KS_IN_MAX; s++) {
+        float v[4];
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const int k = 16 * s + 4 * q + j;
+            const float fa = ldf(rXa, (row_ok && k < in_a) ? oa : OOR, (16 * s + j) * 4);
+            const float fb = ldf(rXb, (row_ok && k >= in_a && k < in_dim) ? ob + (16 * s + j) * 4 : OOR, 0);
+            v[j] = k < in_a ? fa : fb;
+        }
+        bx[s] = f32x4{v[0], v[1], v[2], v[3]};
+    }
+}
+
+// output epilogue of a lane that holds a row's layer-3 sums: z + b3, the optional scale * sigmoid, store
+__device__ __forceinline__ void store_out(f32x4 z4, const float* __restrict__ b3, int act, float scale, float* __restrict__ out, int row, int out_dim) {
+    const float z[4] = {z4.x, z4.y, z4.z, z4.w};
+    for (int i = 0; i < out_dim; i++) {
+        float y = z[i] + b3[i];
+        if (act == KR_ACT_SIGMOID) y = scale / (1.f + __expf(-y));
+        out[(long)row * out_dim + i] = y;
+    }
+}
+
+// backward of ReLU on a quad: the gradient passes where the forward activation hv was positive
+__device__ __forceinline__ f32x4 relu_mask(f32x4 hv, f32x4 acc) {
+    f32x4 dz;
+    dz.x = hv.x > 0.f ? acc.x : 0.f; dz.y = hv.y > 0.f ? acc.y : 0.f; dz.z = hv.z > 0.f ? acc.z : 0.f; dz.w = hv.w > 0.f ? acc.w : 0.f;
+    return dz;
+}
+
+// dx epilogue of a lane that holds a row's <= 4 input gradients, with the optional backward of  a = scale * sigmoid(z):  dz = dx * a (1 - a / scale)
+__device__ __forceinline__ void store_dx(f32x4 accx, int ncol, const float* __restrict__ act_out, float scale, float* __restrict__ dx_out, int row) {
+    const float g[4] = {accx.x, accx.y, accx.z, accx.w};
+    for (int i = 0; i < ncol; i++) {
+        float v = g[i];
+        if (act_out) { const float a = act_out[(long)row * ncol + i]; v *= a * (1.f - a / scale); }
+        dx_out[(long)row * ncol + i] = v;
+    }
+}
+
+// The partial sums of a workgroup's NWS waves (lanes q == 0 hold the <= 4 sums of row nn) meet in scratch, `partial` =
+// [block][wave][64]: on the lanes `lead` (wave 0's lanes q == 0, which the caller tests for its epilogue anyway) the return value is
+// their sum in wave order (deterministic), elsewhere acc itself.  Every thread of the workgroup must call this (a barrier inside).
+template <int NWS>
+__device__ __forceinline__ f32x4 wave_sum(f32x4 acc, float* __restrict__ partial, int wave, int nn, int q, bool lead) {
+    float* pw = partial + ((long)blockIdx.x * NWS + wave) * 64;
+    if (q == 0) *(f32x4*)(pw + 4 * nn) = acc;
+    __threadfence_block();
+    __syncthreads();
+    if (lead) {
+        const rsrc_t rP = rsrc(partial + (long)blockIdx.x * NWS * 64, NWS * 64 * 4);
+#pragma unroll
+        for (int w = 1; w < NWS; w++) acc += ldq_glc(rP, (w * 64 + 4 * nn) * 4, 0);
+    }
+    return acc;
+}
+
+// ---- ONE WAVE = 16 batch rows, all layers in registers.  Layer 1's output quads (NT1 float4 registers) are the B operands of
+// layer 2; every layer-2 output quad feeds layer 3's MFMAs right away, so h2 is never stored.  The kernel is capped at 168 registers per lane (3 waves per SIMD): k_env_step holds all of a
 // CU's LDS and 344 of the 512 registers of every SIMD lane, so these waves can be resident BESIDE it and use the
 // matrix pipes and issue slots the stepping kernel leaves idle - the learner's forward-only passes run in its shadow
 // instead of waiting for its workgroups to retire.  Slower per wave than the LDS kernel (no split of the tiles over
-// four waves), which does not matter there.
-template <int NT1, int NT2, bool VEC>
+// four waves), which does not matter there.  (The host checks h1 % 16 == h2 % 16 == 0 for this form.)
+template <int NT1, int NT2>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_mlp3_wave(
     int n, int in_a, int in_b, int h1, int h2, int out_dim, const float* __restrict__ xa, int lda, const float* __restrict__ xb, int ldb,
     const float* __restrict__ W1, const float* __restrict__ b1, const float* __restrict__ W2, const float* __restrict__ b2,
@@ -118,36 +199,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) void
     const int row = blockIdx.x * ROWS + nn;
     const bool row_ok = row < n;
     const int in_dim = in_a + in_b;
-    // All operand reads are raw buffer loads: ONE 32-bit lane offset per matrix, the tile / k-step advance in the
-    // wave-uniform scalar offset, out-of-range reads return 0 in hardware.  The flat-load version spent 5 VALU + 7 SALU
-    // instructions (address arithmetic, bounds branches) per MFMA - issue slots this kernel shares with the stepping
-    // kernel's wave on the same SIMD.  (The host checks h1 % 16 == h2 % 16 == 0 for this variant.)
-    const auto rW1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(W1), 0, h1 * in_dim * 4, 0x00020000);
-    const auto rW2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(W2), 0, h2 * h1 * 4, 0x00020000);
-    const auto rW3 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(W3), 0, out_dim * h2 * 4, 0x00020000);
-    const auto rXa = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(xa), 0, ((n - 1) * lda + in_a) * 4, 0x00020000);
-    const auto rXb = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(xb ? xb : xa), 0, xb ? ((n - 1) * ldb + in_b) * 4 : 0, 0x00020000);
-#define KS_LDF(rsrc, voff, soff) __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsrc, voff, soff, 0))
+    const rsrc_t rW1 = rsrc(W1, h1 * in_dim * 4), rW2 = rsrc(W2, h2 * h1 * 4), rW3 = rsrc(W3, out_dim * h2 * 4);
     f32x4 h1r[NT1];
     {
-        // B operands of layer 1: the 16 input rows, k = 16 s + 4 q + j.  A row beyond n is out of the buffer's range (0).
-        // (the range check covers the LANE offset only, not the scalar offset: an element that does not exist gets an
-        //  out-of-range lane offset instead of relying on the sum)
-        constexpr int OOR = 0x7ffffff0;
         f32x4 bx[KS_IN_MAX];
-        const int oa = row * lda * 4 + 16 * q, ob = (row * ldb + 4 * q - in_a) * 4;
-#pragma unroll
-        for (int s = 0; s < KS_IN_MAX; s++) {
-            float v[4];
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                const int k = 16 * s + 4 * q + j;
-                const float fa = KS_LDF(rXa, (row_ok && k < in_a) ? oa : OOR, (16 * s + j) * 4);
-                const float fb = KS_LDF(rXb, (row_ok && k >= in_a && k < in_dim) ? ob + (16 * s + j) * 4 : OOR, 0);
-                v[j] = k < in_a ? fa : fb;
-            }
-            bx[s] = f32x4{v[0], v[1], v[2], v[3]};
-        }
+        input_quads(bx, n, row, q, in_a, in_b, xa, lda, xb, ldb);
         // A operands: W1[16 t + nn][16 s + 4 q + j], zero beyond in_dim
         const int o1 = (nn * in_dim + 4 * q) * 4;
 #pragma unroll
@@ -156,8 +212,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) void
 #pragma unroll
             for (int s = 0; s < KS_IN_MAX; s++) {
                 const int so = (16 * t * in_dim + 16 * s) * 4, k0 = 16 * s + 4 * q;
-                const f32x4 w = {KS_LDF(rW1, k0 < in_dim ? o1 : OOR, so), KS_LDF(rW1, k0 + 1 < in_dim ? o1 : OOR, so + 4),
-                                 KS_LDF(rW1, k0 + 2 < in_dim ? o1 : OOR, so + 8), KS_LDF(rW1, k0 + 3 < in_dim ? o1 : OOR, so + 12)};
+                const f32x4 w = {ldf(rW1, k0 < in_dim ? o1 : OOR, so), ldf(rW1, k0 + 1 < in_dim ? o1 : OOR, so + 4),
+                                 ldf(rW1, k0 + 2 < in_dim ? o1 : OOR, so + 8), ldf(rW1, k0 + 3 < in_dim ? o1 : OOR, so + 12)};
                 if (s & 1) acc1 = mfma4(w, bx[s], acc1);
                 else acc0 = mfma4(w, bx[s], acc0);
             }
@@ -167,14 +223,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) void
     }
     f32x4 acc3 = {0.f, 0.f, 0.f, 0.f};
     const int o2 = (nn * h1 + 4 * q) * 4;                       // W2[16 t + nn][16 s + 4 q ..]: 16-byte reads (h1 % 4 == 0)
-    const int o3 = (nn * h2 + 4 * q) * 4;                       // W3[nn][16 t + 4 q ..]: rows >= out_dim are out of range (0)
+    const int o3 = (nn * h2 + 4 * q) * 4;                       // W3[nn][16 t + 4 q ..]: rows >= out_dim do not exist
 #pragma unroll 1
-    for (int t = 0; t < NT2; t++) {
+    for (int t = 0; t < NT2; t ++) {
         f32x4 w[NT1];
 #pragma unroll
-        for (int s = 0; s < NT1; s++)
-            w[s] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rW2, o2, (16 * t * h1 + 16 * s) * 4, 0));
-        const f32x4 w3 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rW3, nn < out_dim ? o3 : 0x7ffffff0, 16 * t * 4, 0));   // rows >= out_dim do not exist
+        for (int s = 0; s < NT1; s++) w[s] = ldq(rW2, o2, (16 * t * h1 + 16 * s) * 4);
+        const f32x4 w3 = ldq(rW3, nn < out_dim ? o3 : OOR, 16 * t * 4);
         f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int s = 0; s < NT1; s++) {
@@ -185,25 +240,17 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) void
         if (h2_out && row_ok) *(f32x4*)(h2_out + (long)row * h2 + t * 16 + 4 * q) = hq;
         acc3 = mfma4(w3, hq, acc3);
     }
-#undef KS_LDF
-    if (q == 0 && row_ok) {
-        const float z[4] = {acc3.x, acc3.y, acc3.z, acc3.w};
-        for (int i = 0; i < out_dim; i++) {
-            float y = z[i] + b3[i];
-            if (act == KR_ACT_SIGMOID) y = scale / (1.f + __expf(-y));
-            out[(long)row * out_dim + i] = y;
-        }
-    }
+    if (q == 0 && row_ok) store_out(acc3, b3, act, scale, out, row, out_dim);
 }
 
-// ---- the LDS-free network with the tiles of a layer SPLIT over NWS waves of one workgroup (still 16 batch rows per workgroup).
+// ---- the tiles of a layer SPLIT over NWS waves of one workgroup (still 16 batch rows per workgroup).
 // One wave per 16 rows is a serial chain of ~1400 MFMAs fed by ~1400 weight loads: 87 us whatever the batch, and the learner's
 // five forward passes are more than half of an update that - early in training - is what an env-step waits for.  Here wave w
 // computes the layer-1 tiles t = w (mod NWS), the waves exchange their output quads through global memory (the caller's
 // h1_out, or scratch; L2 resident, read back with glc loads) across a workgroup barrier - no LDS, so the kernel still runs
 // beside the stepping kernel - then wave w computes the layer-2 tiles t = w (mod NWS) and its share of layer 3, whose partial
-// sums meet in scratch (summed in wave order: deterministic).  Per output element the layer-1 / layer-2 fma chains are those
-// of k_mlp3_wave; only layer 3's sum is associated differently.
+// sums meet in scratch (wave_sum).  Per output element the layer-1 / layer-2 fma chains are those of k_mlp3_wave; only layer
+// 3's sum is associated differently.
 template <int NT1, int NT2, int NWS>
 __global__ __launch_bounds__(64 * NWS) __attribute__((amdgpu_waves_per_eu(KS_SPLIT_WAVES_PER_EU, KS_SPLIT_WAVES_PER_EU))) void k_mlp3_split(
     int n, int in_a, int in_b, int h1, int h2, int out_dim, const float* __restrict__ xa, int lda, const float* __restrict__ xb, int ldb,
@@ -214,38 +261,19 @@ __global__ __launch_bounds__(64 * NWS) __attribute__((amdgpu_waves_per_eu(KS_SPL
     const int row = blockIdx.x * ROWS + nn;
     const bool row_ok = row < n;
     const int in_dim = in_a + in_b;
-    const auto rW1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(W1), 0, h1 * in_dim * 4, 0x00020000);
-    const auto rW2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(W2), 0, h2 * h1 * 4, 0x00020000);
-    const auto rW3 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(W3), 0, out_dim * h2 * 4, 0x00020000);
-    const auto rXa = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(xa), 0, ((n - 1) * lda + in_a) * 4, 0x00020000);
-    const auto rXb = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(xb ? xb : xa), 0, xb ? ((n - 1) * ldb + in_b) * 4 : 0, 0x00020000);
-    const auto rH1 = __builtin_amdgcn_make_buffer_rsrc(h1buf, 0, h1_rows * h1 * 4, 0x00020000);
-#define KS_LDF(rsrc, voff, soff) __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsrc, voff, soff, 0))
-    constexpr int OOR = 0x7ffffff0;
+    const rsrc_t rW1 = rsrc(W1, h1 * in_dim * 4), rW2 = rsrc(W2, h2 * h1 * 4), rW3 = rsrc(W3, out_dim * h2 * 4), rH1 = rsrc(h1buf, h1_rows * h1 * 4);
     {
         f32x4 bx[KS_IN_MAX];
-        const int oa = row * lda * 4 + 16 * q, ob = (row * ldb + 4 * q - in_a) * 4;
-#pragma unroll
-        for (int s = 0; s < KS_IN_MAX; s++) {
-            float v[4];
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                const int k = 16 * s + 4 * q + j;
-                const float fa = KS_LDF(rXa, (row_ok && k < in_a) ? oa : OOR, (16 * s + j) * 4);
-                const float fb = KS_LDF(rXb, (row_ok && k >= in_a && k < in_dim) ? ob + (16 * s + j) * 4 : OOR, 0);
-                v[j] = k < in_a ? fa : fb;
-            }
-            bx[s] = f32x4{v[0], v[1], v[2], v[3]};
-        }
-        const int o1 = (nn * in_dim + 4 * q) * 4;
+        input_quads(bx, n, row, q, in_a, in_b, xa, lda, xb, ldb);
+        const int o1 = (nn * in_dim + 4 * q) * 4;                 // (the tiles of k_mlp3_wave, this wave's share)
 #pragma unroll 1
         for (int t = wave; t < NT1; t += NWS) {
             f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int s = 0; s < KS_IN_MAX; s++) {
                 const int so = (16 * t * in_dim + 16 * s) * 4, k0 = 16 * s + 4 * q;
-                const f32x4 w = {KS_LDF(rW1, k0 < in_dim ? o1 : OOR, so), KS_LDF(rW1, k0 + 1 < in_dim ? o1 : OOR, so + 4),
-                                 KS_LDF(rW1, k0 + 2 < in_dim ? o1 : OOR, so + 8), KS_LDF(rW1, k0 + 3 < in_dim ? o1 : OOR, so + 12)};
+                const f32x4 w = {ldf(rW1, k0 < in_dim ? o1 : OOR, so), ldf(rW1, k0 + 1 < in_dim ? o1 : OOR, so + 4),
+                                 ldf(rW1, k0 + 2 < in_dim ? o1 : OOR, so + 8), ldf(rW1, k0 + 3 < in_dim ? o1 : OOR, so + 12)};
                 if (s & 1) acc1 = mfma4(w, bx[s], acc1);
                 else acc0 = mfma4(w, bx[s], acc0);
             }
@@ -260,18 +288,16 @@ __global__ __launch_bounds__(64 * NWS) __attribute__((amdgpu_waves_per_eu(KS_SPL
     {
         const int oh = row < h1_rows ? (row * h1 + 4 * q) * 4 : OOR;
 #pragma unroll
-        for (int s = 0; s < NT1; s++) h1r[s] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rH1, oh, 16 * s * 4, 1));
+        for (int s = 0; s < NT1; s++) h1r[s] = ldq_glc(rH1, oh, 16 * s * 4);
     }
     f32x4 acc3 = {0.f, 0.f, 0.f, 0.f};
-    const int o2 = (nn * h1 + 4 * q) * 4;
-    const int o3 = (nn * h2 + 4 * q) * 4;
+    const int o2 = (nn * h1 + 4 * q) * 4, o3 = (nn * h2 + 4 * q) * 4;
 #pragma unroll 1
-    for (int t = wave; t < NT2; t += NWS) {
+    for (int t = wave; t < NT2; t += NWS) {                     // (the layer-2 / layer-3 tile loop of k_mlp3_wave, this wave's share)
         f32x4 w[NT1];
 #pragma unroll
-        for (int s = 0; s < NT1; s++)
-            w[s] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rW2, o2, (16 * t * h1 + 16 * s) * 4, 0));
-        const f32x4 w3 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rW3, nn < out_dim ? o3 : OOR, 16 * t * 4, 0));
+        for (int s = 0; s < NT1; s++) w[s] = ldq(rW2, o2, (16 * t * h1 + 16 * s) * 4);
+        const f32x4 w3 = ldq(rW3, nn < out_dim ? o3 : OOR, 16 * t * 4);
         f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int s = 0; s < NT1; s++) {
@@ -282,138 +308,26 @@ __global__ __launch_bounds__(64 * NWS) __attribute__((amdgpu_waves_per_eu(KS_SPL
         if (h2_out && row_ok) *(f32x4*)(h2_out + (long)row * h2 + t * 16 + 4 * q) = hq;
         acc3 = mfma4(w3, hq, acc3);
     }
-#undef KS_LDF
-    // layer 3: the waves' partial sums (lanes q == 0 hold the <= 4 outputs of row nn) meet in scratch
-    float* pw = partial + ((long)blockIdx.x * NWS + wave) * 64;
-    if (q == 0) *(f32x4*)(pw + 4 * nn) = acc3;
-    __threadfence_block();
-    __syncthreads();
-    if (wave == 0 && q == 0 && row_ok) {
-        const auto rP = __builtin_amdgcn_make_buffer_rsrc(partial + (long)blockIdx.x * NWS * 64, 0, NWS * 64 * 4, 0x00020000);
-        f32x4 z4 = acc3;
-#pragma unroll
-        for (int w = 1; w < NWS; w++) {
-            const f32x4 p = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rP, (w * 64 + 4 * nn) * 4, 0, 1));
-            z4 += p;
-        }
-        const float z[4] = {z4.x, z4.y, z4.z, z4.w};
-        for (int i = 0; i < out_dim; i++) {
-            float y = z[i] + b3[i];
-            if (act == KR_ACT_SIGMOID) y = scale / (1.f + __expf(-y));
-            out[(long)row * out_dim + i] = y;
-        }
-    }
+    const f32x4 z4 = wave_sum<NWS>(acc3, partial, wave, nn, q, wave == 0 && q == 0);
+    if (wave == 0 && q == 0 && row_ok) store_out(z4, b3, act, scale, out, row, out_dim);
 }
 
-// ---- backward of the same network, also without LDS (one wave = 16 batch rows).
+// ---- backward of the same network, also without LDS: one wave = 16 batch rows (NWS = 1, k_mlp3_bwd_wave), or the tiles of dz1
+// split over the NWS waves of a workgroup as in k_mlp3_split (k_mlp3_bwd_split).
 // Data gradients: with dz3 = dLoss/d(output pre-activation) [n, out_dim],
 //     dz2 = (dz3 W3) * [h2 > 0],   dz1 = (dz2 W2) * [h1 > 0],   dx = dz1 W1[:, col0 : col0 + ncol]   (optional)
 // again in the transposed orientation: dh^T = W^T dz^T, A = W^T (16 features of the layer below x 4 k), B = dz^T
 // (4 k x 16 rows); the masked output quads are the next product's B operands, exactly as in the forward kernel.
 // dx (<= 4 columns: the action inputs of the critic, DDPGfD.py:345-349) can be followed in the epilogue by the
-// backward of  a = scale * sigmoid(z):  dz = dx * a (1 - a / scale)  (kr_sigmoid_scale_backward), which makes it the
-// dz3 of the actor.  dz2_out / dz1_out may be NULL when only dx is wanted.
-template <int NT1, int NT2>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_mlp3_bwd_wave(
-    int n, int in_dim, int h1, int h2, int out_dim, const float* __restrict__ dz3, const float* __restrict__ W3, const float* __restrict__ h2a,
-    const float* __restrict__ W2, const float* __restrict__ h1a, float* __restrict__ dz2_out, float* __restrict__ dz1_out,
-    const float* __restrict__ W1, int col0, int ncol, const float* __restrict__ act_out, float scale, float* __restrict__ dx_out) {
-    const int lane = threadIdx.x & 63, nn = lane & 15, q = lane >> 4;
-    const int row = blockIdx.x * ROWS + nn;
-    const bool row_ok = row < n;
-    // B operand of the first product: dz3^T, k = output index = q
-    const float b3 = (row_ok && q < out_dim) ? dz3[(long)row * out_dim + q] : 0.f;
-    f32x4 dz2r[NT2];
-#pragma unroll
-    for (int t = 0; t < NT2; t++) {
-        const int f = t * 16 + nn;                                          // A: W3^T[f][k = q] = W3[q][f]
-        const float a3 = (q < out_dim && f < h2) ? W3[(long)q * h2 + f] : 0.f;
-        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a3, b3, acc, 0, 0, 0);
-        const int f4 = t * 16 + 4 * q;
-        f32x4 hv = {0.f, 0.f, 0.f, 0.f};
-        if (row_ok && f4 < h2) hv = *(const f32x4*)(h2a + (long)row * h2 + f4);
-        f32x4 dz;
-        dz.x = hv.x > 0.f ? acc.x : 0.f; dz.y = hv.y > 0.f ? acc.y : 0.f; dz.z = hv.z > 0.f ? acc.z : 0.f; dz.w = hv.w > 0.f ? acc.w : 0.f;
-        dz2r[t] = dz;
-        if (dz2_out && row_ok && f4 < h2) *(f32x4*)(dz2_out + (long)row * h2 + f4) = dz;
-    }
-    f32x4 accx = {0.f, 0.f, 0.f, 0.f};
-    const __amdgpu_buffer_rsrc_t rW2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(W2), 0, h1 * h2 * 4, 0x00020000);
-#pragma unroll 1
-    for (int t = 0; t < NT1; t++) {
-        // A: W2^T[f][k] = W2[k][f], k = 16 s + 4 q + j (rows of W2, stride h1), f = 16 t + nn
-        const int f = t * 16 + nn;
-        // (host checks h1 % 16 == h2 % 16 == 0: every row / column of the tile exists).  Buffer loads: ONE 32-bit lane
-        // offset for the whole tile, the row steps (16 s + j) * h1 are wave-uniform and go in the scalar offset - flat
-        // loads would hold a 64-bit address per load in flight and spill at this register budget.
-        f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-        const int voff = (4 * q * h1 + f) * 4;
-        constexpr int HALF = (NT2 + 1) / 2;
-#pragma unroll
-        for (int half = 0; half < 2; half++) {
-            f32x4 w[HALF];
-#pragma unroll
-            for (int u = 0; u < HALF; u++) {
-                const int s = half * HALF + u;
-                f32x4 v = {0.f, 0.f, 0.f, 0.f};
-                if (s < NT2) {
-                    v.x = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rW2, voff, (16 * s + 0) * h1 * 4, 0));
-                    v.y = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rW2, voff, (16 * s + 1) * h1 * 4, 0));
-                    v.z = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rW2, voff, (16 * s + 2) * h1 * 4, 0));
-                    v.w = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rW2, voff, (16 * s + 3) * h1 * 4, 0));
-                }
-                w[u] = v;
-            }
-#pragma unroll
-            for (int u = 0; u < HALF; u++) {
-                const int s = half * HALF + u;
-                if (s < NT2) {
-                    if (s & 1) acc1 = mfma4(w[u], dz2r[s], acc1);
-                    else acc0 = mfma4(w[u], dz2r[s], acc0);
-                }
-            }
-        }
-        const f32x4 acc = acc0 + acc1;
-        const int f4 = t * 16 + 4 * q;
-        f32x4 hv = {0.f, 0.f, 0.f, 0.f};
-        if (row_ok && f4 < h1) hv = *(const f32x4*)(h1a + (long)row * h1 + f4);
-        f32x4 dz;
-        dz.x = hv.x > 0.f ? acc.x : 0.f; dz.y = hv.y > 0.f ? acc.y : 0.f; dz.z = hv.z > 0.f ? acc.z : 0.f; dz.w = hv.w > 0.f ? acc.w : 0.f;
-        if (dz1_out && row_ok && f4 < h1) *(f32x4*)(dz1_out + (long)row * h1 + f4) = dz;
-        if (dx_out) {
-            // A: W1[:, col0 + m]^T: [m][k] = W1[k][col0 + m], k = 16 t + 4 q + j (rows of W1, stride in_dim), m = nn < ncol
-            f32x4 v = {0.f, 0.f, 0.f, 0.f};
-            if (nn < ncol) {
-                const int k = 16 * t + 4 * q;
-                const float* p = W1 + (long)k * in_dim + col0 + nn;
-                if (k < h1) v.x = p[0];
-                if (k + 1 < h1) v.y = p[in_dim];
-                if (k + 2 < h1) v.z = p[2 * (long)in_dim];
-                if (k + 3 < h1) v.w = p[3 * (long)in_dim];
-            }
-            accx = mfma4(v, dz, accx);
-        }
-    }
-    if (dx_out && q == 0 && row_ok) {
-        const float g[4] = {accx.x, accx.y, accx.z, accx.w};
-        for (int i = 0; i < ncol; i++) {
-            float v = g[i];
-            if (act_out) { const float a = act_out[(long)row * ncol + i]; v *= a * (1.f - a / scale); }
-            dx_out[(long)row * ncol + i] = v;
-        }
-    }
-}
-
-// ... and with the tiles of dz1 split over NWS waves of a workgroup (as k_mlp3_split): every wave computes dz2 itself (one MFMA per
-// tile), wave w the dz1 tiles t = w (mod NWS); the partial sums of dx meet in scratch, summed in wave order.
+// backward of  a = scale * sigmoid(z)  (store_dx; kr_sigmoid_scale_backward), which makes it the dz3 of the actor.
+// dz2_out / dz1_out may be NULL when only dx is wanted.  Every wave computes dz2 itself (one MFMA per tile), wave w the dz1
+// tiles t = w (mod NWS); the partial sums of dx meet in scratch (wave_sum), which NWS = 1 does without.
 template <int NT1, int NT2, int NWS>
-__global__ __launch_bounds__(64 * NWS) __attribute__((amdgpu_waves_per_eu(KS_SPLIT_WAVES_PER_EU, KS_SPLIT_WAVES_PER_EU))) void k_mlp3_bwd_split(
-    int n, int in_dim, int h1, int h2, int out_dim, const float* __restrict__ dz3, const float* __restrict__ W3, const float* __restrict__ h2a,
-    const float* __restrict__ W2, const float* __restrict__ h1a, float* __restrict__ dz2_out, float* __restrict__ dz1_out,
-    const float* __restrict__ W1, int col0, int ncol, const float* __restrict__ act_out, float scale, float* __restrict__ dx_out,
-    float* __restrict__ partial) {
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, nn = lane & 15, q = lane >> 4;
+__device__ __forceinline__ void mlp3_bwd_rows16(int n, int in_dim, int h1, int h2, int out_dim, const float* __restrict__ dz3, const float* __restrict__ W3,
+                                                const float* __restrict__ h2a, const float* __restrict__ W2, const float* __restrict__ h1a,
+                                                float* __restrict__ dz2_out, float* __restrict__ dz1_out, const float* __restrict__ W1, int col0, int ncol,
+                                                const float* __restrict__ act_out, float scale, float* __restrict__ dx_out, float* __restrict__ partial) {
+    const int wave = NWS == 1 ? 0 : threadIdx.x >> 6, lane = threadIdx.x & 63, nn = lane & 15, q = lane >> 4;
     const int row = blockIdx.x * ROWS + nn;
     const bool row_ok = row < n;
     // B operand of the first product: dz3^T, k = output index = q
@@ -428,20 +342,20 @@ __global__ __launch_bounds__(64 * NWS) __attribute__((amdgpu_waves_per_eu(KS_SPL
         const int f4 = t * 16 + 4 * q;
         f32x4 hv = {0.f, 0.f, 0.f, 0.f};
         if (row_ok && f4 < h2) hv = *(const f32x4*)(h2a + (long)row * h2 + f4);
-        f32x4 dz;
-        dz.x = hv.x > 0.f ? acc.x : 0.f; dz.y = hv.y > 0.f ? acc.y : 0.f; dz.z = hv.z > 0.f ? acc.z : 0.f; dz.w = hv.w > 0.f ? acc.w : 0.f;
+        const f32x4 dz = relu_mask(hv, acc);
         dz2r[t] = dz;
-        if (dz2_out && row_ok && f4 < h2 && t % NWS == wave) *(f32x4*)(dz2_out + (long)row * h2 + f4) = dz;
+        if (dz2_out && row_ok && f4 < h2 && (NWS == 1 || t % NWS == wave)) *(f32x4*)(dz2_out + (long)row * h2 + f4) = dz;
     }
     f32x4 accx = {0.f, 0.f, 0.f, 0.f};
-    const __amdgpu_buffer_rsrc_t rW2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(W2), 0, h1 * h2 * 4, 0x00020000);
+    const rsrc_t rW2 = rsrc(W2, h1 * h2 * 4);
 #pragma unroll 1
     for (int t = wave; t < NT1; t += NWS) {
         // A: W2^T[f][k] = W2[k][f], k = 16 s + 4 q + j (rows of W2, stride h1), f = 16 t + nn
         const int f = t * 16 + nn;
         // (host checks h1 % 16 == h2 % 16 == 0: every row / column of the tile exists).  Buffer loads: ONE 32-bit lane
         // offset for the whole tile, the row steps (16 s + j) * h1 are wave-uniform and go in the scalar offset - flat
-        // loads would hold a 64-bit address per load in flight and spill at this register budget.
+        // loads would hold a 64-bit address per load in flight and spill at this register budget.  (The load builtin as it
+        // stands: through kmlp::ldf the split instantiations at 64-64 and 128-128 allocate 1 - 3 more registers.)
         f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
         const int voff = (4 * q * h1 + f) * 4;
         constexpr int HALF = (NT2 + 1) / 2;
@@ -473,8 +387,7 @@ __global__ __launch_bounds__(64 * NWS) __attribute__((amdgpu_waves_per_eu(KS_SPL
         const int f4 = t * 16 + 4 * q;
         f32x4 hv = {0.f, 0.f, 0.f, 0.f};
         if (row_ok && f4 < h1) hv = *(const f32x4*)(h1a + (long)row * h1 + f4);
-        f32x4 dz;
-        dz.x = hv.x > 0.f ? acc.x : 0.f; dz.y = hv.y > 0.f ? acc.y : 0.f; dz.z = hv.z > 0.f ? acc.z : 0.f; dz.w = hv.w > 0.f ? acc.w : 0.f;
+        const f32x4 dz = relu_mask(hv, acc);
         if (dz1_out && row_ok && f4 < h1) *(f32x4*)(dz1_out + (long)row * h1 + f4) = dz;
         if (dx_out) {
             // A: W1[:, col0 + m]^T: [m][k] = W1[k][col0 + m], k = 16 t + 4 q + j (rows of W1, stride in_dim), m = nn < ncol
@@ -490,28 +403,30 @@ __global__ __launch_bounds__(64 * NWS) __attribute__((amdgpu_waves_per_eu(KS_SPL
             accx = mfma4(v, dz, accx);
         }
     }
-    if (dx_out) {
-        float* pw = partial + ((long)blockIdx.x * NWS + wave) * 64;
-        if (q == 0) *(f32x4*)(pw + 4 * nn) = accx;
-        __threadfence_block();
-        __syncthreads();
-        if (wave == 0 && q == 0) {
-            const auto rP = __builtin_amdgcn_make_buffer_rsrc(partial + (long)blockIdx.x * NWS * 64, 0, NWS * 64 * 4, 0x00020000);
-#pragma unroll
-            for (int w = 1; w < NWS; w++) accx += __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rP, (w * 64 + 4 * nn) * 4, 0, 1));
-        }
+    if constexpr (NWS > 1) {
+        if (dx_out) accx = wave_sum<NWS>(accx, partial, wave, nn, q, wave == 0 && q == 0);
     }
-    if (dx_out && wave == 0 && q == 0 && row_ok) {
-        const float g[4] = {accx.x, accx.y, accx.z, accx.w};
-        for (int i = 0; i < ncol; i++) {
-            float v = g[i];
-            if (act_out) { const float a = act_out[(long)row * ncol + i]; v *= a * (1.f - a / scale); }
-            dx_out[(long)row * ncol + i] = v;
-        }
-    }
+    if (dx_out && wave == 0 && q == 0 && row_ok) store_dx(accx, ncol, act_out, scale, dx_out, row);
 }
 
-// ---- the LEAN LDS-free kernels: the same forward and backward for tile pairs too wide for k_mlp3_wave / k_mlp3_bwd_wave, which keep
+template <int NT1, int NT2>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_mlp3_bwd_wave(
+    int n, int in_dim, int h1, int h2, int out_dim, const float* __restrict__ dz3, const float* __restrict__ W3, const float* __restrict__ h2a,
+    const float* __restrict__ W2, const float* __restrict__ h1a, float* __restrict__ dz2_out, float* __restrict__ dz1_out,
+    const float* __restrict__ W1, int col0, int ncol, const float* __restrict__ act_out, float scale, float* __restrict__ dx_out) {
+    mlp3_bwd_rows16<NT1, NT2, 1>(n, in_dim, h1, h2, out_dim, dz3, W3, h2a, W2, h1a, dz2_out, dz1_out, W1, col0, ncol, act_out, scale, dx_out, nullptr);
+}
+
+template <int NT1, int NT2, int NWS>
+__global__ __launch_bounds__(64 * NWS) __attribute__((amdgpu_waves_per_eu(KS_SPLIT_WAVES_PER_EU, KS_SPLIT_WAVES_PER_EU))) void k_mlp3_bwd_split(
+    int n, int in_dim, int h1, int h2, int out_dim, const float* __restrict__ dz3, const float* __restrict__ W3, const float* __restrict__ h2a,
+    const float* __restrict__ W2, const float* __restrict__ h1a, float* __restrict__ dz2_out, float* __restrict__ dz1_out,
+    const float* __restrict__ W1, int col0, int ncol, const float* __restrict__ act_out, float scale, float* __restrict__ dx_out,
+    float* __restrict__ partial) {
+    mlp3_bwd_rows16<NT1, NT2, NWS>(n, in_dim, h1, h2, out_dim, dz3, W3, h2a, W2, h1a, dz2_out, dz1_out, W1, col0, ncol, act_out, scale, dx_out, partial);
+}
+
+// ---- the LEAN kernels: the same forward and backward for tile pairs too wide for k_mlp3_wave / k_mlp3_bwd_wave, which keep
 // a whole hidden layer in registers (at 25 tiles that alone is 100).  The free-running rollout kernel at the reference's 400-300
 // (k_rollout<25,19>) holds 416 of the 512 registers of every SIMD lane for a whole launch: a learner wave is resident beside it
 // only at <= 96, and these two kernels are capped there (amdgpu_waves_per_eu(5, 5): 512 / 5, rounded down to the allocation
@@ -525,12 +440,9 @@ __global__ __launch_bounds__(64 * NWS) __attribute__((amdgpu_waves_per_eu(KS_SPL
 // reduction - gets an out-of-range LANE offset, so it is read as zero and never touches memory (the tile and k steps sit in the
 // scalar offset, which the hardware's range check does not cover: the end of the buffer protects nothing), and is never stored.
 constexpr int LEAN_KC = 5;                   // k-steps per load round: 3 quads x 5 = 60 registers of operands in flight
-constexpr int LEAN_OOR = 0x7ffffff0;
 #define KS_LEAN_ATTR __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5)))
-#define KS_LDF(rsrc, voff, soff) __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsrc, voff, soff, 0))
 // all loads of a round are issued before its first MFMA: left alone, the scheduler interleaves them and waits for each in turn
 #define KS_LEAN_LOADS_FIRST() __builtin_amdgcn_sched_barrier(0)
-#define KS_LDQ(rsrc, voff, soff, aux) __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, soff, aux))
 
 template <int NT1, int NT2>
 __global__ KS_LEAN_ATTR void k_mlp3_lean(
@@ -542,16 +454,16 @@ __global__ KS_LEAN_ATTR void k_mlp3_lean(
     const int row = blockIdx.x * ROWS + nn;
     const bool row_ok = row < n;
     const int in_dim = in_a + in_b;
-    constexpr int OOR = LEAN_OOR;
     const auto rW1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(W1), 0, h1 * in_dim * 4, 0x00020000);
     const auto rW2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(W2), 0, h2 * h1 * 4, 0x00020000);
     const auto rW3 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(W3), 0, out_dim * h2 * 4, 0x00020000);
     const auto rH1 = __builtin_amdgcn_make_buffer_rsrc(h1buf, 0, h1_rows * h1 * 4, 0x00020000);
     {
+        f32x4 bx[KS_IN_MAX];
         const auto rXa = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(xa), 0, ((n - 1) * lda + in_a) * 4, 0x00020000);
         const auto rXb = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(xb ? xb : xa), 0, xb ? ((n - 1) * ldb + in_b) * 4 : 0, 0x00020000);
-        // B operands of layer 1 (as k_mlp3_wave): the 16 input rows, k = 16 s + 4 q + j
-        f32x4 bx[KS_IN_MAX];
+        // B operands of layer 1: input_quads written out, as are this kernel's resources and its output epilogue - through the helpers
+        // the compiler schedules its load rounds 1 - 3 % slower (profiles/mlp_front_end.txt)
         const int oa = row * lda * 4 + 16 * q, ob = (row * ldb + 4 * q - in_a) * 4;
 #pragma unroll
         for (int s = 0; s < KS_IN_MAX; s++) {
@@ -559,8 +471,8 @@ __global__ KS_LEAN_ATTR void k_mlp3_lean(
 #pragma unroll
             for (int j = 0; j < 4; j++) {
                 const int k = 16 * s + 4 * q + j;
-                const float fa = KS_LDF(rXa, (row_ok && k < in_a) ? oa : OOR, (16 * s + j) * 4);
-                const float fb = KS_LDF(rXb, (row_ok && k >= in_a && k < in_dim) ? ob + (16 * s + j) * 4 : OOR, 0);
+                const float fa = ldf(rXa, (row_ok && k < in_a) ? oa : OOR, (16 * s + j) * 4);
+                const float fb = ldf(rXb, (row_ok && k >= in_a && k < in_dim) ? ob + (16 * s + j) * 4 : OOR, 0);
                 v[j] = k < in_a ? fa : fb;
             }
             bx[s] = f32x4{v[0], v[1], v[2], v[3]};
@@ -575,8 +487,8 @@ __global__ KS_LEAN_ATTR void k_mlp3_lean(
 #pragma unroll
             for (int s = 0; s < KS_IN_MAX; s++) {
                 const int so = (16 * t * in_dim + 16 * s) * 4, k0 = 16 * s + 4 * q;
-                w[s] = f32x4{KS_LDF(rW1, (rok && k0 < in_dim) ? o1 : OOR, so), KS_LDF(rW1, (rok && k0 + 1 < in_dim) ? o1 : OOR, so + 4),
-                             KS_LDF(rW1, (rok && k0 + 2 < in_dim) ? o1 : OOR, so + 8), KS_LDF(rW1, (rok && k0 + 3 < in_dim) ? o1 : OOR, so + 12)};
+                w[s] = f32x4{ldf(rW1, (rok && k0 < in_dim) ? o1 : OOR, so), ldf(rW1, (rok && k0 + 1 < in_dim) ? o1 : OOR, so + 4),
+                             ldf(rW1, (rok && k0 + 2 < in_dim) ? o1 : OOR, so + 8), ldf(rW1, (rok && k0 + 3 < in_dim) ? o1 : OOR, so + 12)};
             }
             KS_LEAN_LOADS_FIRST();
 #pragma unroll
@@ -606,9 +518,9 @@ __global__ KS_LEAN_ATTR void k_mlp3_lean(
             for (int u = 0; u < LEAN_KC; u++) {
                 const int s = c * LEAN_KC + u;
                 const bool kok = (NT1 % LEAN_KC == 0 || s < NT1) && 16 * s + 4 * q < h1;
-                hb[u] = KS_LDQ(rH1, kok ? oh : OOR, 16 * s * 4, 1);
-                wa[u] = KS_LDQ(rW2, kok ? oa : OOR, (16 * t * h1 + 16 * s) * 4, 0);
-                wb[u] = KS_LDQ(rW2, kok ? ob : OOR, (16 * (t + 1) * h1 + 16 * s) * 4, 0);
+                hb[u] = ldq_glc(rH1, kok ? oh : OOR, 16 * s * 4);
+                wa[u] = ldq(rW2, kok ? oa : OOR, (16 * t * h1 + 16 * s) * 4);
+                wb[u] = ldq(rW2, kok ? ob : OOR, (16 * (t + 1) * h1 + 16 * s) * 4);
             }
             KS_LEAN_LOADS_FIRST();
 #pragma unroll
@@ -622,7 +534,7 @@ __global__ KS_LEAN_ATTR void k_mlp3_lean(
             const int f4 = (t + u) * 16 + 4 * q;
             const f32x4 hq = bias_relu(u ? accb : acca, b2, f4, h2);
             if (h2_out && row_ok && f4 < h2) *(f32x4*)(h2_out + (long)row * h2 + f4) = hq;
-            const f32x4 w3 = KS_LDQ(rW3, (nn < out_dim && f4 < h2) ? o3 : OOR, 16 * (t + u) * 4, 0);
+            const f32x4 w3 = ldq(rW3, (nn < out_dim && f4 < h2) ? o3 : OOR, 16 * (t + u) * 4);
             acc3 = mfma4(w3, hq, acc3);
         }
     }
@@ -641,17 +553,13 @@ __global__ KS_LEAN_ATTR void k_mlp3_lean(
 template <int NT1, int NT2>
 __global__ KS_LEAN_ATTR void k_mlp3_bwd_lean(
     int n, int in_dim, int h1, int h2, int out_dim, const float* __restrict__ dz3, const float* __restrict__ W3, const float* __restrict__ h2a,
-    const float* __restrict__ W2, const float* __restrict__ h1a, float* __restrict__ dz2buf, int dz2_rows, float* __restrict__ dz1_out,
-    const float* __restrict__ W1, int col0, int ncol, const float* __restrict__ act_out, float scale, float* __restrict__ dx_out) {
+    const float* __restrict__ W2, const float* __restrict__ h1a, float* __restrict__ dz2buf, float* __restrict__ dz1_out,
+    const float* __restrict__ W1, int col0, int ncol, const float* __restrict__ act_out, float scale, float* __restrict__ dx_out, int dz2_rows) {
     const int lane = threadIdx.x & 63, nn = lane & 15, q = lane >> 4;
     const int row = blockIdx.x * ROWS + nn;
     const bool row_ok = row < n;
-    constexpr int OOR = LEAN_OOR;
-    const auto rW3 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(W3), 0, out_dim * h2 * 4, 0x00020000);
-    const auto rW2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(W2), 0, h2 * h1 * 4, 0x00020000);
-    const auto rH2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(h2a), 0, n * h2 * 4, 0x00020000);
-    const auto rH1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(h1a), 0, n * h1 * 4, 0x00020000);
-    const auto rD2 = __builtin_amdgcn_make_buffer_rsrc(dz2buf, 0, dz2_rows * h2 * 4, 0x00020000);
+    const rsrc_t rW3 = rsrc(W3, out_dim * h2 * 4), rW2 = rsrc(W2, h2 * h1 * 4), rH2 = rsrc(h2a, n * h2 * 4), rH1 = rsrc(h1a, n * h1 * 4),
+                 rD2 = rsrc(dz2buf, dz2_rows * h2 * 4);
     // B operand of the first product: dz3^T, k = output index = q
     const float b3 = (row_ok && q < out_dim) ? dz3[(long)row * out_dim + q] : 0.f;
     {
@@ -664,8 +572,8 @@ __global__ KS_LEAN_ATTR void k_mlp3_bwd_lean(
 #pragma unroll
             for (int u = 0; u < 4; u++) {
                 const int t = t0 + u;
-                a3[u] = KS_LDF(rW3, (q < out_dim && 16 * t + nn < h2) ? o3 : OOR, 16 * t * 4);
-                hv[u] = KS_LDQ(rH2, 16 * t + 4 * q < h2 ? oh2 : OOR, 16 * t * 4, 0);
+                a3[u] = ldf(rW3, (q < out_dim && 16 * t + nn < h2) ? o3 : OOR, 16 * t * 4);
+                hv[u] = ldq(rH2, 16 * t + 4 * q < h2 ? oh2 : OOR, 16 * t * 4);
             }
             KS_LEAN_LOADS_FIRST();
 #pragma unroll
@@ -673,15 +581,14 @@ __global__ KS_LEAN_ATTR void k_mlp3_bwd_lean(
                 const int f4 = (t0 + u) * 16 + 4 * q;
                 f32x4 acc = {0.f, 0.f, 0.f, 0.f};
                 acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a3[u], b3, acc, 0, 0, 0);
-                f32x4 dz;
-                dz.x = hv[u].x > 0.f ? acc.x : 0.f; dz.y = hv[u].y > 0.f ? acc.y : 0.f; dz.z = hv[u].z > 0.f ? acc.z : 0.f; dz.w = hv[u].w > 0.f ? acc.w : 0.f;
+                const f32x4 dz = relu_mask(hv[u], acc);
                 if (f4 < h2 && row < dz2_rows) *(f32x4*)(dz2buf + (long)row * h2 + f4) = dz;
             }
         }
     }
     __threadfence_block();          // read back below by the lane that stored them (glc loads)
     f32x4 accx = {0.f, 0.f, 0.f, 0.f};
-    const auto rW1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(W1 ? W1 : W2), 0, W1 ? h1 * in_dim * 4 : 0, 0x00020000);
+    const rsrc_t rW1 = rsrc(W1 ? W1 : W2, W1 ? h1 * in_dim * 4 : 0);
     const int od = row < dz2_rows ? (row * h2 + 4 * q) * 4 : OOR;
     const int oh1 = row_ok ? (row * h1 + 4 * q) * 4 : OOR;
     constexpr int NC = (NT2 + LEAN_KC - 1) / LEAN_KC;
@@ -698,11 +605,11 @@ __global__ KS_LEAN_ATTR void k_mlp3_bwd_lean(
                 const int s = c * LEAN_KC + u;
                 const bool kok = (NT2 % LEAN_KC == 0 || s < NT2) && 16 * s + 4 * q < h2;       // h2 % 4 == 0: a quad exists as a whole
                 const int ka = kok ? va : OOR, kb = kok ? vb : OOR;
-                db[u] = KS_LDQ(rD2, kok ? od : OOR, 16 * s * 4, 1);
-                wa[u] = f32x4{KS_LDF(rW2, ka, (16 * s + 0) * h1 * 4), KS_LDF(rW2, ka, (16 * s + 1) * h1 * 4), KS_LDF(rW2, ka, (16 * s + 2) * h1 * 4),
-                              KS_LDF(rW2, ka, (16 * s + 3) * h1 * 4)};
-                wb[u] = f32x4{KS_LDF(rW2, kb, (16 * s + 0) * h1 * 4), KS_LDF(rW2, kb, (16 * s + 1) * h1 * 4), KS_LDF(rW2, kb, (16 * s + 2) * h1 * 4),
-                              KS_LDF(rW2, kb, (16 * s + 3) * h1 * 4)};
+                db[u] = ldq_glc(rD2, kok ? od : OOR, 16 * s * 4);
+                wa[u] = f32x4{ldf(rW2, ka, (16 * s + 0) * h1 * 4), ldf(rW2, ka, (16 * s + 1) * h1 * 4), ldf(rW2, ka, (16 * s + 2) * h1 * 4),
+                              ldf(rW2, ka, (16 * s + 3) * h1 * 4)};
+                wb[u] = f32x4{ldf(rW2, kb, (16 * s + 0) * h1 * 4), ldf(rW2, kb, (16 * s + 1) * h1 * 4), ldf(rW2, kb, (16 * s + 2) * h1 * 4),
+                              ldf(rW2, kb, (16 * s + 3) * h1 * 4)};
             }
             KS_LEAN_LOADS_FIRST();
 #pragma unroll
@@ -714,31 +621,20 @@ __global__ KS_LEAN_ATTR void k_mlp3_bwd_lean(
 #pragma unroll
         for (int u = 0; u < 2; u++) {
             const int f4 = (t + u) * 16 + 4 * q;
-            const f32x4 acc = u ? accb : acca;
-            const f32x4 hv = KS_LDQ(rH1, f4 < h1 ? oh1 : OOR, 16 * (t + u) * 4, 0);
-            f32x4 dz;
-            dz.x = hv.x > 0.f ? acc.x : 0.f; dz.y = hv.y > 0.f ? acc.y : 0.f; dz.z = hv.z > 0.f ? acc.z : 0.f; dz.w = hv.w > 0.f ? acc.w : 0.f;
+            const f32x4 hv = ldq(rH1, f4 < h1 ? oh1 : OOR, 16 * (t + u) * 4);
+            const f32x4 dz = relu_mask(hv, u ? accb : acca);
             if (dz1_out && row_ok && f4 < h1) *(f32x4*)(dz1_out + (long)row * h1 + f4) = dz;
             if (dx_out) {
                 // A: W1[:, col0 + m]^T: [m][k] = W1[k][col0 + m], k = 16 t + 4 q + j (rows of W1, stride in_dim), m = nn < ncol
                 const int vx = (nn < ncol && f4 < h1) ? ((4 * q * in_dim) + col0 + nn) * 4 : OOR;
                 const int sx = 16 * (t + u) * in_dim * 4;
-                const f32x4 v = {KS_LDF(rW1, vx, sx), KS_LDF(rW1, vx, sx + in_dim * 4), KS_LDF(rW1, vx, sx + 2 * in_dim * 4), KS_LDF(rW1, vx, sx + 3 * in_dim * 4)};
+                const f32x4 v = {ldf(rW1, vx, sx), ldf(rW1, vx, sx + in_dim * 4), ldf(rW1, vx, sx + 2 * in_dim * 4), ldf(rW1, vx, sx + 3 * in_dim * 4)};
                 accx = mfma4(v, dz, accx);
             }
         }
     }
-    if (dx_out && q == 0 && row_ok) {
-        const float g[4] = {accx.x, accx.y, accx.z, accx.w};
-        for (int i = 0; i < ncol; i++) {
-            float v = g[i];
-            if (act_out) { const float a = act_out[(long)row * ncol + i]; v *= a * (1.f - a / scale); }
-            dx_out[(long)row * ncol + i] = v;
-        }
-    }
+    if (dx_out && q == 0 && row_ok) store_dx(accx, ncol, act_out, scale, dx_out, row);
 }
-#undef KS_LDF
-#undef KS_LDQ
 #undef KS_LEAN_LOADS_FIRST
 
 // Weight gradients  dW[M][N] = dz^T h  (dz [n][M], h = [ha | hb] [n][N]) and the bias gradient  db[M] = column sums of dz,
@@ -757,11 +653,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) void
     // Raw buffer loads (as in k_mlp3_wave): per matrix ONE lane offset (row q of a 4-row group, this lane's column), the row
     // advance in the wave-uniform scalar offset; an element that does not exist gets an out-of-range lane offset (-> 0).
     // The flat-load version spent ~10 VALU + ~20 SALU instructions per MFMA on addresses and bounds branches.
-    constexpr int OOR = 0x7ffffff0;
     const auto rZ = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(dz), 0, n * M * 4, 0x00020000);
     const auto rA = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(ha), 0, ((n - 1) * lda + Na) * 4, 0x00020000);
     const auto rB = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(hb ? hb : ha), 0, hb ? ((n - 1) * ldb + Nb) * 4 : 0, 0x00020000);
-#define KS_LDF(rsrc, voff, soff) __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsrc, voff, soff, 0))
     const int vz = m < M ? (q * M + m) * 4 : OOR;
     int va[WG_TN], vb[WG_TN];
 #pragma unroll
@@ -782,11 +676,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) void
         for (int j = 0; j < 4; j++) {
             const int rj = k0 + 4 * j;                                 // wave-uniform; this lane's row is rj + q
             const bool ok = !GUARD || rj + q < r1;
-            a[j] = KS_LDF(rZ, ok ? vz : OOR, rj * M * 4);
+            a[j] = ldf(rZ, ok ? vz : OOR, rj * M * 4);
 #pragma unroll
             for (int u = 0; u < WG_TN; u++) {
-                float v = KS_LDF(rA, ok ? va[u] : OOR, rj * lda * 4);
-                if (HASB) v += KS_LDF(rB, ok ? vb[u] : OOR, rj * ldb * 4);      // at most one of the two exists
+                float v = ldf(rA, ok ? va[u] : OOR, rj * lda * 4);
+                if (HASB) v += ldf(rB, ok ? vb[u] : OOR, rj * ldb * 4);      // at most one of the two exists
                 b[j][u] = v;
             }
         }
@@ -805,7 +699,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) void
         for (int k0 = r0; k0 < full_end; k0 += 16) round(k0, std::false_type{}, std::false_type{});
         if (full_end < r1) round(full_end, std::true_type{}, std::false_type{});
     }
-#undef KS_LDF
     float* out = ws + (long)chunk * ((long)M * N + M);
 #pragma unroll
     for (int u = 0; u < WG_TN; u++) {
@@ -834,35 +727,101 @@ __global__ __launch_bounds__(256) void k_wgrad_reduce(long count_w, long count_b
     else db[i - count_w] = s;
 }
 
-template <int NT1, int NT2, bool SEL>
-int launch(int n, int in_a, int in_b, int h1, int h2, int out_dim, const float* xa, int lda, const float* xb, int ldb, const float* W1,
-           const float* b1, const float* W2, const float* b2, const float* W3, const float* b3, int act, float scale, float* out,
-           float* h1_out, float* h2_out, const SelectArgs& sel, hipStream_t s) {
-    const bool vec = (h1 % 4 == 0) && (h2 % 4 == 0) && ((uintptr_t)W2 % 16 == 0) && ((uintptr_t)W3 % 16 == 0);
-    const dim3 grid((n + ROWS - 1) / ROWS), block(64 * NW);
-    if (vec)
-        hipLaunchKernelGGL((k_mlp3<NT1, NT2, true, SEL>), grid, block, 0, s, n, in_a, in_b, h1, h2, out_dim, xa, lda, xb, ldb, W1, b1, W2, b2, W3, b3,
-                           act, scale, out, h1_out, h2_out, sel);
-    else
-        hipLaunchKernelGGL((k_mlp3<NT1, NT2, false, SEL>), grid, block, 0, s, n, in_a, in_b, h1, h2, out_dim, xa, lda, xb, ldb, W1, b1, W2, b2, W3, b3,
-                           act, scale, out, h1_out, h2_out, sel);
+// ---- host front end.  The arguments the forward entry points share, and those of the backward ones, as kinova_rollout.h names them.
+struct Fwd {
+    int n, in_a, in_b, h1, h2, out_dim;
+    const float* xa; int lda; const float* xb; int ldb;
+    const float *W1, *b1, *W2, *b2, *W3, *b3;
+    int act; float scale;
+    float *out, *h1_out, *h2_out;
+};
+struct Bwd {
+    int n, in_dim, h1, h2, out_dim;
+    const float *dz3, *W3, *h2a, *W2, *h1a;
+    float *dz2_out, *dz1_out;
+    const float* W1; int col0, ncol;
+    const float* act_out; float scale;
+    float* dx_out;
+};
+
+// what every forward form refuses; each entry point adds the conditions of its own form
+bool fwd_args_ok(const Fwd& a) {
+    if ((a.h1_out && (a.h1 % 4 || (uintptr_t)a.h1_out % 16)) || (a.h2_out && (a.h2 % 4 || (uintptr_t)a.h2_out % 16))) return false;
+    if (!a.xa || !a.W1 || !a.b1 || !a.W2 || !a.b2 || !a.W3 || !a.b3 || !a.out || a.in_a <= 0 || a.in_b < 0 || (a.in_b > 0 && !a.xb)) return false;
+    if (a.in_a + a.in_b > 16 * KS_IN_MAX || a.out_dim < 1 || a.out_dim > 4 || a.h1 < 1 || a.h2 < 1) return false;
+    return a.act == KR_ACT_NONE || a.act == KR_ACT_SIGMOID;
+}
+// ... and every backward form (the hidden widths are each form's own)
+bool bwd_args_ok(const Bwd& a) {
+    if (!a.dz3 || !a.W3 || !a.h2a || !a.W2 || !a.h1a || a.out_dim < 1 || a.out_dim > 4) return false;
+    if (a.dx_out && (!a.W1 || a.ncol < 1 || a.ncol > 4 || a.col0 < 0 || a.col0 + a.ncol > a.in_dim)) return false;
+    return !((uintptr_t)a.h1a % 16 || (uintptr_t)a.h2a % 16 || (a.dz1_out && (uintptr_t)a.dz1_out % 16) || (a.dz2_out && (uintptr_t)a.dz2_out % 16));
+}
+// whole tiles, and 16-byte loads of W2 / W3 rows: the one-wave and split forms
+bool whole_tiles(int h1, int h2) { return h1 >= 16 && h2 >= 16 && h1 % 16 == 0 && h2 % 16 == 0; }
+bool aligned16(const void* p) { return (uintptr_t)p % 16 == 0; }
+
+// Tile pairs (NT1, NT2) with an instantiation, one list per form (mlp.py: SUPPORTED_TILES, SHADOW_TILES, LEAN_TILES).
+// LIST(KR_PICK, kernel [, further template arguments]) leaves in `k` the kernel's instantiation for (nt1, nt2), if the list has the pair.
+#define KR_MLP_PAIRS(CASE, ...)                                                                                                      \
+    CASE(16, 16, __VA_ARGS__)    /* 256-256 (BASELINE) */                                                                            \
+    CASE(25, 19, __VA_ARGS__)    /* 400-300 (reference, DDPGfD.py:19-23) */                                                          \
+    CASE(8, 8, __VA_ARGS__)      /* 128-128 */                                                                                       \
+    CASE(4, 4, __VA_ARGS__)      /* 64-64 (tests) */
+// the one-wave and split forms: wider first layers do not fit the register budget
+#define KR_SHADOW_PAIRS(CASE, ...) CASE(16, 16, __VA_ARGS__) CASE(8, 8, __VA_ARGS__) CASE(4, 4, __VA_ARGS__)
+// the lean form: 400-300 and its partial tiles, e.g. 392-292; every lane offset is a 32-bit byte offset: rows * width * 4 must stay below OOR
+#define KR_LEAN_PAIRS(CASE, ...) CASE(25, 19, __VA_ARGS__)
+#define KR_PICK(A, B, K, ...) if (nt1 == A && nt2 == B) k = K<A, B, ##__VA_ARGS__>;
+
+// one workgroup of `threads` per 16 rows; no instantiation (k == nullptr): these widths are not supported
+template <typename... P, typename... A>
+int launch(void (*k)(P...), int n, int threads, hipStream_t s, A... a) {
+    if (!k) return KS_ERR_INVALID;
+    hipLaunchKernelGGL(k, dim3((n + ROWS - 1) / ROWS), dim3(threads), 0, s, (P)a...);
     return hipGetLastError() == hipSuccess ? KS_OK : KS_ERR_HIP;
 }
+// ... of a forward kernel (every one takes the shared arguments up to `out`, then `tail`), of a backward kernel (dz2: where dz2 goes)
+template <typename K, typename... T>
+int launch_fwd(K k, int threads, void* stream, const Fwd& a, T... tail) {
+    return launch(k, a.n, threads, (hipStream_t)stream, a.n, a.in_a, a.in_b, a.h1, a.h2, a.out_dim, a.xa, a.lda, a.xb, a.ldb, a.W1, a.b1, a.W2, a.b2, a.W3, a.b3,
+                  a.act, a.scale, a.out, tail...);
+}
+template <typename K, typename... T>
+int launch_bwd(K k, int threads, void* stream, const Bwd& a, float* dz2, T... tail) {
+    return launch(k, a.n, threads, (hipStream_t)stream, a.n, a.in_dim, a.h1, a.h2, a.out_dim, a.dz3, a.W3, a.h2a, a.W2, a.h1a, dz2, a.dz1_out, a.W1, a.col0, a.ncol,
+                  a.act_out, a.scale, a.dx_out, tail...);
+}
 
+// Where the split and lean forms pass a layer's output quads ([rows][width]) and the split forms' partial sums through global
+// memory: the quads in the caller's own tensor `keep` ([n][width]) or, without one, in scratch for whole blocks of 16 rows;
+// behind them in scratch 64 partial sums per block and wave.  False when scratch is needed and missing, misaligned or too small.
+struct Exchange { float* buf; int rows; float* partial; };
+bool exchange(Exchange& x, int n, int width, float* keep, int partial_waves, float* scratch, int64_t scratch_floats) {
+    const int64_t blocks = (n + ROWS - 1) / ROWS;
+    const int64_t quads = keep ? 0 : blocks * ROWS * width, need = quads + blocks * partial_waves * 64;
+    if (need && (!scratch || !aligned16(scratch) || scratch_floats < need)) return false;
+    x = Exchange{keep ? keep : scratch, keep ? n : (int)blocks * ROWS, scratch + quads};
+    return true;
+}
 
-template <bool SEL>
-int dispatch(int n, int in_a, int in_b, int h1, int h2, int out_dim, const float* xa, int lda, const float* xb, int ldb, const float* W1,
-             const float* b1, const float* W2, const float* b2, const float* W3, const float* b3, int act, float scale, float* out,
-             float* h1_out, float* h2_out, const SelectArgs& sel, hipStream_t s) {
+bool lean_widths_ok(int h1, int h2) {
+    if (h1 < 1 || h2 < 1 || h1 % 4 || h2 % 4) return false;
     const int nt1 = (h1 + 15) / 16, nt2 = (h2 + 15) / 16;
-#define KR_MLP_CASE(A, B) \
-    if (nt1 == A && nt2 == B) return launch<A, B, SEL>(n, in_a, in_b, h1, h2, out_dim, xa, lda, xb, ldb, W1, b1, W2, b2, W3, b3, act, scale, out, h1_out, h2_out, sel, s);
-    KR_MLP_CASE(16, 16)      // 256-256 (BASELINE)
-    KR_MLP_CASE(25, 19)      // 400-300 (reference, DDPGfD.py:19-23)
-    KR_MLP_CASE(8, 8)        // 128-128
-    KR_MLP_CASE(4, 4)        // 64-64 (tests)
-#undef KR_MLP_CASE
-    return KS_ERR_INVALID;   // other widths: the caller keeps its GEMM path
+#define KR_LEAN_IS(A, B, ...) || (nt1 == A && nt2 == B)
+    return false KR_LEAN_PAIRS(KR_LEAN_IS);
+#undef KR_LEAN_IS
+}
+bool lean_fits32(int64_t rows, int64_t width) { return rows * width * 4 < (int64_t)OOR; }
+
+// k_mlp3 (the LDS form, any widths of its tile pairs): kr_mlp3_forward, and with the selection epilogue kr_actor_select
+template <bool SEL>
+int dispatch(const Fwd& a, const SelectArgs& sel, void* stream) {
+    const int nt1 = (a.h1 + 15) / 16, nt2 = (a.h2 + 15) / 16;
+    const bool vec = (a.h1 % 4 == 0) && (a.h2 % 4 == 0) && aligned16(a.W2) && aligned16(a.W3);
+    decltype(&k_mlp3<4, 4, true, SEL>) k = nullptr;      // other widths: the caller keeps its GEMM path
+    if (vec) { KR_MLP_PAIRS(KR_PICK, k_mlp3, true, SEL) } else { KR_MLP_PAIRS(KR_PICK, k_mlp3, false, SEL) }
+    return launch_fwd(k, 64 * NW, stream, a, a.h1_out, a.h2_out, sel);
 }
 
 }  // namespace
@@ -873,39 +832,21 @@ int kr_mlp3_forward(int32_t n, int32_t in_a, int32_t in_b, int32_t h1, int32_t h
                     const float* xb, int32_t ldb, const float* W1, const float* b1, const float* W2, const float* b2,
                     const float* W3, const float* b3, int32_t act, float scale, float* out, float* h1_out, float* h2_out, void* stream) {
     if (n <= 0) return KS_OK;
-    if (((h1_out && (h1 % 4 || (uintptr_t)h1_out % 16)) || (h2_out && (h2 % 4 || (uintptr_t)h2_out % 16)))) return KS_ERR_INVALID;
-    if (!xa || !W1 || !b1 || !W2 || !b2 || !W3 || !b3 || !out || in_a <= 0 || in_b < 0 || (in_b > 0 && !xb)) return KS_ERR_INVALID;
-    if (in_a + in_b > 16 * KS_IN_MAX || out_dim < 1 || out_dim > 4 || h1 < 1 || h2 < 1) return KS_ERR_INVALID;
-    if (act != KR_ACT_NONE && act != KR_ACT_SIGMOID) return KS_ERR_INVALID;
-    return dispatch<false>(n, in_a, in_b, h1, h2, out_dim, xa, lda, xb, ldb, W1, b1, W2, b2, W3, b3, act, scale, out, h1_out, h2_out, SelectArgs{}, (hipStream_t)stream);
+    const Fwd a{n, in_a, in_b, h1, h2, out_dim, xa, lda, xb, ldb, W1, b1, W2, b2, W3, b3, act, scale, out, h1_out, h2_out};
+    if (!fwd_args_ok(a)) return KS_ERR_INVALID;
+    return dispatch<false>(a, SelectArgs{}, stream);
 }
 
 int kr_mlp3_forward_shadow(int32_t n, int32_t in_a, int32_t in_b, int32_t h1, int32_t h2, int32_t out_dim, const float* xa, int32_t lda,
                            const float* xb, int32_t ldb, const float* W1, const float* b1, const float* W2, const float* b2,
                            const float* W3, const float* b3, int32_t act, float scale, float* out, float* h1_out, float* h2_out, void* stream) {
     if (n <= 0) return KS_OK;
-    if (((h1_out && (h1 % 4 || (uintptr_t)h1_out % 16)) || (h2_out && (h2 % 4 || (uintptr_t)h2_out % 16)))) return KS_ERR_INVALID;
-    if (!xa || !W1 || !b1 || !W2 || !b2 || !W3 || !b3 || !out || in_a <= 0 || in_b < 0 || (in_b > 0 && !xb)) return KS_ERR_INVALID;
-    if (in_a + in_b > 16 * KS_IN_MAX || out_dim < 1 || out_dim > 4 || h1 < 1 || h2 < 1) return KS_ERR_INVALID;
-    if (act != KR_ACT_NONE && act != KR_ACT_SIGMOID) return KS_ERR_INVALID;
-    const int nt1 = (h1 + 15) / 16, nt2 = (h2 + 15) / 16;
-    if (h1 % 16 || h2 % 16 || (uintptr_t)W2 % 16 || (uintptr_t)W3 % 16) return KS_ERR_INVALID;      // 16-byte buffer loads, whole tiles
-    const bool vec = true;
-    const dim3 grid((n + ROWS - 1) / ROWS), block(64);
-    hipStream_t s = (hipStream_t)stream;
-#define KR_WAVE_CASE(A, B)                                                                                                                       \
-    if (nt1 == A && nt2 == B) {                                                                                                                  \
-        if (vec) hipLaunchKernelGGL((k_mlp3_wave<A, B, true>), grid, block, 0, s, n, in_a, in_b, h1, h2, out_dim, xa, lda, xb, ldb, W1, b1, W2, b2, \
-                                    W3, b3, act, scale, out, h1_out, h2_out);                                                                    \
-        else hipLaunchKernelGGL((k_mlp3_wave<A, B, false>), grid, block, 0, s, n, in_a, in_b, h1, h2, out_dim, xa, lda, xb, ldb, W1, b1, W2, b2,   \
-                                W3, b3, act, scale, out, h1_out, h2_out);                                                                        \
-        return hipGetLastError() == hipSuccess ? KS_OK : KS_ERR_HIP;                                                                             \
-    }
-    KR_WAVE_CASE(16, 16)     // 256-256 (BASELINE); wider first layers do not fit the register budget
-    KR_WAVE_CASE(8, 8)
-    KR_WAVE_CASE(4, 4)
-#undef KR_WAVE_CASE
-    return KS_ERR_INVALID;
+    const Fwd a{n, in_a, in_b, h1, h2, out_dim, xa, lda, xb, ldb, W1, b1, W2, b2, W3, b3, act, scale, out, h1_out, h2_out};
+    if (!fwd_args_ok(a) || !whole_tiles(h1, h2) || !aligned16(W2) || !aligned16(W3)) return KS_ERR_INVALID;
+    const int nt1 = h1 / 16, nt2 = h2 / 16;
+    decltype(&k_mlp3_wave<4, 4>) k = nullptr;
+    KR_SHADOW_PAIRS(KR_PICK, k_mlp3_wave)
+    return launch_fwd(k, 64, stream, a, h1_out, h2_out);
 }
 
 int kr_mlp3_forward_split(int32_t n, int32_t in_a, int32_t in_b, int32_t h1, int32_t h2, int32_t out_dim, const float* xa, int32_t lda,
@@ -913,148 +854,72 @@ int kr_mlp3_forward_split(int32_t n, int32_t in_a, int32_t in_b, int32_t h1, int
                           const float* W3, const float* b3, int32_t act, float scale, float* out, float* h1_out, float* h2_out,
                           float* scratch, int64_t scratch_floats, int32_t waves, void* stream) {
     if (n <= 0) return KS_OK;
-    if (((h1_out && (h1 % 4 || (uintptr_t)h1_out % 16)) || (h2_out && (h2 % 4 || (uintptr_t)h2_out % 16)))) return KS_ERR_INVALID;
-    if (!xa || !W1 || !b1 || !W2 || !b2 || !W3 || !b3 || !out || in_a <= 0 || in_b < 0 || (in_b > 0 && !xb)) return KS_ERR_INVALID;
-    if (in_a + in_b > 16 * KS_IN_MAX || out_dim < 1 || out_dim > 4 || h1 < 1 || h2 < 1) return KS_ERR_INVALID;
-    if (act != KR_ACT_NONE && act != KR_ACT_SIGMOID) return KS_ERR_INVALID;
-    if (h1 % 16 || h2 % 16 || (uintptr_t)W2 % 16 || (uintptr_t)W3 % 16 || (waves != 2 && waves != 4)) return KS_ERR_INVALID;
-    const int nt1 = h1 / 16, nt2 = h2 / 16, blocks = (n + ROWS - 1) / ROWS;
-    // scratch: [the layer-1 exchange, blocks x 16 rows x h1, unless the caller keeps h1 itself][blocks x waves x 64 partial sums]
-    const int64_t need = (h1_out ? 0 : (int64_t)blocks * ROWS * h1) + (int64_t)blocks * waves * 64;
-    if (!scratch || (uintptr_t)scratch % 16 || scratch_floats < need) return KS_ERR_INVALID;
-    float* h1buf = h1_out ? h1_out : scratch;
-    const int h1_rows = h1_out ? n : blocks * ROWS;
-    float* partial = scratch + (h1_out ? 0 : (int64_t)blocks * ROWS * h1);
-    const dim3 grid(blocks);
-    hipStream_t s = (hipStream_t)stream;
-#define KR_SPLIT_CASE(A, B, NWS)                                                                                                               \
-    if (nt1 == A && nt2 == B && waves == NWS) {                                                                                                \
-        hipLaunchKernelGGL((k_mlp3_split<A, B, NWS>), grid, dim3(64 * NWS), 0, s, n, in_a, in_b, h1, h2, out_dim, xa, lda, xb, ldb, W1, b1, W2, b2, \
-                           W3, b3, act, scale, out, h1buf, h1_rows, h2_out, partial);                                                          \
-        return hipGetLastError() == hipSuccess ? KS_OK : KS_ERR_HIP;                                                                           \
-    }
-    KR_SPLIT_CASE(16, 16, 4) KR_SPLIT_CASE(16, 16, 2)
-    KR_SPLIT_CASE(8, 8, 4) KR_SPLIT_CASE(8, 8, 2)
-    KR_SPLIT_CASE(4, 4, 4) KR_SPLIT_CASE(4, 4, 2)
-#undef KR_SPLIT_CASE
-    return KS_ERR_INVALID;
+    const Fwd a{n, in_a, in_b, h1, h2, out_dim, xa, lda, xb, ldb, W1, b1, W2, b2, W3, b3, act, scale, out, h1_out, h2_out};
+    if (!fwd_args_ok(a) || !whole_tiles(h1, h2) || !aligned16(W2) || !aligned16(W3) || (waves != 2 && waves != 4)) return KS_ERR_INVALID;
+    Exchange x;      // the layer-1 exchange and the layer-3 partial sums
+    if (!exchange(x, n, h1, h1_out, waves, scratch, scratch_floats)) return KS_ERR_INVALID;
+    const int nt1 = h1 / 16, nt2 = h2 / 16;
+    decltype(&k_mlp3_split<4, 4, 2>) k = nullptr;
+    if (waves == 4) { KR_SHADOW_PAIRS(KR_PICK, k_mlp3_split, 4) } else { KR_SHADOW_PAIRS(KR_PICK, k_mlp3_split, 2) }
+    return launch_fwd(k, 64 * waves, stream, a, x.buf, x.rows, h2_out, x.partial);
 }
 
 int kr_mlp3_backward_shadow(int32_t n, int32_t in_dim, int32_t h1, int32_t h2, int32_t out_dim, const float* dz3, const float* W3,
                             const float* h2a, const float* W2, const float* h1a, float* dz2_out, float* dz1_out, const float* W1, int32_t col0,
                             int32_t ncol, const float* act_out, float scale, float* dx_out, void* stream) {
     if (n <= 0) return KS_OK;
-    if (!dz3 || !W3 || !h2a || !W2 || !h1a || out_dim < 1 || out_dim > 4 || h1 < 16 || h2 < 16 || h1 % 16 || h2 % 16) return KS_ERR_INVALID;
-    if (dx_out && (!W1 || ncol < 1 || ncol > 4 || col0 < 0 || col0 + ncol > in_dim)) return KS_ERR_INVALID;
-    if ((uintptr_t)h1a % 16 || (uintptr_t)h2a % 16 || (dz1_out && (uintptr_t)dz1_out % 16) || (dz2_out && (uintptr_t)dz2_out % 16)) return KS_ERR_INVALID;
-    const int nt1 = (h1 + 15) / 16, nt2 = (h2 + 15) / 16;
-    const dim3 grid((n + ROWS - 1) / ROWS), block(64);
-    hipStream_t s = (hipStream_t)stream;
-#define KR_BWD_CASE(A, B)                                                                                                                    \
-    if (nt1 == A && nt2 == B) {                                                                                                              \
-        hipLaunchKernelGGL((k_mlp3_bwd_wave<A, B>), grid, block, 0, s, n, in_dim, h1, h2, out_dim, dz3, W3, h2a, W2, h1a, dz2_out, dz1_out, W1, \
-                           col0, ncol, act_out, scale, dx_out);                                                                              \
-        return hipGetLastError() == hipSuccess ? KS_OK : KS_ERR_HIP;                                                                         \
-    }
-    KR_BWD_CASE(16, 16)
-    KR_BWD_CASE(8, 8)
-    KR_BWD_CASE(4, 4)
-#undef KR_BWD_CASE
-    return KS_ERR_INVALID;
+    const Bwd a{n, in_dim, h1, h2, out_dim, dz3, W3, h2a, W2, h1a, dz2_out, dz1_out, W1, col0, ncol, act_out, scale, dx_out};
+    if (!bwd_args_ok(a) || !whole_tiles(h1, h2)) return KS_ERR_INVALID;
+    const int nt1 = h1 / 16, nt2 = h2 / 16;
+    decltype(&k_mlp3_bwd_wave<4, 4>) k = nullptr;
+    KR_SHADOW_PAIRS(KR_PICK, k_mlp3_bwd_wave)
+    return launch_bwd(k, 64, stream, a, dz2_out);
 }
 
 int kr_mlp3_backward_split(int32_t n, int32_t in_dim, int32_t h1, int32_t h2, int32_t out_dim, const float* dz3, const float* W3,
                             const float* h2a, const float* W2, const float* h1a, float* dz2_out, float* dz1_out, const float* W1, int32_t col0,
                             int32_t ncol, const float* act_out, float scale, float* dx_out, float* scratch, int64_t scratch_floats, int32_t waves, void* stream) {
     if (n <= 0) return KS_OK;
-    if (!dz3 || !W3 || !h2a || !W2 || !h1a || out_dim < 1 || out_dim > 4 || h1 < 16 || h2 < 16 || h1 % 16 || h2 % 16) return KS_ERR_INVALID;
-    if (dx_out && (!W1 || ncol < 1 || ncol > 4 || col0 < 0 || col0 + ncol > in_dim)) return KS_ERR_INVALID;
-    if ((uintptr_t)h1a % 16 || (uintptr_t)h2a % 16 || (dz1_out && (uintptr_t)dz1_out % 16) || (dz2_out && (uintptr_t)dz2_out % 16)) return KS_ERR_INVALID;
-    const int nt1 = (h1 + 15) / 16, nt2 = (h2 + 15) / 16;
-    if ((waves != 2 && waves != 4) || (dx_out && (!scratch || (uintptr_t)scratch % 16 || scratch_floats < (int64_t)((n + ROWS - 1) / ROWS) * waves * 64)))
-        return KS_ERR_INVALID;
-    const dim3 grid((n + ROWS - 1) / ROWS);
-    hipStream_t s = (hipStream_t)stream;
-#define KR_BWDS_CASE(A, B, NWS)                                                                                                              \
-    if (nt1 == A && nt2 == B && waves == NWS) {                                                                                              \
-        hipLaunchKernelGGL((k_mlp3_bwd_split<A, B, NWS>), grid, dim3(64 * NWS), 0, s, n, in_dim, h1, h2, out_dim, dz3, W3, h2a, W2, h1a, dz2_out, \
-                           dz1_out, W1, col0, ncol, act_out, scale, dx_out, scratch);                                                        \
-        return hipGetLastError() == hipSuccess ? KS_OK : KS_ERR_HIP;                                                                         \
-    }
-    KR_BWDS_CASE(16, 16, 4) KR_BWDS_CASE(16, 16, 2)
-    KR_BWDS_CASE(8, 8, 4) KR_BWDS_CASE(8, 8, 2)
-    KR_BWDS_CASE(4, 4, 4) KR_BWDS_CASE(4, 4, 2)
-#undef KR_BWDS_CASE
-    return KS_ERR_INVALID;
+    const Bwd a{n, in_dim, h1, h2, out_dim, dz3, W3, h2a, W2, h1a, dz2_out, dz1_out, W1, col0, ncol, act_out, scale, dx_out};
+    if (!bwd_args_ok(a) || !whole_tiles(h1, h2) || (waves != 2 && waves != 4)) return KS_ERR_INVALID;
+    Exchange x;      // only the partial sums of dx
+    if (!exchange(x, n, 0, nullptr, dx_out ? waves : 0, scratch, scratch_floats)) return KS_ERR_INVALID;
+    const int nt1 = h1 / 16, nt2 = h2 / 16;
+    decltype(&k_mlp3_bwd_split<4, 4, 2>) k = nullptr;
+    if (waves == 4) { KR_SHADOW_PAIRS(KR_PICK, k_mlp3_bwd_split, 4) } else { KR_SHADOW_PAIRS(KR_PICK, k_mlp3_bwd_split, 2) }
+    return launch_bwd(k, 64 * waves, stream, a, dz2_out, x.partial);
 }
-
-// tile pairs of the lean kernels (mlp.py: LEAN_TILES); every lane offset is a 32-bit byte offset: rows * width * 4 must stay below LEAN_OOR
-#define KR_LEAN_PAIRS(CASE) CASE(25, 19)       /* 400-300 (reference, DDPGfD.py:19-23) and its partial tiles, e.g. 392-292 */
-static bool lean_widths_ok(int h1, int h2) {
-    if (h1 < 1 || h2 < 1 || h1 % 4 || h2 % 4) return false;
-    const int nt1 = (h1 + 15) / 16, nt2 = (h2 + 15) / 16;
-#define KR_LEAN_IS(A, B) if (nt1 == A && nt2 == B) return true;
-    KR_LEAN_PAIRS(KR_LEAN_IS)
-#undef KR_LEAN_IS
-    return false;
-}
-static bool lean_fits32(int64_t rows, int64_t width) { return rows * width * 4 < (int64_t)LEAN_OOR; }
 
 int kr_mlp3_forward_lean(int32_t n, int32_t in_a, int32_t in_b, int32_t h1, int32_t h2, int32_t out_dim, const float* xa, int32_t lda,
                          const float* xb, int32_t ldb, const float* W1, const float* b1, const float* W2, const float* b2,
                          const float* W3, const float* b3, int32_t act, float scale, float* out, float* h1_out, float* h2_out,
                          float* scratch, int64_t scratch_floats, void* stream) {
     if (n <= 0) return KS_OK;
-    if (!xa || !W1 || !b1 || !W2 || !b2 || !W3 || !b3 || !out || in_a <= 0 || in_b < 0 || (in_b > 0 && !xb)) return KS_ERR_INVALID;
-    if (in_a + in_b > 16 * KS_IN_MAX || out_dim < 1 || out_dim > 4 || !lean_widths_ok(h1, h2)) return KS_ERR_INVALID;
-    if (act != KR_ACT_NONE && act != KR_ACT_SIGMOID) return KS_ERR_INVALID;
-    if ((uintptr_t)W2 % 16 || (uintptr_t)W3 % 16 || (h1_out && (uintptr_t)h1_out % 16) || (h2_out && (uintptr_t)h2_out % 16)) return KS_ERR_INVALID;
+    const Fwd a{n, in_a, in_b, h1, h2, out_dim, xa, lda, xb, ldb, W1, b1, W2, b2, W3, b3, act, scale, out, h1_out, h2_out};
+    if (!fwd_args_ok(a) || !lean_widths_ok(h1, h2) || !aligned16(W2) || !aligned16(W3)) return KS_ERR_INVALID;
     if (lda < in_a || (in_b > 0 && ldb < in_b)) return KS_ERR_INVALID;
-    const int blocks = (n + ROWS - 1) / ROWS;
-    // scratch: layer 1's output quads of every wave's 16 rows, unless the caller keeps h1 itself
-    const int64_t need = h1_out ? 0 : (int64_t)blocks * ROWS * h1;
-    if (need && (!scratch || (uintptr_t)scratch % 16 || scratch_floats < need)) return KS_ERR_INVALID;
-    if (!lean_fits32((int64_t)blocks * ROWS, h1 > h2 ? h1 : h2) || !lean_fits32(n, lda) || !lean_fits32(n, in_b > 0 ? ldb : 1)) return KS_ERR_INVALID;
-    float* h1buf = h1_out ? h1_out : scratch;
-    const int h1_rows = h1_out ? n : blocks * ROWS;
+    Exchange x;      // layer 1's output quads
+    if (!exchange(x, n, h1, h1_out, 0, scratch, scratch_floats)) return KS_ERR_INVALID;
+    if (!lean_fits32((n + ROWS - 1) / ROWS * ROWS, h1 > h2 ? h1 : h2) || !lean_fits32(n, lda) || !lean_fits32(n, in_b > 0 ? ldb : 1)) return KS_ERR_INVALID;
     const int nt1 = (h1 + 15) / 16, nt2 = (h2 + 15) / 16;
-    hipStream_t s = (hipStream_t)stream;
-#define KR_LEAN_CASE(A, B)                                                                                                                    \
-    if (nt1 == A && nt2 == B) {                                                                                                               \
-        hipLaunchKernelGGL((k_mlp3_lean<A, B>), dim3(blocks), dim3(64), 0, s, n, in_a, in_b, h1, h2, out_dim, xa, lda, xb, ldb, W1, b1, W2, b2,  \
-                           W3, b3, act, scale, out, h1buf, h1_rows, h2_out);                                                                  \
-        return hipGetLastError() == hipSuccess ? KS_OK : KS_ERR_HIP;                                                                          \
-    }
-    KR_LEAN_PAIRS(KR_LEAN_CASE)
-#undef KR_LEAN_CASE
-    return KS_ERR_INVALID;
+    decltype(&k_mlp3_lean<25, 19>) k = nullptr;
+    KR_LEAN_PAIRS(KR_PICK, k_mlp3_lean)
+    return launch_fwd(k, 64, stream, a, x.buf, x.rows, h2_out);
 }
 
 int kr_mlp3_backward_lean(int32_t n, int32_t in_dim, int32_t h1, int32_t h2, int32_t out_dim, const float* dz3, const float* W3,
                           const float* h2a, const float* W2, const float* h1a, float* dz2_out, float* dz1_out, const float* W1, int32_t col0,
                           int32_t ncol, const float* act_out, float scale, float* dx_out, float* scratch, int64_t scratch_floats, void* stream) {
     if (n <= 0) return KS_OK;
-    if (!dz3 || !W3 || !h2a || !W2 || !h1a || out_dim < 1 || out_dim > 4 || !lean_widths_ok(h1, h2)) return KS_ERR_INVALID;
-    if (dx_out && (!W1 || ncol < 1 || ncol > 4 || col0 < 0 || col0 + ncol > in_dim)) return KS_ERR_INVALID;
-    if ((uintptr_t)h1a % 16 || (uintptr_t)h2a % 16 || (dz1_out && (uintptr_t)dz1_out % 16) || (dz2_out && (uintptr_t)dz2_out % 16)) return KS_ERR_INVALID;
-    const int blocks = (n + ROWS - 1) / ROWS;
-    // scratch: the masked dz2 quads of every wave's 16 rows, unless the caller keeps dz2 itself
-    const int64_t need = dz2_out ? 0 : (int64_t)blocks * ROWS * h2;
-    if (need && (!scratch || (uintptr_t)scratch % 16 || scratch_floats < need)) return KS_ERR_INVALID;
-    if (!lean_fits32((int64_t)blocks * ROWS, h1 > h2 ? h1 : h2) || (dx_out && !lean_fits32(h1, in_dim))) return KS_ERR_INVALID;
-    float* dz2buf = dz2_out ? dz2_out : scratch;
-    const int dz2_rows = dz2_out ? n : blocks * ROWS;
+    const Bwd a{n, in_dim, h1, h2, out_dim, dz3, W3, h2a, W2, h1a, dz2_out, dz1_out, W1, col0, ncol, act_out, scale, dx_out};
+    if (!bwd_args_ok(a) || !lean_widths_ok(h1, h2)) return KS_ERR_INVALID;
+    Exchange x;      // the masked dz2 quads
+    if (!exchange(x, n, h2, dz2_out, 0, scratch, scratch_floats)) return KS_ERR_INVALID;
+    if (!lean_fits32((n + ROWS - 1) / ROWS * ROWS, h1 > h2 ? h1 : h2) || (dx_out && !lean_fits32(h1, in_dim))) return KS_ERR_INVALID;
     const int nt1 = (h1 + 15) / 16, nt2 = (h2 + 15) / 16;
-    hipStream_t s = (hipStream_t)stream;
-#define KR_LEAN_CASE(A, B)                                                                                                                    \
-    if (nt1 == A && nt2 == B) {                                                                                                               \
-        hipLaunchKernelGGL((k_mlp3_bwd_lean<A, B>), dim3(blocks), dim3(64), 0, s, n, in_dim, h1, h2, out_dim, dz3, W3, h2a, W2, h1a, dz2buf,    \
-                           dz2_rows, dz1_out, W1, col0, ncol, act_out, scale, dx_out);                                                        \
-        return hipGetLastError() == hipSuccess ? KS_OK : KS_ERR_HIP;                                                                          \
-    }
-    KR_LEAN_PAIRS(KR_LEAN_CASE)
-#undef KR_LEAN_CASE
-    return KS_ERR_INVALID;
+    decltype(&k_mlp3_bwd_lean<25, 19>) k = nullptr;
+    KR_LEAN_PAIRS(KR_PICK, k_mlp3_bwd_lean)
+    return launch_bwd(k, 64, stream, a, x.buf, x.rows);
 }
 
 int kr_weight_grad_shadow(int32_t n, int32_t M, int32_t Na, int32_t Nb, const float* dz, const float* ha, int32_t lda, const float* hb, int32_t ldb,
@@ -1081,8 +946,8 @@ int kr_actor_select(int32_t n, int32_t h1, int32_t h2, const float* obs, const f
     if (!obs || !prev_obs || !has_prev || !t || !ready || !W1 || !b1 || !W2 || !b2 || !W3 || !b3 || !action || !action_t || !lifting) return KS_ERR_INVALID;
     if ((noise == nullptr) == (rng_state == nullptr) || h1 < 1 || h2 < 1) return KS_ERR_INVALID;     // exactly one noise source
     SelectArgs sel{obs, prev_obs, has_prev, t, ready, noise, (unsigned long long)seed, rng_state, sigma, max_action, skip_steps, action, action_t, lifting};
-    return dispatch<true>(n, KR_STATE_DIM, 0, h1, h2, KR_ACTION_DIM, obs, KR_STATE_DIM, nullptr, 0, W1, b1, W2, b2, W3, b3, KR_ACT_SIGMOID, max_action,
-                          actor_out, nullptr, nullptr, sel, (hipStream_t)stream);
+    const Fwd a{n, KR_STATE_DIM, 0, h1, h2, KR_ACTION_DIM, obs, KR_STATE_DIM, nullptr, 0, W1, b1, W2, b2, W3, b3, KR_ACT_SIGMOID, max_action, actor_out, nullptr, nullptr};
+    return dispatch<true>(a, sel, stream);
 }
 
 }  // extern "C"

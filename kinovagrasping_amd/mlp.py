@@ -42,6 +42,31 @@ def _split_waves(n: int) -> int:
     return 4 if (n + 15) // 16 * 4 <= 1024 else 2
 
 
+def _has_split(w1, w2) -> bool:
+    """the split kernels (kr_mlp3_forward_split / kr_mlp3_backward_split) exist for these hidden widths: the square SHADOW_TILES pairs, whole tiles"""
+    return w1.shape[0] == w2.shape[0] and w1.shape[0] % 16 == 0 and w1.shape[0] // 16 in (4, 8, 16)
+
+
+def _stream(t):
+    return ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
+
+
+def _fwd_args(layers, xa, xb, act, scale, out, h1_out, h2_out):
+    """the arguments every kr_mlp3_forward* entry point begins with (n .. h2_out)"""
+    (w1, b1), (w2, b2), (w3, b3) = layers
+    P = _sim._ptr
+    return (xa.shape[0], xa.shape[1], 0 if xb is None else xb.shape[1], w1.shape[0], w2.shape[0], w3.shape[0], P(xa), xa.stride(0), P(xb),
+            0 if xb is None else xb.stride(0), P(w1), P(b1), P(w2), P(b2), P(w3), P(b3), act, float(scale), P(out), P(h1_out), P(h2_out))
+
+
+def _bwd_args(layers, dz3, h1, h2, dz2, dz1, col0, ncol, act_out, scale, dx):
+    """the arguments every kr_mlp3_backward* entry point begins with (n .. dx_out)"""
+    (w1, _), (w2, _), (w3, _) = layers
+    P = _sim._ptr
+    return (dz3.shape[0], w1.shape[1], w1.shape[0], w2.shape[0], w3.shape[0], P(dz3), P(w3), P(h2), P(w2), P(h1), P(dz2), P(dz1), P(w1), col0, ncol,
+            P(act_out), float(scale), P(dx))
+
+
 def mlp3_forward(layers, xa: torch.Tensor, xb: torch.Tensor | None = None, act: int = ACT_NONE, scale: float = 1.0,
                  out: torch.Tensor | None = None, h1_out: torch.Tensor | None = None, h2_out: torch.Tensor | None = None,
                  shadow: bool = False, lean: bool = False) -> torch.Tensor:
@@ -61,38 +86,18 @@ def mlp3_forward(layers, xa: torch.Tensor, xb: torch.Tensor | None = None, act: 
     for h, w in ((h1_out, w1), (h2_out, w2)):
         assert h is None or (h.is_contiguous() and tuple(h.shape) == (n, w.shape[0]) and h.dtype == torch.float32)
     lib, P = _sim.load_library(), _sim._ptr
-    if lean:
-        # layer 1's output goes through global memory: the caller's h1_out, or scratch
-        need = 0 if h1_out is not None else (n + 15) // 16 * 16 * w1.shape[0]
-        scratch = torch.empty(need, device=xa.device, dtype=torch.float32) if need else None
-        rc = lib.kr_mlp3_forward_lean(n, in_a, in_b, w1.shape[0], w2.shape[0], w3.shape[0], P(xa), xa.stride(0), P(xb) if xb is not None else None,
-                                      xb.stride(0) if xb is not None else 0, P(w1), P(b1), P(w2), P(b2), P(w3), P(b3), act, float(scale), P(out),
-                                      P(h1_out), P(h2_out), P(scratch), need, _stream(xa))
-        if rc != 0:
-            raise RuntimeError(f"kr_mlp3_forward_lean failed ({rc}): unsupported layer widths or bad arguments")
-        return out
-    waves = _split_waves(n) if shadow and w1.shape[0] % 16 == 0 and w2.shape[0] % 16 == 0 and w1.shape[0] // 16 in (4, 8, 16) and w1.shape[0] == w2.shape[0] else 0
-    if waves:
-        # the LDS-free launch with each layer's tiles split over 2 / 4 waves of a workgroup (kr_mlp3_forward_split)
-        blocks = (n + 15) // 16
+    blocks = (n + 15) // 16
+    waves = 0 if lean or not (shadow and _has_split(w1, w2)) else _split_waves(n)
+    name, tail = "kr_mlp3_forward_shadow" if shadow else "kr_mlp3_forward", ()
+    if lean or waves:
+        # layer 1's output goes through global memory (the caller's h1_out, or scratch); behind it the split form's 64 partial sums per wave
         need = (0 if h1_out is not None else blocks * 16 * w1.shape[0]) + blocks * waves * 64
-        scratch = torch.empty(need, device=xa.device, dtype=torch.float32)
-        rc = lib.kr_mlp3_forward_split(n, in_a, in_b, w1.shape[0], w2.shape[0], w3.shape[0], P(xa), xa.stride(0), P(xb) if xb is not None else None,
-                                       xb.stride(0) if xb is not None else 0, P(w1), P(b1), P(w2), P(b2), P(w3), P(b3), act, float(scale), P(out),
-                                       P(h1_out), P(h2_out), P(scratch), need, waves, ctypes.c_void_p(torch.cuda.current_stream(xa.device).cuda_stream))
-        if rc != 0:
-            raise RuntimeError(f"kr_mlp3_forward_split failed ({rc})")
-        return out
-    rc = (lib.kr_mlp3_forward_shadow if shadow else lib.kr_mlp3_forward)(n, in_a, in_b, w1.shape[0], w2.shape[0], w3.shape[0], P(xa), xa.stride(0), P(xb) if xb is not None else None,
-                             xb.stride(0) if xb is not None else 0, P(w1), P(b1), P(w2), P(b2), P(w3), P(b3), act, float(scale), P(out), P(h1_out), P(h2_out),
-                             ctypes.c_void_p(torch.cuda.current_stream(xa.device).cuda_stream))
+        scratch = torch.empty(need, device=xa.device, dtype=torch.float32) if need else None
+        name, tail = ("kr_mlp3_forward_lean", (P(scratch), need)) if lean else ("kr_mlp3_forward_split", (P(scratch), need, waves))
+    rc = getattr(lib, name)(*_fwd_args(layers, xa, xb, act, scale, out, h1_out, h2_out), *tail, _stream(xa))
     if rc != 0:
-        raise RuntimeError(f"kr_mlp3_forward failed ({rc}): unsupported layer widths or bad arguments")
+        raise RuntimeError(f"{name if lean or waves else 'kr_mlp3_forward'} failed ({rc})" + ("" if waves else ": unsupported layer widths or bad arguments"))
     return out
-
-
-def _stream(t):
-    return ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
 
 
 def mlp3_backward(layers, dz3: torch.Tensor, h1: torch.Tensor, h2: torch.Tensor, want_dz: bool = True, dx_cols: tuple[int, int] | None = None,
@@ -112,26 +117,21 @@ def mlp3_backward(layers, dz3: torch.Tensor, h1: torch.Tensor, h2: torch.Tensor,
         dx = torch.empty(n, ncol, device=dz3.device, dtype=torch.float32)
         assert act_out is None or (act_out.is_contiguous() and tuple(act_out.shape) == (n, ncol))
     lib, P = _sim.load_library(), _sim._ptr
+    blocks = (n + 15) // 16
+    waves = 0 if lean or not _has_split(w1, w2) else _split_waves(n)
+    name, tail = "kr_mlp3_backward_shadow", ()
     if lean:
         # dz2 goes through global memory: the returned dz2, or scratch
-        need = 0 if dz2 is not None else (n + 15) // 16 * 16 * w2.shape[0]
+        need = 0 if dz2 is not None else blocks * 16 * w2.shape[0]
         scratch = torch.empty(need, device=dz3.device, dtype=torch.float32) if need else None
-        rc = lib.kr_mlp3_backward_lean(n, w1.shape[1], w1.shape[0], w2.shape[0], w3.shape[0], P(dz3), P(w3), P(h2), P(w2), P(h1), P(dz2), P(dz1), P(w1),
-                                       col0, ncol, P(act_out), float(scale), P(dx), P(scratch), need, _stream(dz3))
-        if rc != 0:
-            raise RuntimeError(f"kr_mlp3_backward_lean failed ({rc})")
-        return dz2, dz1, dx
-    waves = _split_waves(n) if w1.shape[0] == w2.shape[0] and w1.shape[0] % 16 == 0 and w1.shape[0] // 16 in (4, 8, 16) else 0
-    if waves:
-        need = (n + 15) // 16 * waves * 64 if dx is not None else 0
+        name, tail = "kr_mlp3_backward_lean", (P(scratch), need)
+    elif waves:
+        need = blocks * waves * 64 if dx is not None else 0
         scratch = torch.empty(max(need, 4), device=dz3.device, dtype=torch.float32)
-        rc = lib.kr_mlp3_backward_split(n, w1.shape[1], w1.shape[0], w2.shape[0], w3.shape[0], P(dz3), P(w3), P(h2), P(w2), P(h1), P(dz2), P(dz1), P(w1),
-                                        col0, ncol, P(act_out), float(scale), P(dx), P(scratch), need, waves, _stream(dz3))
-    else:
-        rc = lib.kr_mlp3_backward_shadow(n, w1.shape[1], w1.shape[0], w2.shape[0], w3.shape[0], P(dz3), P(w3), P(h2), P(w2), P(h1), P(dz2), P(dz1), P(w1),
-                                         col0, ncol, P(act_out), float(scale), P(dx), _stream(dz3))
+        name, tail = "kr_mlp3_backward_split", (P(scratch), need, waves)
+    rc = getattr(lib, name)(*_bwd_args(layers, dz3, h1, h2, dz2, dz1, col0, ncol, act_out, scale, dx), *tail, _stream(dz3))
     if rc != 0:
-        raise RuntimeError(f"kr_mlp3_backward failed ({rc})")
+        raise RuntimeError(f"{name if lean else 'kr_mlp3_backward'} failed ({rc})")
     return dz2, dz1, dx
 
 

@@ -201,13 +201,14 @@ def _bind(L):
     L.kr_sigmoid_scale_backward.argtypes = [i64, vp, f32, vp, vp]
     L.kr_adam_step.argtypes = [i64, vp, vp, vp, vp, vp, f32, f32, f32, f32, f32, vp]
     L.kr_soft_update.argtypes = [i64, vp, vp, f32, vp, i32, vp]
-    L.kr_mlp3_forward.argtypes = [i32] * 6 + [vp, i32, vp, i32] + [vp] * 6 + [i32, f32, vp, vp, vp, vp]
-    L.kr_mlp3_forward_shadow.argtypes = L.kr_mlp3_forward.argtypes
-    L.kr_mlp3_forward_split.argtypes = [i32] * 6 + [vp, i32, vp, i32] + [vp] * 6 + [i32, f32, vp, vp, vp, vp, C.c_int64, i32, vp]
-    L.kr_mlp3_backward_shadow.argtypes = [i32] * 5 + [vp] * 8 + [i32, i32, vp, f32, vp, vp]
-    L.kr_mlp3_backward_split.argtypes = [i32] * 5 + [vp] * 8 + [i32, i32, vp, f32, vp, vp, C.c_int64, i32, vp]
-    L.kr_mlp3_forward_lean.argtypes = [i32] * 6 + [vp, i32, vp, i32] + [vp] * 6 + [i32, f32, vp, vp, vp, vp, C.c_int64, vp]
-    L.kr_mlp3_backward_lean.argtypes = [i32] * 5 + [vp] * 8 + [i32, i32, vp, f32, vp, vp, C.c_int64, vp]
+    mlp_fwd = [i32] * 6 + [vp, i32, vp, i32] + [vp] * 6 + [i32, f32, vp, vp, vp]      # n .. h2_out of every kr_mlp3_forward*
+    mlp_bwd = [i32] * 5 + [vp] * 8 + [i32, i32, vp, f32, vp]                          # n .. dx_out of every kr_mlp3_backward*
+    L.kr_mlp3_forward.argtypes = L.kr_mlp3_forward_shadow.argtypes = mlp_fwd + [vp]
+    L.kr_mlp3_forward_split.argtypes = mlp_fwd + [vp, C.c_int64, i32, vp]
+    L.kr_mlp3_forward_lean.argtypes = mlp_fwd + [vp, C.c_int64, vp]
+    L.kr_mlp3_backward_shadow.argtypes = mlp_bwd + [vp]
+    L.kr_mlp3_backward_split.argtypes = mlp_bwd + [vp, C.c_int64, i32, vp]
+    L.kr_mlp3_backward_lean.argtypes = mlp_bwd + [vp, C.c_int64, vp]
     L.kr_weight_grad_shadow.argtypes = [i32] * 4 + [vp, vp, i32, vp, i32, i32, vp, vp, vp, vp]
     L.kr_actor_select.argtypes = [i32] * 3 + [vp] * 12 + [C.c_uint64, vp, f32, f32, i32] + [vp] * 5
     return L
