@@ -150,6 +150,9 @@ template <typename T> __device__ __forceinline__ const Model<T>* stage_model(con
 // size of a PairRec in DEVICE code (LDS pointers are 4 bytes there; the host pass of this file sees 8)
 template <typename T> constexpr int pair_rec_bytes() { return MULTI_GEOM ? (sizeof(T) == 4 ? 128 : 160) : (sizeof(T) == 4 ? 96 : 144); }   // (multi-geom: generic table pointers, 8 bytes)
 
+// The env blocks (per-env scratch, SCR_TOTAL words each) behind the hull tables and pair records: 16-byte aligned
+template <typename T> __device__ __forceinline__ KS_LDS T* env_blocks(KS_LDS T* lds, int hull_words) { return lds + ((hull_words >> 2) << 2); }
+
 // Global -> LDS copy of a table by the whole workgroup in B-byte words (both ends B-byte aligned, `bytes` a multiple of B), four
 // loads in flight per thread: the tables of a workgroup are ~50 KB, and copied element by element (floats, 16-bit ids) the
 // staging was 56 dependent load -> store rounds = 27 us at the head of every launch.
@@ -581,6 +584,10 @@ __device__ __noinline__ void wg_rays(const Model<float>& m, const Buffers<float>
 template <typename T> struct ObsOut {
     T* obs; T* reward; uint8_t* done; T* info; T* final_obs;
     int horizon, auto_reset, env_major;
+    bool operator==(const ObsOut& o) const {
+        return obs == o.obs && reward == o.reward && done == o.done && info == o.info && final_obs == o.final_obs && horizon == o.horizon &&
+               auto_reset == o.auto_reset && env_major == o.env_major;
+    }
 };
 template <bool WAVE_SCOPE>
 __device__ void wg_obs(const Model<float>& m, const Buffers<float>& b, int N, int slot0, int epw, KS_LDS unsigned* w, const ObsOut<float>& o);
@@ -697,7 +704,7 @@ __device__ __forceinline__ void env_step_body(const Model<T>* __restrict__ model
     float* prof = nullptr;
 #endif
     if constexpr (USE_LDS) {
-        KS_LDS T* blk = lds + ((hull_words >> 2) << 2) + e * SCR_TOTAL;
+        KS_LDS T* blk = env_blocks(lds, hull_words) + e * SCR_TOTAL;
         ScratchC<T, KS_LDS T*> scr{blk};
         // state and per-step constants in the env's LDS block, reached through generic pointers
         T* stp = (T*)(blk + SCR_STATE);
@@ -756,16 +763,16 @@ __device__ __forceinline__ void env_step_body(const Model<T>* __restrict__ model
             __syncthreads();
             // (the out-of-line tails take the pointer table and the output record by reference: from device memory - a
             // reference to the by-value kernel arguments made every lane copy them to its stack, 224 bytes written through per launch)
-            if (ray_pool) wg_ray_pool(models, m, *bdev, N, epw, (KS_LDS unsigned*)(lds + ((hull_words >> 2) << 2)), n_wg, ray_pool == 2);
+            if (ray_pool) wg_ray_pool(models, m, *bdev, N, epw, (KS_LDS unsigned*)(env_blocks(lds, hull_words)), n_wg, ray_pool == 2);
             else {
-                wg_rays<false>(m, *bdev, N, blockIdx.x * epw, epw, (KS_LDS unsigned*)(lds + ((hull_words >> 2) << 2)) KS_RAY_PROF_ARG(nullptr));
+                wg_rays<false>(m, *bdev, N, blockIdx.x * epw, epw, (KS_LDS unsigned*)(env_blocks(lds, hull_words)) KS_RAY_PROF_ARG(nullptr));
                 __threadfence_block();
                 __syncthreads();
             }
-            if (obs_in_step) wg_obs<false>(m, *bdev, N, blockIdx.x * epw, epw, (KS_LDS unsigned*)(lds + ((hull_words >> 2) << 2)), *out);
+            if (obs_in_step) wg_obs<false>(m, *bdev, N, blockIdx.x * epw, epw, (KS_LDS unsigned*)(env_blocks(lds, hull_words)), *out);
             if (ray_pool) {
                 // the last workgroup to leave clears the pool for the next launch
-                KS_LDS int* last = (KS_LDS int*)(lds + ((hull_words >> 2) << 2));
+                KS_LDS int* last = (KS_LDS int*)(env_blocks(lds, hull_words));
                 __syncthreads();
                 if (threadIdx.x == 0) *last = atomicAdd(&b.rayq[2], 1) == n_wg - 1;
                 __syncthreads();
@@ -804,6 +811,20 @@ __device__ __forceinline__ long long uniform64(long long v) {      // lane 0's v
     const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)v), hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)((unsigned long long)v >> 32));
     return (long long)(((unsigned long long)hi << 32) | lo);
 }
+// The tail that the two policy functions share, in its two steps around their staleness checks.  policy_squash: the row's action from the
+// actor's output z4 and the layer-3 bias b3 - the LAST words read from the weight buffer, so it runs before the check.  policy_select,
+// once the weights are known to have been whole: exploration noise, check_grasp and the scripted lift (krsel::select_one).
+__device__ __forceinline__ void policy_squash(const ks_rollout_args& ra, const kmlp::f32x4& z4, const float* b3, float (&y)[4]) {
+    const float z[4] = {z4.x, z4.y, z4.z, z4.w};
+#pragma unroll
+    for (int i = 0; i < 4; i++) y[i] = ra.max_action / (1.f + __expf(-(z[i] + b3[i])));
+}
+__device__ __forceinline__ void policy_select(const ks_rollout_args& ra, int N, int row_env, const float (&y)[4]) {
+    float nz[4];
+    krsel::normal4(ra.seed, (unsigned long long)ra.steps_total[row_env], (uint32_t)row_env, nz);
+    krsel::select_one(row_env, N, y, nz, ra.obs, ra.prev_obs, ra.has_prev, ra.t, ra.ready, ra.sigma, ra.max_action, ra.skip_steps, ra.action, ra.action_t,
+                      ra.lifting);
+}
 template <int NT1, int NT2, bool EXACT = false>
 __device__ __noinline__ void rollout_policy(const ks_rollout_args* __restrict__ rap, int N, int row_env, KS_LDS float* blocks) {
     const ks_rollout_args& ra = *rap;
@@ -829,12 +850,7 @@ __device__ __noinline__ void rollout_policy(const ks_rollout_args* __restrict__ 
         // the last words read from buffer ver % 3 - the layer-3 bias - are taken BEFORE the staleness check below, and a fence keeps
         // the check's load behind them: everything the action is computed from has then been read when the counter is looked at
         float y[4] = {0.f, 0.f, 0.f, 0.f};
-        if (mine) {
-            const float z[4] = {z4.x, z4.y, z4.z, z4.w};
-            const float* b3 = pw + ra.off_b3;
-#pragma unroll
-            for (int i = 0; i < 4; i++) y[i] = ra.max_action / (1.f + __expf(-(z[i] + b3[i])));
-        }
+        if (mine) policy_squash(ra, z4, pw + ra.off_b3, y);
         // ALL FOUR waves' reads of buffer ver % 3 must be complete before the counter is looked at again: the barrier waits for every
         // wave to reach this point (each wave's loads are consumed by the arithmetic above, so they have returned), and the agent-scope
         // acquire fence keeps thread 0's second load of the counter - written by another kernel - behind it.
@@ -848,12 +864,7 @@ __device__ __noinline__ void rollout_policy(const ks_rollout_args* __restrict__ 
         const bool stale = vbox[1] >= 2;
         if (stale && threadIdx.x == 0 && ra.repeats) atomicAdd((unsigned long long*)ra.repeats, 1ull);
         if (!stale) {
-            if (mine) {
-                float nz[4];
-                krsel::normal4(ra.seed, (unsigned long long)ra.steps_total[row_env], (uint32_t)row_env, nz);
-                krsel::select_one(row_env, N, y, nz, ra.obs, ra.prev_obs, ra.has_prev, ra.t, ra.ready, ra.sigma, ra.max_action, ra.skip_steps, ra.action,
-                                  ra.action_t, ra.lifting);
-            }
+            if (mine) policy_select(ra, N, row_env, y);
             return;
         }
         __syncthreads();
@@ -966,12 +977,60 @@ __global__ void k_rollout_queue_init(int* __restrict__ queue, int n_groups) {
     }
 }
 
-// One env-step of the workgroup's envs (the body of k_rollout's loop).
+// ---- round 6: the waves of a workgroup run free.  As a workgroup (rollout_iter<.., false>) the four waves join five times per env-step
+// (policy | 15 substeps | rays | observation | replay write), so every env-step costs the workgroup its SLOWEST wave (measured model,
+// profiles/r05_wave_sorting.txt: workgroup cost 1408 k cycles per env-step against 1091 k for the mean wave).  Nothing in an env-step
+// needs the other waves: per-env data is private to the wave's own four env blocks, the model and the hull tables are read-only.
+// Here the unit of the persistent loop is ONE WAVE with its four envs: the actor forward for its own four rows (a 16-column MFMA
+// tile a quarter full, bit-equal per row to the 4-wave tile), its own rays (the same work-sharing queue among 64 lanes), its own
+// observation and replay rows - and no s_barrier between kernel entry and exit.  Scratch of the tails: the wave's own four (then
+// dead) env blocks.
 template <int NT1, int NT2>
+__device__ __noinline__ void rollout_policy_wave(const ks_rollout_args* __restrict__ rap, int N, int row_env, KS_LDS float* wblocks) {
+    const ks_rollout_args& ra = *rap;
+    const int S = krsel::S, A = krsel::A;
+    constexpr int NR = 4;
+    kmlp::f32x4(*H1)[NR] = (kmlp::f32x4(*)[NR])(float*)wblocks;
+    kmlp::f32x4(*H2)[NR] = H1 + NT1 * 4;
+    const int lane = threadIdx.x & 63;
+    for (;;) {
+        // (the wave's own look at the version counter: waves of a workgroup may act on different - each complete - weight versions)
+        const long long ver = uniform64(__hip_atomic_load(ra.actor_ver, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+        const float* pw = ra.actor_pub + (ver % 3) * ra.actor_stride;
+        kmlp::f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
+        const bool mine = kmlp::mlp3_rows_wave<NT1, NT2, true, NR>(lane, (long)row_env, S, ra.h1, ra.h2, A, ra.obs, S, kmlp::x_bytes(N, 0, S, S), pw + ra.off_w1,
+                                                                     pw + ra.off_b1, pw + ra.off_w2, pw + ra.off_b2, pw + ra.off_w3, H1, H2, z4);
+        float y[4] = {0.f, 0.f, 0.f, 0.f};
+        if (mine) policy_squash(ra, z4, pw + ra.off_b3, y);
+        // every read of buffer ver % 3 by this wave has been consumed by the arithmetic above; the acquire keeps the second look at
+        // the counter behind them (see rollout_policy: a buffer is rewritten two publications later)
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+        const long long ver2 = uniform64(__hip_atomic_load(ra.actor_ver, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+        if (ver2 - ver < 2) {
+            if (mine) policy_select(ra, N, row_env, y);
+            return;
+        }
+        if (lane == 0 && ra.repeats) atomicAdd((unsigned long long*)ra.repeats, 1ull);
+    }
+}
+
+#ifdef KS_ROLLOUT_STAMP
+// diagnostic build: wall-clock ticks (100 MHz) of the four phases, summed over crews (workgroups or waves) and env-steps in counters[4..7]
+#define KS_RS(i) { const long long t1_ = wall_clock64(); if (C::tid() == 0) atomicAdd((unsigned long long*)&rap->counters[4 + i], (unsigned long long)(t1_ - tk)); tk = t1_; }
+#else
+#define KS_RS(i)
+#endif
+// One env-step (the body of k_rollout's loop) by one crew: the workgroup with the 16 envs of group grp (WAVE_SCOPE = false: joined by
+// barriers), or ONE WAVE with its own four of them (slots grp * epw + 4 * wave ..: the barrier-free loop).  Five phases - policy |
+// 15 substeps | rays | observation | replay write - that differ between the two only in who joins, which slots and env blocks the
+// crew owns, and which policy function runs.
+template <int NT1, int NT2, bool WAVE_SCOPE>
 __device__ __forceinline__ void rollout_iter(const Model<float>& m, const Hulls<float>& hu, const Buffers<float>* __restrict__ bdev, int N, int frame_skip,
-                                          int iters, int epw, int pair_memory, const ObsOut<float>* __restrict__ out,
-                                          const ks_rollout_args* __restrict__ rap, KS_LDS float* blocks, int grp) {
+                                             int iters, int epw, int pair_memory, const ObsOut<float>* __restrict__ out,
+                                             const ks_rollout_args* __restrict__ rap, KS_LDS float* blocks, int grp) {
     using T = float;
+    using C = Crew<WAVE_SCOPE>;
     const Buffers<T>& b = *bdev;
     const int e = threadIdx.x / LANE_STRIDE;
     const Team<SUBS> team{(int)threadIdx.x % LANE_STRIDE};
@@ -979,22 +1038,27 @@ __device__ __forceinline__ void rollout_iter(const Model<float>& m, const Hulls<
     // grp: the 16-env group of the slot list this workgroup steps now (its own, blockIdx.x, unless the launch has fewer workgroups than groups)
     const int env = e < epw ? b.slot_env[grp * epw + e] : -1;
     const bool active = !(team.sub >= SUBS || env < 0);
-    KS_LDS unsigned* w = (KS_LDS unsigned*)blocks;
+    // the crew's slots of the list and its env blocks: scratch of the policy and of the tails while the blocks are dead
+    const int wave = WAVE_SCOPE ? (int)(threadIdx.x >> 6) : 0;
+    const int slot0 = grp * epw + 4 * wave, cepw = WAVE_SCOPE ? (epw - 4 * wave < 4 ? (epw - 4 * wave < 0 ? 0 : epw - 4 * wave) : 4) : epw;
+    KS_LDS T* cblocks = blocks + 4 * wave * SCR_TOTAL;
+    KS_LDS unsigned* w = (KS_LDS unsigned*)cblocks;
+    // the crew's join between two phases (a wave on its own: Crew::sync's fence + wave barrier is all of it)
+    const auto join = [] {
+        if constexpr (!WAVE_SCOPE) __threadfence_block();
+        C::sync();
+    };
 #ifdef KS_ROLLOUT_STAMP
-    // diagnostic build: wall-clock ticks (100 MHz) of the four phases, summed over workgroups and env-steps in counters[4..7]
     long long tk = wall_clock64();
-#define KS_RS(i) { const long long t1_ = wall_clock64(); if (threadIdx.x == 0) atomicAdd((unsigned long long*)&rap->counters[4 + i], (unsigned long long)(t1_ - tk)); tk = t1_; }
-#else
-#define KS_RS(i)
 #endif
     {
-        const int nn = threadIdx.x & 15;
-        const int row_env = nn < epw ? b.slot_env[grp * epw + nn] : -1;   // the policy row of this lane (the same in all four waves)
-        if (b.ctl->mode != 0) rollout_controller(b.ctl, rap, N, threadIdx.x < 16 ? row_env : -1);      // (uniform: a scripted controller acts)
-        else rollout_policy<NT1, NT2>(rap, N, row_env, blocks);
+        const int nn = C::tid() & 15;
+        const int row_env = nn < cepw ? b.slot_env[slot0 + nn] : -1;      // the policy row of this lane (workgroup: the same in all four waves)
+        if (b.ctl->mode != 0) rollout_controller(b.ctl, rap, N, C::tid() < 16 ? row_env : -1);      // (uniform: a scripted controller acts)
+        else if constexpr (WAVE_SCOPE) rollout_policy_wave<NT1, NT2>(rap, N, row_env, cblocks);
+        else rollout_policy<NT1, NT2>(rap, N, row_env, cblocks);
     }
-    __threadfence_block();
-    __syncthreads();
+    join();
     KS_RS(0)
     // ---- the env-step (k_env_step's LDS path)
     if (active) {
@@ -1030,146 +1094,41 @@ __device__ __forceinline__ void rollout_iter(const Model<float>& m, const Hulls<
         if (status) atomicOr(&b.status[env], status);
         if (team.sub == 0) b.ncon[env] = ncon;
     }
-    __threadfence_block();
-    __syncthreads();
+    join();
     KS_RS(1)
-    wg_rays<false>(m, b, N, grp * epw, epw, w KS_RAY_PROF_ARG((long long*)&rap->counters[8 + 4 * 512]));
-    __threadfence_block();
-    __syncthreads();
+    wg_rays<WAVE_SCOPE>(m, b, N, slot0, cepw, w KS_RAY_PROF_ARG((long long*)&rap->counters[8 + 4 * 512]));
+    join();
     KS_RS(2)
-    wg_obs<false>(m, b, N, grp * epw, epw, w, *out);
-    __threadfence_block();
-    __syncthreads();
+    wg_obs<WAVE_SCOPE>(m, b, N, slot0, cepw, w, *out);
+    join();
     if (active) rollout_store<float>(rap, N, env, team.sub);
-    __threadfence_block();
-    __syncthreads();
+    join();
     KS_RS(3)
-#undef KS_RS
 }
-
-// ---- round 6: the waves of a workgroup run free.  rollout_iter above joins the four waves of a workgroup five times per env-step
-// (policy | 15 substeps | rays | observation | replay write), so every env-step costs the workgroup its SLOWEST wave (measured model,
-// profiles/r05_wave_sorting.txt: workgroup cost 1408 k cycles per env-step against 1091 k for the mean wave).  Nothing in an env-step
-// needs the other waves: per-env data is private to the wave's own four env blocks, the model and the hull tables are read-only.
-// Here the unit of the persistent loop is ONE WAVE with its four envs: the actor forward for its own four rows (a 16-column MFMA
-// tile a quarter full, bit-equal per row to the 4-wave tile), its own rays (the same work-sharing queue among 64 lanes), its own
-// observation and replay rows - and no s_barrier between kernel entry and exit.  Scratch of the tails: the wave's own four (then
-// dead) env blocks.
-template <int NT1, int NT2>
-__device__ __noinline__ void rollout_policy_wave(const ks_rollout_args* __restrict__ rap, int N, int row_env, KS_LDS float* wblocks) {
-    const ks_rollout_args& ra = *rap;
-    const int S = krsel::S, A = krsel::A;
-    constexpr int NR = 4;
-    kmlp::f32x4(*H1)[NR] = (kmlp::f32x4(*)[NR])(float*)wblocks;
-    kmlp::f32x4(*H2)[NR] = H1 + NT1 * 4;
-    const int lane = threadIdx.x & 63;
-    for (;;) {
-        // (the wave's own look at the version counter: waves of a workgroup may act on different - each complete - weight versions)
-        const long long ver = uniform64(__hip_atomic_load(ra.actor_ver, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        const float* pw = ra.actor_pub + (ver % 3) * ra.actor_stride;
-        kmlp::f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
-        const bool mine = kmlp::mlp3_rows_wave<NT1, NT2, true, NR>(lane, (long)row_env, S, ra.h1, ra.h2, A, ra.obs, S, kmlp::x_bytes(N, 0, S, S), pw + ra.off_w1,
-                                                                     pw + ra.off_b1, pw + ra.off_w2, pw + ra.off_b2, pw + ra.off_w3, H1, H2, z4);
-        float y[4] = {0.f, 0.f, 0.f, 0.f};
-        if (mine) {
-            const float z[4] = {z4.x, z4.y, z4.z, z4.w};
-            const float* b3 = pw + ra.off_b3;
-#pragma unroll
-            for (int i = 0; i < 4; i++) y[i] = ra.max_action / (1.f + __expf(-(z[i] + b3[i])));
-        }
-        // every read of buffer ver % 3 by this wave has been consumed by the arithmetic above; the acquire keeps the second look at
-        // the counter behind them (see rollout_policy: a buffer is rewritten two publications later)
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        const long long ver2 = uniform64(__hip_atomic_load(ra.actor_ver, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-        if (ver2 - ver < 2) {
-            if (mine) {
-                float nz[4];
-                krsel::normal4(ra.seed, (unsigned long long)ra.steps_total[row_env], (uint32_t)row_env, nz);
-                krsel::select_one(row_env, N, y, nz, ra.obs, ra.prev_obs, ra.has_prev, ra.t, ra.ready, ra.sigma, ra.max_action, ra.skip_steps, ra.action,
-                                  ra.action_t, ra.lifting);
-            }
-            return;
-        }
-        if (lane == 0 && ra.repeats) atomicAdd((unsigned long long*)ra.repeats, 1ull);
-    }
-}
-
-// One env-step of ONE WAVE's four envs (slots grp * epw + 4 * wave ..): the body of k_rollout's barrier-free loop.
-template <int NT1, int NT2>
-__device__ __forceinline__ void rollout_iter_wave(const Model<float>& m, const Hulls<float>& hu, const Buffers<float>* __restrict__ bdev, int N, int frame_skip,
-                                               int iters, int epw, int pair_memory, const ObsOut<float>* __restrict__ out,
-                                               const ks_rollout_args* __restrict__ rap, KS_LDS float* blocks, int grp) {
-    using T = float;
-    using C = Crew<true>;
-    const Buffers<T>& b = *bdev;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int e = threadIdx.x / LANE_STRIDE;
-    const Team<SUBS> team{(int)threadIdx.x % LANE_STRIDE};
-    const int env = e < epw ? b.slot_env[grp * epw + e] : -1;
-    const bool active = env >= 0;
-    const int wslot0 = grp * epw + 4 * wave, wepw = epw - 4 * wave < 4 ? (epw - 4 * wave < 0 ? 0 : epw - 4 * wave) : 4;   // this wave's slots
-    KS_LDS T* wblocks = blocks + 4 * wave * SCR_TOTAL;
-    KS_LDS unsigned* w = (KS_LDS unsigned*)wblocks;
-#ifdef KS_ROLLOUT_STAMP
-    // diagnostic build: the same four phase sums as rollout_iter's (counters[4..7]), here over WAVES and env-steps
-    long long tk = wall_clock64();
-#define KS_RS(i) { const long long t1_ = wall_clock64(); if (lane == 0) atomicAdd((unsigned long long*)&rap->counters[4 + i], (unsigned long long)(t1_ - tk)); tk = t1_; }
-#else
-#define KS_RS(i)
-#endif
-    {
-        const int nn = lane & 15;
-        const int row_env = nn < wepw ? b.slot_env[wslot0 + nn] : -1;
-        if (b.ctl->mode != 0) rollout_controller(b.ctl, rap, N, lane < 16 ? row_env : -1);
-        else rollout_policy_wave<NT1, NT2>(rap, N, row_env, wblocks);
-    }
-    C::sync();
-    KS_RS(0)
-    if (active) {
-        T hq[4], act[4];
-        KS_UNROLL
-        for (int i = 0; i < 4; i++) { hq[i] = b.hand_quat[(long)i * N + env]; act[i] = rap->action_t[(long)i * N + env]; }
-        int ncon = 0, status = 0;
-        ColW<T> snap{b.snap + env, N};
-        KS_LDS T* blk = blocks + e * SCR_TOTAL;
-        ScratchC<T, KS_LDS T*> scr{blk};
-        T* stp = (T*)(blk + SCR_STATE);
-        load_state_team<T, SUBS>(b, env, N, stp, team.sub);
-        load_env_params(scr, team, b, env, N);
-        constexpr int WPL = (NPAIR_MAX + SUBS - 1) / SUBS;
-        PairWarm gw[WPL];
-        unsigned* pm = b.pairmem + ((long)env * SUBS + team.sub) * (WPL * WARM_WORDS);
-        KS_UNROLL
-        for (int q = 0; q < WPL; q++) {
-            KS_UNROLL
-            for (int j = 0; j < WARM_WORDS; j++) gw[q].w[j] = pair_memory ? pm[q * WARM_WORDS + j] : 0u;
-        }
-        lane_env_step(m, hu, *(LaneState<T>*)stp, hq, act, scr, team, snap, frame_skip, iters, ncon, status, (float*)nullptr, stp + NQ + 2 * NV, gw,
-                      []() {});
-        if (pair_memory) {
-            KS_UNROLL
-            for (int q = 0; q < WPL; q++) {
-                KS_UNROLL
-                for (int j = 0; j < WARM_WORDS; j++) pm[q * WARM_WORDS + j] = gw[q].w[j];
-            }
-        }
-        team.sync();
-        store_state_team<T, SUBS>(b, env, N, stp, team.sub);
-        if (status) atomicOr(&b.status[env], status);
-        if (team.sub == 0) b.ncon[env] = ncon;
-    }
-    C::sync();
-    KS_RS(1)
-    wg_rays<true>(m, b, N, wslot0, wepw, w KS_RAY_PROF_ARG((long long*)&rap->counters[8 + 4 * 512]));
-    C::sync();
-    KS_RS(2)
-    wg_obs<true>(m, b, N, wslot0, wepw, w, *out);
-    C::sync();
-    if (active) rollout_store<float>(rap, N, env, team.sub);
-    C::sync();
-    KS_RS(3)
 #undef KS_RS
+
+// How the rollout kernels deal the 16-env groups of the slot list to a launch's persistent workgroups: in contiguous runs (the list
+// is sorted by object, so a workgroup's groups mostly share their hull tables), or - n_groups < 0 - round-robin (workgroup w steps
+// groups w, w + G, w + 2 G ...: more table restaging, but cheap and expensive objects average out over a workgroup's groups).
+// This workgroup steps groups g0, g0 + gstep, ... < g1.
+struct GroupDeal {
+    int n, g0, g1, gstep;
+    __device__ __forceinline__ explicit GroupDeal(int n_groups) {
+        const bool rr = n_groups < 0;
+        n = rr ? -n_groups : n_groups;
+        g0 = rr ? (int)blockIdx.x : (int)((long)blockIdx.x * n / gridDim.x);
+        g1 = rr ? n : (int)((long)(blockIdx.x + 1) * n / gridDim.x);
+        gstep = rr ? (int)gridDim.x : 1;
+    }
+    __device__ __forceinline__ bool several() const { return g1 - g0 > gstep; }      // more than one group: the staged object may change
+};
+// does the group the workgroup steps next hold another object than the one whose tables are in LDS?  Then that one is noted as
+// staged: the caller restages
+__device__ __forceinline__ bool object_differs(const int32_t* wg_model, int grp, int& staged) {
+    const int want = __builtin_amdgcn_readfirstlane(wg_model[grp]);
+    if (want == staged) return false;
+    staged = want;
+    return true;
 }
 
 // another object's model constants and hull tables into the workgroup's LDS (out of line: nothing of it may stay in registers across
@@ -1192,49 +1151,51 @@ __global__ __launch_bounds__(WG) KS_ROLLOUT_REGS void k_rollout(const Model<floa
 #ifdef KS_ROLLOUT_STAMP
     const long long wk_entry = wall_clock64();      // diagnostic build: counters[] is [8 + 4 * 512 + 8] there (pipeline.AsyncTrainer allocates that)
 #endif
-    // The 16-env groups of the slot list [n_groups] are dealt to the launch's workgroups in contiguous runs (the list is sorted by
-    // object, so a workgroup's groups mostly share their hull tables): one group per workgroup when they all fit the GPU at once
-    // (4096 envs on 256 CUs), two or three when they do not (BASELINE config 5: 8192 envs) - a persistent workgroup then takes its
-    // groups' env-steps in turn, every group always on the same CU (its state never changes caches), instead of a second round of
-    // workgroups that could only start when a first-round workgroup had finished ALL its env-steps.
-    // (n_groups < 0: the groups are dealt round-robin instead - workgroup w steps groups w, w + G, w + 2 G ... - which mixes objects
-    // within a workgroup: more table restaging, but cheap and expensive objects average out over a workgroup's groups)
-    const bool deal_rr = n_groups < 0;
-    if (deal_rr) n_groups = -n_groups;
-    const int g0 = deal_rr ? (int)blockIdx.x : (int)((long)blockIdx.x * n_groups / gridDim.x);
-    const int g1 = deal_rr ? n_groups : (int)((long)(blockIdx.x + 1) * n_groups / gridDim.x);
-    const int gstep = deal_rr ? (int)gridDim.x : 1;
+    // The 16-env groups of the slot list are dealt to the launch's workgroups (GroupDeal): one group per workgroup when they all fit
+    // the GPU at once (4096 envs on 256 CUs), two or three when they do not (BASELINE config 5: 8192 envs) - a persistent workgroup
+    // then takes its groups' env-steps in turn, every group always on the same CU (its state never changes caches), instead of a second
+    // round of workgroups that could only start when a first-round workgroup had finished ALL its env-steps.
+    const GroupDeal deal(n_groups);
     KS_LDS T* const lds0 = (KS_LDS T*)smem;
     KS_LDS T* const lds = lds0 + model_words<T>();
     Hulls<T>* const hup = (Hulls<T>*)(smem + (sizeof(Model<T>) + 15) / 16 * 16);
-    int staged = __builtin_amdgcn_readfirstlane(b.wg_model[g0]);
+    int staged = __builtin_amdgcn_readfirstlane(b.wg_model[deal.g0]);
     const Model<T>* ml = stage_model_and_tables<T, WG>(models + staged, lds0);
     int hull_words = 0;
     __syncthreads();
     stage_hulls<T, true>(*ml, lds, hull_words, *hup, true);
-    KS_LDS T* blocks = lds + ((hull_words >> 2) << 2);                 // the 16 env blocks; scratch of the tails between the steps
+    KS_LDS T* blocks = env_blocks(lds, hull_words);                 // the 16 env blocks; scratch of the tails between the steps
 #ifdef KS_ROLLOUT_STAMP
     const long long wk_loop = wall_clock64();
     const long long ck_loop = clock64();
 #endif
+    // One env-step of group grp by this workgroup, or - wave_scope - by each of its waves on its own (rollout_iter).  The loop's pointers
+    // are laundered through empty asm statements in front of every iteration: otherwise the compiler hoists loop-invariant address
+    // arithmetic and model constants out of the loop and keeps them in registers for the whole launch (388 registers per lane instead
+    // of ~344; as an out-of-line call the body saves its callee-saved registers to scratch: 1.5 KB per lane) - and the learner's waves
+    // (<= 168 registers) must fit beside this kernel on every SIMD.
+    // (a macro, not a lambda: as a closure, the queue's push then reading grp for want of the laundered gi, the kernel took 368 bytes of
+    // scratch per lane instead of 352 and up to three more spills)
+#define KS_STEP_GROUP(WAVE_SCOPE, GRP)                                                                                      \
+    const Model<T>* mi = ml;                                                                                                \
+    Hulls<T>* hi = hup;                                                                                                     \
+    const Buffers<T>* bi = bdev;                                                                                            \
+    const ObsOut<T>* oi = out;                                                                                              \
+    const ks_rollout_args* ri = rap;                                                                                        \
+    KS_LDS T* ki = blocks;                                                                                                  \
+    int gi = GRP;                                                                                                           \
+    asm volatile("" : "+s"(mi), "+s"(hi), "+s"(bi), "+s"(oi), "+s"(ri), "+s"(gi));                                          \
+    asm volatile("" : "+v"(ki));                                                                                            \
+    rollout_iter<NT1, NT2, WAVE_SCOPE>(*mi, *hi, bi, N, frame_skip, iters, epw, pair_memory, oi, ri, ki, gi)
     if (wave_free) {
         // ---- ONE GROUP PER WORKGROUP (4096 envs on 256 CUs, the metric's shape), round 6: from here on the four waves never meet again -
-        // each loops over its own four envs (rollout_iter_wave) and leaves when it has done its n_iter env-steps.
+        // each loops over its own four envs (rollout_iter<.., true>) and leaves when it has done its n_iter env-steps.
         // (opt-in time budget, ks_rollout_args.budget_ticks: the wave starts no further env-step once the budget has passed - at least one)
         const long long budget = rap->budget_ticks, t_end = wall_clock64() + budget;
 #pragma clang loop unroll(disable)
         for (int it = 0; it < n_iter; it++) {
             if (budget > 0 && it > 0 && wall_clock64() - t_end > 0) break;
-            const Model<T>* mi = ml;
-            Hulls<T>* hi = hup;
-            const Buffers<T>* bi = bdev;
-            const ObsOut<T>* oi = out;
-            const ks_rollout_args* ri = rap;
-            KS_LDS T* ki = blocks;
-            int gi = g0;
-            asm volatile("" : "+s"(mi), "+s"(hi), "+s"(bi), "+s"(oi), "+s"(ri), "+s"(gi));
-            asm volatile("" : "+v"(ki));
-            rollout_iter_wave<NT1, NT2>(*mi, *hi, bi, N, frame_skip, iters, epw, pair_memory, oi, ri, ki, gi);
+            KS_STEP_GROUP(true, deal.g0);
         }
         return;
     }
@@ -1254,7 +1215,7 @@ __global__ __launch_bounds__(WG) KS_ROLLOUT_REGS void k_rollout(const Model<floa
         __shared__ int s_grp;
         int* const q_head = queue, * const q_tail = queue + 1, * const q_steps = queue + ROLLOUT_Q_STEPS;
         unsigned* const ring = (unsigned*)(queue + ROLLOUT_Q_RING);
-        const int total = n_groups * n_iter;
+        const int total = deal.n * n_iter;
 #pragma clang loop unroll(disable)
         for (;;) {
             __syncthreads();
@@ -1276,21 +1237,8 @@ __global__ __launch_bounds__(WG) KS_ROLLOUT_REGS void k_rollout(const Model<floa
             const int grp = __builtin_amdgcn_readfirstlane(s_grp);
             if (grp < 0) break;
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");              // the group's state as its last env-step - on whatever CU - left it
-            const int want = __builtin_amdgcn_readfirstlane(bdev->wg_model[grp]);
-            if (want != staged) {
-                staged = want;
-                blocks = lds + rollout_restage(models + staged, lds0, hup);
-            }
-            const Model<T>* mi = ml;
-            Hulls<T>* hi = hup;
-            const Buffers<T>* bi = bdev;
-            const ObsOut<T>* oi = out;
-            const ks_rollout_args* ri = rap;
-            KS_LDS T* ki = blocks;
-            int gi = grp;
-            asm volatile("" : "+s"(mi), "+s"(hi), "+s"(bi), "+s"(oi), "+s"(ri), "+s"(gi));
-            asm volatile("" : "+v"(ki));
-            rollout_iter<NT1, NT2>(*mi, *hi, bi, N, frame_skip, iters, epw, pair_memory, oi, ri, ki, gi);
+            if (object_differs(bdev->wg_model, grp, staged)) blocks = lds + rollout_restage(models + staged, lds0, hup);
+            KS_STEP_GROUP(false, grp);
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");              // every wave: its stores of this env-step, before the group is handed on
             __syncthreads();
             if (threadIdx.x == 0) {
@@ -1305,34 +1253,17 @@ __global__ __launch_bounds__(WG) KS_ROLLOUT_REGS void k_rollout(const Model<floa
         }
         return;
     }
-    // The loop's pointers are laundered through empty asm statements at the top of every iteration: otherwise the compiler hoists
-    // loop-invariant address arithmetic and model constants out of the loop and keeps them in registers for the whole launch
-    // (388 registers per lane instead of ~344; as an out-of-line call the body saves its callee-saved registers to scratch:
-    // 1.5 KB per lane) - and the learner's waves (<= 168 registers) must fit beside this kernel on every SIMD.
+    // ---- A FIXED DEAL: the workgroup's groups in turn
 #pragma clang loop unroll(disable)
     for (int it = 0; it < n_iter; it++) {
 #pragma clang loop unroll(disable)
-        for (int grp = g0; grp < g1; grp += gstep) {
-            if (g1 - g0 > gstep) {
-                // another group of this workgroup: restage the tables when its object differs from the one in LDS (~10 us)
-                const int want = __builtin_amdgcn_readfirstlane(bdev->wg_model[grp]);
-                if (want != staged) {
-                    staged = want;
-                    blocks = lds + rollout_restage(models + staged, lds0, hup);
-                }
-            }
-            const Model<T>* mi = ml;
-            Hulls<T>* hi = hup;
-            const Buffers<T>* bi = bdev;
-            const ObsOut<T>* oi = out;
-            const ks_rollout_args* ri = rap;
-            KS_LDS T* ki = blocks;
-            int gi = grp;
-            asm volatile("" : "+s"(mi), "+s"(hi), "+s"(bi), "+s"(oi), "+s"(ri), "+s"(gi));
-            asm volatile("" : "+v"(ki));
-            rollout_iter<NT1, NT2>(*mi, *hi, bi, N, frame_skip, iters, epw, pair_memory, oi, ri, ki, gi);
+        for (int grp = deal.g0; grp < deal.g1; grp += deal.gstep) {
+            // another group of this workgroup: restage the tables when its object differs from the one in LDS (~10 us)
+            if (deal.several() && object_differs(bdev->wg_model, grp, staged)) blocks = lds + rollout_restage(models + staged, lds0, hup);
+            KS_STEP_GROUP(false, grp);
         }
     }
+#undef KS_STEP_GROUP
 #ifdef KS_ROLLOUT_STAMP
     if (threadIdx.x == 0 && blockIdx.x < 512) {
         // per workgroup, LAST launch: entry (absolute ticks), entry -> loop, loop duration; [8 + 1536 ..]: first entry / last exit of the launch
@@ -1374,21 +1305,16 @@ __global__ __launch_bounds__(WG) void k_substep(const Model<T>* __restrict__ mod
     for (int i = 0; i < NU; i++) c[i] = ctrl[(long)i * N + env];
     hand_rotation(hq, R7);
     int ncon = 0, status = 0;
-    if constexpr (USE_LDS) {
-        ScratchC<T, KS_LDS T*> scr{lds + ((hull_words >> 2) << 2) + e * SCR_TOTAL};
+    // one mj_step on the env's scratch: its LDS block, or (fp64) its field-major block of global memory
+    const auto forward = [&](auto scr) {
         load_env_params(scr, team, b, env, N);
         reset_pair_words<T>(scr, team);
         mj_forward_step(m, hu, st.qpos, st.qvel, st.warm, c, R7, scr, team, iters, true, ncon, status);
         if (team.sub == 0)
             for (int k = 0; k < (tap ? ncon * CON_STRIDE : 0); k++) b.contact[(long)k * N + env] = scr(SCR_CON + k);
-    } else {
-        Scratch<T> scr{b.gscratch + env, N};
-        load_env_params(scr, team, b, env, N);
-        reset_pair_words<T>(scr, team);
-        mj_forward_step(m, hu, st.qpos, st.qvel, st.warm, c, R7, scr, team, iters, true, ncon, status);
-        if (team.sub == 0)
-            for (int k = 0; k < (tap ? ncon * CON_STRIDE : 0); k++) b.contact[(long)k * N + env] = scr(SCR_CON + k);
-    }
+    };
+    if constexpr (USE_LDS) forward(ScratchC<T, KS_LDS T*>{env_blocks(lds, hull_words) + e * SCR_TOTAL});
+    else forward(Scratch<T>{b.gscratch + env, N});
     if (status) atomicOr(&b.status[env], status);
     if (team.sub != 0) return;
     store_state(b, env, N, st);
@@ -1693,9 +1619,9 @@ template <typename T> __device__ __forceinline__ void param_ranges_draw(const Pa
 
 // An episode of `env` restarts (obs_finish, after the next start is drawn): with parameter ranges, count the episode, draw its mass and
 // friction and store them into envp - the env-step that follows loads them (load_env_params) as it loads the state the restart wrote:
-// both are plain global stores of the lane that finishes the env, ahead of the same fence + barrier (rollout_iter, rollout_iter_f64:
-// __threadfence_block + __syncthreads; rollout_iter_wave: Crew::sync's workgroup fence + wave barrier; the queue form: the agent-scope
-// release before the group is handed on) that orders the restarted state and a pool's env_qpos0 before the team's next loads.  Out of
+// both are plain global stores of the lane that finishes the env, ahead of the same fence + barrier (rollout_iter as a workgroup,
+// rollout_iter_f64: __threadfence_block + __syncthreads; rollout_iter as a wave: Crew::sync's workgroup fence + wave barrier; the queue
+// form: the agent-scope release before the group is handed on) that orders the restarted state and a pool's env_qpos0 before the team's next loads.  Out of
 // line for the reason start_pool_restart is: ONE copy per precision with registers of its own.  Without ranges: one load and back.
 template <typename T> __device__ __noinline__ void param_ranges_restart(const ParamRanges<T>* dr, int env, int N) {
     if (dr->active <= 0) return;
@@ -1999,30 +1925,21 @@ __global__ __launch_bounds__(WG) void k_rollout_f64(const Model<double>* __restr
                                                     const ks_rollout_args* __restrict__ rap, int n_iter, int n_groups, int ws_offset) {
     using T = double;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    // k_rollout's deal (n_groups < 0: round-robin)
-    const bool deal_rr = n_groups < 0;
-    if (deal_rr) n_groups = -n_groups;
-    const int g0 = deal_rr ? (int)blockIdx.x : (int)((long)blockIdx.x * n_groups / gridDim.x);
-    const int g1 = deal_rr ? n_groups : (int)((long)(blockIdx.x + 1) * n_groups / gridDim.x);
-    const int gstep = deal_rr ? (int)gridDim.x : 1;
+    const GroupDeal deal(n_groups);                                          // k_rollout's fixed deals
     KS_LDS T* const lds = (KS_LDS T*)smem;                                   // the hull tables, as k_env_step<double> stages them
     KS_LDS float* const ws = (KS_LDS float*)(smem + ws_offset);              // behind them: the policy tile, then the ray stacks
-    int staged = __builtin_amdgcn_readfirstlane(b.wg_model[g0]);
+    int staged = __builtin_amdgcn_readfirstlane(b.wg_model[deal.g0]);
     int hull_words = 0;
     Hulls<T> hu;
     stage_hulls<T, false>(models[staged], lds, hull_words, hu);
 #pragma clang loop unroll(disable)
     for (int it = 0; it < n_iter; it++) {
 #pragma clang loop unroll(disable)
-        for (int grp = g0; grp < g1; grp += gstep) {
-            if (g1 - g0 > gstep) {
-                // another group of this workgroup: restage the tables and rebuild the descriptor when its object differs
-                const int want = __builtin_amdgcn_readfirstlane(b.wg_model[grp]);
-                if (want != staged) {
-                    staged = want;
-                    __syncthreads();
-                    stage_hulls<T, false>(models[staged], lds, hull_words, hu);
-                }
+        for (int grp = deal.g0; grp < deal.g1; grp += deal.gstep) {
+            // another group of this workgroup: restage the tables and rebuild the descriptor when its object differs
+            if (deal.several() && object_differs(b.wg_model, grp, staged)) {
+                __syncthreads();
+                stage_hulls<T, false>(models[staged], lds, hull_words, hu);
             }
             rollout_iter_f64<NT1, NT2>(models, models[staged], hu, *bdev, N, frame_skip, iters, epw, *out, rap, ws, grp);
         }
@@ -2035,6 +1952,12 @@ struct CtxBase {
     int device;
     std::string error;
     bool model_loaded = false;
+    // the guard of every call that needs the model: KS_OK, or KS_ERR_STATE with "<fn> before ks_load_model"
+    int need_model(const char* fn) {
+        if (model_loaded) return KS_OK;
+        error = std::string(fn) + " before ks_load_model";
+        return KS_ERR_STATE;
+    }
     virtual ~CtxBase() {}
     virtual int load_models(int n_models, const void* const* blobs, const size_t* sizes) = 0;
     virtual int reset(const int32_t* ids, int n, const void* q0, const void* hq, const int32_t* object_id, const void* mass_friction, void* obs,
@@ -2277,10 +2200,7 @@ template <typename T> struct Ctx : CtxBase {
         if (obs_in_step && cfg.frame_skip >= 1 && !(getenv("KS_RAY_POOL") && getenv("KS_RAY_POOL")[0] == '0')) {
             ray_pool = 2;
         }
-        hipLaunchKernelGGL(k_slots, dim3(1), dim3(SLOT_THREADS), 0, 0, b.obj_id, cfg.n_envs, n_models, lpw, n_wg, b.slot_env, b.wg_model, b.n_used);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipDeviceSynchronize());
-        HIPCHK(hipMemcpy(&n_groups, b.n_used, sizeof(int32_t), hipMemcpyDeviceToHost));
+        if ((r = regroup(0, true))) return r;
         if ((r = alloc(&d_b, (size_t)1))) return r;
         if ((r = alloc(&d_out, (size_t)1))) return r;
         if (!h_out) HIPCHK(hipHostMalloc((void**)&h_out, (H_OUT_RING + CAPTURE_RECORDS) * sizeof(ObsOut<T>), hipHostMallocDefault));
@@ -2337,67 +2257,105 @@ template <typename T> struct Ctx : CtxBase {
         obs_in_step = rays_in_step && (size_t)(wg_rays_words(EPW_MAX) + wg_obs_words(EPW_MAX) + 4) <= (size_t)SCR_TOTAL * lpw &&
                       !(getenv("KS_OBS_IN_STEP") && getenv("KS_OBS_IN_STEP")[0] == '0');
         if (getenv("KS_DEBUG")) fprintf(stderr, "[ks] stepping kernel: %d envs per workgroup, LDS %zu B (tables %zu B, %zu B per env), limit %zu\n", lpw, step_lds, hull_bytes, per_env, lds_max);
-        if constexpr (sizeof(T) == 4) HIPCHK(hipFuncSetAttribute((const void*)k_env_step_f32, hipFuncAttributeMaxDynamicSharedMemorySize, (int)step_lds));
-        else HIPCHK(hipFuncSetAttribute((const void*)k_env_step<T, USE_LDS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)step_lds));
+        HIPCHK(hipFuncSetAttribute((const void*)step_kernel(), hipFuncAttributeMaxDynamicSharedMemorySize, (int)step_lds));
         HIPCHK(hipFuncSetAttribute((const void*)k_substep<T, USE_LDS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)step_lds));
         return KS_OK;
     }
-    int post_reset(void* obs, hipStream_t s) {
+    // ks_step's kernel: the capped fp32 product, or the fp64 instantiation of the same body
+    static constexpr auto step_kernel() {
+        if constexpr (sizeof(T) == 4) return &k_env_step_f32;
+        else return &k_env_step<T, USE_LDS>;
+    }
+    // where results go, with the context's episode settings
+    ObsOut<T> out_record(void* obs, void* reward, uint8_t* done, void* info, void* final_obs) const {
+        return ObsOut<T>{(T*)obs, (T*)reward, done, (T*)info, (T*)final_obs, cfg.horizon, cfg.auto_reset, cfg.obs_env_major};
+    }
+    // the stepping kernel's work list, grouped by object (k_slots), and how many of its groups hold envs: that decides how ks_rollout
+    // schedules them (one group per workgroup: free waves), so it is read back - loading models and a reset that changes objects are
+    // no hot paths; under stream capture the conservative count (every slot of the list) stands
+    // (loading: ks_load_model's call, which checks the launch and waits for the whole device - the allocations' zero fills included - first)
+    int regroup(hipStream_t s, bool loading = false) {
+        hipLaunchKernelGGL(k_slots, dim3(1), dim3(SLOT_THREADS), 0, s, b.obj_id, cfg.n_envs, n_models, lpw, n_wg, b.slot_env, b.wg_model, b.n_used);
+        if (loading) {
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipDeviceSynchronize());
+        } else if (stream_is_capturing(s)) { n_groups = n_wg; return KS_OK; }
+        HIPCHK(hipMemcpyAsync(&n_groups, b.n_used, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        return KS_OK;
+    }
+    // back to no start pool / no episode log / no parameter ranges (the setters with 0 / NULL, a reset that changes objects, lost storage)
+    void clear_pool(hipStream_t s) {
+        if (pool_k > 0) hipLaunchKernelGGL((k_pool_clear<T>), dim3(1), dim3(1), 0, s, b);
+        pool_k = 0;
+    }
+    void clear_elog(hipStream_t s) {
+        if (elog_capacity > 0) hipLaunchKernelGGL((k_elog_clear<T>), dim3(1), dim3(1), 0, s, b);
+        elog_capacity = 0;
+    }
+    void clear_ranges(hipStream_t s) {
+        if (dr_active) hipLaunchKernelGGL((k_ranges_clear<T>), dim3(1), dim3(1), 0, s, b);
+        dr_active = false;
+    }
+    // Device storage that is grown on demand and kept until the context goes: at least n items (`bytes` for them) behind `store`.
+    // false: no device memory - the old storage is gone too, the caller clears what used it and reports.
+    // (hipFree waits for the device: nothing that is still running reads or writes the storage it gives back)
+    template <typename U> static bool grow(U*& store, size_t& cap, size_t n, size_t bytes) {
+        if (n <= cap) return true;
+        if (store) { (void)hipFree(store); store = nullptr; cap = 0; }
+        if (hipMalloc((void**)&store, bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            store = nullptr;
+            return false;
+        }
+        cap = n;
+        return true;
+    }
+    // the reset pass over the flagged envs of `e` (the context's buffers, or a start pool's preparation set): state <- stored initial
+    // state, its rays, its observation to `obs` (may be NULL) and to e.obs0
+    void reset_pass(const Buffers<T>& e, void* obs, hipStream_t s) {
         const int N = cfg.n_envs;
+        hipLaunchKernelGGL((k_reset<T, USE_LDS>), dim3(blocks()), dim3(WAVE), 0, s, d_model, e, N, 0);
+        hipLaunchKernelGGL((k_rays<T>), dim3((N + RAY_ENVS - 1) / RAY_ENVS, NRAY), dim3(WAVE), 0, s, d_model, e, N, 1);
+        hipLaunchKernelGGL((k_obs<T>), dim3(blocks()), dim3(WAVE), 0, s, d_model, e, N, 1, out_record(obs, nullptr, nullptr, nullptr, nullptr));
+    }
+    int post_reset(void* obs, hipStream_t s) {
         if (b.rayq) HIPCHK(hipMemsetAsync(b.rayq, 0, (4 + 2 * (size_t)n_wg) * sizeof(int32_t), s));    // (clean even after an aborted launch)
-        hipLaunchKernelGGL((k_reset<T, USE_LDS>), dim3(blocks()), dim3(WAVE), 0, s, d_model, b, N, 0);
-        hipLaunchKernelGGL((k_rays<T>), dim3((N + RAY_ENVS - 1) / RAY_ENVS, NRAY), dim3(WAVE), 0, s, d_model, b, N, 1);
-        hipLaunchKernelGGL((k_obs<T>), dim3(blocks()), dim3(WAVE), 0, s, d_model, b, N, 1,
-                           ObsOut<T>{(T*)obs, nullptr, nullptr, nullptr, nullptr, cfg.horizon, cfg.auto_reset, cfg.obs_env_major});
+        reset_pass(b, obs, s);
         HIPCHK(hipGetLastError());
         return KS_OK;
     }
     int reset(const int32_t* ids, int n, const void* q0, const void* hq, const int32_t* object_id, const void* mass_friction, void* obs,
               hipStream_t s) override {
-        if (!model_loaded) { error = "ks_reset before ks_load_model"; return KS_ERR_STATE; }
+        if (int r = need_model("ks_reset")) return r;
         if (n <= 0 || n > cfg.n_envs || !q0 || !hq || (!ids && n != cfg.n_envs)) { error = "ks_reset: bad arguments"; return KS_ERR_INVALID; }
         hipLaunchKernelGGL((k_store_init<T>), dim3((n + 255) / 256), dim3(256), 0, s, b, ids, n, (const T*)q0, (const T*)hq, object_id,
                            (const T*)mass_friction, n_models, cfg.n_envs);
-        // a pool entry is a start of the object the env held when the pool was set: a call that (re)assigns objects ends the pool
-        if (object_id && pool_k > 0) {
-            hipLaunchKernelGGL((k_pool_clear<T>), dim3(1), dim3(1), 0, s, b);
-            pool_k = 0;
-        }
-        // ... and so are parameter ranges: a range belonged to the object the env held
-        if (object_id && dr_active) {
-            hipLaunchKernelGGL((k_ranges_clear<T>), dim3(1), dim3(1), 0, s, b);
-            dr_active = false;
-        }
-        // objects changed: regroup the stepping kernel's work list by object
-        if (object_id && n_models > 1)
-        {
-            hipLaunchKernelGGL(k_slots, dim3(1), dim3(SLOT_THREADS), 0, s, b.obj_id, cfg.n_envs, n_models, lpw, n_wg, b.slot_env, b.wg_model, b.n_used);
-            // how many groups hold envs decides how ks_rollout schedules them (one group per workgroup: free waves): read it back - a reset that
-            // changes objects is not a hot path; under stream capture the conservative count (every slot of the list) stands
-            if (!stream_is_capturing(s)) {
-                HIPCHK(hipMemcpyAsync(&n_groups, b.n_used, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-                HIPCHK(hipStreamSynchronize(s));
-            } else n_groups = n_wg;
+        if (object_id) {
+            // a pool entry is a start of the object the env held when the pool was set: a call that (re)assigns objects ends the pool
+            clear_pool(s);
+            // ... and so are parameter ranges: a range belonged to the object the env held
+            clear_ranges(s);
+            // objects changed: regroup the stepping kernel's work list by object
+            if (n_models > 1)
+                if (int r = regroup(s)) return r;
         }
         return post_reset(obs, s);
     }
     int step(const void* action, void* obs, void* reward, uint8_t* done, void* info, void* final_obs, hipStream_t s) override {
-        if (!model_loaded) { error = "ks_step before ks_load_model"; return KS_ERR_STATE; }
+        if (int r = need_model("ks_step")) return r;
         if (!action) { error = "ks_step: action is NULL"; return KS_ERR_INVALID; }
         const int N = cfg.n_envs;
         // ks_kernel_time's samples: every ev_stride-th launch is bracketed by two events (each costs ~4 us of stream time)
         const bool timed = ev_used < NEV && (step_calls++ % ev_stride) == 0;
-        const ObsOut<T> out{(T*)obs, (T*)reward, done, (T*)info, (T*)final_obs, cfg.horizon, cfg.auto_reset, cfg.obs_env_major};
-        const bool same = out.obs == out_sent.obs && out.reward == out_sent.reward && out.done == out_sent.done && out.info == out_sent.info &&
-                          out.final_obs == out_sent.final_obs && out.horizon == out_sent.horizon && out.auto_reset == out_sent.auto_reset &&
-                          out.env_major == out_sent.env_major;
+        const ObsOut<T> out = out_record(obs, reward, done, info, final_obs);
         // Under stream capture the copy below is only RECORDED (it runs at every replay of the graph, not now): the device copy
         // cannot be taken as current afterwards, so a capturing call always records the copy and never marks it as sent.
         // Once the context holds ANY captured record (captured_out > 0) a replayed graph may have overwritten d_out with its own
         // pinned record since the last eager call - replays are invisible here - so the "same pointers as last time" shortcut is
         // off for good and every eager call re-sends its record (eager + captured calls with different buffers).
         const bool capturing = stream_is_capturing(s);
-        if (obs_in_step && (capturing || captured_out > 0 || !(same && out_valid))) {
+        if (obs_in_step && (capturing || captured_out > 0 || !(out == out_sent && out_valid))) {
             out_valid = !capturing;
             out_sent = out;
             ObsOut<T>* slot = pinned_record(capturing, h_out, (unsigned)h_out_next++, captured_out);
@@ -2406,14 +2364,9 @@ template <typename T> struct Ctx : CtxBase {
             HIPCHK(hipMemcpyAsync(d_out, slot, sizeof out, hipMemcpyHostToDevice, s));
         }
         if (timed) HIPCHK(hipEventRecord(ev0[ev_used], s));
-        if constexpr (sizeof(T) == 4)
-            hipLaunchKernelGGL(k_env_step_f32, dim3(n_wg), dim3(WG), step_lds, s, d_model, b, (const Buffers<T>*)d_b, (const T*)action, N,
-                               cfg.frame_skip, cfg.solver_iterations, lpw, cfg.contact_tap, (int)rays_in_step, (int)(USE_LDS && cfg.pair_memory),
-                               (int)obs_in_step, (const ObsOut<T>*)d_out, ray_pool, n_wg);
-        else
-            hipLaunchKernelGGL((k_env_step<T, USE_LDS>), dim3(n_wg), dim3(WG), step_lds, s, d_model, b, (const Buffers<T>*)d_b, (const T*)action, N,
-                               cfg.frame_skip, cfg.solver_iterations, lpw, cfg.contact_tap, (int)rays_in_step, (int)(USE_LDS && cfg.pair_memory),
-                               (int)obs_in_step, (const ObsOut<T>*)d_out, ray_pool, n_wg);
+        hipLaunchKernelGGL(step_kernel(), dim3(n_wg), dim3(WG), step_lds, s, d_model, b, (const Buffers<T>*)d_b, (const T*)action, N, cfg.frame_skip,
+                           cfg.solver_iterations, lpw, cfg.contact_tap, (int)rays_in_step, (int)(USE_LDS && cfg.pair_memory), (int)obs_in_step,
+                           (const ObsOut<T>*)d_out, ray_pool, n_wg);
         if (timed) { HIPCHK(hipEventRecord(ev1[ev_used], s)); ev_used++; }
         if (!rays_in_step) hipLaunchKernelGGL((k_rays<T>), dim3((N + RAY_ENVS - 1) / RAY_ENVS, NRAY), dim3(WAVE), 0, s, d_model, b, N, 0);
         if (!obs_in_step) hipLaunchKernelGGL((k_obs<T>), dim3(blocks()), dim3(WAVE), 0, s, d_model, b, N, 0, out);
@@ -2440,7 +2393,7 @@ template <typename T> struct Ctx : CtxBase {
     }
     // the launch's output record (the context's sim_* buffers) and argument record -> device memory
     int send_rollout_records(const ks_rollout_args* ra, hipStream_t s) {
-        const ObsOut<T> out{(T*)ra->sim_obs, (T*)ra->sim_reward, ra->sim_done, (T*)ra->sim_info, (T*)ra->sim_final_obs, cfg.horizon, cfg.auto_reset, cfg.obs_env_major};
+        const ObsOut<T> out = out_record(ra->sim_obs, ra->sim_reward, ra->sim_done, ra->sim_info, ra->sim_final_obs);
         const bool capturing = stream_is_capturing(s);
         ObsOut<T>* slot = pinned_record(capturing, h_out, (unsigned)h_out_next++, captured_out);
         if (!slot) { error = "ks_rollout: more captured calls than the context keeps output records for"; return KS_ERR_STATE; }
@@ -2451,6 +2404,31 @@ template <typename T> struct Ctx : CtxBase {
         if (!rslot) { error = "ks_rollout: more captured calls than the context keeps argument records for"; return KS_ERR_STATE; }
         *rslot = *ra;
         HIPCHK(hipMemcpyAsync(d_ra, rslot, sizeof *ra, hipMemcpyHostToDevice, s));
+        return KS_OK;
+    }
+    // LDS of the policy phase for hidden widths h1-h2 (16-column tiles): as a workgroup (rollout_policy) H1, H2 and P, [tiles * 4 + 4][16]
+    // float4, and the version box; as one wave (rollout_policy_wave) H1 and H2, [tiles * 4][4] float4
+    static constexpr int policy_tiles(int h1, int h2) { return (h1 + 15) / 16 + (h2 + 15) / 16; }
+    static constexpr size_t policy_lds_bytes(int h1, int h2) { return (size_t)(policy_tiles(h1, h2) * 4 + 4) * 16 * 16 + 16; }
+    static constexpr size_t policy_wave_lds_bytes(int h1, int h2) { return (size_t)(policy_tiles(h1, h2) * 4) * 4 * 16; }
+    // The hidden widths the rollout kernels are instantiated for, as pairs of 16-column tiles: launch(Tiles<NT1, NT2>) launches the
+    // caller's kernel family at the pair that serves h1-h2.
+    template <int A, int B> struct Tiles { static constexpr int NT1 = A, NT2 = B; };
+    template <typename F> int launch_for_widths(const ks_rollout_args* ra, F launch) {
+        const int t1 = (ra->h1 + 15) / 16, t2 = (ra->h2 + 15) / 16;
+        if (t1 == 16 && t2 == 16) return launch(Tiles<16, 16>{});
+        if (t1 == 25 && t2 == 19) return launch(Tiles<25, 19>{});
+        if (t1 == 8 && t2 == 8) return launch(Tiles<8, 8>{});
+        if (t1 == 4 && t2 == 4) return launch(Tiles<4, 4>{});
+        if (ctl_mode != 0) return launch(Tiles<16, 16>{});      // (any instantiation serves a controller)
+        error = "ks_rollout: hidden widths must be 256-256, 400-300, 128-128 or 64-64";
+        return KS_ERR_INVALID;
+    }
+    // a rollout kernel with `lds` bytes of dynamic LDS on the launch's persistent workgroups: one per group, at most the resident ones
+    template <typename K, typename... A> int launch_rollout(K kernel, size_t lds, hipStream_t s, A... args) {
+        HIPCHK(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(kernel, dim3(n_groups < resident_wgs ? n_groups : resident_wgs), dim3(WG), lds, s, args...);
+        HIPCHK(hipGetLastError());
         return KS_OK;
     }
     // exact mode (fp64 contexts, standard library): k_rollout_f64
@@ -2467,49 +2445,36 @@ template <typename T> struct Ctx : CtxBase {
         if (ra->budget_ticks != 0) { error = "ks_rollout: a time budget needs the wave form of the rollout kernel (ks_rollout_plan: KS_PLAN_WAVES); fp64 contexts have none"; return KS_ERR_STATE; }
         // dynamic LDS: the hull tables (k_env_step<double>'s step_lds), then the policy tile or the ray stacks (phases apart)
         const size_t ws_offset = (step_lds + 15) / 16 * 16;
-        const size_t policy_bytes = (size_t)(((ra->h1 + 15) / 16 + (ra->h2 + 15) / 16) * 4 + 4) * 16 * 16 + 16;
-        const size_t lds = ws_offset + std::max(policy_bytes, (size_t)F64_RAY_BYTES);
+        const size_t lds = ws_offset + std::max(policy_lds_bytes(ra->h1, ra->h2), (size_t)F64_RAY_BYTES);
         if (lds > 160 * 1024) { error = "ks_rollout: no LDS for the policy beside this object's hull tables"; return KS_ERR_STATE; }
         if ((r = send_rollout_records(ra, s))) return r;
-        const int N = cfg.n_envs;
-        const int t1 = (ra->h1 + 15) / 16, t2 = (ra->h2 + 15) / 16;
-        const bool no_actor = ctl_mode != 0 && !((t1 == 25 && t2 == 19) || (t1 == 8 && t2 == 8) || (t1 == 4 && t2 == 4));     // (any instantiation serves a controller)
-#define KS_ROLLOUT_F64_CASE(A, B)                                                                                                                     \
-    if ((t1 == A && t2 == B) || (A == 16 && no_actor)) {                                                                                             \
-        HIPCHK(hipFuncSetAttribute((const void*)k_rollout_f64<A, B>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                          \
-        hipLaunchKernelGGL((k_rollout_f64<A, B>), dim3(n_groups < resident_wgs ? n_groups : resident_wgs), dim3(WG), lds, s, d_model, b,                  \
-                           (const Buffers<T>*)d_b, N, cfg.frame_skip, cfg.solver_iterations, lpw, (const ObsOut<T>*)d_out, (const ks_rollout_args*)d_ra,    \
-                           n_iter, rollout_round_robin ? -n_groups : n_groups, (int)ws_offset);                                                           \
-        HIPCHK(hipGetLastError());                                                                                                                    \
-        return KS_OK;                                                                                                                                 \
-    }
-        KS_ROLLOUT_F64_CASE(16, 16)
-        KS_ROLLOUT_F64_CASE(25, 19)
-        KS_ROLLOUT_F64_CASE(8, 8)
-        KS_ROLLOUT_F64_CASE(4, 4)
-#undef KS_ROLLOUT_F64_CASE
-        error = "ks_rollout: hidden widths must be 256-256, 400-300, 128-128 or 64-64";
-        return KS_ERR_INVALID;
+        return launch_for_widths(ra, [&](auto tiles) {
+            using W = decltype(tiles);
+            return launch_rollout(k_rollout_f64<W::NT1, W::NT2>, lds, s, d_model, b, (const Buffers<T>*)d_b, cfg.n_envs, cfg.frame_skip, cfg.solver_iterations,
+                                  lpw, (const ObsOut<T>*)d_out, (const ks_rollout_args*)d_ra, n_iter, rollout_round_robin ? -n_groups : n_groups,
+                                  (int)ws_offset);
+        });
 #endif
     }
     int rollout(int n_iter, const ks_rollout_args* ra, hipStream_t s) override {
-        if (!model_loaded) { error = "ks_rollout before ks_load_model"; return KS_ERR_STATE; }
+        if (int r = need_model("ks_rollout")) return r;
         if constexpr (sizeof(T) != 4) return rollout_exact(n_iter, ra, s);
         else {
             int r;
             if ((r = check_rollout_buffers(n_iter, ra))) return r;
             if (!obs_in_step || !cfg.obs_env_major || !cfg.auto_reset) { error = "ks_rollout needs the in-kernel observation path, env-major observations and auto_reset"; return KS_ERR_STATE; }
             if ((r = check_rollout_actor(ra))) return r;
-            if ((size_t)(((ra->h1 + 15) / 16 + (ra->h2 + 15) / 16) * 4 + 4) * 16 * 16 + 16 > (size_t)SCR_TOTAL * lpw * sizeof(T)) { error = "ks_rollout: no LDS for the policy"; return KS_ERR_STATE; }
+            if (policy_lds_bytes(ra->h1, ra->h2) > (size_t)SCR_TOTAL * lpw * sizeof(T)) { error = "ks_rollout: no LDS for the policy"; return KS_ERR_STATE; }
             const int N = cfg.n_envs;
-            if (ra->budget_ticks != 0 && (ra->budget_ticks < 0 || !(plan_waves() && (size_t)(((ra->h1 + 15) / 16 + (ra->h2 + 15) / 16) * 4) * 4 * 16 <= (size_t)SCR_TOTAL * 4 * sizeof(T)))) {
+            // one group per workgroup, and a wave's policy tile fits its own four env blocks: the waves run free
+            const bool wave_free = plan_waves() && policy_wave_lds_bytes(ra->h1, ra->h2) <= (size_t)SCR_TOTAL * 4 * sizeof(T);
+            if (ra->budget_ticks != 0 && (ra->budget_ticks < 0 || !wave_free)) {
                 error = "ks_rollout: a time budget needs the wave form of the rollout kernel (ks_rollout_plan: KS_PLAN_WAVES)";
                 return KS_ERR_STATE;
             }
             if ((r = send_rollout_records(ra, s))) return r;
             // more groups than resident workgroups: the ready queue (k_rollout); else one group per workgroup, nothing to deal
             const bool use_queue = plan_queue();
-            const bool wave_free = plan_waves() && (size_t)(((ra->h1 + 15) / 16 + (ra->h2 + 15) / 16) * 4) * 4 * 16 <= (size_t)SCR_TOTAL * 4 * sizeof(T);
             if (use_queue) {
                 hipLaunchKernelGGL(k_rollout_queue_init, dim3(1), dim3(256), 0, s, d_queue, n_groups);
             }
@@ -2517,24 +2482,12 @@ template <typename T> struct Ctx : CtxBase {
                 if (rollout_phase_deal == 2 && N <= PHASE_ENVS_MAX) hipLaunchKernelGGL(k_slots_by_phase, dim3(1), dim3(PHASE_THREADS), 0, s, (const int64_t*)ra->t, N, n_wg * lpw, b.slot_env);
                 else if (lpw <= 16) hipLaunchKernelGGL(k_slots_by_phase_in_groups, dim3((n_groups + 255) / 256), dim3(256), 0, s, (const int64_t*)ra->t, n_groups, lpw, b.slot_env);
             }
-            const int t1 = (ra->h1 + 15) / 16, t2 = (ra->h2 + 15) / 16;
-            const bool no_actor = ctl_mode != 0 && !((t1 == 25 && t2 == 19) || (t1 == 8 && t2 == 8) || (t1 == 4 && t2 == 4));     // (any instantiation serves a controller)
-#define KS_ROLLOUT_CASE(A, B)                                                                                                                         \
-    if ((t1 == A && t2 == B) || (A == 16 && no_actor)) {                                                                                                 \
-        HIPCHK(hipFuncSetAttribute((const void*)k_rollout<A, B>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)step_lds));                        \
-        hipLaunchKernelGGL((k_rollout<A, B>), dim3(n_groups < resident_wgs ? n_groups : resident_wgs), dim3(WG), step_lds, s, d_model, b, (const Buffers<T>*)d_b, N, cfg.frame_skip,              \
-                           cfg.solver_iterations, lpw, (int)cfg.pair_memory, (const ObsOut<T>*)d_out, (const ks_rollout_args*)d_ra, n_iter,                                              \
-                           (use_queue || !rollout_round_robin) ? n_groups : -n_groups, use_queue ? d_queue : (int*)nullptr, (int)wave_free);                                                                       \
-        HIPCHK(hipGetLastError());                                                                                                                    \
-        return KS_OK;                                                                                                                                 \
-    }
-            KS_ROLLOUT_CASE(16, 16)
-            KS_ROLLOUT_CASE(25, 19)
-            KS_ROLLOUT_CASE(8, 8)
-            KS_ROLLOUT_CASE(4, 4)
-#undef KS_ROLLOUT_CASE
-            error = "ks_rollout: hidden widths must be 256-256, 400-300, 128-128 or 64-64";
-            return KS_ERR_INVALID;
+            return launch_for_widths(ra, [&](auto tiles) {
+                using W = decltype(tiles);
+                return launch_rollout(k_rollout<W::NT1, W::NT2>, step_lds, s, d_model, b, (const Buffers<T>*)d_b, N, cfg.frame_skip, cfg.solver_iterations, lpw,
+                                      (int)cfg.pair_memory, (const ObsOut<T>*)d_out, (const ks_rollout_args*)d_ra, n_iter,
+                                      (use_queue || !rollout_round_robin) ? n_groups : -n_groups, use_queue ? d_queue : (int*)nullptr, (int)wave_free);
+            });
         }
     }
     // more groups than resident workgroups: the ready queue (k_rollout); else one group per workgroup, nothing to deal
@@ -2545,7 +2498,7 @@ template <typename T> struct Ctx : CtxBase {
                (size_t)(wg_rays_words(4, WAVE) + wg_obs_words(4) + 4) <= (size_t)SCR_TOTAL * 4;
     }
     int rollout_plan(int32_t* mode, int32_t* groups, int32_t* workgroups) override {
-        if (!model_loaded) { error = "ks_rollout_plan before ks_load_model"; return KS_ERR_STATE; }
+        if (int r = need_model("ks_rollout_plan")) return r;
         if constexpr (sizeof(T) != 4) {
             // exact mode (k_rollout_f64): barrier-joined workgroups, groups beyond one per workgroup in a fixed deal - never the queue
             if (mode) *mode = n_groups <= resident_wgs ? KS_PLAN_WORKGROUPS : (rollout_round_robin ? KS_PLAN_ROUND_ROBIN : KS_PLAN_RUNS);
@@ -2555,10 +2508,9 @@ template <typename T> struct Ctx : CtxBase {
         return KS_OK;
     }
     int set_start_pool(int k, const void* q0, const void* hq, uint64_t seed, void* obs, hipStream_t s) override {
-        if (!model_loaded) { error = "ks_set_start_pool before ks_load_model"; return KS_ERR_STATE; }
+        if (int r = need_model("ks_set_start_pool")) return r;
         if (k == 0) {                                           // no pool: auto-resets return to the stored initial state again
-            if (pool_k > 0) hipLaunchKernelGGL((k_pool_clear<T>), dim3(1), dim3(1), 0, s, b);
-            pool_k = 0;
+            clear_pool(s);
             HIPCHK(hipGetLastError());
             return KS_OK;
         }
@@ -2577,20 +2529,12 @@ template <typename T> struct Ctx : CtxBase {
             if ((r = alloc(&t.snap, SNAP_TOTAL * N))) return r;
             pb = t;
         }
-        if ((size_t)k > pool_cap) {
-            // (hipFree waits for the device: nothing that is still running reads the storage it gives back)
-            if (pool_store) { (void)hipFree(pool_store); pool_store = nullptr; pool_cap = 0; }
-            const size_t bytes = (size_t)k * N * POOL_VALUES * sizeof(T);
-            if (hipMalloc((void**)&pool_store, bytes) != hipSuccess) {
-                (void)hipGetLastError();
-                pool_store = nullptr;
-                if (pool_k > 0) hipLaunchKernelGGL((k_pool_clear<T>), dim3(1), dim3(1), 0, s, b);      // (the old pool went with its storage)
-                pool_k = 0;
-                error = "ks_set_start_pool: no device memory for " + std::to_string(k) + " starts x " + std::to_string(N) + " envs x " +
-                        std::to_string(POOL_VALUES) + " values (" + std::to_string(bytes) + " bytes)";
-                return KS_ERR_HIP;
-            }
-            pool_cap = (size_t)k;
+        const size_t bytes = (size_t)k * N * POOL_VALUES * sizeof(T);
+        if (!grow(pool_store, pool_cap, (size_t)k, bytes)) {
+            clear_pool(s);                                      // (the old pool went with its storage)
+            error = "ks_set_start_pool: no device memory for " + std::to_string(k) + " starts x " + std::to_string(N) + " envs x " +
+                    std::to_string(POOL_VALUES) + " values (" + std::to_string(bytes) + " bytes)";
+            return KS_ERR_HIP;
         }
         T* pq = pool_store;
         T* ph = pq + (size_t)k * NQ * N;
@@ -2606,10 +2550,7 @@ template <typename T> struct Ctx : CtxBase {
             e.hand_quat = ph + (size_t)j * 4 * N;
             e.obs0 = po + (size_t)j * N * NOBS;
             HIPCHK(hipMemsetAsync(e.flag, 1, N, s));
-            hipLaunchKernelGGL((k_reset<T, USE_LDS>), dim3(blocks()), dim3(WAVE), 0, s, d_model, e, (int)N, 0);
-            hipLaunchKernelGGL((k_rays<T>), dim3(((int)N + RAY_ENVS - 1) / RAY_ENVS, NRAY), dim3(WAVE), 0, s, d_model, e, (int)N, 1);
-            hipLaunchKernelGGL((k_obs<T>), dim3(blocks()), dim3(WAVE), 0, s, d_model, e, (int)N, 1,
-                               ObsOut<T>{nullptr, nullptr, nullptr, nullptr, nullptr, cfg.horizon, cfg.auto_reset, cfg.obs_env_major});
+            reset_pass(e, nullptr, s);
         }
         HIPCHK(hipGetLastError());
         // ... and every env to its draw for episode 0
@@ -2626,11 +2567,10 @@ template <typename T> struct Ctx : CtxBase {
         return KS_OK;
     }
     int set_episode_log(int capacity, hipStream_t s) override {
-        if (!model_loaded) { error = "ks_set_episode_log before ks_load_model"; return KS_ERR_STATE; }
+        if (int r = need_model("ks_set_episode_log")) return r;
         if (!cfg.auto_reset) { error = "ks_set_episode_log: the log is written where an episode restarts inside the stepping kernels - the context needs auto_reset"; return KS_ERR_STATE; }
         if (capacity == 0) {                                    // no log: the ring keeps its storage and its last content
-            if (elog_capacity > 0) hipLaunchKernelGGL((k_elog_clear<T>), dim3(1), dim3(1), 0, s, b);
-            elog_capacity = 0;
+            clear_elog(s);
             HIPCHK(hipGetLastError());
             return KS_OK;
         }
@@ -2639,21 +2579,13 @@ template <typename T> struct Ctx : CtxBase {
             error = "ks_set_episode_log: n_envs <= capacity <= " + std::to_string(KS_EPISODE_LOG_CAPACITY_MAX) + " records (0 clears the log)";
             return KS_ERR_INVALID;
         }
-        if ((size_t)capacity > elog_cap) {
-            // (hipFree waits for the device: nothing that is still running writes the storage it gives back)
-            if (elog_ring) { (void)hipFree(elog_ring); elog_ring = nullptr; elog_cap = 0; }
-            const size_t bytes = (size_t)capacity * sizeof(ks_episode_record);
-            if (hipMalloc((void**)&elog_ring, bytes) != hipSuccess) {
-                (void)hipGetLastError();
-                elog_ring = nullptr;
-                if (elog_capacity > 0) hipLaunchKernelGGL((k_elog_clear<T>), dim3(1), dim3(1), 0, s, b);      // (the old log went with its storage)
-                elog_capacity = 0;
-                error = "ks_set_episode_log: no device memory for " + std::to_string(capacity) + " records (" + std::to_string(bytes) + " bytes)";
-                return KS_ERR_HIP;
-            }
-            elog_cap = (size_t)capacity;
+        const size_t bytes = (size_t)capacity * sizeof(ks_episode_record);
+        if (!grow(elog_ring, elog_cap, (size_t)capacity, bytes)) {
+            clear_elog(s);                                      // (the old log went with its storage)
+            error = "ks_set_episode_log: no device memory for " + std::to_string(capacity) + " records (" + std::to_string(bytes) + " bytes)";
+            return KS_ERR_HIP;
         }
-        HIPCHK(hipMemsetAsync(elog_ring, 0, (size_t)capacity * sizeof(ks_episode_record), s));
+        HIPCHK(hipMemsetAsync(elog_ring, 0, bytes, s));
         const EpisodeLog<T> rec{capacity, 0, elog_written, elog_ring, elog_ordinal, b.obj_id, b.obs0, b.pool};
         hipLaunchKernelGGL((k_elog_begin<T>), dim3((N + 255) / 256), dim3(256), 0, s, b, rec, N);
         HIPCHK(hipGetLastError());
@@ -2661,11 +2593,10 @@ template <typename T> struct Ctx : CtxBase {
         return KS_OK;
     }
     int set_param_ranges(const void* ranges, uint64_t seed, hipStream_t s) override {
-        if (!model_loaded) { error = "ks_set_param_ranges before ks_load_model"; return KS_ERR_STATE; }
+        if (int r = need_model("ks_set_param_ranges")) return r;
         if (!cfg.auto_reset) { error = "ks_set_param_ranges: the parameters are drawn where an episode restarts inside the stepping kernels - the context needs auto_reset"; return KS_ERR_STATE; }
         if (!ranges) {                                          // no ranges: every env keeps the values of its running episode
-            if (dr_active) hipLaunchKernelGGL((k_ranges_clear<T>), dim3(1), dim3(1), 0, s, b);
-            dr_active = false;
+            clear_ranges(s);
             HIPCHK(hipGetLastError());
             return KS_OK;
         }
@@ -2685,7 +2616,7 @@ template <typename T> struct Ctx : CtxBase {
         return KS_OK;
     }
     int get_env_params(void* mass, void* mu, int64_t* episode, hipStream_t s) override {
-        if (!model_loaded) { error = "ks_get_env_params before ks_load_model"; return KS_ERR_STATE; }
+        if (int r = need_model("ks_get_env_params")) return r;
         const size_t N = cfg.n_envs;
         if (mass) HIPCHK(hipMemcpyAsync(mass, b.envp, N * sizeof(T), hipMemcpyDefault, s));
         if (mu) HIPCHK(hipMemcpyAsync(mu, b.envp + N, N * sizeof(T), hipMemcpyDefault, s));
@@ -2696,7 +2627,7 @@ template <typename T> struct Ctx : CtxBase {
         return KS_OK;
     }
     int set_rollout_controller(int mode, int lift_rule, hipStream_t s) override {
-        if (!model_loaded) { error = "ks_set_rollout_controller before ks_load_model"; return KS_ERR_STATE; }
+        if (int r = need_model("ks_set_rollout_controller")) return r;
         if (mode != KS_CONTROLLER_NONE && !krsel::controller_args_ok(mode, lift_rule)) {
             error = "ks_set_rollout_controller: mode 0 (none), 1 (naive), 2 (position-dependent) or 3 (combined); lift rule 0 (train) or 1 (expert)";
             return KS_ERR_INVALID;
@@ -2710,7 +2641,7 @@ template <typename T> struct Ctx : CtxBase {
         return KS_OK;
     }
     int get_rollout_controller(int32_t* mode, int32_t* lift_rule, float* init, hipStream_t s) override {
-        if (!model_loaded) { error = "ks_get_rollout_controller before ks_load_model"; return KS_ERR_STATE; }
+        if (int r = need_model("ks_get_rollout_controller")) return r;
         if (mode) *mode = ctl_mode;
         if (lift_rule) *lift_rule = ctl_lift_rule;
         if (init) HIPCHK(hipMemcpyAsync(init, ctl_init, (size_t)2 * cfg.n_envs * sizeof(float), hipMemcpyDeviceToDevice, s));
@@ -2723,7 +2654,7 @@ template <typename T> struct Ctx : CtxBase {
         return KS_OK;
     }
     int substep(const void* ctrl, hipStream_t s) override {
-        if (!model_loaded) { error = "ks_substep before ks_load_model"; return KS_ERR_STATE; }
+        if (int r = need_model("ks_substep")) return r;
         hipLaunchKernelGGL((k_substep<T, USE_LDS>), dim3(n_wg), dim3(WG), step_lds, s, d_model, b, (const T*)ctrl, cfg.n_envs,
                            cfg.solver_iterations, lpw, cfg.contact_tap);
         HIPCHK(hipGetLastError());
@@ -2747,14 +2678,14 @@ template <typename T> struct Ctx : CtxBase {
         return KS_OK;
     }
     int set_env_params(const void* mass, const void* mu, hipStream_t s) override {
-        if (!model_loaded) { error = "ks_set_env_params before ks_load_model"; return KS_ERR_STATE; }
+        if (int r = need_model("ks_set_env_params")) return r;
         const size_t N = cfg.n_envs;
         if (mass) HIPCHK(hipMemcpyAsync(b.envp, mass, N * sizeof(T), hipMemcpyDefault, s));
         if (mu) HIPCHK(hipMemcpyAsync(b.envp + N, mu, N * sizeof(T), hipMemcpyDefault, s));
         return KS_OK;
     }
     int obs_from_snapshot(const void* snap, const void* rays, void* obs, void* reward, uint8_t* done, void* info, hipStream_t s) override {
-        if (!model_loaded) { error = "ks_obs_from_snapshot before ks_load_model"; return KS_ERR_STATE; }
+        if (int r = need_model("ks_obs_from_snapshot")) return r;
         if (!snap || !rays || !obs) { error = "ks_obs_from_snapshot: snapshot, rays and obs are required"; return KS_ERR_INVALID; }
         const size_t N = cfg.n_envs;
         HIPCHK(hipMemcpyAsync(b.snap, snap, (size_t)SNAP_TOTAL * N * sizeof(T), hipMemcpyDefault, s));
@@ -2785,6 +2716,12 @@ template <typename T> struct Ctx : CtxBase {
 struct ks_ctx {
     CtxBase* impl;
 };
+
+// an export's call to its context's method (a stream arrives as void*)
+template <typename... P, typename... A> static int ctx_call(ks_ctx* ctx, int (CtxBase::*method)(P...), A... args) {
+    if (!ctx) return KS_ERR_INVALID;
+    return (ctx->impl->*method)(args...);
+}
 
 extern "C" {
 
@@ -2845,81 +2782,61 @@ int ks_load_models(ks_ctx* ctx, int32_t n_models, const void* const* blobs, cons
     return ctx->impl->load_models(n_models, blobs, nbytes);
 }
 int ks_reset(ks_ctx* ctx, const int32_t* ids, int32_t n, const void* q0, const void* hq, void* obs, void* stream) {
-    if (!ctx) return KS_ERR_INVALID;
-    return ctx->impl->reset(ids, n, q0, hq, nullptr, nullptr, obs, (hipStream_t)stream);
+    return ctx_call(ctx, &CtxBase::reset, ids, n, q0, hq, nullptr, nullptr, obs, (hipStream_t)stream);
 }
-int ks_reset_objects(ks_ctx* ctx, const int32_t* ids, int32_t n, const void* q0, const void* hq, const int32_t* object_id, const void* mass_friction,
-                     void* obs, void* stream) {
-    if (!ctx) return KS_ERR_INVALID;
-    return ctx->impl->reset(ids, n, q0, hq, object_id, mass_friction, obs, (hipStream_t)stream);
+int ks_reset_objects(ks_ctx* ctx, const int32_t* ids, int32_t n, const void* q0, const void* hq, const int32_t* object_id, const void* mass_friction, void* obs, void* stream) {
+    return ctx_call(ctx, &CtxBase::reset, ids, n, q0, hq, object_id, mass_friction, obs, (hipStream_t)stream);
 }
 int ks_step(ks_ctx* ctx, const void* action, void* obs, void* reward, uint8_t* done, void* info, void* final_obs, void* stream) {
-    if (!ctx) return KS_ERR_INVALID;
-    return ctx->impl->step(action, obs, reward, done, info, final_obs, (hipStream_t)stream);
+    return ctx_call(ctx, &CtxBase::step, action, obs, reward, done, info, final_obs, (hipStream_t)stream);
 }
 int ks_get_state(ks_ctx* ctx, void* qpos, void* qvel, void* warm, void* contact, int32_t* ncon, int32_t* status, void* stream) {
-    if (!ctx) return KS_ERR_INVALID;
-    return ctx->impl->get_state(qpos, qvel, warm, contact, ncon, status, (hipStream_t)stream);
+    return ctx_call(ctx, &CtxBase::get_state, qpos, qvel, warm, contact, ncon, status, (hipStream_t)stream);
 }
 int ks_set_state(ks_ctx* ctx, const void* qpos, const void* qvel, const void* warm, void* stream) {
-    if (!ctx) return KS_ERR_INVALID;
-    return ctx->impl->set_state(qpos, qvel, warm, (hipStream_t)stream);
+    return ctx_call(ctx, &CtxBase::set_state, qpos, qvel, warm, (hipStream_t)stream);
 }
 int ks_set_env_params(ks_ctx* ctx, const void* obj_mass, const void* obj_mu, void* stream) {
-    if (!ctx) return KS_ERR_INVALID;
-    return ctx->impl->set_env_params(obj_mass, obj_mu, (hipStream_t)stream);
+    return ctx_call(ctx, &CtxBase::set_env_params, obj_mass, obj_mu, (hipStream_t)stream);
 }
 int ks_rollout(ks_ctx* ctx, int32_t n_iter, const ks_rollout_args* args_host, void* stream) {
-    if (!ctx) return KS_ERR_INVALID;
-    return ctx->impl->rollout(n_iter, args_host, (hipStream_t)stream);
+    return ctx_call(ctx, &CtxBase::rollout, n_iter, args_host, (hipStream_t)stream);
 }
 int ks_rollout_plan(ks_ctx* ctx, int32_t* mode, int32_t* groups, int32_t* workgroups) {
-    if (!ctx) return KS_ERR_INVALID;
-    return ctx->impl->rollout_plan(mode, groups, workgroups);
+    return ctx_call(ctx, &CtxBase::rollout_plan, mode, groups, workgroups);
 }
 int ks_set_start_pool(ks_ctx* ctx, int32_t k, const void* qpos0, const void* hand_quat, uint64_t seed, void* obs, void* stream) {
-    if (!ctx) return KS_ERR_INVALID;
-    return ctx->impl->set_start_pool(k, qpos0, hand_quat, seed, obs, (hipStream_t)stream);
+    return ctx_call(ctx, &CtxBase::set_start_pool, k, qpos0, hand_quat, seed, obs, (hipStream_t)stream);
 }
 int ks_get_start_index(ks_ctx* ctx, int32_t* index, int64_t* episode, void* stream) {
-    if (!ctx) return KS_ERR_INVALID;
-    return ctx->impl->get_start_index(index, episode, (hipStream_t)stream);
+    return ctx_call(ctx, &CtxBase::get_start_index, index, episode, (hipStream_t)stream);
 }
 int ks_set_episode_log(ks_ctx* ctx, int32_t capacity, void* stream) {
-    if (!ctx) return KS_ERR_INVALID;
-    return ctx->impl->set_episode_log(capacity, (hipStream_t)stream);
+    return ctx_call(ctx, &CtxBase::set_episode_log, capacity, (hipStream_t)stream);
 }
 int ks_set_param_ranges(ks_ctx* ctx, const void* ranges, uint64_t seed, void* stream) {
-    if (!ctx) return KS_ERR_INVALID;
-    return ctx->impl->set_param_ranges(ranges, seed, (hipStream_t)stream);
+    return ctx_call(ctx, &CtxBase::set_param_ranges, ranges, seed, (hipStream_t)stream);
 }
 int ks_get_env_params(ks_ctx* ctx, void* mass, void* mu, int64_t* episode, void* stream) {
-    if (!ctx) return KS_ERR_INVALID;
-    return ctx->impl->get_env_params(mass, mu, episode, (hipStream_t)stream);
+    return ctx_call(ctx, &CtxBase::get_env_params, mass, mu, episode, (hipStream_t)stream);
 }
 int ks_set_rollout_controller(ks_ctx* ctx, int32_t mode, int32_t lift_rule, void* stream) {
-    if (!ctx) return KS_ERR_INVALID;
-    return ctx->impl->set_rollout_controller(mode, lift_rule, (hipStream_t)stream);
+    return ctx_call(ctx, &CtxBase::set_rollout_controller, mode, lift_rule, (hipStream_t)stream);
 }
 int ks_get_rollout_controller(ks_ctx* ctx, int32_t* mode, int32_t* lift_rule, float* init, void* stream) {
-    if (!ctx) return KS_ERR_INVALID;
-    return ctx->impl->get_rollout_controller(mode, lift_rule, init, (hipStream_t)stream);
+    return ctx_call(ctx, &CtxBase::get_rollout_controller, mode, lift_rule, init, (hipStream_t)stream);
 }
 int ks_get_episode_log(ks_ctx* ctx, ks_episode_record* ring_out, int64_t* written_out, void* stream) {
-    if (!ctx) return KS_ERR_INVALID;
-    return ctx->impl->get_episode_log(ring_out, written_out, (hipStream_t)stream);
+    return ctx_call(ctx, &CtxBase::get_episode_log, ring_out, written_out, (hipStream_t)stream);
 }
 int ks_substep(ks_ctx* ctx, const void* ctrl, void* stream) {
-    if (!ctx) return KS_ERR_INVALID;
-    return ctx->impl->substep(ctrl, (hipStream_t)stream);
+    return ctx_call(ctx, &CtxBase::substep, ctrl, (hipStream_t)stream);
 }
 int ks_obs_from_snapshot(ks_ctx* ctx, const void* snap, const void* rays, void* obs, void* reward, uint8_t* done, void* info, void* stream) {
-    if (!ctx) return KS_ERR_INVALID;
-    return ctx->impl->obs_from_snapshot(snap, rays, obs, reward, done, info, (hipStream_t)stream);
+    return ctx_call(ctx, &CtxBase::obs_from_snapshot, snap, rays, obs, reward, done, info, (hipStream_t)stream);
 }
 int ks_kernel_time(ks_ctx* ctx, int reset, double* avg_ms, int64_t* launches) {
-    if (!ctx) return KS_ERR_INVALID;
-    return ctx->impl->kernel_time(reset, avg_ms, launches);
+    return ctx_call(ctx, &CtxBase::kernel_time, reset, avg_ms, launches);
 }
 
 }  // extern "C"
