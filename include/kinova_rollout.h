@@ -201,6 +201,39 @@ int kr_sample_windows_prioritized(int32_t batch, int32_t batch_agent, int32_t ho
                                   const float *u_start, uint64_t seed, const int64_t *draw, float *state, float *action, float *next_state,
                                   float *reward, float *not_done, float *weight, float *next_ends, int32_t *picked, void *stream);
 
+/* kr_sample_windows_balanced and kr_sample_windows_prioritized combined: the class of every batch slot by the balanced rule, the episode within
+ * that class by priority.  The rings carry both columns; agent_class / expert_class, n_classes, rotation as in kr_sample_windows_balanced,
+ * agent_prio / expert_prio, beta and picked as in kr_sample_windows_prioritized (a table of a ring without batch slots may be NULL).  Per
+ * ring segment of the batch, whose first slot is b0:
+ *   eligible   the count - 1 oldest episodes of the ring, age a = 0 .. count - 2 in slot (head - count + a) mod capacity;
+ *              p_a = max(ep_prio[slot], 1);
+ *   slot b     wants class c = (b - b0 + rotation + (draw ? draw[0] : 0)) mod n_classes (non-negative);
+ *   q_a        p_a where the tag of age a is c, else 0; a tag outside [0, n_classes) belongs to no class.  m_c the number of eligible episodes
+ *              of the class, T_c the sum (uint64) of the q_a, pmin_c the least p_a of the class;
+ *   m_c > 0    with the slot's episode uniform ue:  t = min(T_c - 1, (uint64)((double)ue * (double)T_c))  - one IEEE double product -, and
+ *              the slot takes the episode at the SMALLEST age whose inclusive prefix sum q_0 + .. + q_a exceeds t: an episode of class c.
+ *              Every real window row of it gets  w_b = powf((float)pmin_c / (float)p_b, beta[0]),  padding rows 0: the importance weight that
+ *              corrects the draw back to kr_sample_windows_balanced's distribution, uniform within the class, (T_c / (m_c p_b))^beta, over
+ *              its maximum over the class - as kr_sample_windows_prioritized normalises each ring on its own;
+ *   m_c == 0   kr_sample_windows_prioritized's rule and weight over all eligible episodes of the ring (kr_sample_windows_balanced falls
+ *              back to the uniform rule in the same case).
+ * A ring with fewer than two episodes, window starts, the final window, the output layout, next_ends, picked and the uniforms - the caller's
+ * or Philox with kr_sample_windows_draw's key, counters and tags -: as the two samplers.  Hence:
+ *   - with n_classes == 1 and every tag 0, or with no eligible tag inside [0, n_classes), the batch equals kr_sample_windows_prioritized's;
+ *   - with every priority 65536 the slot takes the floor((double)ue * m_c)-th oldest episode of its class and every real weight is exactly 1.
+ * Two launches: the pick (`batch` waves; each walks its ring's one or two contiguous pieces of BOTH tables twice - sum and minimum of the
+ * class, then locate -, 16-byte loads of the priorities where aligned and of the tags where the two tables sit alike relative to a 16-byte
+ * boundary, which they need not, per-element loads otherwise and at the pieces' ends, nothing outside them read, no atomics, no LDS) and
+ * kr_sample_windows_prioritized's gather, w_b and the slot travelling the same way.
+ * KS_ERR_INVALID, nothing launched or written: what kr_sample_windows_mixed refuses; n_classes < 1 or > 64; a NULL beta; for a ring that has
+ * batch slots, a NULL class or priority table or capacity > 2^20. */
+int kr_sample_windows_balanced_prioritized(int32_t batch, int32_t batch_agent, int32_t horizon, int32_t n_steps, const kr_ring *agent,
+                                           const kr_ring *expert, const int32_t *agent_class, const int32_t *expert_class, int32_t n_classes,
+                                           int32_t rotation, const uint32_t *agent_prio, const uint32_t *expert_prio, const float *beta,
+                                           const float *u_ep, const float *u_start, uint64_t seed, const int64_t *draw, float *state,
+                                           float *action, float *next_state, float *reward, float *not_done, float *weight, float *next_ends,
+                                           int32_t *picked, void *stream);
+
 /* The priorities of the episodes a batch was read from, from the critic's errors on it: issued after kr_critic_grad on the same q, tq1
  * [batch * W], reward [batch * W, n_steps], weight [batch * W] and on the sampler's picked [batch]; W = horizon - n_steps.
  *   real row   r = b W + w is real iff weight[r] > 0;

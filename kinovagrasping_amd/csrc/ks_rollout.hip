@@ -427,9 +427,12 @@ __device__ __forceinline__ uint32_t prio_at(const uint32_t* __restrict__ tab, in
 
 // vector q of a piece that has one (qa < qb), in two steps so that a group's loads can be issued back to back: the load itself is
 // unconditional - beyond the piece's last vector, of that one - and what it brought is put right afterwards, 0 beyond the last vector
+__device__ __forceinline__ uint32_t prio_first(int q, const PrioPiece& p) {
+    return (uint32_t)(4 * (q < p.qb ? q : p.qb - 1) - p.mis);                  // (>= s0 >= 0; unsigned: a 32-bit offset to a uniform base)
+}
+
 __device__ __forceinline__ v4u prio_raw(const uint32_t* __restrict__ tab, int q, const PrioPiece& p) {
-    const uint32_t e = (uint32_t)(4 * (q < p.qb ? q : p.qb - 1) - p.mis);      // (>= s0 >= 0; unsigned: a 32-bit offset to a uniform base)
-    return *(const v4u*)(tab + e);
+    return *(const v4u*)(tab + prio_first(q, p));
 }
 
 __device__ __forceinline__ v4u prio_fix(v4u v, int q, const PrioPiece& p) {
@@ -451,75 +454,141 @@ __device__ __forceinline__ unsigned long long sum4(v4u v) {
 
 __device__ __forceinline__ uint32_t min_inside(uint32_t m, uint32_t p) { return p != 0u && p < m ? p : m; }
 
-// the sum and the minimum of the piece's priorities: lane partials only (integers: exact in any order), the caller reduces over the wave
-__device__ __forceinline__ void prio_total(const uint32_t* __restrict__ tab, int s0, int s1, int lane, unsigned long long& sum, uint32_t& least) {
+// The walk under a class mask (MASKED, kr_sample_windows_balanced_prioritized): an episode whose tag is not `c` counts with priority 0 - it adds
+// nothing to the sum, is no candidate for the minimum and is never located; with `all` set every episode counts, the unmasked walk's
+// results.  The tags of a vector's four episodes come with one 16-byte load where the two tables sit alike relative to a 16-byte boundary
+// (`aligned`), else with four loads of the same elements: the vectors are the priority table's, and nothing outside the piece is read of
+// either table.  MASKED_TRIPS trips to a group: two groups of vectors of BOTH tables in the registers PRIO_TRIPS trips of one table take.
+constexpr int MASKED_TRIPS = 3;
+struct ClassMask { const int* tags; int c; bool all, aligned; };
+
+__device__ __forceinline__ ClassMask class_mask(const int* tags, const uint32_t* tab, int c, bool all) {
+    return ClassMask{tags, c, all, ((((uintptr_t)tags ^ (uintptr_t)tab) >> 2) & 3) == 0};
+}
+
+__device__ __forceinline__ v4i tags_raw(int q, const PrioPiece& p, const ClassMask& m) {
+    const int* at = m.tags + prio_first(q, p);
+    if (m.aligned) return *(const v4i*)at;
+    return v4i{at[0], at[1], at[2], at[3]};
+}
+
+__device__ __forceinline__ v4u prio_masked(v4u v, v4i t, const ClassMask& m) {
+    v.x = m.all || t.x == m.c ? v.x : 0u; v.y = m.all || t.y == m.c ? v.y : 0u;
+    v.z = m.all || t.z == m.c ? v.z : 0u; v.w = m.all || t.w == m.c ? v.w : 0u;
+    return v;
+}
+
+// prio_at under the mask
+template <bool MASKED>
+__device__ __forceinline__ uint32_t prio_edge(const uint32_t* __restrict__ tab, int e, int lo, int hi, const ClassMask& m) {
+    uint32_t x = prio_at(tab, e, lo, hi);
+    if constexpr (MASKED) {
+        if (x != 0u && !m.all && m.tags[e] != m.c) x = 0u;                      // (x != 0: e lies inside)
+    }
+    return x;
+}
+
+// prio_fix under the mask, t the vector's tags
+template <bool MASKED>
+__device__ __forceinline__ v4u prio_value(v4u v, v4i t, int q, const PrioPiece& p, const ClassMask& m) {
+    v = prio_fix(v, q, p);
+    if constexpr (MASKED) v = prio_masked(v, t, m);
+    return v;
+}
+
+// the sum and the minimum of the piece's priorities (MASKED: of those the mask m lets through): lane partials only (integers: exact in any
+// order), the caller reduces over the wave
+template <int TRIPS = PRIO_TRIPS, bool MASKED = false>
+__device__ __forceinline__ void prio_total(const uint32_t* __restrict__ tab, int s0, int s1, int lane, unsigned long long& sum, uint32_t& least,
+                                           const ClassMask& m = ClassMask{}) {
     if (s1 <= s0) return;
     const PrioPiece p = prio_piece(tab, s0, s1);
-    const uint32_t edge = lane < 3 ? prio_at(tab, p.s0 + lane, p.s0, p.ha) : (lane < 6 ? prio_at(tab, p.hb + lane - 3, p.hb, p.s1) : 0u);
+    const uint32_t edge = lane < 3 ? prio_edge<MASKED>(tab, p.s0 + lane, p.s0, p.ha, m)
+                                   : (lane < 6 ? prio_edge<MASKED>(tab, p.hb + lane - 3, p.hb, p.s1, m) : 0u);
     sum += edge;
     least = min_inside(least, edge);
     if (p.qa >= p.qb) return;
-    constexpr int GROUP = PRIO_TRIPS * WAVE;
-    v4u cur[PRIO_TRIPS], nxt[PRIO_TRIPS];
+    constexpr int GROUP = TRIPS * WAVE;
+    v4u cur[TRIPS], nxt[TRIPS];
+    v4i tcur[TRIPS] = {}, tnxt[TRIPS] = {};                                     // (the tags: MASKED only)
 #pragma unroll
-    for (int u = 0; u < PRIO_TRIPS; u++) cur[u] = prio_raw(tab, p.qa + u * WAVE + lane, p);
+    for (int u = 0; u < TRIPS; u++) {
+        cur[u] = prio_raw(tab, p.qa + u * WAVE + lane, p);
+        if constexpr (MASKED) tcur[u] = tags_raw(p.qa + u * WAVE + lane, p, m);
+    }
     for (int g0 = p.qa; g0 < p.qb; g0 += GROUP) {
 #pragma unroll
-        for (int u = 0; u < PRIO_TRIPS; u++) nxt[u] = prio_raw(tab, g0 + GROUP + u * WAVE + lane, p);
+        for (int u = 0; u < TRIPS; u++) {
+            nxt[u] = prio_raw(tab, g0 + GROUP + u * WAVE + lane, p);
+            if constexpr (MASKED) tnxt[u] = tags_raw(g0 + GROUP + u * WAVE + lane, p, m);
+        }
 #pragma unroll
-        for (int u = 0; u < PRIO_TRIPS; u++) {
-            const v4u v = prio_fix(cur[u], g0 + u * WAVE + lane, p);
+        for (int u = 0; u < TRIPS; u++) {
+            const v4u v = prio_value<MASKED>(cur[u], tcur[u], g0 + u * WAVE + lane, p, m);
             sum += sum4(v);
             least = min_inside(min_inside(min_inside(min_inside(least, v.x), v.y), v.z), v.w);
         }
 #pragma unroll
-        for (int u = 0; u < PRIO_TRIPS; u++) cur[u] = nxt[u];
+        for (int u = 0; u < TRIPS; u++) { cur[u] = nxt[u]; tcur[u] = tnxt[u]; }
     }
 }
 
 // the index, within the table, of the piece's first element - age order: the head, then trip by trip, lane by lane, the lane's four in turn,
 // then the tail - whose inclusive prefix sum over the piece exceeds `target` (< the piece's sum, so there is one; -1 otherwise), and its
 // priority.  One wave sum per group; the group that holds the target is then read once more and taken apart trip by trip, and its one trip
-// lane by lane.  The same in every lane.
-__device__ __forceinline__ int prio_locate(const uint32_t* __restrict__ tab, int s0, int s1, unsigned long long target, int lane, uint32_t& prio) {
+// lane by lane.  The same in every lane.  MASKED: the priorities as the mask m leaves them; an episode it hides is never the one named.
+template <int TRIPS = PRIO_TRIPS, bool MASKED = false>
+__device__ __forceinline__ int prio_locate(const uint32_t* __restrict__ tab, int s0, int s1, unsigned long long target, int lane, uint32_t& prio,
+                                           const ClassMask& m = ClassMask{}) {
     if (s1 <= s0) return -1;
     const PrioPiece p = prio_piece(tab, s0, s1);
     unsigned long long seen = 0;
 #pragma unroll
     for (int i = 0; i < 3; i++) {
-        const uint32_t x = prio_at(tab, p.s0 + i, p.s0, p.ha);
+        const uint32_t x = prio_edge<MASKED>(tab, p.s0 + i, p.s0, p.ha, m);
         if (x != 0u && target < seen + x) { prio = x; return p.s0 + i; }
         seen += x;
     }
-    constexpr int GROUP = PRIO_TRIPS * WAVE;
+    constexpr int GROUP = TRIPS * WAVE;
     int hit_group = -1;
     if (p.qa < p.qb) {
-        v4u cur[PRIO_TRIPS], nxt[PRIO_TRIPS];
+        v4u cur[TRIPS], nxt[TRIPS];
+        v4i tcur[TRIPS] = {}, tnxt[TRIPS] = {};
 #pragma unroll
-        for (int u = 0; u < PRIO_TRIPS; u++) cur[u] = prio_raw(tab, p.qa + u * WAVE + lane, p);
+        for (int u = 0; u < TRIPS; u++) {
+            cur[u] = prio_raw(tab, p.qa + u * WAVE + lane, p);
+            if constexpr (MASKED) tcur[u] = tags_raw(p.qa + u * WAVE + lane, p, m);
+        }
         for (int g0 = p.qa; g0 < p.qb; g0 += GROUP) {
 #pragma unroll
-            for (int u = 0; u < PRIO_TRIPS; u++) nxt[u] = prio_raw(tab, g0 + GROUP + u * WAVE + lane, p);
+            for (int u = 0; u < TRIPS; u++) {
+                nxt[u] = prio_raw(tab, g0 + GROUP + u * WAVE + lane, p);
+                if constexpr (MASKED) tnxt[u] = tags_raw(g0 + GROUP + u * WAVE + lane, p, m);
+            }
             unsigned long long mine = 0;
 #pragma unroll
-            for (int u = 0; u < PRIO_TRIPS; u++) mine += sum4(prio_fix(cur[u], g0 + u * WAVE + lane, p));
+            for (int u = 0; u < TRIPS; u++) mine += sum4(prio_value<MASKED>(cur[u], tcur[u], g0 + u * WAVE + lane, p, m));
             const unsigned long long group = wave_sum_u64(mine);
             if (target < seen + group) { hit_group = g0; break; }             // (wave-uniform)
             seen += group;
 #pragma unroll
-            for (int u = 0; u < PRIO_TRIPS; u++) cur[u] = nxt[u];
+            for (int u = 0; u < TRIPS; u++) { cur[u] = nxt[u]; tcur[u] = tnxt[u]; }
         }
     }
     if (hit_group >= 0) {
-        v4u grp[PRIO_TRIPS];
+        v4u grp[TRIPS];
+        v4i tgrp[TRIPS] = {};
 #pragma unroll
-        for (int u = 0; u < PRIO_TRIPS; u++) grp[u] = prio_raw(tab, hit_group + u * WAVE + lane, p);
+        for (int u = 0; u < TRIPS; u++) {
+            grp[u] = prio_raw(tab, hit_group + u * WAVE + lane, p);
+            if constexpr (MASKED) tgrp[u] = tags_raw(hit_group + u * WAVE + lane, p, m);
+        }
         v4u hit = {0u, 0u, 0u, 0u};
         int trip = 0;
         bool found = false;
 #pragma unroll
-        for (int u = 0; u < PRIO_TRIPS; u++) {
-            const v4u v = prio_fix(grp[u], hit_group + u * WAVE + lane, p);
+        for (int u = 0; u < TRIPS; u++) {
+            const v4u v = prio_value<MASKED>(grp[u], tgrp[u], hit_group + u * WAVE + lane, p, m);
             const unsigned long long tot = wave_sum_u64(sum4(v));
             if (!found && target < seen + tot) { hit = v; trip = hit_group + u * WAVE; found = true; }
             if (!found) seen += tot;
@@ -548,7 +617,7 @@ __device__ __forceinline__ int prio_locate(const uint32_t* __restrict__ tab, int
     }
 #pragma unroll
     for (int i = 0; i < 3; i++) {
-        const uint32_t x = prio_at(tab, p.hb + i, p.hb, p.s1);
+        const uint32_t x = prio_edge<MASKED>(tab, p.hb + i, p.hb, p.s1, m);
         if (x != 0u && target < seen + x) { prio = x; return p.hb + i; }
         seen += x;
     }
@@ -602,6 +671,73 @@ __global__ __launch_bounds__(WAVE) void k_pick_prioritized(int B, int B_agent, i
         uint32_t p = least;
         const bool older = t < t_a;
         ep = prio_locate(tab, older ? (int)first : 0, (int)(older ? end_a : end_b), older ? t : t - t_a, lane, p);
+        wb = powf((float)least / (float)p, beta[0]);
+    }
+    if (ep < 0) ep = uniform_episode(ue, cnt, head, capacity);
+    for (int w = lane; w < W; w += WAVE) {
+        weight[(long)b * W + w] = wb;
+        if (picked == nullptr) ((int*)reward)[((long)b * W + w) * n_steps] = (int)ep;
+    }
+    if (picked != nullptr && lane == 0) picked[b] = (int)ep;
+}
+
+// The pick of kr_sample_windows_balanced_prioritized: k_pick_balanced's class c for the slot, then k_pick_prioritized's rule over the eligible
+// episodes tagged c alone - their sum T_c, their minimum, the episode at the smallest age whose inclusive prefix sum of the masked priorities
+// exceeds t, the weight powf(pmin_c / p_b, beta).  Where no eligible episode is tagged c (T_c == 0: a priority reads as at least 1) the walk is
+// made once more over all of them, which is k_pick_prioritized itself.  Both tables are walked twice, the priority table's vectors setting
+// the pace (ClassMask).  Outputs as k_pick_prioritized.
+__global__ __launch_bounds__(WAVE) void k_pick_balanced_prioritized(int B, int B_agent, int W, int n_steps, Ring ra, Ring re,
+                                                                    const int* __restrict__ agent_class, const int* __restrict__ expert_class,
+                                                                    int n_classes, int rotation, const uint32_t* __restrict__ agent_prio,
+                                                                    const uint32_t* __restrict__ expert_prio, const float* __restrict__ beta,
+                                                                    const float* __restrict__ u_ep, unsigned long long seed,
+                                                                    const int64_t* __restrict__ draw, int* __restrict__ picked,
+                                                                    float* __restrict__ reward, float* __restrict__ weight) {
+#pragma clang fp contract(off)
+    const int b = blockIdx.x, lane = threadIdx.x;
+    if (b >= B) return;
+    const bool is_agent = b < B_agent;
+    const Ring& g = is_agent ? ra : re;
+    const uint32_t* tab = is_agent ? agent_prio : expert_prio;
+    const int* tags = is_agent ? agent_class : expert_class;
+    const long cnt = g.count[0], head = g.head[0];
+    const int capacity = g.capacity;
+    const float ue = sample_uniform(u_ep, b, 0x5a4du, seed, draw);
+    long want = (long)(b - (is_agent ? 0 : B_agent)) + rotation + (draw != nullptr ? draw[0] : 0);
+    want %= n_classes;
+    const int c = (int)(want < 0 ? want + n_classes : want);
+    long first = (head - cnt) % capacity;
+    first = first < 0 ? first + capacity : first;
+    long eligible = cnt - 1 > 0 ? cnt - 1 : 0;
+    eligible = eligible < capacity ? eligible : capacity - 1;                   // (count <= capacity)
+    const long end_a = first + eligible < capacity ? first + eligible : capacity;   // piece A: slots [first, end_a), the older ones
+    const long end_b = first + eligible - end_a;                                // piece B: slots [0, end_b) behind the wrap
+    long ep = -1;
+    float wb = 1.0f;
+    if (eligible > 0) {
+        unsigned long long t_a = 0, total = 0;
+        uint32_t least = 0xffffffffu;
+        ClassMask m = class_mask(tags, tab, c, false);
+#pragma nounroll
+        for (int pass = 0; pass < 4 && (pass < 2 || total == 0); pass++) {          // (passes 0, 1: the class's pieces A, B; 2, 3: everybody's)
+            const int piece = pass & 1;
+            m.all = pass >= 2;
+            unsigned long long sum = 0;
+            prio_total<MASKED_TRIPS, true>(tab, piece ? 0 : (int)first, (int)(piece ? end_b : end_a), lane, sum, least, m);
+            sum = wave_sum_u64(sum);
+            if (!piece) t_a = sum;
+            total = piece ? t_a + sum : 0;
+        }
+#pragma unroll
+        for (int o = WAVE / 2; o > 0; o >>= 1) {
+            const uint32_t other = (uint32_t)__shfl_xor((int)least, o);
+            least = other < least ? other : least;
+        }
+        unsigned long long t = (unsigned long long)__dmul_rn((double)ue, (double)total);
+        t = t < total - 1 ? t : total - 1;
+        uint32_t p = least;
+        const bool older = t < t_a;
+        ep = prio_locate<MASKED_TRIPS, true>(tab, older ? (int)first : 0, (int)(older ? end_a : end_b), older ? t : t - t_a, lane, p, m);
         wb = powf((float)least / (float)p, beta[0]);
     }
     if (ep < 0) ep = uniform_episode(ue, cnt, head, capacity);
@@ -985,6 +1121,28 @@ int kr_sample_windows_prioritized(int32_t batch, int32_t batch_agent, int32_t ho
     const int* slots = picked != nullptr ? picked : (const int*)reward;
     hipLaunchKernelGGL(k_pick_prioritized, dim3(batch), dim3(WAVE), 0, (hipStream_t)stream, batch, batch_agent, horizon - n_steps, n_steps, to_ring(agent),
                        to_ring(expert), agent_prio, expert_prio, beta, u_ep, (unsigned long long)seed, draw, picked, reward, weight);
+    if (launched() != KS_OK) return KS_ERR_HIP;
+    return gather_windows(batch, batch_agent, horizon, n_steps, agent, expert, slots, row_major, u_start, seed, draw, next_ends, state, action, next_state,
+                          reward, not_done, weight, weight, stream);
+}
+
+int kr_sample_windows_balanced_prioritized(int32_t batch, int32_t batch_agent, int32_t horizon, int32_t n_steps, const kr_ring* agent,
+                                           const kr_ring* expert, const int32_t* agent_class, const int32_t* expert_class, int32_t n_classes,
+                                           int32_t rotation, const uint32_t* agent_prio, const uint32_t* expert_prio, const float* beta,
+                                           const float* u_ep, const float* u_start, uint64_t seed, const int64_t* draw, float* state, float* action,
+                                           float* next_state, float* reward, float* not_done, float* weight, float* next_ends, int32_t* picked,
+                                           void* stream) {
+    if (!sample_args_ok(batch, batch_agent, horizon, n_steps, agent, expert, u_ep, u_start, draw, state, action, next_state, reward, not_done, weight) ||
+        n_classes < 1 || n_classes > 64 || !beta ||
+        (batch_agent > 0 && (!agent_class || !agent_prio || agent->capacity > (1 << 20))) ||
+        (batch_agent < batch && (!expert_class || !expert_prio || expert->capacity > (1 << 20))))
+        return KS_ERR_INVALID;
+    // the weight and, without `picked`, the slot travel to the gather as in kr_sample_windows_prioritized
+    const int row_major = picked == nullptr ? n_steps : 0;
+    const int* slots = picked != nullptr ? picked : (const int*)reward;
+    hipLaunchKernelGGL(k_pick_balanced_prioritized, dim3(batch), dim3(WAVE), 0, (hipStream_t)stream, batch, batch_agent, horizon - n_steps, n_steps,
+                       to_ring(agent), to_ring(expert), agent_class, expert_class, n_classes, rotation, agent_prio, expert_prio, beta, u_ep,
+                       (unsigned long long)seed, draw, picked, reward, weight);
     if (launched() != KS_OK) return KS_ERR_HIP;
     return gather_windows(batch, batch_agent, horizon, n_steps, agent, expert, slots, row_major, u_start, seed, draw, next_ends, state, action, next_state,
                           reward, not_done, weight, weight, stream);

@@ -96,7 +96,8 @@ def policy_basename(policy_dir) -> str:
 
 def run_stage(plan, policy, n_envs: int = 1024, rounds: int = 10, updates_per_round: int = 100, expert_prob: float = 0.3, seed: int = 2,
               device: int = 0, load_previous: bool = True, save: bool = True, eval_envs: int | None = None, starts_per_env: int = 0,
-              param_ranges=None, free_running: bool = False, balanced: bool | None = None, budget_ms: float | None = None):
+              param_ranges=None, free_running: bool = False, balanced: bool | None = None, budget_ms: float | None = None, prioritized: bool = False,
+              per_alpha: float = 0.3, per_beta: float = 1.0, per_eps: float = 1e-3, per_eps_expert: float = 1.0):
     """One stage of the curriculum on the GPU simulator (the batched counterpart of rl_experiment + train_policy,
     main_DDPGfD.py:600-621, 776-800): start from the previous stage's policy and agent replay, mix in the expert
     replay of the stage's shapes at `expert_prob` (DDPGfD.py:232-254), train, evaluate, save policy + replay + info.
@@ -137,6 +138,10 @@ def run_stage(plan, policy, n_envs: int = 1024, rounds: int = 10, updates_per_ro
     of the episodes that ended in the rounds) and the starts running when the rounds end.  The result gains `env_steps` (the sum of the
     envs' step counters), `replay_class_counts` ({shape: episodes in the agent ring}) and `batch_class_slots` ({shape: slots of the
     last update's agent segment}, from the sampler's `picked`; empty without balanced).
+    prioritized (free_running=True only, ValueError otherwise), per_*: AsyncTrainer's prioritized replay with the demonstration bonus - the
+    trainer enables priorities on the agent ring and on the expert ring; with balanced each batch is drawn by sample_balanced_prioritized, the
+    shapes' shares by the balanced rule and the episode within a shape by priority.  The result gains `priority_max`: {"agent": ...,
+    "expert": ... (None without an expert mix)}, the largest priority an update has written to each ring, in units of 1 / 65536.
     Returns a dict (num_success, num_total, paths, ...)."""
     import torch
 
@@ -151,6 +156,8 @@ def run_stage(plan, policy, n_envs: int = 1024, rounds: int = 10, updates_per_ro
         raise ValueError("run_stage: free_running episodes restart inside the rollout kernel - they need starts_per_env > 0")
     if not free_running and (balanced or budget_ms is not None):
         raise ValueError("run_stage: balanced / budget_ms belong to free_running=True")
+    if prioritized and not free_running:
+        raise ValueError("run_stage: prioritized belongs to free_running=True")
     dirs = plan["dirs"]
     known = scenarios.SHAPES + scenarios.MEDIUM_SHAPES + scenarios.EXTRA_SHAPES + scenarios.MULTI_GEOM_SHAPES
     shapes = [s for s in plan["requested_shapes"] if s in known]
@@ -243,7 +250,8 @@ def run_stage(plan, policy, n_envs: int = 1024, rounds: int = 10, updates_per_ro
     if free_running:
         from .pipeline import AsyncTrainer
         trainer = AsyncTrainer(sim, policy, replay, eng, batch_episodes=policy.batch_size, expert_replay=expert if mix else None, expert_prob=expert_prob,
-                               updates_per_step=max(1, round(updates_per_round / 30)), balanced=balanced)
+                               updates_per_step=max(1, round(updates_per_round / 30)), balanced=balanced, prioritized=prioritized, per_alpha=per_alpha,
+                               per_beta=per_beta, per_eps=per_eps, per_eps_expert=per_eps_expert)
         trainer.capture()
     for r in range(rounds if free_running else 0):             # a round = one launch, the updates beside it
         trainer.run(30, budget_ms=budget_ms)
@@ -270,6 +278,8 @@ def run_stage(plan, policy, n_envs: int = 1024, rounds: int = 10, updates_per_ro
             b_agent = int(trainer.batch_episodes * (1 - expert_prob)) if mix else trainer.batch_episodes
             got = replay.ep_class[trainer.picked[:b_agent].long()].cpu().numpy()
             free_out["batch_class_slots"] = {s: int((got == i).sum()) for i, s in enumerate(shapes)}
+        if prioritized:
+            free_out["priority_max"] = {"agent": replay.priority_max(), "expert": expert.priority_max() if mix else None}
         n_updates = trainer.updates
     for r in range(0 if free_running else rounds):             # lock step: a round = 30 eng.step() calls, then the updates
         if starts_per_env <= 0:

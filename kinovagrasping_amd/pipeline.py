@@ -97,16 +97,17 @@ class GraphedTrainer:
         per_eps for the agent's episodes and per_eps_expert, the demonstration bonus, for the expert's; importance weights
         (p_min / p)^per_beta in the batch's weight column - and every update writes the priorities of the episodes it saw
         (kr_update_priorities after kr_critic_grad).  Calls enable_priorities() on the ring(s); self.picked as with balanced;
-        set_per_beta anneals beta, also under captured graphs.  Priorities are per rank: nothing about them is exchanged.  Not together
-        with balanced (ValueError)."""
-        if prioritized and balanced:
-            raise ValueError("prioritized=True and balanced=True: one sampler draws a batch; combining the two is not implemented")
+        set_per_beta anneals beta, also under captured graphs.  Priorities are per rank: nothing about them is exchanged.
+        balanced and prioritized: every batch is drawn with replay.sample_balanced_prioritized - the slot's class by the balanced rule, the
+        episode within the class by priority -, everything else as with prioritized."""
         assert engine.gen is None, "graph capture uses the default CUDA generator"
         self.sim, self.policy, self.replay, self.eng = sim, policy, replay, engine
         self.expert_replay, self.expert_prob = expert_replay, float(expert_prob)
         self.balanced, self.picked = bool(balanced), None
         self.prioritized = bool(prioritized)
         self.per_alpha, self.per_eps, self.per_eps_expert = float(per_alpha), float(per_eps), float(per_eps_expert)
+        if self.balanced and (getattr(replay, "ep_class", None) is None or (expert_replay is not None and getattr(expert_replay, "ep_class", None) is None)):
+            raise ValueError("balanced=True: the replay (and the expert replay) must have classes set (DeviceEpisodeReplay.set_env_classes)")
         if self.prioritized:
             if not replay.native:
                 raise ValueError("prioritized=True needs a device ring (DeviceEpisodeReplay on the GPU)")
@@ -115,15 +116,15 @@ class GraphedTrainer:
                 expert_replay.enable_priorities()
             self.per_beta = torch.full((1,), float(per_beta), device=replay.device)
             self.per_delta = torch.zeros(batch_episodes, device=replay.device)      # the last update's delta per batch episode (logging, tests)
-        if self.balanced and (getattr(replay, "ep_class", None) is None or (expert_replay is not None and getattr(expert_replay, "ep_class", None) is None)):
-            raise ValueError("balanced=True: the replay (and the expert replay) must have classes set (DeviceEpisodeReplay.set_env_classes)")
         if self.balanced and not replay.native:
             raise ValueError("balanced=True needs a device ring (DeviceEpisodeReplay on the GPU)")
         if expert_replay is not None and not (replay.native and expert_replay.native):
             raise ValueError("GraphedTrainer: the expert mix needs device rings (DeviceEpisodeReplay on the GPU)")
         # the sampler of every update, chosen once; self.mix: the expert ring when batches mix its episodes in, else None
         self.mix = expert_replay if (expert_replay is not None and self.expert_prob > 0) else None
-        if self.prioritized:
+        if self.prioritized and self.balanced:
+            self._sampler = partial(replay.sample_balanced_prioritized, self.mix, batch_episodes, self.expert_prob, self.per_beta)
+        elif self.prioritized:
             self._sampler = partial(replay.sample_prioritized, self.mix, batch_episodes, self.expert_prob, self.per_beta)
         elif self.balanced:
             self._sampler = partial(replay.sample_balanced, self.mix, batch_episodes, self.expert_prob)

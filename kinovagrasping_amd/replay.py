@@ -578,14 +578,72 @@ class DeviceEpisodeReplay:
         if expert is not None and (expert.horizon != self.horizon or expert.n_steps != self.n_steps):
             raise ValueError("sample_prioritized: the expert ring must have the agent ring's horizon and n_steps")
         b_agent = batch_size if expert is None else int(batch_size * (1 - prob))
-        if not torch.is_tensor(beta):
-            beta = torch.full((1,), float(beta), device=self.device)
-        if beta.dtype != torch.float32 or beta.numel() != 1:
-            raise ValueError("sample_prioritized: beta is a float or a float32 tensor with one element")
+        beta = self._beta_tensor(beta, "sample_prioritized")
         if self.native and (expert is None or expert.native):
             tables = (self._ptr(self.ep_prio), None if expert is None else self._ptr(expert.ep_prio), self._ptr(beta))
             return self._sample_native("kr_sample_windows_prioritized", expert, batch_size, b_agent, tables, uniforms, draw, seed, generator, True)
         return self._sample_torch(expert, batch_size, b_agent, uniforms, generator, lambda ring, ue: ring._pick_prioritized(ue, beta))
+
+    def _beta_tensor(self, beta, what):
+        if not torch.is_tensor(beta):
+            beta = torch.full((1,), float(beta), device=self.device)
+        if beta.dtype != torch.float32 or beta.numel() != 1:
+            raise ValueError(f"{what}: beta is a float or a float32 tensor with one element")
+        return beta
+
+    def _pick_balanced_prioritized(self, ue, rotation, d, beta):
+        """sample_balanced_prioritized's pick on this ring (torch path, the checker of k_pick_balanced_prioritized): _pick_balanced's class
+        for every batch slot of the ring's segment, then _pick_prioritized's rule and weight over the eligible episodes of that class -
+        over all of them where the class has none.  ue [nb] the episode uniforms."""
+        nb, cap, nc = ue.shape[0], self.capacity, len(self.class_names)
+        cnt, head = self._count, self._head
+        ages = torch.arange(max(cap - 1, 1), device=self.device)            # eligible: ages 0 .. count - 2
+        slots = (head - cnt + ages) % cap
+        inside = ages < cnt - 1
+        prio = self.priorities()[slots].clamp(min=1)
+        prio = torch.where(inside, prio, torch.zeros_like(prio))
+        tags = torch.where(inside, self.ep_class[slots].long(), torch.full_like(ages, -1))
+        want = (torch.arange(nb, device=self.device) + int(rotation) + d) % nc           # (non-negative: the divisor's sign)
+        match = tags.unsqueeze(0) == want.unsqueeze(1)                       # [nb, cap - 1]
+        mask = (match | ~match.any(1, keepdim=True)) & inside.unsqueeze(0)   # a class without eligible episodes: everybody
+        q = torch.where(mask, prio.unsqueeze(0), torch.zeros_like(prio).unsqueeze(0))
+        csum = q.cumsum(1)                                                   # int64: below 2^52
+        total = csum[:, -1]
+        t = torch.minimum((ue.double() * total.double()).long(), (total - 1).clamp(min=0))
+        at = (csum > t.unsqueeze(1)).long().argmax(1)                       # the smallest age whose inclusive prefix sum exceeds t
+        least = torch.where(mask, prio.unsqueeze(0), torch.full_like(q, 1 << 32)).min(1).values
+        ratio = least.float() / prio[at].clamp(min=1).float()
+        weight = torch.pow(ratio.double(), beta.to(self.device).float().double()).float()
+        some = total > 0
+        return torch.where(some, (head - cnt + at) % cap, self._pick_uniform(ue)), torch.where(some, weight, torch.ones_like(weight))
+
+    def sample_balanced_prioritized(self, expert, batch_size, prob=0.3, beta=1.0, uniforms=None, draw=None, seed=0, rotation=0, generator=None):
+        """sample_balanced and sample_prioritized combined (the ring has both columns: set_env_classes, enable_priorities): slot i of a
+        ring's segment of the batch wants class (i + rotation + draw) mod n_classes, as in sample_balanced, and draws among the eligible
+        episodes of that class in proportion to their priorities, as sample_prioritized does among all of them: with T_c their sum, the
+        episode at the smallest age whose inclusive prefix sum of the class's priorities exceeds min(T_c - 1, floor((double)u * T_c)).  Its
+        real rows carry (pmin_c / p)^beta, pmin_c the least priority of the class: the weight that corrects the draw back to
+        sample_balanced's, uniform within the class, over its maximum over the class.  A class without eligible episodes falls back to
+        sample_prioritized's draw and weight over all of them.  So the classes' shares of a segment are sample_balanced's whatever the
+        priorities are.  Arguments and return layout of sample_prioritized, `rotation` of sample_balanced.  On the GPU two launches
+        (kr_sample_windows_balanced_prioritized: the pick, the gather); the torch path is the same rule and their checker."""
+        if self.ep_class is None or (expert is not None and expert.ep_class is None):
+            raise ValueError("sample_balanced_prioritized: the ring has no classes (set_env_classes)")
+        if self.ep_prio is None or (expert is not None and expert.ep_prio is None):
+            raise ValueError("sample_balanced_prioritized: the ring has no priorities (enable_priorities)")
+        if expert is not None and (expert.horizon != self.horizon or expert.n_steps != self.n_steps or expert.class_names != self.class_names):
+            raise ValueError("sample_balanced_prioritized: the expert ring must have the agent ring's horizon, n_steps and class names")
+        b_agent = batch_size if expert is None else int(batch_size * (1 - prob))
+        beta = self._beta_tensor(beta, "sample_balanced_prioritized")
+        if self.native and (expert is None or expert.native):
+            P = self._ptr
+            tables = (P(self.ep_class), None if expert is None else P(expert.ep_class), len(self.class_names), int(rotation),
+                      P(self.ep_prio), None if expert is None else P(expert.ep_prio), P(beta))
+            return self._sample_native("kr_sample_windows_balanced_prioritized", expert, batch_size, b_agent, tables, uniforms, draw, seed, generator,
+                                       True)
+        d = 0 if draw is None else int(draw)
+        return self._sample_torch(expert, batch_size, b_agent, uniforms, generator,
+                                  lambda ring, ue: ring._pick_balanced_prioritized(ue, rotation, d, beta))
 
     def update_priorities(self, expert, q, tq1, reward, weight, picked, prob=0.3, discount=0.995, alpha=0.3, eps=1e-3, eps_expert=1.0, delta_out=None):
         """kr_update_priorities: after the critic's forward on a batch of sample_prioritized - q [R], tq1 [R] (the 1-step target critic's

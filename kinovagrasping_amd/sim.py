@@ -96,7 +96,7 @@ EXPORTS = ["ks_default_config", "ks_create", "ks_destroy", "ks_last_error", "ks_
            "ks_set_param_ranges", "ks_get_env_params"]
 # include/kinova_rollout.h
 ROLLOUT_EXPORTS = ["kr_select_action", "kr_store_transition", "kr_rank_episodes", "kr_wait_min", "kr_wait_min_counted", "kr_commit_episodes", "kr_advance_ring",
-                   "kr_sample_windows", "kr_sample_windows_draw", "kr_sample_windows_mixed", "kr_commit_classes", "kr_sample_windows_balanced", "kr_commit_priorities", "kr_sample_windows_prioritized", "kr_update_priorities", "kr_xchg_create", "kr_xchg_connect", "kr_xchg_allreduce_mean", "kr_xchg_status",
+                   "kr_sample_windows", "kr_sample_windows_draw", "kr_sample_windows_mixed", "kr_commit_classes", "kr_sample_windows_balanced", "kr_commit_priorities", "kr_sample_windows_prioritized", "kr_sample_windows_balanced_prioritized", "kr_update_priorities", "kr_xchg_create", "kr_xchg_connect", "kr_xchg_allreduce_mean", "kr_xchg_status",
                    "kr_xchg_destroy", "kr_critic_grad", "kr_update_prologue", "kr_relu_backward", "kr_sigmoid_scale_backward", "kr_adam_step", "kr_soft_update",
                    "kr_mlp3_forward", "kr_mlp3_forward_shadow", "kr_mlp3_forward_split", "kr_mlp3_backward_shadow", "kr_mlp3_backward_split", "kr_weight_grad_shadow",
                    "kr_mlp3_forward_lean", "kr_mlp3_backward_lean",
@@ -187,6 +187,8 @@ def _bind(L):
     L.kr_sample_windows_balanced.argtypes = [i32, i32, i32, i32, C.POINTER(KrRing), C.POINTER(KrRing), vp, vp, i32, i32, vp, vp, C.c_uint64, vp] + [vp] * 8 + [vp]
     L.kr_commit_priorities.argtypes = [i32, i32] + [vp] * 5 + [vp]
     L.kr_sample_windows_prioritized.argtypes = [i32, i32, i32, i32, C.POINTER(KrRing), C.POINTER(KrRing), vp, vp, vp, vp, vp, C.c_uint64, vp] + [vp] * 8 + [vp]
+    L.kr_sample_windows_balanced_prioritized.argtypes = [i32, i32, i32, i32, C.POINTER(KrRing), C.POINTER(KrRing), vp, vp, i32, i32, vp, vp, vp, vp, vp,
+                                                         C.c_uint64, vp] + [vp] * 8 + [vp]
     L.kr_update_priorities.argtypes = [i32, i32, i32, i32] + [vp] * 4 + [f32, vp, f32, f32, f32] + [vp] * 5 + [vp]
     L.kr_xchg_create.argtypes = [C.POINTER(vp), i32, i32, C.c_int64, vp]
     L.kr_xchg_connect.argtypes = [vp, C.c_char_p]
