@@ -36,7 +36,7 @@ import torch
 
 sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
 from kinovagrasping_amd import scenarios                       # noqa: E402
-from kinovagrasping_amd.ddpgfd import DDPGfD                   # noqa: E402
+from kinovagrasping_amd.ddpgfd import DDPGfD, TD3fD            # noqa: E402
 from kinovagrasping_amd.demonstrators import run_controller_episodes, run_controller_free_running  # noqa: E402
 from kinovagrasping_amd.evaluate import eval_policy, eval_policy_free_running  # noqa: E402
 from kinovagrasping_amd.metrics import EpisodeLedger, param_success_table, save_heatmap_coords      # noqa: E402
@@ -85,6 +85,13 @@ def main():
     ap.add_argument("--critic-lr", type=float, default=1e-3, help="reference: Adam's default 1e-3 (DDPGfD.py:61)")
     ap.add_argument("--tau", type=float, default=0.001, help="soft target update rate (reference: 0.0005, main_DDPGfD.py:894 - for 100 updates per episode of one env)")
     ap.add_argument("--target-every", type=int, default=1, help="target networks follow every this many updates (reference: 10, DDPGfD.py:64-66,360-366)")
+    ap.add_argument("--td3", action="store_true", help="TD3fD: twin critics with the minimum in the targets, noise-smoothed target actions, a delayed actor "
+                    "(ddpgfd.TD3fD) - against the single critic's over-estimated Q; profiles/td3fd.txt has what it does on the reference's schedule")
+    ap.add_argument("--policy-noise", type=float, default=None, help="with --td3: std of the target smoothing noise (default 0.1 x max_action = 0.08)")
+    ap.add_argument("--noise-clip", type=float, default=None, help="with --td3: clip of the target smoothing noise (default 0.25 x max_action = 0.2)")
+    ap.add_argument("--policy-freq", type=int, default=2, help="with --td3: the actor steps on every this many updates")
+    ap.add_argument("--log-q", action="store_true", help="print the mean Q(s, pi(s)) of the last update's batch beside the critic loss (the critic's own estimate: "
+                    "the best possible return is 50)")
     ap.add_argument("--expl-noise", type=float, default=0.1, help="exploration noise, std = 0.8 x this (main_DDPGfD.py:443-446: 0.1)")
     ap.add_argument("--dump-replay", default=None, help="write the replay (last 1500 agent + first 400 expert episodes) and the four networks as one .npz "
                     "(tools/r06/reference_learner_on_replay.py runs the REFERENCE's train_batch on it)")
@@ -128,7 +135,13 @@ def main():
         print(f"start pool: {args.starts_per_env} starts per env, {qp.shape[0] * n * 102 * 4 / 1e6:.0f} MB on the device")
     else:
         q0, hq = start_states(n, args.shape, rng)
-    policy = DDPGfD(82, 4, 0.8, 5, tau=args.tau, batch_size=args.batch_episodes, hidden=tuple(args.hidden), device=dev)
+    if args.td3:
+        policy = TD3fD(82, 4, 0.8, 5, tau=args.tau, batch_size=args.batch_episodes, hidden=tuple(args.hidden), device=dev, policy_noise=args.policy_noise,
+                       noise_clip=args.noise_clip, policy_freq=args.policy_freq)
+        policy.critic2_optimizer.param_groups[0]["lr"] = args.critic_lr
+        print(f"TD3fD: target smoothing noise {policy.policy_noise:g} clipped at {policy.noise_clip:g}, actor steps every {policy.policy_freq} update(s)")
+    else:
+        policy = DDPGfD(82, 4, 0.8, 5, tau=args.tau, batch_size=args.batch_episodes, hidden=tuple(args.hidden), device=dev)
     policy.network_repl_freq = args.target_every
     policy.actor_optimizer.param_groups[0]["lr"] = args.actor_lr
     policy.critic_optimizer.param_groups[0]["lr"] = args.critic_lr
@@ -146,6 +159,7 @@ def main():
     tr = Trainer(sim, policy, agent, eng, batch_episodes=args.batch_episodes, expert_replay=expert, expert_prob=args.expert_prob if expert is not None else 0.3,
                  updates_per_step=args.updates_per_step, prioritized=args.prioritized, per_alpha=args.per_alpha, per_beta=args.per_beta0,
                  per_eps_expert=args.per_eps_expert)
+    tr.native.track_actor_loss = args.log_q          # (before the capture: the evaluation is part of the captured update)
     tr.capture()
     if args.free_running:
         tr.run(36, learn=False)
@@ -213,7 +227,10 @@ def main():
                 res = eval_policy(sim_eval, policy, sim_eval.reset(qe, hqe))
             ev = f"  eval (no noise, 1024 starts): lift success {res['num_success'] / 1024:.3f}"
             t_eval += time.perf_counter() - te
-        print(f"step {it + 60:5d}  episodes {d_ep:7d}  training lift rate {d_lift / max(1, d_ep):.3f}  critic loss {ls[0]:9.3f}  {n * (it + 60) / dt:9.0f} env-steps/s{ev}")
+        print(f"step {it + 60:5d}  episodes {d_ep:7d}  training lift rate {d_lift / max(1, d_ep):.3f}  critic loss {ls[0]:9.3f}{f' / {ls[3]:9.3f}' if args.td3 else ''}{f'  mean Q {-tr.native.actor_loss.item():8.3f}' if args.log_q else ''}  {n * (it + 60) / dt:9.0f} env-steps/s{ev}")
+    if args.free_running:
+        c = tr.counts()
+        print(f"free-running rollout: {c['episodes_finished']} episodes finished, {c['episodes_dropped']} dropped, {c['pacing_timeouts']} pacing time-outs, {tr.updates} updates")
     if args.dump_replay:
         tr.flush(finish_update=True)
         torch.cuda.synchronize()
@@ -232,7 +249,7 @@ def main():
     if args.save:
         tr.flush(finish_update=True)
         policy.save(args.save)
-        print("saved", args.save + "_{actor,critic,actor_optimizer,critic_optimizer}")
+        print("saved", args.save + ("_{actor,critic,critic2,actor_optimizer,critic_optimizer,critic2_optimizer}" if args.td3 else "_{actor,critic,actor_optimizer,critic_optimizer}"))
     sim.close()
     sim_eval.close()
 

@@ -281,6 +281,43 @@ int kr_adam_step(int64_t count, float *param, const float *grad, float *exp_avg,
                  float beta1, float beta2, float eps, float weight_decay, void *stream);
 int kr_soft_update(int64_t count, const float *param, float *target, float tau, const int64_t *it, int32_t freq, void *stream);
 
+/* ---- TD3fD (ddpgfd.TD3fD; Fujimoto et al. 2018 on the n-step / demonstration update above): twin critics, smoothed target actions, a
+ * delayed actor.  One launch each, fp32 without contraction, no LDS.
+ *
+ *   kr_target_smooth     the target actor's output action [rows, 4] (16-byte aligned), in place, per element:
+ *                          e = sigma * z;   e = e < -clip ? -clip : (e > clip ? clip : e);
+ *                          s = action + e;  action = s < 0 ? 0 : (s > max_action ? max_action : s)
+ *                        - two roundings and two exact clamps; a NaN in action or z fails every comparison and reaches the output.
+ *                        z: exactly one of `noise` ([rows, 4] N(0,1) draws, 16-byte aligned) and `draw` (a device counter, as
+ *                        kr_actor_select's) is given.  With draw, the four z of row r are ONE Philox4x32-10 call with counter
+ *                        (r, draw[0] low word, draw[0] high word, 0x5433) and key (seed low word, seed high word), bits -> uniforms ->
+ *                        Box-Muller exactly as kr_actor_select's exploration noise (whose tag is 0x4b52; the samplers' are 0x5a4d /
+ *                        0x5a4e): a stream of its own under the same seed and update counter.  One thread per row, grid-stride.
+ *                        KS_ERR_INVALID, nothing launched or written: rows <= 0; a NULL or misaligned action; both or neither of noise
+ *                        and draw; a misaligned noise; sigma or clip negative or NaN; max_action <= 0 or NaN.
+ *   kr_twin_critic_grad  kr_critic_grad for two critics q1, q2 [rows] on the minimum of two target critics:
+ *                          m1 = min(tq1_a, tq1_b),  mn = min(tqn_a, tqn_b)   - NaN if either operand is NaN -;
+ *                          tmin[r] = m1,  tmin[rows + r] = mn   (exact);
+ *                          target_Q, target_QN from m1, mn by kr_critic_grad's expressions in its order;
+ *                          dq_k = w / sum(w) * (2 (q_k - target_Q) + 0.5 * 2 (q_k - target_QN));
+ *                          losses[0..2] = (loss, L1, LN) of critic 1, losses[3..5] of critic 2.
+ *                        One wave, butterfly sums; weight NULL = all ones; weight_sum[0] = 0 gives all-zero dq and losses (tmin is
+ *                        written all the same).  With q2 = q1, tq1_b = tq1_a, tqn_b = tqn_a: kr_critic_grad's bits, twice.
+ *                        KS_ERR_INVALID, nothing launched or written: rows <= 0, n_steps <= 0, a NULL q1, q2, tq1_a, tq1_b, tqn_a, tqn_b,
+ *                        reward, weight_sum, dq1, dq2, tmin or losses.
+ *   kr_adam_step_every   the delayed actor's optimizer: acts only if step[0] > 0 and step[0] % every == 0, and then is kr_adam_step as
+ *                        step number step[0] / every; otherwise param, grad, exp_avg and exp_avg_sq are untouched.  every = 1 is
+ *                        kr_adam_step.  KS_ERR_INVALID, nothing launched or written: what kr_adam_step refuses (count <= 0, a NULL
+ *                        pointer); every <= 0.
+ */
+int kr_target_smooth(int32_t rows, float *action, const float *noise, uint64_t seed, const int64_t *draw, float sigma, float clip,
+                     float max_action, void *stream);
+int kr_twin_critic_grad(int32_t rows, int32_t n_steps, const float *q1, const float *q2, const float *tq1_a, const float *tq1_b,
+                        const float *tqn_a, const float *tqn_b, const float *reward, const float *weight, const float *weight_sum,
+                        float discount, float *dq1, float *dq2, float *tmin, float *losses, void *stream);
+int kr_adam_step_every(int64_t count, float *param, const float *grad, float *exp_avg, float *exp_avg_sq, const int64_t *step, int32_t every,
+                       float lr, float beta1, float beta2, float eps, float weight_decay, void *stream);
+
 /* ---- fused 3-layer MLP forward on the matrix cores (fp32 MFMA): Actor.forward (DDPGfD.py:29-32) and
  * Critic.forward (DDPGfD.py:47-50) as ONE launch each:
  *     out[n,out_dim] = f(W3 relu(W2 relu(W1 x + b1) + b2) + b3),   f = identity (KR_ACT_NONE) or scale * sigmoid

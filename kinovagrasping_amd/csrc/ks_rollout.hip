@@ -865,6 +865,74 @@ __global__ __launch_bounds__(WAVE) void k_critic_grad(int R, int n, const float*
     if (threadIdx.x == 0) { losses[1] = l1 * inv; losses[2] = ln * inv; losses[0] = l1 * inv + 0.5f * (ln * inv); }
 }
 
+// TD3's clipped double-Q minimum; NaN if either operand is NaN (a diverged critic stays visible)
+__device__ __forceinline__ float nan_min(float a, float b) { return a != a ? a : (b != b ? b : (b < a ? b : a)); }
+
+// k_critic_grad for two critics on the minimum of two target critics: the same expressions in the same order per critic
+__global__ __launch_bounds__(WAVE) void k_twin_critic_grad(int R, int n, const float* __restrict__ q1, const float* __restrict__ q2,
+                                                           const float* __restrict__ tq1_a, const float* __restrict__ tq1_b,
+                                                           const float* __restrict__ tqn_a, const float* __restrict__ tqn_b,
+                                                           const float* __restrict__ reward, const float* __restrict__ weight,
+                                                           const float* __restrict__ wsum, float discount, float* __restrict__ dq1,
+                                                           float* __restrict__ dq2, float* __restrict__ tmin, float* losses) {
+#pragma clang fp contract(off)
+    const float inv = wsum[0] > 0.0f ? 1.0f / wsum[0] : 0.0f;
+    float l1a = 0, lna = 0, l1b = 0, lnb = 0;
+    for (int r = threadIdx.x; r < R; r += WAVE) {
+        const float m1 = nan_min(tq1_a[r], tq1_b[r]), mn = nan_min(tqn_a[r], tqn_b[r]);
+        tmin[r] = m1;
+        tmin[(long)R + r] = mn;
+        const float t1 = reward[(long)r * n] + discount * m1;
+        float ret = 0, g = 1.0f;
+        for (int i = 0; i < n; i++) { ret += g * reward[(long)r * n + i]; g *= discount; }
+        const float tn = ret + g * mn;
+        const float w = weight ? weight[r] : 1.0f;
+        const float e1a = q1[r] - t1, ena = q1[r] - tn, e1b = q2[r] - t1, enb = q2[r] - tn;
+        l1a += w * e1a * e1a;
+        lna += w * ena * ena;
+        l1b += w * e1b * e1b;
+        lnb += w * enb * enb;
+        dq1[r] = w * inv * (2.0f * e1a + 0.5f * 2.0f * ena);
+        dq2[r] = w * inv * (2.0f * e1b + 0.5f * 2.0f * enb);
+    }
+    l1a = wave_sum(l1a);
+    lna = wave_sum(lna);
+    l1b = wave_sum(l1b);
+    lnb = wave_sum(lnb);
+    if (threadIdx.x == 0) {
+        losses[1] = l1a * inv; losses[2] = lna * inv; losses[0] = l1a * inv + 0.5f * (lna * inv);
+        losses[4] = l1b * inv; losses[5] = lnb * inv; losses[3] = l1b * inv + 0.5f * (lnb * inv);
+    }
+}
+
+// TD3's target policy smoothing on the target actor's [rows, 4] output, in place: one thread per row, the row as one 16-byte load / store
+__global__ __launch_bounds__(256) void k_target_smooth(int rows, float* __restrict__ action, const float* __restrict__ noise,
+                                                       unsigned long long seed, const int64_t* __restrict__ draw, float sigma, float clip,
+                                                       float max_action) {
+#pragma clang fp contract(off)
+    static_assert(A == 4, "one float4 per row");
+    const unsigned long long d = draw ? (unsigned long long)draw[0] : 0ull;
+    for (long r = (long)blockIdx.x * 256 + threadIdx.x; r < rows; r += (long)gridDim.x * 256) {
+        const float4 a4 = reinterpret_cast<const float4*>(action)[r];
+        float a[A] = {a4.x, a4.y, a4.z, a4.w}, z[A];
+        if (noise) {
+            const float4 z4 = reinterpret_cast<const float4*>(noise)[r];
+            z[0] = z4.x; z[1] = z4.y; z[2] = z4.z; z[3] = z4.w;
+        } else {
+            krsel::normal4_tagged(seed, d, (uint32_t)r, krsel::TAG_TARGET_SMOOTH, z);
+        }
+#pragma unroll
+        for (int k = 0; k < A; k++) {
+            // (a NaN fails every comparison and passes through)
+            float e = sigma * z[k];
+            e = e < -clip ? -clip : (e > clip ? clip : e);
+            const float s = a[k] + e;
+            a[k] = s < 0.0f ? 0.0f : (s > max_action ? max_action : s);
+        }
+        reinterpret_cast<float4*>(action)[r] = make_float4(a[0], a[1], a[2], a[3]);
+    }
+}
+
 // start of an update's body: what used to be eight tiny library launches (sum, clamp, mul, div, copy, add, fill, copy)
 __global__ __launch_bounds__(WAVE) void k_update_prologue(int R, int n, const float* __restrict__ weight, float* __restrict__ wsum,
                                                           float* __restrict__ dq_actor, int64_t* it, int64_t* it_head, int pipelined) {
@@ -890,13 +958,10 @@ __global__ __launch_bounds__(256) void k_sigmoid_scale_backward(long count, cons
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < count; i += (long)gridDim.x * 256) grad[i] *= a[i] * (1.0f - a[i] / max_action);
 }
 
-__global__ __launch_bounds__(256) void k_adam_step(long count, float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                   float* __restrict__ v, const int64_t* __restrict__ step, float lr, float b1, float b2,
-                                                   float eps, float wd) {
+// torch.optim.Adam, single-tensor formulation, as step number t (bias corrections)
+__device__ __forceinline__ void adam_apply(long count, float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                           float* __restrict__ v, float t, float lr, float b1, float b2, float eps, float wd) {
 #pragma clang fp contract(off)
-    // torch.optim.Adam, single-tensor formulation: bias corrections from the (already incremented) device step
-    if (step[0] <= 0) return;                 // no update has produced gradients yet
-    const float t = (float)step[0];
     const float bc1 = 1.0f - powf(b1, t), bc2 = 1.0f - powf(b2, t);
     const float step_size = lr / bc1, bc2s = sqrtf(bc2);
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < count; i += (long)gridDim.x * 256) {
@@ -909,6 +974,23 @@ __global__ __launch_bounds__(256) void k_adam_step(long count, float* __restrict
         const float denom = sqrtf(vi) / bc2s + eps;
         p[i] = p[i] - step_size * (mi / denom);
     }
+}
+
+__global__ __launch_bounds__(256) void k_adam_step(long count, float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                   float* __restrict__ v, const int64_t* __restrict__ step, float lr, float b1, float b2,
+                                                   float eps, float wd) {
+    // bias corrections from the (already incremented) device step
+    if (step[0] <= 0) return;                 // no update has produced gradients yet
+    adam_apply(count, p, g, m, v, (float)step[0], lr, b1, b2, eps, wd);
+}
+
+// TD3's delayed actor: the step of every `every`-th update, numbered step / every; nothing is touched on the others
+__global__ __launch_bounds__(256) void k_adam_step_every(long count, float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                         float* __restrict__ v, const int64_t* __restrict__ step, int every, float lr, float b1,
+                                                         float b2, float eps, float wd) {
+    const int64_t s = step[0];
+    if (s <= 0 || s % every != 0) return;
+    adam_apply(count, p, g, m, v, (float)(s / every), lr, b1, b2, eps, wd);
 }
 
 __global__ __launch_bounds__(256) void k_soft_update(long count, const float* __restrict__ p, float* __restrict__ tp, float tau,
@@ -1192,6 +1274,34 @@ int kr_adam_step(int64_t count, float* param, const float* grad, float* exp_avg,
     if (count <= 0 || !param || !grad || !exp_avg || !exp_avg_sq || !step) return KS_ERR_INVALID;
     hipLaunchKernelGGL(k_adam_step, dim3(grid_for(count)), dim3(256), 0, (hipStream_t)stream, (long)count, param, grad, exp_avg, exp_avg_sq, step, lr,
                        beta1, beta2, eps, weight_decay);
+    return launched();
+}
+
+int kr_adam_step_every(int64_t count, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, const int64_t* step, int32_t every,
+                       float lr, float beta1, float beta2, float eps, float weight_decay, void* stream) {
+    if (count <= 0 || every <= 0 || !param || !grad || !exp_avg || !exp_avg_sq || !step) return KS_ERR_INVALID;
+    hipLaunchKernelGGL(k_adam_step_every, dim3(grid_for(count)), dim3(256), 0, (hipStream_t)stream, (long)count, param, grad, exp_avg, exp_avg_sq, step,
+                       every, lr, beta1, beta2, eps, weight_decay);
+    return launched();
+}
+
+int kr_twin_critic_grad(int32_t rows, int32_t n_steps, const float* q1, const float* q2, const float* tq1_a, const float* tq1_b, const float* tqn_a,
+                        const float* tqn_b, const float* reward, const float* weight, const float* weight_sum, float discount, float* dq1, float* dq2,
+                        float* tmin, float* losses, void* stream) {
+    if (rows <= 0 || n_steps <= 0 || !q1 || !q2 || !tq1_a || !tq1_b || !tqn_a || !tqn_b || !reward || !weight_sum || !dq1 || !dq2 || !tmin || !losses)
+        return KS_ERR_INVALID;
+    hipLaunchKernelGGL(k_twin_critic_grad, dim3(1), dim3(WAVE), 0, (hipStream_t)stream, rows, n_steps, q1, q2, tq1_a, tq1_b, tqn_a, tqn_b, reward, weight,
+                       weight_sum, discount, dq1, dq2, tmin, losses);
+    return launched();
+}
+
+int kr_target_smooth(int32_t rows, float* action, const float* noise, uint64_t seed, const int64_t* draw, float sigma, float clip, float max_action,
+                     void* stream) {
+    if (rows <= 0 || !action || (noise != nullptr) == (draw != nullptr) || !(sigma >= 0.0f) || !(clip >= 0.0f) || !(max_action > 0.0f) ||
+        ((uintptr_t)action & 15) != 0 || ((uintptr_t)noise & 15) != 0)
+        return KS_ERR_INVALID;
+    hipLaunchKernelGGL(k_target_smooth, dim3(grid_for(rows)), dim3(256), 0, (hipStream_t)stream, rows, action, noise, (unsigned long long)seed, draw, sigma,
+                       clip, max_action);
     return launched();
 }
 

@@ -54,10 +54,10 @@ __device__ __forceinline__ void philox4x32(uint32_t c0, uint32_t c1, uint32_t c2
     r[0] = c0; r[1] = c1; r[2] = c2; r[3] = c3;
 }
 
-// 4 independent N(0,1) draws for (seed, step, env): Philox bits -> uniforms in (0,1) -> Box-Muller
-__device__ __forceinline__ void normal4(uint64_t seed, uint64_t step, uint32_t env, float* z) {
+// 4 independent N(0,1) draws for (seed, step, env) on the stream `tag`: Philox bits -> uniforms in (0,1) -> Box-Muller
+__device__ __forceinline__ void normal4_tagged(uint64_t seed, uint64_t step, uint32_t env, uint32_t tag, float* z) {
     uint32_t r[4];
-    philox4x32(env, (uint32_t)step, (uint32_t)(step >> 32), 0x4b52u, (uint32_t)seed, (uint32_t)(seed >> 32), r);
+    philox4x32(env, (uint32_t)step, (uint32_t)(step >> 32), tag, (uint32_t)seed, (uint32_t)(seed >> 32), r);
     const float u0 = ((float)(r[0] >> 8) + 0.5f) * (1.0f / 16777216.0f), u1 = ((float)(r[1] >> 8) + 0.5f) * (1.0f / 16777216.0f);
     const float u2 = ((float)(r[2] >> 8) + 0.5f) * (1.0f / 16777216.0f), u3 = ((float)(r[3] >> 8) + 0.5f) * (1.0f / 16777216.0f);
     const float ra = sqrtf(-2.0f * __logf(u0)), rb = sqrtf(-2.0f * __logf(u2));
@@ -66,5 +66,10 @@ __device__ __forceinline__ void normal4(uint64_t seed, uint64_t step, uint32_t e
     __sincosf(6.283185307179586f * u3, &sb, &cb);
     z[0] = ra * ca; z[1] = ra * sa; z[2] = rb * cb; z[3] = rb * sb;
 }
+
+// the exploration noise's stream (tag 0x4b52); 0x5433 is the learner's target-smoothing stream (kr_target_smooth)
+constexpr uint32_t TAG_EXPLORE = 0x4b52u, TAG_TARGET_SMOOTH = 0x5433u;
+
+__device__ __forceinline__ void normal4(uint64_t seed, uint64_t step, uint32_t env, float* z) { normal4_tagged(seed, step, env, TAG_EXPLORE, z); }
 
 }  // namespace krsel

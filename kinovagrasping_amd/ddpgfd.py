@@ -13,6 +13,10 @@ widths are parameters: 400-300 is the reference (parity), 256-256 is what BASELI
 MI355X notes: everything stays on the GPU (no per-step host round trip as in DDPGfD.py:71-73); the
 GEMMs run on the matrix cores through PyTorch-ROCm (hipBLASLt); with world_size > 1 the gradients of
 both networks are averaged with ONE all-reduce over a flat fp32 buffer (RCCL over xGMI).
+
+`TD3fD(DDPGfD)` is the same learner with TD3's remedy for the single critic's over-estimation (twin critics with the minimum in the
+target, noise-smoothed target actions, a delayed actor); `DDPGfD` itself is unchanged by it, and a TD3fD checkpoint loads into a
+DDPGfD (the reference's four files plus two for the second critic).
 """
 from __future__ import annotations
 
@@ -234,5 +238,129 @@ class DDPGfD:
         if sync_targets:
             self.critic_target.load_state_dict(self.critic.state_dict())
             self.actor_target.load_state_dict(self.actor.state_dict())
+        self._load_extra(filename, weights_only, sync_targets)
         if self._native is not None:
             self._native.import_optimizer_state()     # ... and back: the native learner continues from the loaded Adam state
+
+    def _load_extra(self, filename, weights_only, sync_targets):
+        """files beyond the reference's four (TD3fD's second critic); they are ignored here, so a TD3fD checkpoint loads into a DDPGfD"""
+
+
+class TD3fD(DDPGfD):
+    """DDPGfD with TD3's three parts (Fujimoto et al. 2018; the reference group's `Old Code/TD3.py`) on the n-step / demonstration update:
+
+    * twin critics: `critic2` / `critic2_target` (independently initialised) and `critic2_optimizer` (the critic's hyper-parameters); both
+      targets (1-step and n-step) bootstrap from min(critic_target, critic2_target);
+    * smoothed target actions: clamp(actor_target(s') + clamp(policy_noise * z, -noise_clip, noise_clip), 0, max_action), z ~ N(0, 1).
+      TD3's published 0.2 / 0.5 are stated for a unit action half-range; this actor's half-range is max_action / 2, hence the defaults
+      policy_noise = 0.1 * max_action and noise_clip = 0.25 * max_action;
+    * a delayed actor: its optimizer steps on the updates with it % policy_freq == 0 only (its own step count is it / policy_freq); the
+      gradient of the other updates is computed and dropped.  The soft update of the three target networks keeps its
+      network_repl_freq gate on `it`.
+
+    The actor loss goes through critic 1 only, as in TD3.  These autograd phases are the specification of the native form
+    (learner_native.NativeDDPGfDUpdate takes a TD3fD policy).  Checkpoints: the reference's four files plus `<prefix>_critic2` and
+    `<prefix>_critic2_optimizer`."""
+
+    def __init__(self, state_dim=82, action_dim=4, max_action=0.8, n=5, discount=0.995, tau=0.0005, batch_size=64, hidden=(400, 300),
+                 device="cpu", process_group=None, capturable=False, policy_noise=None, noise_clip=None, policy_freq=2):
+        super().__init__(state_dim, action_dim, max_action, n, discount, tau, batch_size, hidden, device, process_group, capturable)
+        self.critic2 = Critic(state_dim, action_dim, hidden).to(self.device)
+        self.critic2_target = copy.deepcopy(self.critic2)
+        self.critic2_optimizer = torch.optim.Adam(self.critic2.parameters(), weight_decay=1e-4, capturable=self.capturable)
+        for name in ("critic2", "critic2_target"):
+            self._flat_params[name] = _flatten_parameters(getattr(self, name))
+        self.policy_noise = 0.1 * max_action if policy_noise is None else float(policy_noise)
+        self.noise_clip = 0.25 * max_action if noise_clip is None else float(noise_clip)
+        self.policy_freq = int(policy_freq)
+        if not (self.policy_noise >= 0 and self.noise_clip >= 0 and self.policy_freq >= 1):
+            raise ValueError("TD3fD: policy_noise and noise_clip must be >= 0, policy_freq >= 1")
+
+    def train_on_batch(self, state, action, next_state, reward, weight=None, target_noise=None):
+        """As DDPGfD.train_on_batch; returns (actor, critic, critic_L1, critic_LN, critic2, critic2_L1, critic2_LN).  target_noise: the
+        N(0, 1) draws of the target smoothing, [2R, 4] (None: torch.randn)."""
+        losses_c = self.phase_critic(state, action, next_state, reward, weight, target_noise)
+        self._allreduce_grads(list(self.critic.parameters()) + list(self.critic2.parameters()))
+        actor_loss = self.phase_actor(state, weight)
+        self._allreduce_grads(list(self.actor.parameters()))
+        self.phase_targets()
+        return (actor_loss,) + losses_c
+
+    def phase_critic(self, state, action, next_state, reward, weight=None, target_noise=None):
+        """smoothed target actions, the twin targets' minimum, both critics' losses + backward.  Returns (critic, L1, LN) of critic 1, then
+        of critic 2."""
+        reward = reward.unsqueeze(-1)
+        with torch.no_grad():
+            R = reward.shape[0]
+            nx = torch.cat([next_state[:, 0], next_state[:, -1]], 0)
+            a = self.actor_target(nx)
+            z = torch.randn_like(a) if target_noise is None else target_noise
+            ta = (a + (self.policy_noise * z).clamp(-self.noise_clip, self.noise_clip)).clamp(0, self.max_action)
+            tq = torch.min(self.critic_target(nx, ta), self.critic2_target(nx, ta))
+            target_Q = reward[:, 0] + self.discount * tq[:R]
+            n_step_return = (reward.squeeze(-1) * self._disc).sum(1)
+            target_QN = (n_step_return + (self.discount ** self.n) * tq[R:].squeeze(-1)).unsqueeze(-1)
+        out, total = (), None
+        for critic in (self.critic, self.critic2):
+            current_Q = critic(state[:, 0], action[:, 0])
+            L1 = self._mean((current_Q - target_Q) ** 2, 1, weight)
+            LN = self._mean((current_Q - target_QN) ** 2, 1, weight)
+            loss = L1 + 0.5 * LN
+            total = loss if total is None else total + loss
+            out += (loss.detach(), L1.detach(), LN.detach())
+        self.critic_optimizer.zero_grad()
+        self.critic2_optimizer.zero_grad()
+        total.backward()
+        return out
+
+    def phase_actor(self, state, weight=None):
+        """both critics' steps, then the actor loss through critic 1 + backward"""
+        self.critic2_optimizer.step()
+        return super().phase_actor(state, weight)
+
+    def phase_targets(self):
+        """the actor's step on every policy_freq-th call + soft update of the three target networks on every 10th call"""
+        self.total_it += 1
+        fp = self._flat_params
+        pairs = ((fp["critic"], fp["critic_target"]), (fp["critic2"], fp["critic2_target"]), (fp["actor"], fp["actor_target"]))
+        if self.capturable:
+            # device-side gates: the step is taken and then undone where the gate is closed (same arithmetic where it is open)
+            self._it_dev += 1
+            opt, flat = self.actor_optimizer, fp["actor"]
+            step_now = self._it_dev % self.policy_freq == 0
+            params = [p for p in opt.param_groups[0]["params"] if p.grad is not None]
+            keys = ("step", "exp_avg", "exp_avg_sq")
+            before = [{k: opt.state[p][k].clone() for k in keys} if opt.state.get(p) else None for p in params]
+            flat_before = flat.clone()
+            opt.step()
+            with torch.no_grad():
+                flat.copy_(torch.where(step_now, flat, flat_before))
+                for p, old in zip(params, before):
+                    for k in keys:
+                        cur = opt.state[p][k]
+                        cur.copy_(torch.where(step_now, cur, torch.zeros_like(cur) if old is None else old[k]))
+                fire = self._it_dev % self.network_repl_freq == 0
+                for p, tp in pairs:
+                    tp.copy_(torch.where(fire, self.tau * p + (1 - self.tau) * tp, tp))
+            return
+        if self.total_it % self.policy_freq == 0:
+            self.actor_optimizer.step()
+        if self.total_it % self.network_repl_freq == 0:
+            with torch.no_grad():
+                for p, tp in pairs:
+                    tp.copy_(self.tau * p + (1 - self.tau) * tp)
+
+    def save(self, filename):
+        super().save(filename)
+        torch.save(self.critic2.state_dict(), filename + "_critic2")
+        torch.save(self.critic2_optimizer.state_dict(), filename + "_critic2_optimizer")
+
+    def _load_extra(self, filename, weights_only, sync_targets):
+        """a four-file checkpoint leaves critic2 as it is"""
+        import os
+        if os.path.exists(filename + "_critic2"):
+            self.critic2.load_state_dict(torch.load(filename + "_critic2", map_location=self.device, weights_only=weights_only))
+        if os.path.exists(filename + "_critic2_optimizer"):
+            self.critic2_optimizer.load_state_dict(torch.load(filename + "_critic2_optimizer", map_location=self.device, weights_only=weights_only))
+        if sync_targets:
+            self.critic2_target.load_state_dict(self.critic2.state_dict())

@@ -17,6 +17,11 @@
   GEMMs straight into one flat gradient buffer per network; the forward-only target networks and the critic forward
   still go through the fused LDS kernel (kr_mlp3_forward) when the width has an instantiation.  ~75 launches.
 
+With a ddpgfd.TD3fD policy the same three forms run TD3fD: the target actor's output is smoothed in place (kr_target_smooth, in-kernel
+Philox noise keyed by the update count), both target critics and both critics run the passes above, ONE kr_twin_critic_grad forms the
+targets from the target critics' minimum and both loss gradients, and the actor's Adam step is kr_adam_step_every (every
+policy_freq-th update).  A DDPGfD policy's launch sequence is what it was.
+
 Common to both: targets + critic loss gradient, Adam and the soft target update are one kernel each (kr_critic_grad,
 kr_adam_step, kr_soft_update); with world_size > 1 the flat gradient buffers are all-reduced directly (no pack /
 unpack).  Same arithmetic as the reference (critic loss L1 + 0.5 LN on masked row means, actor loss -mean Q(s, pi(s))
@@ -62,11 +67,20 @@ class NativeDDPGfDUpdate:
         True asks for an update without a single launch that needs LDS - the default LDS-free kernels where the width has them, the
         lean ones (mlp.LEAN_TILES: 400-300) where it does not, ValueError when it has neither."""
         assert policy.device.type == "cuda", "the learner glue kernels are GPU only"
+        import os
+        # a ddpgfd.TD3fD policy: a second critic pair, smoothed target actions, the actor's step on every policy_freq-th update
+        self.td3 = "critic2" in policy._flat_params
+        if self.td3 and os.environ.get("KS_LEARNER_FORK", "0") == "1":
+            raise ValueError("NativeDDPGfDUpdate: the fork form (KS_LEARNER_FORK=1) has no TD3fD variant")
         self.p = policy
         self.lib = _sim.load_library()
         fp = policy._flat_params
         self.critic, self.actor = _Net(policy.critic, fp["critic"]), _Net(policy.actor, fp["actor"])
         self.critic_t, self.actor_t = _Net(policy.critic_target, fp["critic_target"]), _Net(policy.actor_target, fp["actor_target"])
+        if self.td3:
+            self.critic2, self.critic2_t = _Net(policy.critic2, fp["critic2"]), _Net(policy.critic2_target, fp["critic2_target"])
+        # key of the target smoothing's in-kernel noise stream (counter: the update count); pipeline.GraphedTrainer hands over its sampler's
+        self.seed = int(torch.initial_seed()) & 0xFFFFFFFFFFFFFFFF
         self.it = torch.zeros(1, dtype=torch.long, device=policy.device)      # updates done (Adam step of both nets)
         # Pipelined form (phase_head): the actor's Adam step + soft target update of update k run at the START of update
         # k + 1.  `it_head` is k while that step is pending and 0 otherwise, so the head is a no-op when nothing is pending
@@ -77,10 +91,13 @@ class NativeDDPGfDUpdate:
         self.pipelined = False        # set by pipeline.GraphedTrainer: the body marks its actor step pending for the next head
         policy._native = self                                                  # DDPGfD.save / load keep the Adam state in sync
         self.import_optimizer_state()
-        self.losses = torch.zeros(3, device=policy.device)                   # critic loss, L1, LN of the last update
+        self.losses = torch.zeros(6 if self.td3 else 3, device=policy.device)   # critic loss, L1, LN of the last update (TD3fD: then critic 2's)
         ao, co = policy.actor_optimizer.param_groups[0], policy.critic_optimizer.param_groups[0]
         self.hyper_a = (ao["lr"], ao["betas"][0], ao["betas"][1], ao["eps"], ao["weight_decay"])
         self.hyper_c = (co["lr"], co["betas"][0], co["betas"][1], co["eps"], co["weight_decay"])
+        if self.td3:
+            c2o = policy.critic2_optimizer.param_groups[0]
+            self.hyper_c2 = (c2o["lr"], c2o["betas"][0], c2o["betas"][1], c2o["eps"], c2o["weight_decay"])
         # How much of the update runs on the hand-written MFMA kernels of csrc/ks_mlp.hip (mlp.py):
         #  * fused_targets: the forward-only target networks (3200 rows) and the critic's forward (1600 rows, activations
         #    kept for the backward pass) as ONE launch each instead of three library GEMMs + glue;
@@ -89,7 +106,6 @@ class NativeDDPGfDUpdate:
         #  * lds_free: the backward passes too (mlp.mlp3_backward, mlp.weight_grad) - then no launch of the update needs
         #    LDS and the whole learner runs in the simulator's shadow.  Widths 256-256 / 128-128 / 64-64.
         # Otherwise (e.g. the reference's 400-300) the passes go through the library GEMMs (hipBLASLt).
-        import os
         tl = [list(zip(net.W, net.b)) for net in (self.actor_t, self.critic_t)]
         ins = [net.W[0].shape[1] for net in (self.actor_t, self.critic_t)]
         mult = lambda k: all(w.shape[0] % k == 0 for w in self.critic.W[:2] + self.actor.W[:2])
@@ -169,18 +185,36 @@ class NativeDDPGfDUpdate:
         self._chk(self.lib.kr_adam_step(net.flat.numel(), P(net.flat), P(net.grad), P(net.exp_avg), P(net.exp_avg_sq),
                                         P(self.it if step is None else step), lr, b1, b2, eps, wd, self._st()), "kr_adam_step")
 
+    def _adam_actor(self, step):
+        """the actor's Adam step for the update counted by `step`; TD3fD: on every policy_freq-th update only, numbered step / policy_freq"""
+        if not self.td3:
+            return self._adam(self.actor, self.hyper_a, step=step)
+        lr, b1, b2, eps, wd = self.hyper_a
+        net, P = self.actor, _sim._ptr
+        self._chk(self.lib.kr_adam_step_every(net.flat.numel(), P(net.flat), P(net.grad), P(net.exp_avg), P(net.exp_avg_sq), P(step),
+                                              self.p.policy_freq, lr, b1, b2, eps, wd, self._st()), "kr_adam_step_every")
+
+    def _soft_updates(self, it):
+        pol, P = self.p, _sim._ptr
+        pairs = ((self.critic, self.critic_t),) + (((self.critic2, self.critic2_t),) if self.td3 else ()) + ((self.actor, self.actor_t),)
+        for net, tgt in pairs:
+            self._chk(self.lib.kr_soft_update(net.flat.numel(), P(net.flat), P(tgt.flat), pol.tau, P(it), pol.network_repl_freq, self._st()),
+                      "kr_soft_update")
+
     # -- optimizer state <-> torch.optim.Adam (the reference's 4-file checkpoint keeps it: DDPGfD.py:371-382) ------------
     def _optim_pairs(self):
-        return ((self.actor, self.p.actor_optimizer), (self.critic, self.p.critic_optimizer))
+        pairs = ((self.actor, self.p.actor_optimizer), (self.critic, self.p.critic_optimizer))
+        return pairs + (((self.critic2, self.p.critic2_optimizer),) if self.td3 else ())
 
     def export_optimizer_state(self):
         """Make policy.{actor,critic}_optimizer.state describe the native Adam state: exp_avg / exp_avg_sq are VIEWS of the
-        flat moment buffers (they stay current), `step` is the number of updates applied.  Applies a pending pipelined
-        actor step first, so that both networks are at the same update."""
+        flat moment buffers (they stay current), `step` is the number of updates applied (TD3fD's delayed actor: the number of steps it
+        took, it // policy_freq).  Applies a pending pipelined actor step first, so that both networks are at the same update."""
         torch.cuda.synchronize(self.p.device)          # a pipelined update may still be running on the learner's stream
         self.finish_pending()
-        step = float(self.it.item())
+        it = int(self.it.item())
         for net, opt in self._optim_pairs():
+            step = float(it // self.p.policy_freq if (self.td3 and net is self.actor) else it)
             off = 0
             for p in opt.param_groups[0]["params"]:
                 n = p.numel()
@@ -202,10 +236,19 @@ class NativeDDPGfDUpdate:
                     if stt["exp_avg"].data_ptr() != net.exp_avg[off:off + n].data_ptr():
                         net.exp_avg[off:off + n].copy_(stt["exp_avg"].reshape(-1))
                         net.exp_avg_sq[off:off + n].copy_(stt["exp_avg_sq"].reshape(-1))
-                    steps.append(int(float(stt["step"])))
+                    steps.append((int(float(stt["step"])), net is self.actor))
                 off += n
-        if steps:
+        if steps and self.td3:
+            # the critics count the updates; the delayed actor has taken every policy_freq-th of them
+            critics = [s for s, is_actor in steps if not is_actor]
+            its = critics if critics else [s * self.p.policy_freq for s, _ in steps]
+            assert min(its) == max(its) and all(s == its[0] // self.p.policy_freq for s, is_actor in steps if is_actor), \
+                "actor and critic optimizers are at different steps"
+            steps = its
+        elif steps:
+            steps = [s for s, _ in steps]
             assert min(steps) == max(steps), "actor and critic optimizers are at different steps"
+        if steps:
             self.it.fill_(steps[0])
             self.it_head.zero_()
             self.p.total_it = steps[0]
@@ -231,10 +274,14 @@ class NativeDDPGfDUpdate:
 
     # -- the three phases ---------------------------------------------------------------------------------------------
     @torch.no_grad()
-    def phase_critic(self, state, action, next_state, reward, weight=None, next_ends=None, priorities=None):
+    def phase_critic(self, state, action, next_state, reward, weight=None, next_ends=None, priorities=None, target_noise=None):
         """targets, critic forward, loss gradient, critic weight gradients -> self.critic.grad.  priorities (prioritized replay): a callable
         (q, tq1, reward, weight) issued right after kr_critic_grad on that kernel's own operands - DeviceEpisodeReplay.update_priorities with
-        the batch's `picked` bound; None: the launch sequence has no such step."""
+        the batch's `picked` bound; None: the launch sequence has no such step.
+        With a TD3fD policy: the target actor's forward, kr_target_smooth on its output, both target critics on the smoothed action, both
+        critics' forward, ONE kr_twin_critic_grad, the backward and weight-gradient passes once per critic; returns six losses and
+        `priorities` receives (q1, tmin, reward, weight).  target_noise [2R, 4]: the smoothing's N(0, 1) draws; None: the in-kernel stream
+        keyed by (self.seed, self.it)."""
         pol, P = self.p, _sim._ptr
         R = reward.shape[0]
         if weight is None:
@@ -272,54 +319,86 @@ class NativeDDPGfDUpdate:
             _mlp.weight_grad(dz1, s0, a0, c.gW[0], c.gb[0])
             self._join(0, 1)
             return self.losses[0], self.losses[1], self.losses[2]
-        if self.fused_targets:
-            # forward-only networks: one fused fp32-MFMA launch each (mlp.mlp3_forward) instead of 3 GEMMs + glue
-            ta = _mlp.mlp3_forward(list(zip(self.actor_t.W, self.actor_t.b)), nx, act=_mlp.ACT_SIGMOID, scale=pol.max_action, **self._targets_form)
-            tq = _mlp.mlp3_forward(list(zip(self.critic_t.W, self.critic_t.b)), nx, ta, act=_mlp.ACT_NONE, **self._targets_form)
-        else:
-            _, _, ta = self._actor_forward(self.actor_t, nx)
-            ct = self.critic_t
-            tq = torch.addmm(ct.b[2], self._lin_relu(ct, 1, self._lin_relu(ct, 0, torch.cat([nx, ta], 1))), ct.W[2].t())
+        ta = self._target_actions(nx)
         c = self.critic
-        if self.lds_free:
-            # the whole critic step without LDS: forward, loss gradient, data and weight gradients (csrc/ks_mlp.hip)
-            cl = list(zip(c.W, c.b))
-            s0, a0 = state[:, 0], action[:, 0]
-            h1, h2 = s0.new_empty(R, c.W[0].shape[0]), s0.new_empty(R, c.W[1].shape[0])
-            q = _mlp.mlp3_forward(cl, s0, a0, act=_mlp.ACT_NONE, h1_out=h1, h2_out=h2, **self._form)
-            dq = torch.empty_like(q)
+        if self.td3:
+            # TD3fD: smoothed target actions, both target critics on them, both critics' forward, ONE loss-gradient launch on the targets' minimum
+            assert ta.is_contiguous() and (target_noise is None or (target_noise.is_contiguous() and target_noise.dtype == torch.float32 and
+                                                                    target_noise.device == ta.device and tuple(target_noise.shape) == tuple(ta.shape)))
+            self._chk(self.lib.kr_target_smooth(ta.shape[0], P(ta), P(target_noise), self.seed, None if target_noise is not None else P(self.it),
+                                                pol.policy_noise, pol.noise_clip, pol.max_action, self._st()), "kr_target_smooth")
+            c2 = self.critic2
+            tq, tq2 = self._target_q(self.critic_t, nx, ta), self._target_q(self.critic2_t, nx, ta)
+            (q, saved), (q2, saved2) = self._critic_forward(c, state, action), self._critic_forward(c2, state, action)
+            dq, dq2, tmin = torch.empty_like(q), torch.empty_like(q2), q.new_empty(2 * R)
             reward = reward.contiguous()
-            self._chk(self.lib.kr_critic_grad(R, pol.n, P(q), P(tq), P(tq[R:]), P(reward), P(weight), P(self.wsum), pol.discount, P(dq), P(self.losses),
-                                              self._st()), "kr_critic_grad")
+            self._chk(self.lib.kr_twin_critic_grad(R, pol.n, P(q), P(q2), P(tq), P(tq2), P(tq[R:]), P(tq2[R:]), P(reward), P(weight), P(self.wsum),
+                                                   pol.discount, P(dq), P(dq2), P(tmin), P(self.losses), self._st()), "kr_twin_critic_grad")
             if priorities is not None:
-                priorities(q, tq, reward, weight)
-            dz2, dz1, _ = _mlp.mlp3_backward(cl, dq, h1, h2, lean=self.lean_kernels)
-            _mlp.weight_grad(dq, h2, None, c.gW[2], c.gb[2])
-            _mlp.weight_grad(dz2, h1, None, c.gW[1], c.gb[1])
-            _mlp.weight_grad(dz1, s0, a0, c.gW[0], c.gb[0])
-            return self.losses[0], self.losses[1], self.losses[2]
-        x0 = torch.cat([state[:, 0], action[:, 0]], 1)
-        if self.fused_targets and self.fuse_critic_fwd:
-            h1, h2 = x0.new_empty(R, c.W[0].shape[0]), x0.new_empty(R, c.W[1].shape[0])
-            q = _mlp.mlp3_forward(list(zip(c.W, c.b)), state[:, 0], action[:, 0], act=_mlp.ACT_NONE, h1_out=h1, h2_out=h2, **self._targets_form)
-        else:
-            h1 = self._lin_relu(c, 0, x0)
-            h2 = self._lin_relu(c, 1, h1)
-            q = torch.addmm(c.b[2], h2, c.W[2].t())
+                priorities(q, tmin, reward, weight)          # the target the update used
+            self._critic_backward(c, dq, saved)
+            self._critic_backward(c2, dq2, saved2)
+            return tuple(self.losses[k] for k in range(6))
+        tq = self._target_q(self.critic_t, nx, ta)
+        q, saved = self._critic_forward(c, state, action)
         dq = torch.empty_like(q)
         reward = reward.contiguous()
         self._chk(self.lib.kr_critic_grad(R, pol.n, P(q), P(tq), P(tq[R:]), P(reward), P(weight), P(self.wsum), pol.discount, P(dq), P(self.losses),
                                           self._st()), "kr_critic_grad")
         if priorities is not None:
             priorities(q, tq, reward, weight)
-        self._weight_grads(c, x0, h1, h2, dq)
+        self._critic_backward(c, dq, saved)
         return self.losses[0], self.losses[1], self.losses[2]
+
+    # the passes of phase_critic, per network (TD3fD runs the critic's twice)
+    def _target_actions(self, nx):
+        if self.fused_targets:
+            # forward-only networks: one fused fp32-MFMA launch each (mlp.mlp3_forward) instead of 3 GEMMs + glue
+            return _mlp.mlp3_forward(list(zip(self.actor_t.W, self.actor_t.b)), nx, act=_mlp.ACT_SIGMOID, scale=self.p.max_action, **self._targets_form)
+        return self._actor_forward(self.actor_t, nx)[2]
+
+    def _target_q(self, ct, nx, ta):
+        if self.fused_targets:
+            return _mlp.mlp3_forward(list(zip(ct.W, ct.b)), nx, ta, act=_mlp.ACT_NONE, **self._targets_form)
+        return torch.addmm(ct.b[2], self._lin_relu(ct, 1, self._lin_relu(ct, 0, torch.cat([nx, ta], 1))), ct.W[2].t())
+
+    def _critic_forward(self, c, state, action):
+        """Q of the windows' first rows; returns (q, what _critic_backward needs)"""
+        s0, a0 = state[:, 0], action[:, 0]
+        R = s0.shape[0]
+        if self.lds_free:
+            # the whole critic step without LDS: forward, loss gradient, data and weight gradients (csrc/ks_mlp.hip)
+            h1, h2 = s0.new_empty(R, c.W[0].shape[0]), s0.new_empty(R, c.W[1].shape[0])
+            q = _mlp.mlp3_forward(list(zip(c.W, c.b)), s0, a0, act=_mlp.ACT_NONE, h1_out=h1, h2_out=h2, **self._form)
+            return q, (s0, a0, h1, h2)
+        x0 = torch.cat([s0, a0], 1)
+        if self.fused_targets and self.fuse_critic_fwd:
+            h1, h2 = x0.new_empty(R, c.W[0].shape[0]), x0.new_empty(R, c.W[1].shape[0])
+            q = _mlp.mlp3_forward(list(zip(c.W, c.b)), s0, a0, act=_mlp.ACT_NONE, h1_out=h1, h2_out=h2, **self._targets_form)
+        else:
+            h1 = self._lin_relu(c, 0, x0)
+            h2 = self._lin_relu(c, 1, h1)
+            q = torch.addmm(c.b[2], h2, c.W[2].t())
+        return q, (x0, h1, h2)
+
+    def _critic_backward(self, c, dq, saved):
+        """dq = dLoss/dQ -> c.grad"""
+        if self.lds_free:
+            s0, a0, h1, h2 = saved
+            dz2, dz1, _ = _mlp.mlp3_backward(list(zip(c.W, c.b)), dq, h1, h2, lean=self.lean_kernels)
+            _mlp.weight_grad(dq, h2, None, c.gW[2], c.gb[2])
+            _mlp.weight_grad(dz2, h1, None, c.gW[1], c.gb[1])
+            _mlp.weight_grad(dz1, s0, a0, c.gW[0], c.gb[0])
+        else:
+            self._weight_grads(c, *saved, dq)
 
     @torch.no_grad()
     def phase_actor(self, state, weight=None):
         """critic Adam step, then the actor loss -mean_w Q(s, pi(s)) over all n-step rows -> self.actor.grad"""
         pol, P = self.p, _sim._ptr
         self._adam(self.critic, self.hyper_c)
+        if self.td3:
+            self._adam(self.critic2, self.hyper_c2)
         n = state.shape[1]
         sa = state.reshape(-1, state.shape[2])
         a_, c = self.actor, self.critic
@@ -382,23 +461,17 @@ class NativeDDPGfDUpdate:
         the actor's weights change at one known, early point of every update instead of at its end.  Gated on the device
         counter `it_head` (set by mark_pending at the end of an update's body, cleared here): a no-op when no actor step is
         pending."""
-        pol, P = self.p, _sim._ptr
-        self._adam(self.actor, self.hyper_a, step=self.it_head)
-        for net, tgt in ((self.critic, self.critic_t), (self.actor, self.actor_t)):
-            self._chk(self.lib.kr_soft_update(net.flat.numel(), P(net.flat), P(tgt.flat), pol.tau, P(self.it_head), pol.network_repl_freq, self._st()),
-                      "kr_soft_update")
+        self._adam_actor(self.it_head)
+        self._soft_updates(self.it_head)
         # (no clearing here: in the pipelined form every body re-marks it_head and a head always runs between two bodies;
         # finish_pending, the eager caller, clears it)
 
     @torch.no_grad()
     def phase_targets(self):
         """actor Adam step + soft target update on every network_repl_freq-th update"""
-        pol, P = self.p, _sim._ptr
-        self._adam(self.actor, self.hyper_a)
-        pol.total_it += 1
-        for net, tgt in ((self.critic, self.critic_t), (self.actor, self.actor_t)):
-            self._chk(self.lib.kr_soft_update(net.flat.numel(), P(net.flat), P(tgt.flat), pol.tau, P(self.it), pol.network_repl_freq, self._st()),
-                      "kr_soft_update")
+        self._adam_actor(self.it)
+        self.p.total_it += 1
+        self._soft_updates(self.it)
 
     def allreduce(self, net):
         """average the flat gradient buffer of `net` ("critic" / "actor") over the process group (RCCL), in place"""
@@ -415,9 +488,11 @@ class NativeDDPGfDUpdate:
         dist.all_reduce(g, op=dist.ReduceOp.SUM, group=self.p.process_group)
         g.div_(world)
 
-    def train_on_batch(self, state, action, next_state, reward, weight=None):
-        losses = self.phase_critic(state, action, next_state, reward, weight)
+    def train_on_batch(self, state, action, next_state, reward, weight=None, target_noise=None):
+        losses = self.phase_critic(state, action, next_state, reward, weight, target_noise=target_noise)
         self.allreduce("critic")
+        if self.td3:
+            self.allreduce("critic2")
         self.phase_actor(state, weight)
         self.allreduce("actor")
         self.phase_targets()

@@ -177,6 +177,7 @@ class GraphedTrainer:
             else:
                 self.exchange_note = f"{backend} all_reduce"
         self.sample_seed = int(torch.initial_seed())          # the window sampler's Philox key
+        self.native.seed = self.sample_seed & 0xFFFFFFFFFFFFFFFF   # ... and the key of a TD3fD policy's target smoothing (a stream of its own tag)
         # first-contact safety on a real node: every `check_every` updates the exchange's error word is read (a rank whose wait for a
         # peer ran out stops reducing: fail loudly instead of training diverged replicas) and the replicas' weight checksums are
         # compared over the process group.  Both are host reads, hence not every update.
@@ -218,10 +219,20 @@ class GraphedTrainer:
     def _phase2(self):
         self.native.phase_actor(self.batch[0], self.batch[5])     # (its actor Adam step runs in the next update's head: native.pipelined)
 
+    def _allreduce_critics(self):
+        self.native.allreduce("critic")
+        if self.native.td3:
+            self.native.allreduce("critic2")
+
+    def _opt_nets(self):
+        """the networks that have an optimizer (a TD3fD policy: the second critic too)"""
+        nat = self.native
+        return (nat.actor, nat.critic) + ((nat.critic2,) if nat.td3 else ())
+
     def _learn_eager(self):
         self._head()
         self._phase1()
-        self.native.allreduce("critic")
+        self._allreduce_critics()
         self._phase2()
         self.native.allreduce("actor")
 
@@ -243,7 +254,7 @@ class GraphedTrainer:
         # warm-up only warms the allocator and the GEMM selection, it never trains.
         nat, pol = self.native, self.policy
         saved = {k: v.clone() for k, v in pol._flat_params.items()}
-        saved_opt = [(net, net.grad.clone(), net.exp_avg.clone(), net.exp_avg_sq.clone()) for net in (nat.actor, nat.critic)]
+        saved_opt = [(net, net.grad.clone(), net.exp_avg.clone(), net.exp_avg_sq.clone()) for net in self._opt_nets()]
         saved_it, saved_head, saved_total = nat.it.clone(), nat.it_head.clone(), pol.total_it
         saved_prio = self._priority_state()
         s = torch.cuda.Stream(self.dev)
@@ -310,20 +321,22 @@ class GraphedTrainer:
             self.g_learn[0].replay()
         else:
             self.g_learn[0].replay()
-            self.native.allreduce("critic")
+            self._allreduce_critics()
             self.g_learn[1].replay()
             self.native.allreduce("actor")
         self.updates += 1
         if self.check_every and self.check_in_body and self.updates % self.check_every == 0:
             self.check_replicas()
 
+    def _network_names(self):
+        return ("actor", "critic", "actor_target", "critic_target") + (("critic2", "critic2_target") if self.native.td3 else ())
+
     def replica_checksum_spread(self) -> float:
-        """max over the four networks of |max - min| over the ranks of two checksums (sum, sum of |.|) of the flat parameters: 0.0
+        """max over the networks (four; six with a TD3fD policy) of |max - min| over the ranks of two checksums (sum, sum of |.|) of the flat parameters: 0.0
         when the replicas are bit-identical.  Two small collectives on the process group + a host read."""
         import torch.distributed as dist
         pol = self.policy
-        chk = torch.stack([f(pol._flat_params[k].double()) for k in ("actor", "critic", "actor_target", "critic_target")
-                           for f in (torch.sum, lambda x: x.abs().sum())])
+        chk = torch.stack([f(pol._flat_params[k].double()) for k in self._network_names() for f in (torch.sum, lambda x: x.abs().sum())])
         hi, lo = chk.clone(), chk.clone()
         dist.all_reduce(hi, op=dist.ReduceOp.MAX, group=pol.process_group)
         dist.all_reduce(lo, op=dist.ReduceOp.MIN, group=pol.process_group)
@@ -610,7 +623,7 @@ class AsyncTrainer(GraphedTrainer):
     def _capture(self, warmup_updates):
         nat, pol = self.native, self.policy
         saved = {k: v.clone() for k, v in pol._flat_params.items()}
-        saved_opt = [(net, net.grad.clone(), net.exp_avg.clone(), net.exp_avg_sq.clone()) for net in (nat.actor, nat.critic)]
+        saved_opt = [(net, net.grad.clone(), net.exp_avg.clone(), net.exp_avg_sq.clone()) for net in self._opt_nets()]
         saved_it, saved_head, saved_total = nat.it.clone(), nat.it_head.clone(), pol.total_it
         saved_prio = self._priority_state()
         s = torch.cuda.Stream(self.dev)
@@ -713,15 +726,15 @@ class AsyncTrainer(GraphedTrainer):
             self.check_replicas()
 
     def average_replicas(self):
-        """replica_sync == "average-per-launch": the pending (pipelined) actor step is applied, then the flat parameter buffers of the four
-        networks and the Adam moments of actor and critic are averaged over the process group (library collectives on the current stream: they
+        """replica_sync == "average-per-launch": the pending (pipelined) actor step is applied, then the flat parameter buffers of the
+        networks (four; six with a TD3fD policy) and the Adam moments of actor and critic(s) are averaged over the process group (library collectives on the current stream: they
         execute once the persistent launch has released the CUs' LDS), and the averaged actor becomes the newest published version."""
         import torch.distributed as dist
         nat, pol = self.native, self.policy
         nat.finish_pending()
         world = dist.get_world_size(pol.process_group)
-        bufs = [pol._flat_params[k] for k in ("actor", "critic", "actor_target", "critic_target")]
-        bufs += [b for net in (nat.actor, nat.critic) for b in (net.exp_avg, net.exp_avg_sq)]
+        bufs = [pol._flat_params[k] for k in self._network_names()]
+        bufs += [b for net in self._opt_nets() for b in (net.exp_avg, net.exp_avg_sq)]
         # ONE all-reduce: the eight flat buffers packed into one (5.6 MB at 256-256), averaged, unpacked (ADVICE r5: it was eight blocking
         # all-reduces and eight scaling kernels per launch boundary)
         flat = torch.cat([b.reshape(-1) for b in bufs])
