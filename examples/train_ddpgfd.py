@@ -13,6 +13,7 @@
 
     python examples/train_ddpgfd.py --envs 1024 --steps 600 --hidden 256 256 (or 400 300: the reference's widths, free-running too) [--free-running] [--expert-prob 0] [--starts-per-env 64]
                                     [--success-map DIR] [--demonstrations free-running] [--randomize-params] [--prioritized]
+                                    [--q-bounds 0 50] [--huber-delta 10] [--max-grad-norm 10]
 
 --success-map DIR (with --free-running): the stepping kernel logs every finished training episode (ks_set_episode_log); at every report
 the script folds the log (metrics.EpisodeLedger) and writes DIR/per_shape_success.jsonl and the success / fail start coordinates of the
@@ -91,7 +92,13 @@ def main():
     ap.add_argument("--noise-clip", type=float, default=None, help="with --td3: clip of the target smoothing noise (default 0.25 x max_action = 0.2)")
     ap.add_argument("--policy-freq", type=int, default=2, help="with --td3: the actor steps on every this many updates")
     ap.add_argument("--log-q", action="store_true", help="print the mean Q(s, pi(s)) of the last update's batch beside the critic loss (the critic's own estimate: "
-                    "the best possible return is 50)")
+                    "the best possible return is 50); with --max-grad-norm also the critic's gradient norm and clip coefficient of that update")
+    ap.add_argument("--q-bounds", type=float, nargs=2, default=None, metavar=("LO", "HI"), help="clamp the bootstrapped target-critic value to [LO, HI] before it "
+                    "enters the 1-step and the n-step target (the attainable return here: 0 50); default: no clamp")
+    ap.add_argument("--huber-delta", type=float, default=None, metavar="D", help="Huber-shaped TD loss: e^2 up to |e| = D, D (2 |e| - D) beyond, so a row's pull on "
+                    "the critic stops growing at 2 D; default: the plain square")
+    ap.add_argument("--max-grad-norm", type=float, default=None, metavar="G", help="clip each network's gradient to the global L2 norm G right before its Adam step "
+                    "(torch.nn.utils.clip_grad_norm_; kr_grad_sqnorm + kr_adam_step_clipped); default: no clip")
     ap.add_argument("--expl-noise", type=float, default=0.1, help="exploration noise, std = 0.8 x this (main_DDPGfD.py:443-446: 0.1)")
     ap.add_argument("--dump-replay", default=None, help="write the replay (last 1500 agent + first 400 expert episodes) and the four networks as one .npz "
                     "(tools/r06/reference_learner_on_replay.py runs the REFERENCE's train_batch on it)")
@@ -99,6 +106,7 @@ def main():
     args = ap.parse_args()
     if args.success_map and not args.free_running:
         ap.error("--success-map needs --free-running")
+    bounded = dict(q_bounds=None if args.q_bounds is None else tuple(args.q_bounds), huber_delta=args.huber_delta, max_grad_norm=args.max_grad_norm)
     torch.manual_seed(args.seed)
     rng = np.random.RandomState(args.seed)
     dev = torch.device("cuda", 0)
@@ -137,11 +145,13 @@ def main():
         q0, hq = start_states(n, args.shape, rng)
     if args.td3:
         policy = TD3fD(82, 4, 0.8, 5, tau=args.tau, batch_size=args.batch_episodes, hidden=tuple(args.hidden), device=dev, policy_noise=args.policy_noise,
-                       noise_clip=args.noise_clip, policy_freq=args.policy_freq)
+                       noise_clip=args.noise_clip, policy_freq=args.policy_freq, **bounded)
         policy.critic2_optimizer.param_groups[0]["lr"] = args.critic_lr
         print(f"TD3fD: target smoothing noise {policy.policy_noise:g} clipped at {policy.noise_clip:g}, actor steps every {policy.policy_freq} update(s)")
     else:
-        policy = DDPGfD(82, 4, 0.8, 5, tau=args.tau, batch_size=args.batch_episodes, hidden=tuple(args.hidden), device=dev)
+        policy = DDPGfD(82, 4, 0.8, 5, tau=args.tau, batch_size=args.batch_episodes, hidden=tuple(args.hidden), device=dev, **bounded)
+    if any(v is not None for v in bounded.values()):
+        print(f"bounded critic update: q_bounds {policy.q_bounds}, huber_delta {policy.huber_delta}, max_grad_norm {policy.max_grad_norm}")
     policy.network_repl_freq = args.target_every
     policy.actor_optimizer.param_groups[0]["lr"] = args.actor_lr
     policy.critic_optimizer.param_groups[0]["lr"] = args.critic_lr
@@ -216,6 +226,10 @@ def main():
         dt = time.perf_counter() - t0 - t_eval
         ls = tr.native.losses.tolist()
         ev = ""
+        clip = ""
+        if args.log_q and args.max_grad_norm is not None:
+            norm_c, coef_c = tr.native.clip[1].tolist()
+            clip = f"  critic grad norm {norm_c:9.3f} coef {coef_c:6.4f}"
         if args.eval_every and (it + 60) % args.eval_every == 0:
             te = time.perf_counter()
             tr.flush(finish_update=True)                     # the actor the next rollout step would use
@@ -227,7 +241,7 @@ def main():
                 res = eval_policy(sim_eval, policy, sim_eval.reset(qe, hqe))
             ev = f"  eval (no noise, 1024 starts): lift success {res['num_success'] / 1024:.3f}"
             t_eval += time.perf_counter() - te
-        print(f"step {it + 60:5d}  episodes {d_ep:7d}  training lift rate {d_lift / max(1, d_ep):.3f}  critic loss {ls[0]:9.3f}{f' / {ls[3]:9.3f}' if args.td3 else ''}{f'  mean Q {-tr.native.actor_loss.item():8.3f}' if args.log_q else ''}  {n * (it + 60) / dt:9.0f} env-steps/s{ev}")
+        print(f"step {it + 60:5d}  episodes {d_ep:7d}  training lift rate {d_lift / max(1, d_ep):.3f}  critic loss {ls[0]:9.3f}{f' / {ls[3]:9.3f}' if args.td3 else ''}{f'  mean Q {-tr.native.actor_loss.item():8.3f}' if args.log_q else ''}{clip}  {n * (it + 60) / dt:9.0f} env-steps/s{ev}")
     if args.free_running:
         c = tr.counts()
         print(f"free-running rollout: {c['episodes_finished']} episodes finished, {c['episodes_dropped']} dropped, {c['pacing_timeouts']} pacing time-outs, {tr.updates} updates")

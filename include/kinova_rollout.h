@@ -318,6 +318,56 @@ int kr_twin_critic_grad(int32_t rows, int32_t n_steps, const float *q1, const fl
 int kr_adam_step_every(int64_t count, float *param, const float *grad, float *exp_avg, float *exp_avg_sq, const int64_t *step, int32_t every,
                        float lr, float beta1, float beta2, float eps, float weight_decay, void *stream);
 
+/* ---- the bounded critic update (ddpgfd.DDPGfD / TD3fD with q_bounds, huber_delta, max_grad_norm): a clamp on the bootstrapped value, a
+ * Huber-shaped TD loss, a global gradient-norm clip per network.  One launch each, fp32 without contraction (the norm: fp64), no LDS, no
+ * scratch, vector loads and stores only.
+ *
+ *   kr_critic_grad_bounded  kr_critic_grad (q2, tq1_b, tqn_b and dq2 all NULL: one critic, losses[0..2]) or kr_twin_critic_grad (all four
+ *                        given: two critics, losses[0..5]) on a clamped bootstrap and with the loss rho in place of the square.  Per row:
+ *                          m1 = tq1_a, or min(tq1_a, tq1_b) - NaN if either operand is NaN - for two critics;  mn likewise from tqn;
+ *                          b1 = m1 < q_lo ? q_lo : (m1 > q_hi ? q_hi : m1),  bn likewise from mn   - a NaN passes through -;
+ *                          tboot[r] = b1,  tboot[rows + r] = bn   (exact): the bootstrap the update used, which kr_update_priorities reads;
+ *                          target_Q, target_QN from b1, bn by kr_critic_grad's expressions in its order;
+ *                          e1 = q_k - target_Q,  en = q_k - target_QN;
+ *                          c(e)   = e where not |e| > huber_delta, else huber_delta with e's sign;
+ *                          rho(e) = e^2 where not |e| > huber_delta, else huber_delta (2 |e| - huber_delta)   - twice the usual Huber
+ *                                   function, so that huber_delta = +inf is the square and not half of it; a NaN e takes the square branch -;
+ *                          dq_k = w / sum(w) * (2 c(e1) + 0.5 * 2 c(en));
+ *                          L1, LN = sum_r w rho(e1), sum_r w rho(en) over sum(w), the terms in fp32 (the square branch is fl(fl(w e) e), as
+ *                                   kr_critic_grad's), lane sums and a butterfly;  losses[0] = fl(losses[1] + fl(0.5 losses[2])), and
+ *                                   likewise losses[3..5] for critic 2.
+ *                        One wave, butterfly sums; weight NULL = all ones; weight_sum[0] = 0 gives all-zero dq and losses (tboot is written
+ *                        all the same).  With q_lo = -inf, q_hi = +inf, huber_delta = +inf every output bit is kr_critic_grad's (one
+ *                        critic; tboot = (tq1, tqn)) or kr_twin_critic_grad's (two; tboot = tmin).
+ *                        KS_ERR_INVALID, nothing launched or written: rows <= 0, n_steps <= 0; a NULL q1, tq1_a, tqn_a, reward, weight_sum,
+ *                        dq1, tboot or losses; some but not all of q2, tq1_b, tqn_b, dq2 NULL; q_lo or q_hi NaN, q_lo > q_hi;
+ *                        huber_delta <= 0 or NaN.
+ *   kr_grad_sqnorm       the squared L2 norm of grad [count] (4-byte aligned: the flat gradient buffers are sliced) as KR_NORM_PARTS fp64
+ *                        partial sums: workgroup b (one wave), lane l adds (double)grad[i] * (double)grad[i] - the widening and the square
+ *                        are exact - over i = 64 b + l + 4096 k, k = 0, 1, ... in that order, then the 64 lanes' sums are combined by an
+ *                        xor butterfly (offsets 32, 16, ..., 1) into partials[b].  The result is a function of (grad, count) alone: no
+ *                        atomics, no dependence on the schedule or the grid.  grad is not written.
+ *                        KS_ERR_INVALID, nothing launched or written: count <= 0, a NULL grad or partials.
+ *   kr_adam_step_clipped kr_adam_step_every behind torch.nn.utils.clip_grad_norm_(params, max_norm): every wave loads the KR_NORM_PARTS
+ *                        partials, one per lane, and adds them by the same fp64 butterfly (so all waves hold the same bits); then in fp32
+ *                          norm = sqrtf((float)total);  coef = max_norm / (norm + 1e-6f);  coef = coef > 1 ? 1 : coef   (a NaN stays NaN)
+ *                        and the step is kr_adam_step_every's with grad[i] * coef in place of grad[i] (scaled before the weight-decay
+ *                        term); grad itself is not written.  The gate on step and every is kr_adam_step_every's.  clip_out (optional,
+ *                        float [2]) receives (norm, coef) from one lane, also when the gate is closed.  max_norm = +inf with finite
+ *                        gradients: kr_adam_step_every's four buffers in every bit.
+ *                        KS_ERR_INVALID, nothing launched or written: what kr_adam_step_every refuses (count <= 0, a NULL param, grad,
+ *                        exp_avg, exp_avg_sq or step, every <= 0); a NULL partials; max_norm <= 0 or NaN.
+ */
+#define KR_NORM_PARTS 64
+int kr_critic_grad_bounded(int32_t rows, int32_t n_steps, const float *q1, const float *q2, const float *tq1_a, const float *tq1_b,
+                           const float *tqn_a, const float *tqn_b, const float *reward, const float *weight, const float *weight_sum,
+                           float discount, float q_lo, float q_hi, float huber_delta, float *dq1, float *dq2, float *tboot, float *losses,
+                           void *stream);
+int kr_grad_sqnorm(int64_t count, const float *grad, double *partials, void *stream);
+int kr_adam_step_clipped(int64_t count, float *param, const float *grad, float *exp_avg, float *exp_avg_sq, const int64_t *step, int32_t every,
+                         const double *partials, float max_norm, float lr, float beta1, float beta2, float eps, float weight_decay,
+                         float *clip_out, void *stream);
+
 /* ---- fused 3-layer MLP forward on the matrix cores (fp32 MFMA): Actor.forward (DDPGfD.py:29-32) and
  * Critic.forward (DDPGfD.py:47-50) as ONE launch each:
  *     out[n,out_dim] = f(W3 relu(W2 relu(W1 x + b1) + b2) + b3),   f = identity (KR_ACT_NONE) or scale * sigmoid

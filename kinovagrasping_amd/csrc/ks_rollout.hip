@@ -905,6 +905,62 @@ __global__ __launch_bounds__(WAVE) void k_twin_critic_grad(int R, int n, const f
     }
 }
 
+// The bounded critic update (kr_critic_grad_bounded): the bootstrapped value clamped to [lo, hi] - a NaN fails both comparisons and passes -
+// and the loss shaped as twice the Huber function: rho(e) = e^2 where not |e| > d, d (2 |e| - d) otherwise, whose derivative is
+// 2 clamp(e, -d, d).  The square branch is k_critic_grad's own term in its order, so infinite bounds and an infinite d give its bits.
+__device__ __forceinline__ float bound_q(float m, float lo, float hi) { return m < lo ? lo : (m > hi ? hi : m); }
+__device__ __forceinline__ float huber_clip(float e, float d) { return fabsf(e) > d ? (e < 0.0f ? -d : d) : e; }
+__device__ __forceinline__ float huber_term(float w, float e, float d) {
+#pragma clang fp contract(off)
+    const float a = fabsf(e);
+    return a > d ? w * (d * (2.0f * a - d)) : w * e * e;
+}
+
+// k_critic_grad (TWIN = false: q2, tq1_b, tqn_b, dq2 unused, three losses) and k_twin_critic_grad (TWIN = true, six) on the clamped bootstrap
+template <bool TWIN>
+__global__ __launch_bounds__(WAVE) void k_critic_grad_bounded(int R, int n, const float* __restrict__ q1, const float* __restrict__ q2,
+                                                              const float* __restrict__ tq1_a, const float* __restrict__ tq1_b,
+                                                              const float* __restrict__ tqn_a, const float* __restrict__ tqn_b,
+                                                              const float* __restrict__ reward, const float* __restrict__ weight,
+                                                              const float* __restrict__ wsum, float discount, float lo, float hi, float delta,
+                                                              float* __restrict__ dq1, float* __restrict__ dq2, float* __restrict__ tboot,
+                                                              float* losses) {
+#pragma clang fp contract(off)
+    const float inv = wsum[0] > 0.0f ? 1.0f / wsum[0] : 0.0f;
+    float l1a = 0, lna = 0, l1b = 0, lnb = 0;
+    for (int r = threadIdx.x; r < R; r += WAVE) {
+        const float m1 = TWIN ? nan_min(tq1_a[r], tq1_b[r]) : tq1_a[r], mn = TWIN ? nan_min(tqn_a[r], tqn_b[r]) : tqn_a[r];
+        const float b1 = bound_q(m1, lo, hi), bn = bound_q(mn, lo, hi);
+        tboot[r] = b1;
+        tboot[(long)R + r] = bn;
+        const float t1 = reward[(long)r * n] + discount * b1;
+        float ret = 0, g = 1.0f;
+        for (int i = 0; i < n; i++) { ret += g * reward[(long)r * n + i]; g *= discount; }
+        const float tn = ret + g * bn;
+        const float w = weight ? weight[r] : 1.0f;
+        const float e1a = q1[r] - t1, ena = q1[r] - tn;
+        l1a += huber_term(w, e1a, delta);
+        lna += huber_term(w, ena, delta);
+        dq1[r] = w * inv * (2.0f * huber_clip(e1a, delta) + 0.5f * 2.0f * huber_clip(ena, delta));
+        if (TWIN) {
+            const float e1b = q2[r] - t1, enb = q2[r] - tn;
+            l1b += huber_term(w, e1b, delta);
+            lnb += huber_term(w, enb, delta);
+            dq2[r] = w * inv * (2.0f * huber_clip(e1b, delta) + 0.5f * 2.0f * huber_clip(enb, delta));
+        }
+    }
+    l1a = wave_sum(l1a);
+    lna = wave_sum(lna);
+    if (TWIN) {
+        l1b = wave_sum(l1b);
+        lnb = wave_sum(lnb);
+    }
+    if (threadIdx.x == 0) {
+        losses[1] = l1a * inv; losses[2] = lna * inv; losses[0] = l1a * inv + 0.5f * (lna * inv);
+        if (TWIN) { losses[4] = l1b * inv; losses[5] = lnb * inv; losses[3] = l1b * inv + 0.5f * (lnb * inv); }
+    }
+}
+
 // TD3's target policy smoothing on the target actor's [rows, 4] output, in place: one thread per row, the row as one 16-byte load / store
 __global__ __launch_bounds__(256) void k_target_smooth(int rows, float* __restrict__ action, const float* __restrict__ noise,
                                                        unsigned long long seed, const int64_t* __restrict__ draw, float sigma, float clip,
@@ -959,13 +1015,16 @@ __global__ __launch_bounds__(256) void k_sigmoid_scale_backward(long count, cons
 }
 
 // torch.optim.Adam, single-tensor formulation, as step number t (bias corrections)
+// (CLIP: the gradient is g * coef, scaled before the weight-decay term as torch.nn.utils.clip_grad_norm_ does; g itself is not written)
+template <bool CLIP = false>
 __device__ __forceinline__ void adam_apply(long count, float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                           float* __restrict__ v, float t, float lr, float b1, float b2, float eps, float wd) {
+                                           float* __restrict__ v, float t, float lr, float b1, float b2, float eps, float wd, float coef = 1.0f) {
 #pragma clang fp contract(off)
     const float bc1 = 1.0f - powf(b1, t), bc2 = 1.0f - powf(b2, t);
     const float step_size = lr / bc1, bc2s = sqrtf(bc2);
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < count; i += (long)gridDim.x * 256) {
         float gi = g[i];
+        if (CLIP) gi = gi * coef;
         if (wd != 0.0f) gi = gi + wd * p[i];
         const float mi = m[i] + (gi - m[i]) * (1.0f - b1);            // exp_avg.lerp_(grad, 1 - beta1)
         const float vi = v[i] * b2 + (1.0f - b2) * gi * gi;           // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, 1 - beta2)
@@ -991,6 +1050,47 @@ __global__ __launch_bounds__(256) void k_adam_step_every(long count, float* __re
     const int64_t s = step[0];
     if (s <= 0 || s % every != 0) return;
     adam_apply(count, p, g, m, v, (float)(s / every), lr, b1, b2, eps, wd);
+}
+
+// Global gradient-norm clip (torch.nn.utils.clip_grad_norm_), two launches.  The squared norm: KR_NORM_PARTS workgroups of one wave, lane l of
+// workgroup b sums the exact fp64 squares of g[b 64 + l + 4096 k], k = 0, 1, ... in that order, an xor butterfly gives partials[b]: a function
+// of (g, count) alone, whatever the schedule, and no float atomics.  4-byte loads: the flat buffers are sliced.
+constexpr int NORM_PARTS = KR_NORM_PARTS;
+static_assert(NORM_PARTS == WAVE, "k_adam_step_clipped loads one partial per lane");
+
+__device__ __forceinline__ double wave_sum_f64(double x) {
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int o = WAVE / 2; o > 0; o >>= 1) x += __shfl_xor(x, o);
+    return x;
+}
+
+__global__ __launch_bounds__(WAVE) void k_grad_sqnorm(long count, const float* __restrict__ g, double* __restrict__ partials) {
+#pragma clang fp contract(off)
+    double s = 0.0;
+    for (long i = (long)blockIdx.x * WAVE + threadIdx.x; i < count; i += (long)NORM_PARTS * WAVE) {
+        const double gi = (double)g[i];
+        s += gi * gi;
+    }
+    s = wave_sum_f64(s);
+    if (threadIdx.x == 0) partials[blockIdx.x] = s;
+}
+
+// k_adam_step_every on g * coef, coef = min(max_norm / (norm + 1e-6), 1): every wave sums the same 64 partials by the same butterfly, so all
+// hold the same bits.  clip_out (optional) = (norm, coef), written whatever the gate says.
+__global__ __launch_bounds__(256) void k_adam_step_clipped(long count, float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                           float* __restrict__ v, const int64_t* __restrict__ step, int every,
+                                                           const double* __restrict__ partials, float max_norm, float lr, float b1, float b2,
+                                                           float eps, float wd, float* __restrict__ clip_out) {
+#pragma clang fp contract(off)
+    const double total = wave_sum_f64(partials[threadIdx.x & (WAVE - 1)]);
+    const float norm = sqrtf((float)total);
+    float coef = max_norm / (norm + 1e-6f);
+    coef = coef > 1.0f ? 1.0f : coef;                     // (a NaN stays NaN, as with torch.clamp(max=1))
+    if (clip_out && blockIdx.x == 0 && threadIdx.x == 0) { clip_out[0] = norm; clip_out[1] = coef; }
+    const int64_t s = step[0];
+    if (s <= 0 || s % every != 0) return;
+    adam_apply<true>(count, p, g, m, v, (float)(s / every), lr, b1, b2, eps, wd, coef);
 }
 
 __global__ __launch_bounds__(256) void k_soft_update(long count, const float* __restrict__ p, float* __restrict__ tp, float tau,
@@ -1302,6 +1402,37 @@ int kr_target_smooth(int32_t rows, float* action, const float* noise, uint64_t s
         return KS_ERR_INVALID;
     hipLaunchKernelGGL(k_target_smooth, dim3(grid_for(rows)), dim3(256), 0, (hipStream_t)stream, rows, action, noise, (unsigned long long)seed, draw, sigma,
                        clip, max_action);
+    return launched();
+}
+
+int kr_critic_grad_bounded(int32_t rows, int32_t n_steps, const float* q1, const float* q2, const float* tq1_a, const float* tq1_b, const float* tqn_a,
+                           const float* tqn_b, const float* reward, const float* weight, const float* weight_sum, float discount, float q_lo, float q_hi,
+                           float huber_delta, float* dq1, float* dq2, float* tboot, float* losses, void* stream) {
+    if (rows <= 0 || n_steps <= 0 || !q1 || !tq1_a || !tqn_a || !reward || !weight_sum || !dq1 || !tboot || !losses) return KS_ERR_INVALID;
+    const bool twin = q2 != nullptr;
+    if ((dq2 != nullptr) != twin || (tq1_b != nullptr) != twin || (tqn_b != nullptr) != twin) return KS_ERR_INVALID;
+    if (!(q_lo <= q_hi) || !(huber_delta > 0.0f)) return KS_ERR_INVALID;                       // (a NaN fails either comparison)
+    if (twin)
+        hipLaunchKernelGGL(k_critic_grad_bounded<true>, dim3(1), dim3(WAVE), 0, (hipStream_t)stream, rows, n_steps, q1, q2, tq1_a, tq1_b, tqn_a, tqn_b,
+                           reward, weight, weight_sum, discount, q_lo, q_hi, huber_delta, dq1, dq2, tboot, losses);
+    else
+        hipLaunchKernelGGL(k_critic_grad_bounded<false>, dim3(1), dim3(WAVE), 0, (hipStream_t)stream, rows, n_steps, q1, q2, tq1_a, tq1_b, tqn_a, tqn_b,
+                           reward, weight, weight_sum, discount, q_lo, q_hi, huber_delta, dq1, dq2, tboot, losses);
+    return launched();
+}
+
+int kr_grad_sqnorm(int64_t count, const float* grad, double* partials, void* stream) {
+    if (count <= 0 || !grad || !partials) return KS_ERR_INVALID;
+    hipLaunchKernelGGL(k_grad_sqnorm, dim3(NORM_PARTS), dim3(WAVE), 0, (hipStream_t)stream, (long)count, grad, partials);
+    return launched();
+}
+
+int kr_adam_step_clipped(int64_t count, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, const int64_t* step, int32_t every,
+                         const double* partials, float max_norm, float lr, float beta1, float beta2, float eps, float weight_decay, float* clip_out,
+                         void* stream) {
+    if (count <= 0 || every <= 0 || !param || !grad || !exp_avg || !exp_avg_sq || !step || !partials || !(max_norm > 0.0f)) return KS_ERR_INVALID;
+    hipLaunchKernelGGL(k_adam_step_clipped, dim3(grid_for(count)), dim3(256), 0, (hipStream_t)stream, (long)count, param, grad, exp_avg, exp_avg_sq, step,
+                       every, partials, max_norm, lr, beta1, beta2, eps, weight_decay, clip_out);
     return launched();
 }
 

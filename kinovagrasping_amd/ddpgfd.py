@@ -17,6 +17,10 @@ both networks are averaged with ONE all-reduce over a flat fp32 buffer (RCCL ove
 `TD3fD(DDPGfD)` is the same learner with TD3's remedy for the single critic's over-estimation (twin critics with the minimum in the
 target, noise-smoothed target actions, a delayed actor); `DDPGfD` itself is unchanged by it, and a TD3fD checkpoint loads into a
 DDPGfD (the reference's four files plus two for the second critic).
+
+Both take three controls on the critic update, each None (off: the update as it was) by default: `q_bounds=(lo, hi)` clamps the
+bootstrapped target-critic value, `huber_delta` shapes the TD loss, `max_grad_norm` clips each network's gradient norm before its step
+(see DDPGfD's docstring; the native form: kr_critic_grad_bounded / kr_grad_sqnorm / kr_adam_step_clipped, learner_native.py).
 """
 from __future__ import annotations
 
@@ -73,9 +77,34 @@ def _flatten_parameters(module: nn.Module) -> torch.Tensor:
     return flat
 
 
+def _bounded_settings(q_bounds, huber_delta, max_grad_norm):
+    """the three controls of the bounded critic update, validated; None = today's code path (not the infinite value)"""
+    if q_bounds is not None:
+        lo, hi = (float(x) for x in q_bounds)
+        if not lo <= hi:                                   # (a NaN fails the comparison)
+            raise ValueError("q_bounds=(lo, hi) needs lo <= hi, neither NaN")
+        q_bounds = (lo, hi)
+    if huber_delta is not None:
+        huber_delta = float(huber_delta)
+        if not huber_delta > 0:
+            raise ValueError("huber_delta must be > 0")
+    if max_grad_norm is not None:
+        max_grad_norm = float(max_grad_norm)
+        if not max_grad_norm > 0:
+            raise ValueError("max_grad_norm must be > 0")
+    return q_bounds, huber_delta, max_grad_norm
+
+
 class DDPGfD:
+    """q_bounds=(lo, hi): the target critic's output is clamped to [lo, hi] before it enters either target (the bootstrap, not the sum: a
+    return the policy can attain lies in the range, so a correct critic is not changed).  huber_delta=d: per row and target the square
+    e^2 becomes rho(e) = e^2 where not |e| > d, d (2 |e| - d) otherwise - twice the usual Huber function, d = inf is the square; its
+    gradient is 2 clamp(e, -d, d).  max_grad_norm=g: torch.nn.utils.clip_grad_norm_(params, g) per network right before each
+    optimizer's step (after the gradient exchange).  All three default to None = the update as it was; there is no new state."""
+
     def __init__(self, state_dim=82, action_dim=4, max_action=0.8, n=5, discount=0.995, tau=0.0005, batch_size=64,
-                 hidden=(400, 300), device="cpu", process_group=None, capturable=False):
+                 hidden=(400, 300), device="cpu", process_group=None, capturable=False, q_bounds=None, huber_delta=None, max_grad_norm=None):
+        self.q_bounds, self.huber_delta, self.max_grad_norm = _bounded_settings(q_bounds, huber_delta, max_grad_norm)
         self.device = torch.device(device)
         self.actor = Actor(state_dim, action_dim, max_action, hidden).to(self.device)
         self.actor_target = copy.deepcopy(self.actor)
@@ -150,6 +179,24 @@ class DDPGfD:
         w = weight.view(-1, *([1] * (x.dim() - 1)))
         return (x * w).sum() / (w.sum().clamp_min(1.0) * per_row)      # 0 / 1 weights: exact unless the batch is all padding
 
+    def _bound(self, tq):
+        """the bootstrapped value the targets take (q_bounds)"""
+        return tq if self.q_bounds is None else tq.clamp(self.q_bounds[0], self.q_bounds[1])
+
+    def _rho(self, e):
+        """the TD loss per row and target (huber_delta); a NaN error takes the square branch and stays NaN"""
+        if self.huber_delta is None:
+            return e ** 2
+        # c (2 e - c) with c = clamp(e, -d, d): e^2 inside, d (2 |e| - d) outside, gradient 2 c - and no inf * 0 in the backward pass
+        # of a branch that is not taken, so that d = inf is the square in every bit
+        c = e.clamp(-self.huber_delta, self.huber_delta)
+        return c * (2 * e - c)
+
+    def _clip(self, module):
+        """the global gradient-norm clip of one network, right before its optimizer's step (max_grad_norm)"""
+        if self.max_grad_norm is not None:
+            torch.nn.utils.clip_grad_norm_(module.parameters(), self.max_grad_norm)
+
     def phase_critic(self, state, action, next_state, reward, weight=None):
         """targets + critic loss + backward (DDPGfD.py:256-330).  Returns (critic, L1, LN) losses."""
         reward = reward.unsqueeze(-1)
@@ -157,13 +204,13 @@ class DDPGfD:
             # both target evaluations (1-step: next_state[:, 0], n-step: next_state[:, -1]) in one pass of the target nets
             R = reward.shape[0]
             nx = torch.cat([next_state[:, 0], next_state[:, -1]], 0)
-            tq = self.critic_target(nx, self.actor_target(nx))
+            tq = self._bound(self.critic_target(nx, self.actor_target(nx)))
             target_Q = reward[:, 0] + self.discount * tq[:R]
             n_step_return = (reward.squeeze(-1) * self._disc).sum(1)
             target_QN = (n_step_return + (self.discount ** self.n) * tq[R:].squeeze(-1)).unsqueeze(-1)
         current_Q = self.critic(state[:, 0], action[:, 0])
-        critic_L1 = self._mean((current_Q - target_Q) ** 2, 1, weight)
-        critic_LN = self._mean((current_Q - target_QN) ** 2, 1, weight)
+        critic_L1 = self._mean(self._rho(current_Q - target_Q), 1, weight)
+        critic_LN = self._mean(self._rho(current_Q - target_QN), 1, weight)
         critic_loss = critic_L1 + 0.5 * critic_LN
         self.critic_optimizer.zero_grad()
         critic_loss.backward()
@@ -171,6 +218,7 @@ class DDPGfD:
 
     def phase_actor(self, state, weight=None):
         """critic step, then actor loss + backward (DDPGfD.py:331-352)"""
+        self._clip(self.critic)
         self.critic_optimizer.step()
         # the critic is only a differentiable function here: no weight gradients for it (the reference computes and
         # discards them)
@@ -185,6 +233,7 @@ class DDPGfD:
 
     def phase_targets(self):
         """actor step + soft target update on every 10th call (DDPGfD.py:353-366)"""
+        self._clip(self.actor)
         self.actor_optimizer.step()
         self.total_it += 1
         fp = self._flat_params
@@ -263,8 +312,10 @@ class TD3fD(DDPGfD):
     `<prefix>_critic2_optimizer`."""
 
     def __init__(self, state_dim=82, action_dim=4, max_action=0.8, n=5, discount=0.995, tau=0.0005, batch_size=64, hidden=(400, 300),
-                 device="cpu", process_group=None, capturable=False, policy_noise=None, noise_clip=None, policy_freq=2):
-        super().__init__(state_dim, action_dim, max_action, n, discount, tau, batch_size, hidden, device, process_group, capturable)
+                 device="cpu", process_group=None, capturable=False, policy_noise=None, noise_clip=None, policy_freq=2, q_bounds=None,
+                 huber_delta=None, max_grad_norm=None):
+        super().__init__(state_dim, action_dim, max_action, n, discount, tau, batch_size, hidden, device, process_group, capturable,
+                         q_bounds=q_bounds, huber_delta=huber_delta, max_grad_norm=max_grad_norm)
         self.critic2 = Critic(state_dim, action_dim, hidden).to(self.device)
         self.critic2_target = copy.deepcopy(self.critic2)
         self.critic2_optimizer = torch.optim.Adam(self.critic2.parameters(), weight_decay=1e-4, capturable=self.capturable)
@@ -296,15 +347,15 @@ class TD3fD(DDPGfD):
             a = self.actor_target(nx)
             z = torch.randn_like(a) if target_noise is None else target_noise
             ta = (a + (self.policy_noise * z).clamp(-self.noise_clip, self.noise_clip)).clamp(0, self.max_action)
-            tq = torch.min(self.critic_target(nx, ta), self.critic2_target(nx, ta))
+            tq = self._bound(torch.min(self.critic_target(nx, ta), self.critic2_target(nx, ta)))      # the clamp after the minimum
             target_Q = reward[:, 0] + self.discount * tq[:R]
             n_step_return = (reward.squeeze(-1) * self._disc).sum(1)
             target_QN = (n_step_return + (self.discount ** self.n) * tq[R:].squeeze(-1)).unsqueeze(-1)
         out, total = (), None
         for critic in (self.critic, self.critic2):
             current_Q = critic(state[:, 0], action[:, 0])
-            L1 = self._mean((current_Q - target_Q) ** 2, 1, weight)
-            LN = self._mean((current_Q - target_QN) ** 2, 1, weight)
+            L1 = self._mean(self._rho(current_Q - target_Q), 1, weight)
+            LN = self._mean(self._rho(current_Q - target_QN), 1, weight)
             loss = L1 + 0.5 * LN
             total = loss if total is None else total + loss
             out += (loss.detach(), L1.detach(), LN.detach())
@@ -315,6 +366,7 @@ class TD3fD(DDPGfD):
 
     def phase_actor(self, state, weight=None):
         """both critics' steps, then the actor loss through critic 1 + backward"""
+        self._clip(self.critic2)
         self.critic2_optimizer.step()
         return super().phase_actor(state, weight)
 
@@ -332,6 +384,7 @@ class TD3fD(DDPGfD):
             keys = ("step", "exp_avg", "exp_avg_sq")
             before = [{k: opt.state[p][k].clone() for k in keys} if opt.state.get(p) else None for p in params]
             flat_before = flat.clone()
+            self._clip(self.actor)                 # (before the step that the gate may undo)
             opt.step()
             with torch.no_grad():
                 flat.copy_(torch.where(step_now, flat, flat_before))
@@ -344,6 +397,7 @@ class TD3fD(DDPGfD):
                     tp.copy_(torch.where(fire, self.tau * p + (1 - self.tau) * tp, tp))
             return
         if self.total_it % self.policy_freq == 0:
+            self._clip(self.actor)
             self.actor_optimizer.step()
         if self.total_it % self.network_repl_freq == 0:
             with torch.no_grad():

@@ -22,6 +22,14 @@ Philox noise keyed by the update count), both target critics and both critics ru
 targets from the target critics' minimum and both loss gradients, and the actor's Adam step is kr_adam_step_every (every
 policy_freq-th update).  A DDPGfD policy's launch sequence is what it was.
 
+With q_bounds / huber_delta / max_grad_norm set on the policy (ddpgfd.DDPGfD and TD3fD, all None by default) the update is bounded: ONE
+kr_critic_grad_bounded takes the place of kr_critic_grad / kr_twin_critic_grad - the bootstrapped value clamped to q_bounds, the TD loss
+Huber-shaped, the unset one of the two passed as its infinite value - and hands the priorities the bootstrap it used (tboot); with
+max_grad_norm every Adam launch becomes kr_grad_sqnorm (64 fp64 partial sums of the flat gradient buffer, no atomics) + kr_adam_step_clipped
+(clip_grad_norm_'s coefficient from them, then the step on g * coef; `every` is 1 for the critics and policy_freq for TD3fD's actor), and
+self.clip [3, 2] holds the (norm, coef) of actor, critic and critic2.  In the pipelined form the actor's norm is taken at the head, on the
+gradient buffer the body left.  All LDS-free, in all three forms; with the three unset the launch sequence is what it was.
+
 Common to both: targets + critic loss gradient, Adam and the soft target update are one kernel each (kr_critic_grad,
 kr_adam_step, kr_soft_update); with world_size > 1 the flat gradient buffers are all-reduced directly (no pack /
 unpack).  Same arithmetic as the reference (critic loss L1 + 0.5 LN on masked row means, actor loss -mean Q(s, pi(s))
@@ -72,6 +80,18 @@ class NativeDDPGfDUpdate:
         self.td3 = "critic2" in policy._flat_params
         if self.td3 and os.environ.get("KS_LEARNER_FORK", "0") == "1":
             raise ValueError("NativeDDPGfDUpdate: the fork form (KS_LEARNER_FORK=1) has no TD3fD variant")
+        # the bounded critic update (ddpgfd: q_bounds, huber_delta, max_grad_norm; None = the launch sequence as it was)
+        q_bounds, huber_delta = getattr(policy, "q_bounds", None), getattr(policy, "huber_delta", None)
+        self.max_grad_norm = getattr(policy, "max_grad_norm", None)
+        self.bounded = q_bounds is not None or huber_delta is not None
+        if (self.bounded or self.max_grad_norm is not None) and os.environ.get("KS_LEARNER_FORK", "0") == "1":
+            raise ValueError("NativeDDPGfDUpdate: the fork form (KS_LEARNER_FORK=1) has no bounded variant (q_bounds / huber_delta / max_grad_norm)")
+        inf = float("inf")
+        self.q_lo, self.q_hi = (-inf, inf) if q_bounds is None else q_bounds
+        self.huber_delta = inf if huber_delta is None else huber_delta
+        # (norm, coef) of the last clipped step of actor, critic, critic2 (zeros while max_grad_norm is None) and kr_grad_sqnorm's partial sums
+        self.clip = torch.zeros(3, 2, device=policy.device)
+        self._partials = torch.zeros(3, _sim.KR_NORM_PARTS, dtype=torch.float64, device=policy.device) if self.max_grad_norm is not None else None
         self.p = policy
         self.lib = _sim.load_library()
         fp = policy._flat_params
@@ -179,9 +199,19 @@ class NativeDDPGfDUpdate:
     def _relu_bwd(self, act, grad):
         self._chk(self.lib.kr_relu_backward(grad.numel(), _sim._ptr(act), _sim._ptr(grad), self._st()), "kr_relu_backward")
 
+    def _adam_clipped(self, net, hyper, step, every, slot):
+        """the Adam step behind the global gradient-norm clip: the squared norm as 64 fp64 partial sums, then the step on g * coef"""
+        lr, b1, b2, eps, wd = hyper
+        P, n, parts = _sim._ptr, net.flat.numel(), self._partials[slot]
+        self._chk(self.lib.kr_grad_sqnorm(n, P(net.grad), P(parts), self._st()), "kr_grad_sqnorm")
+        self._chk(self.lib.kr_adam_step_clipped(n, P(net.flat), P(net.grad), P(net.exp_avg), P(net.exp_avg_sq), P(step), every, P(parts),
+                                                self.max_grad_norm, lr, b1, b2, eps, wd, P(self.clip[slot]), self._st()), "kr_adam_step_clipped")
+
     def _adam(self, net, hyper, step=None):
         lr, b1, b2, eps, wd = hyper
         P = _sim._ptr
+        if self.max_grad_norm is not None:
+            return self._adam_clipped(net, hyper, self.it if step is None else step, 1, 0 if net is self.actor else (1 if net is self.critic else 2))
         self._chk(self.lib.kr_adam_step(net.flat.numel(), P(net.flat), P(net.grad), P(net.exp_avg), P(net.exp_avg_sq),
                                         P(self.it if step is None else step), lr, b1, b2, eps, wd, self._st()), "kr_adam_step")
 
@@ -189,6 +219,8 @@ class NativeDDPGfDUpdate:
         """the actor's Adam step for the update counted by `step`; TD3fD: on every policy_freq-th update only, numbered step / policy_freq"""
         if not self.td3:
             return self._adam(self.actor, self.hyper_a, step=step)
+        if self.max_grad_norm is not None:
+            return self._adam_clipped(self.actor, self.hyper_a, step, self.p.policy_freq, 0)
         lr, b1, b2, eps, wd = self.hyper_a
         net, P = self.actor, _sim._ptr
         self._chk(self.lib.kr_adam_step_every(net.flat.numel(), P(net.flat), P(net.grad), P(net.exp_avg), P(net.exp_avg_sq), P(step),
@@ -280,8 +312,9 @@ class NativeDDPGfDUpdate:
         the batch's `picked` bound; None: the launch sequence has no such step.
         With a TD3fD policy: the target actor's forward, kr_target_smooth on its output, both target critics on the smoothed action, both
         critics' forward, ONE kr_twin_critic_grad, the backward and weight-gradient passes once per critic; returns six losses and
-        `priorities` receives (q1, tmin, reward, weight).  target_noise [2R, 4]: the smoothing's N(0, 1) draws; None: the in-kernel stream
-        keyed by (self.seed, self.it)."""
+        `priorities` receives (q1, tmin, reward, weight).  With q_bounds or huber_delta set: ONE kr_critic_grad_bounded in place of either
+        loss-gradient launch, and `priorities` receives (q, tboot, reward, weight), the clamped bootstrap.
+        target_noise [2R, 4]: the smoothing's N(0, 1) draws; None: the in-kernel stream keyed by (self.seed, self.it)."""
         pol, P = self.p, _sim._ptr
         R = reward.shape[0]
         if weight is None:
@@ -332,8 +365,13 @@ class NativeDDPGfDUpdate:
             (q, saved), (q2, saved2) = self._critic_forward(c, state, action), self._critic_forward(c2, state, action)
             dq, dq2, tmin = torch.empty_like(q), torch.empty_like(q2), q.new_empty(2 * R)
             reward = reward.contiguous()
-            self._chk(self.lib.kr_twin_critic_grad(R, pol.n, P(q), P(q2), P(tq), P(tq2), P(tq[R:]), P(tq2[R:]), P(reward), P(weight), P(self.wsum),
-                                                   pol.discount, P(dq), P(dq2), P(tmin), P(self.losses), self._st()), "kr_twin_critic_grad")
+            if self.bounded:
+                self._chk(self.lib.kr_critic_grad_bounded(R, pol.n, P(q), P(q2), P(tq), P(tq2), P(tq[R:]), P(tq2[R:]), P(reward), P(weight), P(self.wsum),
+                                                          pol.discount, self.q_lo, self.q_hi, self.huber_delta, P(dq), P(dq2), P(tmin), P(self.losses),
+                                                          self._st()), "kr_critic_grad_bounded")
+            else:
+                self._chk(self.lib.kr_twin_critic_grad(R, pol.n, P(q), P(q2), P(tq), P(tq2), P(tq[R:]), P(tq2[R:]), P(reward), P(weight), P(self.wsum),
+                                                       pol.discount, P(dq), P(dq2), P(tmin), P(self.losses), self._st()), "kr_twin_critic_grad")
             if priorities is not None:
                 priorities(q, tmin, reward, weight)          # the target the update used
             self._critic_backward(c, dq, saved)
@@ -343,6 +381,15 @@ class NativeDDPGfDUpdate:
         q, saved = self._critic_forward(c, state, action)
         dq = torch.empty_like(q)
         reward = reward.contiguous()
+        if self.bounded:
+            tboot = q.new_empty(2 * R)
+            self._chk(self.lib.kr_critic_grad_bounded(R, pol.n, P(q), None, P(tq), None, P(tq[R:]), None, P(reward), P(weight), P(self.wsum), pol.discount,
+                                                      self.q_lo, self.q_hi, self.huber_delta, P(dq), None, P(tboot), P(self.losses), self._st()),
+                      "kr_critic_grad_bounded")
+            if priorities is not None:
+                priorities(q, tboot, reward, weight)             # the bootstrap the update used
+            self._critic_backward(c, dq, saved)
+            return self.losses[0], self.losses[1], self.losses[2]
         self._chk(self.lib.kr_critic_grad(R, pol.n, P(q), P(tq), P(tq[R:]), P(reward), P(weight), P(self.wsum), pol.discount, P(dq), P(self.losses),
                                           self._st()), "kr_critic_grad")
         if priorities is not None:
