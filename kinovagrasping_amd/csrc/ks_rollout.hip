@@ -842,72 +842,12 @@ __device__ __forceinline__ float wave_sum(float x) {
     return x;
 }
 
-__global__ __launch_bounds__(WAVE) void k_critic_grad(int R, int n, const float* __restrict__ q, const float* __restrict__ tq1,
-                                                      const float* __restrict__ tqn, const float* __restrict__ reward,
-                                                      const float* __restrict__ weight, const float* __restrict__ wsum, float discount,
-                                                      float* __restrict__ dq, float* losses) {
-#pragma clang fp contract(off)
-    // single wave: the batch is a few thousand rows; the masked means are wave reductions
-    const float inv = wsum[0] > 0.0f ? 1.0f / wsum[0] : 0.0f;     // an all-padding batch (empty replay) has zero loss and gradient
-    float l1 = 0, ln = 0;
-    for (int r = threadIdx.x; r < R; r += WAVE) {
-        const float t1 = reward[(long)r * n] + discount * tq1[r];
-        float ret = 0, g = 1.0f;
-        for (int i = 0; i < n; i++) { ret += g * reward[(long)r * n + i]; g *= discount; }
-        const float tn = ret + g * tqn[r];
-        const float w = weight ? weight[r] : 1.0f, e1 = q[r] - t1, en = q[r] - tn;
-        l1 += w * e1 * e1;
-        ln += w * en * en;
-        dq[r] = w * inv * (2.0f * e1 + 0.5f * 2.0f * en);
-    }
-    l1 = wave_sum(l1);
-    ln = wave_sum(ln);
-    if (threadIdx.x == 0) { losses[1] = l1 * inv; losses[2] = ln * inv; losses[0] = l1 * inv + 0.5f * (ln * inv); }
-}
-
 // TD3's clipped double-Q minimum; NaN if either operand is NaN (a diverged critic stays visible)
 __device__ __forceinline__ float nan_min(float a, float b) { return a != a ? a : (b != b ? b : (b < a ? b : a)); }
 
-// k_critic_grad for two critics on the minimum of two target critics: the same expressions in the same order per critic
-__global__ __launch_bounds__(WAVE) void k_twin_critic_grad(int R, int n, const float* __restrict__ q1, const float* __restrict__ q2,
-                                                           const float* __restrict__ tq1_a, const float* __restrict__ tq1_b,
-                                                           const float* __restrict__ tqn_a, const float* __restrict__ tqn_b,
-                                                           const float* __restrict__ reward, const float* __restrict__ weight,
-                                                           const float* __restrict__ wsum, float discount, float* __restrict__ dq1,
-                                                           float* __restrict__ dq2, float* __restrict__ tmin, float* losses) {
-#pragma clang fp contract(off)
-    const float inv = wsum[0] > 0.0f ? 1.0f / wsum[0] : 0.0f;
-    float l1a = 0, lna = 0, l1b = 0, lnb = 0;
-    for (int r = threadIdx.x; r < R; r += WAVE) {
-        const float m1 = nan_min(tq1_a[r], tq1_b[r]), mn = nan_min(tqn_a[r], tqn_b[r]);
-        tmin[r] = m1;
-        tmin[(long)R + r] = mn;
-        const float t1 = reward[(long)r * n] + discount * m1;
-        float ret = 0, g = 1.0f;
-        for (int i = 0; i < n; i++) { ret += g * reward[(long)r * n + i]; g *= discount; }
-        const float tn = ret + g * mn;
-        const float w = weight ? weight[r] : 1.0f;
-        const float e1a = q1[r] - t1, ena = q1[r] - tn, e1b = q2[r] - t1, enb = q2[r] - tn;
-        l1a += w * e1a * e1a;
-        lna += w * ena * ena;
-        l1b += w * e1b * e1b;
-        lnb += w * enb * enb;
-        dq1[r] = w * inv * (2.0f * e1a + 0.5f * 2.0f * ena);
-        dq2[r] = w * inv * (2.0f * e1b + 0.5f * 2.0f * enb);
-    }
-    l1a = wave_sum(l1a);
-    lna = wave_sum(lna);
-    l1b = wave_sum(l1b);
-    lnb = wave_sum(lnb);
-    if (threadIdx.x == 0) {
-        losses[1] = l1a * inv; losses[2] = lna * inv; losses[0] = l1a * inv + 0.5f * (lna * inv);
-        losses[4] = l1b * inv; losses[5] = lnb * inv; losses[3] = l1b * inv + 0.5f * (lnb * inv);
-    }
-}
-
-// The bounded critic update (kr_critic_grad_bounded): the bootstrapped value clamped to [lo, hi] - a NaN fails both comparisons and passes -
-// and the loss shaped as twice the Huber function: rho(e) = e^2 where not |e| > d, d (2 |e| - d) otherwise, whose derivative is
-// 2 clamp(e, -d, d).  The square branch is k_critic_grad's own term in its order, so infinite bounds and an infinite d give its bits.
+// The bounded critic update: the bootstrapped value clamped to [lo, hi] - a NaN fails both comparisons and passes - and the loss shaped as
+// twice the Huber function: rho(e) = e^2 where not |e| > d, d (2 |e| - d) otherwise, whose derivative is 2 clamp(e, -d, d).  The square
+// branch is the unbounded term in its order, so infinite bounds and an infinite d give the unbounded update's bits.
 __device__ __forceinline__ float bound_q(float m, float lo, float hi) { return m < lo ? lo : (m > hi ? hi : m); }
 __device__ __forceinline__ float huber_clip(float e, float d) { return fabsf(e) > d ? (e < 0.0f ? -d : d) : e; }
 __device__ __forceinline__ float huber_term(float w, float e, float d) {
@@ -916,48 +856,63 @@ __device__ __forceinline__ float huber_term(float w, float e, float d) {
     return a > d ? w * (d * (2.0f * a - d)) : w * e * e;
 }
 
-// k_critic_grad (TWIN = false: q2, tq1_b, tqn_b, dq2 unused, three losses) and k_twin_critic_grad (TWIN = true, six) on the clamped bootstrap
-template <bool TWIN>
-__global__ __launch_bounds__(WAVE) void k_critic_grad_bounded(int R, int n, const float* __restrict__ q1, const float* __restrict__ q2,
-                                                              const float* __restrict__ tq1_a, const float* __restrict__ tq1_b,
-                                                              const float* __restrict__ tqn_a, const float* __restrict__ tqn_b,
-                                                              const float* __restrict__ reward, const float* __restrict__ weight,
-                                                              const float* __restrict__ wsum, float discount, float lo, float hi, float delta,
-                                                              float* __restrict__ dq1, float* __restrict__ dq2, float* __restrict__ tboot,
-                                                              float* losses) {
+// one critic's share of a row: its 1-step and n-step errors into the loss sums; returns dLoss/dQ of L1 + 0.5 LN
+template <bool BOUNDED>
+__device__ __forceinline__ float td_row(float q, float t1, float tn, float w, float inv, float d, float& l1, float& ln) {
 #pragma clang fp contract(off)
-    const float inv = wsum[0] > 0.0f ? 1.0f / wsum[0] : 0.0f;
+    const float e1 = q - t1, en = q - tn;
+    if constexpr (BOUNDED) {
+        l1 += huber_term(w, e1, d);
+        ln += huber_term(w, en, d);
+        return w * inv * (2.0f * huber_clip(e1, d) + 0.5f * 2.0f * huber_clip(en, d));
+    } else {
+        l1 += w * e1 * e1;
+        ln += w * en * en;
+        return w * inv * (2.0f * e1 + 0.5f * 2.0f * en);
+    }
+}
+
+// (critic loss, L1, LN) of one critic from its summed terms
+__device__ __forceinline__ void loss_triple(float l1, float ln, float inv, float* out) {
+#pragma clang fp contract(off)
+    out[1] = l1 * inv; out[2] = ln * inv; out[0] = l1 * inv + 0.5f * (ln * inv);
+}
+
+// Targets and critic loss gradient, the one body of kr_critic_grad <false, false>, kr_twin_critic_grad <true, false> and
+// kr_critic_grad_bounded <TWIN, true>.  Per row: the bootstrap pair (1-step, n-step) is the target critic's, with TWIN the nan_min of the
+// two target critics', with BOUNDED then clamped, and where it is not simply tq1_a / tqn_a it is written to tboot [2R] for the priorities;
+// t1 and tn from it; each critic's td_row.  Unused with TWIN = false: q2, tq1_b, tqn_b, dq2, losses[3..5]; with BOUNDED = false: lo, hi,
+// delta; with neither: tboot.  A single wave: the batch is a few thousand rows; the masked means are wave reductions.
+template <bool TWIN, bool BOUNDED>
+__global__ __launch_bounds__(WAVE) void k_critic_grad(int R, int n, const float* __restrict__ q1, const float* __restrict__ q2,
+                                                      const float* __restrict__ tq1_a, const float* __restrict__ tq1_b,
+                                                      const float* __restrict__ tqn_a, const float* __restrict__ tqn_b,
+                                                      const float* __restrict__ reward, const float* __restrict__ weight,
+                                                      const float* __restrict__ wsum, float discount, float lo, float hi, float delta,
+                                                      float* __restrict__ dq1, float* __restrict__ dq2, float* __restrict__ tboot,
+                                                      float* losses) {
+#pragma clang fp contract(off)
+    const float inv = wsum[0] > 0.0f ? 1.0f / wsum[0] : 0.0f;     // an all-padding batch (empty replay) has zero loss and gradient
     float l1a = 0, lna = 0, l1b = 0, lnb = 0;
     for (int r = threadIdx.x; r < R; r += WAVE) {
-        const float m1 = TWIN ? nan_min(tq1_a[r], tq1_b[r]) : tq1_a[r], mn = TWIN ? nan_min(tqn_a[r], tqn_b[r]) : tqn_a[r];
-        const float b1 = bound_q(m1, lo, hi), bn = bound_q(mn, lo, hi);
-        tboot[r] = b1;
-        tboot[(long)R + r] = bn;
+        float b1 = tq1_a[r], bn = tqn_a[r];
+        if constexpr (TWIN) { b1 = nan_min(b1, tq1_b[r]); bn = nan_min(bn, tqn_b[r]); }
+        if constexpr (BOUNDED) { b1 = bound_q(b1, lo, hi); bn = bound_q(bn, lo, hi); }
+        if constexpr (TWIN || BOUNDED) { tboot[r] = b1; tboot[(long)R + r] = bn; }
         const float t1 = reward[(long)r * n] + discount * b1;
         float ret = 0, g = 1.0f;
         for (int i = 0; i < n; i++) { ret += g * reward[(long)r * n + i]; g *= discount; }
         const float tn = ret + g * bn;
         const float w = weight ? weight[r] : 1.0f;
-        const float e1a = q1[r] - t1, ena = q1[r] - tn;
-        l1a += huber_term(w, e1a, delta);
-        lna += huber_term(w, ena, delta);
-        dq1[r] = w * inv * (2.0f * huber_clip(e1a, delta) + 0.5f * 2.0f * huber_clip(ena, delta));
-        if (TWIN) {
-            const float e1b = q2[r] - t1, enb = q2[r] - tn;
-            l1b += huber_term(w, e1b, delta);
-            lnb += huber_term(w, enb, delta);
-            dq2[r] = w * inv * (2.0f * huber_clip(e1b, delta) + 0.5f * 2.0f * huber_clip(enb, delta));
-        }
+        dq1[r] = td_row<BOUNDED>(q1[r], t1, tn, w, inv, delta, l1a, lna);
+        if constexpr (TWIN) dq2[r] = td_row<BOUNDED>(q2[r], t1, tn, w, inv, delta, l1b, lnb);
     }
     l1a = wave_sum(l1a);
     lna = wave_sum(lna);
-    if (TWIN) {
-        l1b = wave_sum(l1b);
-        lnb = wave_sum(lnb);
-    }
+    if constexpr (TWIN) { l1b = wave_sum(l1b); lnb = wave_sum(lnb); }
     if (threadIdx.x == 0) {
-        losses[1] = l1a * inv; losses[2] = lna * inv; losses[0] = l1a * inv + 0.5f * (lna * inv);
-        if (TWIN) { losses[4] = l1b * inv; losses[5] = lnb * inv; losses[3] = l1b * inv + 0.5f * (lnb * inv); }
+        loss_triple(l1a, lna, inv, losses);
+        if constexpr (TWIN) loss_triple(l1b, lnb, inv, losses + 3);
     }
 }
 
@@ -1044,12 +999,19 @@ __global__ __launch_bounds__(256) void k_adam_step(long count, float* __restrict
 }
 
 // TD3's delayed actor: the step of every `every`-th update, numbered step / every; nothing is touched on the others
+template <bool CLIP = false>
+__device__ __forceinline__ void adam_apply_every(long count, float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                 float* __restrict__ v, const int64_t* __restrict__ step, int every, float lr, float b1,
+                                                 float b2, float eps, float wd, float coef = 1.0f) {
+    const int64_t s = step[0];
+    if (s <= 0 || s % every != 0) return;
+    adam_apply<CLIP>(count, p, g, m, v, (float)(s / every), lr, b1, b2, eps, wd, coef);
+}
+
 __global__ __launch_bounds__(256) void k_adam_step_every(long count, float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                          float* __restrict__ v, const int64_t* __restrict__ step, int every, float lr, float b1,
                                                          float b2, float eps, float wd) {
-    const int64_t s = step[0];
-    if (s <= 0 || s % every != 0) return;
-    adam_apply(count, p, g, m, v, (float)(s / every), lr, b1, b2, eps, wd);
+    adam_apply_every(count, p, g, m, v, step, every, lr, b1, b2, eps, wd);
 }
 
 // Global gradient-norm clip (torch.nn.utils.clip_grad_norm_), two launches.  The squared norm: KR_NORM_PARTS workgroups of one wave, lane l of
@@ -1088,9 +1050,7 @@ __global__ __launch_bounds__(256) void k_adam_step_clipped(long count, float* __
     float coef = max_norm / (norm + 1e-6f);
     coef = coef > 1.0f ? 1.0f : coef;                     // (a NaN stays NaN, as with torch.clamp(max=1))
     if (clip_out && blockIdx.x == 0 && threadIdx.x == 0) { clip_out[0] = norm; clip_out[1] = coef; }
-    const int64_t s = step[0];
-    if (s <= 0 || s % every != 0) return;
-    adam_apply<true>(count, p, g, m, v, (float)(s / every), lr, b1, b2, eps, wd, coef);
+    adam_apply_every<true>(count, p, g, m, v, step, every, lr, b1, b2, eps, wd, coef);
 }
 
 __global__ __launch_bounds__(256) void k_soft_update(long count, const float* __restrict__ p, float* __restrict__ tp, float tau,
@@ -1342,12 +1302,47 @@ int kr_update_priorities(int32_t batch, int32_t batch_agent, int32_t horizon, in
     return launched();
 }
 
+// The one launch path of kr_critic_grad / kr_twin_critic_grad / kr_critic_grad_bounded.  twin: two critics on two target critics - q2, tq1_b,
+// tqn_b and dq2 are all there or all absent; tboot [2R] is there exactly when the kernel writes it (twin or bounded).
+static int critic_grad_launch(bool twin, bool bounded, int32_t rows, int32_t n_steps, const float* q1, const float* q2, const float* tq1_a,
+                              const float* tq1_b, const float* tqn_a, const float* tqn_b, const float* reward, const float* weight,
+                              const float* weight_sum, float discount, float q_lo, float q_hi, float huber_delta, float* dq1, float* dq2,
+                              float* tboot, float* losses, void* stream) {
+    if (rows <= 0 || n_steps <= 0 || !q1 || !tq1_a || !tqn_a || !reward || !weight_sum || !dq1 || !losses) return KS_ERR_INVALID;
+    if ((q2 != nullptr) != twin || (dq2 != nullptr) != twin || (tq1_b != nullptr) != twin || (tqn_b != nullptr) != twin) return KS_ERR_INVALID;
+    if ((tboot != nullptr) != (twin || bounded)) return KS_ERR_INVALID;
+    if (bounded && (!(q_lo <= q_hi) || !(huber_delta > 0.0f))) return KS_ERR_INVALID;          // (a NaN fails either comparison)
+    const auto kernel = twin ? (bounded ? k_critic_grad<true, true> : k_critic_grad<true, false>)
+                             : (bounded ? k_critic_grad<false, true> : k_critic_grad<false, false>);
+    hipLaunchKernelGGL(kernel, dim3(1), dim3(WAVE), 0, (hipStream_t)stream, rows, n_steps, q1, q2, tq1_a, tq1_b, tqn_a, tqn_b, reward, weight, weight_sum,
+                       discount, q_lo, q_hi, huber_delta, dq1, dq2, tboot, losses);
+    return launched();
+}
+
+// ... and of kr_adam_step / kr_adam_step_every / kr_adam_step_clipped (every and partials / max_norm / clip_out: of the forms that have them)
+enum AdamForm { ADAM_PLAIN, ADAM_EVERY, ADAM_CLIPPED };
+static int adam_launch(AdamForm form, int64_t count, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, const int64_t* step,
+                       int32_t every, const double* partials, float max_norm, float lr, float beta1, float beta2, float eps, float weight_decay,
+                       float* clip_out, void* stream) {
+    if (count <= 0 || every <= 0 || !param || !grad || !exp_avg || !exp_avg_sq || !step) return KS_ERR_INVALID;
+    if (form == ADAM_CLIPPED && (!partials || !(max_norm > 0.0f))) return KS_ERR_INVALID;
+    const dim3 grid(grid_for(count)), block(256);
+    const hipStream_t st = (hipStream_t)stream;
+    const long n = (long)count;
+    if (form == ADAM_PLAIN)
+        hipLaunchKernelGGL(k_adam_step, grid, block, 0, st, n, param, grad, exp_avg, exp_avg_sq, step, lr, beta1, beta2, eps, weight_decay);
+    else if (form == ADAM_EVERY)
+        hipLaunchKernelGGL(k_adam_step_every, grid, block, 0, st, n, param, grad, exp_avg, exp_avg_sq, step, every, lr, beta1, beta2, eps, weight_decay);
+    else
+        hipLaunchKernelGGL(k_adam_step_clipped, grid, block, 0, st, n, param, grad, exp_avg, exp_avg_sq, step, every, partials, max_norm, lr, beta1, beta2,
+                           eps, weight_decay, clip_out);
+    return launched();
+}
+
 int kr_critic_grad(int32_t rows, int32_t n_steps, const float* q, const float* tq1, const float* tqn, const float* reward, const float* weight,
                    const float* weight_sum, float discount, float* dq, float* losses, void* stream) {
-    if (rows <= 0 || n_steps <= 0 || !q || !tq1 || !tqn || !reward || !weight_sum || !dq || !losses) return KS_ERR_INVALID;
-    hipLaunchKernelGGL(k_critic_grad, dim3(1), dim3(WAVE), 0, (hipStream_t)stream, rows, n_steps, q, tq1, tqn, reward, weight, weight_sum, discount, dq,
-                       losses);
-    return launched();
+    return critic_grad_launch(false, false, rows, n_steps, q, nullptr, tq1, nullptr, tqn, nullptr, reward, weight, weight_sum, discount, 0.0f, 0.0f, 0.0f,
+                              dq, nullptr, nullptr, losses, stream);
 }
 
 int kr_update_prologue(int32_t rows, int32_t n_steps, const float* weight, float* weight_sum, float* dq_actor, int64_t* it, int64_t* it_head,
@@ -1371,28 +1366,19 @@ int kr_sigmoid_scale_backward(int64_t count, const float* a, float max_action, f
 
 int kr_adam_step(int64_t count, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, const int64_t* step, float lr, float beta1,
                  float beta2, float eps, float weight_decay, void* stream) {
-    if (count <= 0 || !param || !grad || !exp_avg || !exp_avg_sq || !step) return KS_ERR_INVALID;
-    hipLaunchKernelGGL(k_adam_step, dim3(grid_for(count)), dim3(256), 0, (hipStream_t)stream, (long)count, param, grad, exp_avg, exp_avg_sq, step, lr,
-                       beta1, beta2, eps, weight_decay);
-    return launched();
+    return adam_launch(ADAM_PLAIN, count, param, grad, exp_avg, exp_avg_sq, step, 1, nullptr, 0.0f, lr, beta1, beta2, eps, weight_decay, nullptr, stream);
 }
 
 int kr_adam_step_every(int64_t count, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, const int64_t* step, int32_t every,
                        float lr, float beta1, float beta2, float eps, float weight_decay, void* stream) {
-    if (count <= 0 || every <= 0 || !param || !grad || !exp_avg || !exp_avg_sq || !step) return KS_ERR_INVALID;
-    hipLaunchKernelGGL(k_adam_step_every, dim3(grid_for(count)), dim3(256), 0, (hipStream_t)stream, (long)count, param, grad, exp_avg, exp_avg_sq, step,
-                       every, lr, beta1, beta2, eps, weight_decay);
-    return launched();
+    return adam_launch(ADAM_EVERY, count, param, grad, exp_avg, exp_avg_sq, step, every, nullptr, 0.0f, lr, beta1, beta2, eps, weight_decay, nullptr, stream);
 }
 
 int kr_twin_critic_grad(int32_t rows, int32_t n_steps, const float* q1, const float* q2, const float* tq1_a, const float* tq1_b, const float* tqn_a,
                         const float* tqn_b, const float* reward, const float* weight, const float* weight_sum, float discount, float* dq1, float* dq2,
                         float* tmin, float* losses, void* stream) {
-    if (rows <= 0 || n_steps <= 0 || !q1 || !q2 || !tq1_a || !tq1_b || !tqn_a || !tqn_b || !reward || !weight_sum || !dq1 || !dq2 || !tmin || !losses)
-        return KS_ERR_INVALID;
-    hipLaunchKernelGGL(k_twin_critic_grad, dim3(1), dim3(WAVE), 0, (hipStream_t)stream, rows, n_steps, q1, q2, tq1_a, tq1_b, tqn_a, tqn_b, reward, weight,
-                       weight_sum, discount, dq1, dq2, tmin, losses);
-    return launched();
+    return critic_grad_launch(true, false, rows, n_steps, q1, q2, tq1_a, tq1_b, tqn_a, tqn_b, reward, weight, weight_sum, discount, 0.0f, 0.0f, 0.0f, dq1,
+                              dq2, tmin, losses, stream);
 }
 
 int kr_target_smooth(int32_t rows, float* action, const float* noise, uint64_t seed, const int64_t* draw, float sigma, float clip, float max_action,
@@ -1408,17 +1394,8 @@ int kr_target_smooth(int32_t rows, float* action, const float* noise, uint64_t s
 int kr_critic_grad_bounded(int32_t rows, int32_t n_steps, const float* q1, const float* q2, const float* tq1_a, const float* tq1_b, const float* tqn_a,
                            const float* tqn_b, const float* reward, const float* weight, const float* weight_sum, float discount, float q_lo, float q_hi,
                            float huber_delta, float* dq1, float* dq2, float* tboot, float* losses, void* stream) {
-    if (rows <= 0 || n_steps <= 0 || !q1 || !tq1_a || !tqn_a || !reward || !weight_sum || !dq1 || !tboot || !losses) return KS_ERR_INVALID;
-    const bool twin = q2 != nullptr;
-    if ((dq2 != nullptr) != twin || (tq1_b != nullptr) != twin || (tqn_b != nullptr) != twin) return KS_ERR_INVALID;
-    if (!(q_lo <= q_hi) || !(huber_delta > 0.0f)) return KS_ERR_INVALID;                       // (a NaN fails either comparison)
-    if (twin)
-        hipLaunchKernelGGL(k_critic_grad_bounded<true>, dim3(1), dim3(WAVE), 0, (hipStream_t)stream, rows, n_steps, q1, q2, tq1_a, tq1_b, tqn_a, tqn_b,
-                           reward, weight, weight_sum, discount, q_lo, q_hi, huber_delta, dq1, dq2, tboot, losses);
-    else
-        hipLaunchKernelGGL(k_critic_grad_bounded<false>, dim3(1), dim3(WAVE), 0, (hipStream_t)stream, rows, n_steps, q1, q2, tq1_a, tq1_b, tqn_a, tqn_b,
-                           reward, weight, weight_sum, discount, q_lo, q_hi, huber_delta, dq1, dq2, tboot, losses);
-    return launched();
+    return critic_grad_launch(q2 != nullptr, true, rows, n_steps, q1, q2, tq1_a, tq1_b, tqn_a, tqn_b, reward, weight, weight_sum, discount, q_lo, q_hi,
+                              huber_delta, dq1, dq2, tboot, losses, stream);
 }
 
 int kr_grad_sqnorm(int64_t count, const float* grad, double* partials, void* stream) {
@@ -1430,10 +1407,8 @@ int kr_grad_sqnorm(int64_t count, const float* grad, double* partials, void* str
 int kr_adam_step_clipped(int64_t count, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, const int64_t* step, int32_t every,
                          const double* partials, float max_norm, float lr, float beta1, float beta2, float eps, float weight_decay, float* clip_out,
                          void* stream) {
-    if (count <= 0 || every <= 0 || !param || !grad || !exp_avg || !exp_avg_sq || !step || !partials || !(max_norm > 0.0f)) return KS_ERR_INVALID;
-    hipLaunchKernelGGL(k_adam_step_clipped, dim3(grid_for(count)), dim3(256), 0, (hipStream_t)stream, (long)count, param, grad, exp_avg, exp_avg_sq, step,
-                       every, partials, max_norm, lr, beta1, beta2, eps, weight_decay, clip_out);
-    return launched();
+    return adam_launch(ADAM_CLIPPED, count, param, grad, exp_avg, exp_avg_sq, step, every, partials, max_norm, lr, beta1, beta2, eps, weight_decay,
+                       clip_out, stream);
 }
 
 int kr_soft_update(int64_t count, const float* param, float* target, float tau, const int64_t* it, int32_t freq, void* stream) {

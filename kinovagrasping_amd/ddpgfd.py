@@ -197,24 +197,39 @@ class DDPGfD:
         if self.max_grad_norm is not None:
             torch.nn.utils.clip_grad_norm_(module.parameters(), self.max_grad_norm)
 
-    def phase_critic(self, state, action, next_state, reward, weight=None):
-        """targets + critic loss + backward (DDPGfD.py:256-330).  Returns (critic, L1, LN) losses."""
+    def _bootstrap(self, nx, target_noise=None):
+        """the target critic's value of the target actor's action at the states nx (before q_bounds)"""
+        if target_noise is not None:
+            raise ValueError("DDPGfD has no target smoothing: target_noise belongs to TD3fD")
+        return self.critic_target(nx, self.actor_target(nx))
+
+    def _critics(self):
+        """the (critic, optimizer) pairs phase_critic trains on the common targets"""
+        return ((self.critic, self.critic_optimizer),)
+
+    def phase_critic(self, state, action, next_state, reward, weight=None, target_noise=None):
+        """targets + critic loss + backward (DDPGfD.py:256-330).  Returns (critic, L1, LN) losses, per critic of _critics()."""
         reward = reward.unsqueeze(-1)
         with torch.no_grad():
             # both target evaluations (1-step: next_state[:, 0], n-step: next_state[:, -1]) in one pass of the target nets
             R = reward.shape[0]
             nx = torch.cat([next_state[:, 0], next_state[:, -1]], 0)
-            tq = self._bound(self.critic_target(nx, self.actor_target(nx)))
+            tq = self._bound(self._bootstrap(nx, target_noise))
             target_Q = reward[:, 0] + self.discount * tq[:R]
             n_step_return = (reward.squeeze(-1) * self._disc).sum(1)
             target_QN = (n_step_return + (self.discount ** self.n) * tq[R:].squeeze(-1)).unsqueeze(-1)
-        current_Q = self.critic(state[:, 0], action[:, 0])
-        critic_L1 = self._mean(self._rho(current_Q - target_Q), 1, weight)
-        critic_LN = self._mean(self._rho(current_Q - target_QN), 1, weight)
-        critic_loss = critic_L1 + 0.5 * critic_LN
-        self.critic_optimizer.zero_grad()
-        critic_loss.backward()
-        return critic_loss.detach(), critic_L1.detach(), critic_LN.detach()
+        out, total = (), None
+        for critic, _ in self._critics():
+            current_Q = critic(state[:, 0], action[:, 0])
+            L1 = self._mean(self._rho(current_Q - target_Q), 1, weight)
+            LN = self._mean(self._rho(current_Q - target_QN), 1, weight)
+            loss = L1 + 0.5 * LN
+            total = loss if total is None else total + loss
+            out += (loss.detach(), L1.detach(), LN.detach())
+        for _, optimizer in self._critics():
+            optimizer.zero_grad()
+        total.backward()
+        return out
 
     def phase_actor(self, state, weight=None):
         """critic step, then actor loss + backward (DDPGfD.py:331-352)"""
@@ -337,32 +352,16 @@ class TD3fD(DDPGfD):
         self.phase_targets()
         return (actor_loss,) + losses_c
 
-    def phase_critic(self, state, action, next_state, reward, weight=None, target_noise=None):
-        """smoothed target actions, the twin targets' minimum, both critics' losses + backward.  Returns (critic, L1, LN) of critic 1, then
-        of critic 2."""
-        reward = reward.unsqueeze(-1)
-        with torch.no_grad():
-            R = reward.shape[0]
-            nx = torch.cat([next_state[:, 0], next_state[:, -1]], 0)
-            a = self.actor_target(nx)
-            z = torch.randn_like(a) if target_noise is None else target_noise
-            ta = (a + (self.policy_noise * z).clamp(-self.noise_clip, self.noise_clip)).clamp(0, self.max_action)
-            tq = self._bound(torch.min(self.critic_target(nx, ta), self.critic2_target(nx, ta)))      # the clamp after the minimum
-            target_Q = reward[:, 0] + self.discount * tq[:R]
-            n_step_return = (reward.squeeze(-1) * self._disc).sum(1)
-            target_QN = (n_step_return + (self.discount ** self.n) * tq[R:].squeeze(-1)).unsqueeze(-1)
-        out, total = (), None
-        for critic in (self.critic, self.critic2):
-            current_Q = critic(state[:, 0], action[:, 0])
-            L1 = self._mean(self._rho(current_Q - target_Q), 1, weight)
-            LN = self._mean(self._rho(current_Q - target_QN), 1, weight)
-            loss = L1 + 0.5 * LN
-            total = loss if total is None else total + loss
-            out += (loss.detach(), L1.detach(), LN.detach())
-        self.critic_optimizer.zero_grad()
-        self.critic2_optimizer.zero_grad()
-        total.backward()
-        return out
+    # DDPGfD.phase_critic with these two: smoothed target actions, the twin targets' minimum (q_bounds clamps after it), both critics'
+    # losses summed before one backward().  It returns (critic, L1, LN) of critic 1, then of critic 2.
+    def _bootstrap(self, nx, target_noise=None):
+        a = self.actor_target(nx)
+        z = torch.randn_like(a) if target_noise is None else target_noise
+        ta = (a + (self.policy_noise * z).clamp(-self.noise_clip, self.noise_clip)).clamp(0, self.max_action)
+        return torch.min(self.critic_target(nx, ta), self.critic2_target(nx, ta))
+
+    def _critics(self):
+        return ((self.critic, self.critic_optimizer), (self.critic2, self.critic2_optimizer))
 
     def phase_actor(self, state, weight=None):
         """both critics' steps, then the actor loss through critic 1 + backward"""

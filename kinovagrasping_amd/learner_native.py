@@ -17,21 +17,22 @@
   GEMMs straight into one flat gradient buffer per network; the forward-only target networks and the critic forward
   still go through the fused LDS kernel (kr_mlp3_forward) when the width has an instantiation.  ~75 launches.
 
-With a ddpgfd.TD3fD policy the same three forms run TD3fD: the target actor's output is smoothed in place (kr_target_smooth, in-kernel
-Philox noise keyed by the update count), both target critics and both critics run the passes above, ONE kr_twin_critic_grad forms the
-targets from the target critics' minimum and both loss gradients, and the actor's Adam step is kr_adam_step_every (every
-policy_freq-th update).  A DDPGfD policy's launch sequence is what it was.
+Common to the three: one sequence of phases over the policy's critics - one for ddpgfd.DDPGfD, two for ddpgfd.TD3fD, whose target
+actor's output is first smoothed in place (kr_target_smooth, in-kernel Philox noise keyed by the update count) - with ONE launch for the
+targets and every critic's loss gradient (_loss_grad), one Adam launch per network (_adam) and one soft target update each
+(kr_soft_update).  Which entry point a launch is follows from the policy alone, and each keeps the launch sequence and bits of the others
+where they coincide:
 
-With q_bounds / huber_delta / max_grad_norm set on the policy (ddpgfd.DDPGfD and TD3fD, all None by default) the update is bounded: ONE
-kr_critic_grad_bounded takes the place of kr_critic_grad / kr_twin_critic_grad - the bootstrapped value clamped to q_bounds, the TD loss
-Huber-shaped, the unset one of the two passed as its infinite value - and hands the priorities the bootstrap it used (tboot); with
-max_grad_norm every Adam launch becomes kr_grad_sqnorm (64 fp64 partial sums of the flat gradient buffer, no atomics) + kr_adam_step_clipped
-(clip_grad_norm_'s coefficient from them, then the step on g * coef; `every` is 1 for the critics and policy_freq for TD3fD's actor), and
-self.clip [3, 2] holds the (norm, coef) of actor, critic and critic2.  In the pipelined form the actor's norm is taken at the head, on the
-gradient buffer the body left.  All LDS-free, in all three forms; with the three unset the launch sequence is what it was.
+* the loss gradient: kr_critic_grad for one critic, kr_twin_critic_grad (the bootstrap is the target critics' minimum) for two,
+  kr_critic_grad_bounded for either when q_bounds or huber_delta is set on the policy (both None by default) - the bootstrapped value
+  clamped to q_bounds, the TD loss Huber-shaped, the unset one of the two passed as its infinite value.  The priorities are handed the
+  bootstrap the launch used: the target critic's own, or the [2R] minimum / clamped one it wrote;
+* Adam: kr_adam_step; for TD3fD's delayed actor kr_adam_step_every (every policy_freq-th update); with max_grad_norm set (None by
+  default) kr_grad_sqnorm (64 fp64 partial sums of the flat gradient buffer, no atomics) + kr_adam_step_clipped (clip_grad_norm_'s
+  coefficient from them, then the step on g * coef; `every` is 1 but for TD3fD's actor), self.clip [3, 2] holding the (norm, coef) of
+  actor, critic and critic2.  In the pipelined form the actor's norm is taken at the head, on the gradient buffer the body left.
 
-Common to both: targets + critic loss gradient, Adam and the soft target update are one kernel each (kr_critic_grad,
-kr_adam_step, kr_soft_update); with world_size > 1 the flat gradient buffers are all-reduced directly (no pack /
+All of these are LDS-free.  With world_size > 1 the flat gradient buffers are all-reduced directly (no pack /
 unpack).  Same arithmetic as the reference (critic loss L1 + 0.5 LN on masked row means, actor loss -mean Q(s, pi(s))
 over all n-step rows, Adam lr 1e-4 / default lr + weight_decay 1e-4, soft target update every 10th call);
 tests/test_gpu_parity.py checks both forms against the autograd implementation (ddpgfd.DDPGfD.train_on_batch).  The
@@ -40,6 +41,7 @@ exchange between them.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 
 import torch
@@ -49,9 +51,14 @@ from . import sim as _sim
 
 
 class _Net:
-    """views of one MLP's flat parameter buffer + a flat gradient buffer of the same layout + Adam state"""
+    """views of one MLP's flat parameter buffer + a flat gradient buffer of the same layout + Adam state; a trained network also has its
+    optimizer's hyper-parameters and its row (`slot`) of NativeDDPGfDUpdate.clip / _partials"""
 
-    def __init__(self, module, flat):
+    def __init__(self, module, flat, optimizer=None, slot=None):
+        if optimizer is not None:
+            g = optimizer.param_groups[0]
+            self.hyper = (g["lr"], g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"])
+        self.slot = slot
         self.flat = flat
         self.grad = torch.zeros_like(flat)
         self.exp_avg = torch.zeros_like(flat)
@@ -67,6 +74,7 @@ class _Net:
                 dst_g.append(self.grad[off:off + n].view_as(p))
                 off += n
         assert off == flat.numel()
+        self.layers = list(zip(self.W, self.b))          # as mlp.py takes them
 
 
 class NativeDDPGfDUpdate:
@@ -78,13 +86,14 @@ class NativeDDPGfDUpdate:
         import os
         # a ddpgfd.TD3fD policy: a second critic pair, smoothed target actions, the actor's step on every policy_freq-th update
         self.td3 = "critic2" in policy._flat_params
-        if self.td3 and os.environ.get("KS_LEARNER_FORK", "0") == "1":
+        fork = os.environ.get("KS_LEARNER_FORK", "0") == "1"
+        if self.td3 and fork:
             raise ValueError("NativeDDPGfDUpdate: the fork form (KS_LEARNER_FORK=1) has no TD3fD variant")
         # the bounded critic update (ddpgfd: q_bounds, huber_delta, max_grad_norm; None = the launch sequence as it was)
         q_bounds, huber_delta = getattr(policy, "q_bounds", None), getattr(policy, "huber_delta", None)
         self.max_grad_norm = getattr(policy, "max_grad_norm", None)
         self.bounded = q_bounds is not None or huber_delta is not None
-        if (self.bounded or self.max_grad_norm is not None) and os.environ.get("KS_LEARNER_FORK", "0") == "1":
+        if (self.bounded or self.max_grad_norm is not None) and fork:
             raise ValueError("NativeDDPGfDUpdate: the fork form (KS_LEARNER_FORK=1) has no bounded variant (q_bounds / huber_delta / max_grad_norm)")
         inf = float("inf")
         self.q_lo, self.q_hi = (-inf, inf) if q_bounds is None else q_bounds
@@ -95,10 +104,14 @@ class NativeDDPGfDUpdate:
         self.p = policy
         self.lib = _sim.load_library()
         fp = policy._flat_params
-        self.critic, self.actor = _Net(policy.critic, fp["critic"]), _Net(policy.actor, fp["actor"])
+        self.critic = _Net(policy.critic, fp["critic"], policy.critic_optimizer, slot=1)
+        self.actor = _Net(policy.actor, fp["actor"], policy.actor_optimizer, slot=0)
         self.critic_t, self.actor_t = _Net(policy.critic_target, fp["critic_target"]), _Net(policy.actor_target, fp["actor_target"])
+        self.critics, self.critic_targets = [self.critic], [self.critic_t]
         if self.td3:
-            self.critic2, self.critic2_t = _Net(policy.critic2, fp["critic2"]), _Net(policy.critic2_target, fp["critic2_target"])
+            self.critic2 = _Net(policy.critic2, fp["critic2"], policy.critic2_optimizer, slot=2)
+            self.critic2_t = _Net(policy.critic2_target, fp["critic2_target"])
+            self.critics, self.critic_targets = [self.critic, self.critic2], [self.critic_t, self.critic2_t]
         # key of the target smoothing's in-kernel noise stream (counter: the update count); pipeline.GraphedTrainer hands over its sampler's
         self.seed = int(torch.initial_seed()) & 0xFFFFFFFFFFFFFFFF
         self.it = torch.zeros(1, dtype=torch.long, device=policy.device)      # updates done (Adam step of both nets)
@@ -112,12 +125,6 @@ class NativeDDPGfDUpdate:
         policy._native = self                                                  # DDPGfD.save / load keep the Adam state in sync
         self.import_optimizer_state()
         self.losses = torch.zeros(6 if self.td3 else 3, device=policy.device)   # critic loss, L1, LN of the last update (TD3fD: then critic 2's)
-        ao, co = policy.actor_optimizer.param_groups[0], policy.critic_optimizer.param_groups[0]
-        self.hyper_a = (ao["lr"], ao["betas"][0], ao["betas"][1], ao["eps"], ao["weight_decay"])
-        self.hyper_c = (co["lr"], co["betas"][0], co["betas"][1], co["eps"], co["weight_decay"])
-        if self.td3:
-            c2o = policy.critic2_optimizer.param_groups[0]
-            self.hyper_c2 = (c2o["lr"], c2o["betas"][0], c2o["betas"][1], c2o["eps"], c2o["weight_decay"])
         # How much of the update runs on the hand-written MFMA kernels of csrc/ks_mlp.hip (mlp.py):
         #  * fused_targets: the forward-only target networks (3200 rows) and the critic's forward (1600 rows, activations
         #    kept for the backward pass) as ONE launch each instead of three library GEMMs + glue;
@@ -126,7 +133,7 @@ class NativeDDPGfDUpdate:
         #  * lds_free: the backward passes too (mlp.mlp3_backward, mlp.weight_grad) - then no launch of the update needs
         #    LDS and the whole learner runs in the simulator's shadow.  Widths 256-256 / 128-128 / 64-64.
         # Otherwise (e.g. the reference's 400-300) the passes go through the library GEMMs (hipBLASLt).
-        tl = [list(zip(net.W, net.b)) for net in (self.actor_t, self.critic_t)]
+        tl = [net.layers for net in (self.actor_t, self.critic_t)]
         ins = [net.W[0].shape[1] for net in (self.actor_t, self.critic_t)]
         mult = lambda k: all(w.shape[0] % k == 0 for w in self.critic.W[:2] + self.actor.W[:2])
         self.fused_targets = mult(4) and all(_mlp.supported(layers, d) for layers, d in zip(tl, ins))
@@ -139,7 +146,7 @@ class NativeDDPGfDUpdate:
         self.lean_kernels = False
         if self.lean and not self.lds_free:
             nets = (self.actor, self.critic, self.actor_t, self.critic_t)
-            if not all(_mlp.supported(list(zip(net.W, net.b)), net.W[0].shape[1], lean=True) for net in nets):
+            if not all(_mlp.supported(net.layers, net.W[0].shape[1], lean=True) for net in nets):
                 raise ValueError("NativeDDPGfDUpdate(lean=True): hidden widths %s have neither the LDS-free learner kernels (256-256 / 128-128 / "
                                  "64-64) nor the lean ones (400-300)" % (tuple(w.shape[0] for w in self.actor.W[:2]),))
             self.lean_kernels = self.fused_targets = self.lds_free = True
@@ -162,21 +169,25 @@ class NativeDDPGfDUpdate:
         # persistent rollout kernel the training step went from 1.34 to 2.09 ms per env-step (3.05 -> 1.96 M env-steps/s) and episodes were
         # dropped: three learner launches at a time compete with the rollout's waves for the SIMDs' issue slots, and the update is off
         # the critical path at one update per env-step anyway.  Kept for learner-bound regimes (updates_per_step >= 2 in lock step).
-        self.fork = self.lds_free and os.environ.get("KS_LEARNER_FORK", "0") == "1"
+        self.fork = self.lds_free and fork
         self._sides = [torch.cuda.Stream(policy.device) for _ in range(2)] if self.fork else []
 
     # -- helpers ------------------------------------------------------------------------------------------------------
     def _branch(self, k):
-        """context: side stream k, ordered behind everything enqueued on the current stream so far (a fork); _join() brings it back"""
+        """context, the fork form: side stream k, ordered behind everything enqueued on the current stream so far (a fork); _join() brings
+        it back.  Otherwise: the current stream."""
+        if not self.fork:
+            return contextlib.nullcontext()
         cur = torch.cuda.current_stream(self.p.device)
         side = self._sides[k]
         side.wait_stream(cur)
         return torch.cuda.stream(side)
 
     def _join(self, *ks):
-        cur = torch.cuda.current_stream(self.p.device)
-        for k in ks:
-            cur.wait_stream(self._sides[k])
+        if self.fork:
+            cur = torch.cuda.current_stream(self.p.device)
+            for k in ks:
+                cur.wait_stream(self._sides[k])
 
     def _st(self):
         return ctypes.c_void_p(torch.cuda.current_stream(self.p.device).cuda_stream)
@@ -199,37 +210,27 @@ class NativeDDPGfDUpdate:
     def _relu_bwd(self, act, grad):
         self._chk(self.lib.kr_relu_backward(grad.numel(), _sim._ptr(act), _sim._ptr(grad), self._st()), "kr_relu_backward")
 
-    def _adam_clipped(self, net, hyper, step, every, slot):
-        """the Adam step behind the global gradient-norm clip: the squared norm as 64 fp64 partial sums, then the step on g * coef"""
-        lr, b1, b2, eps, wd = hyper
-        P, n, parts = _sim._ptr, net.flat.numel(), self._partials[slot]
-        self._chk(self.lib.kr_grad_sqnorm(n, P(net.grad), P(parts), self._st()), "kr_grad_sqnorm")
-        self._chk(self.lib.kr_adam_step_clipped(n, P(net.flat), P(net.grad), P(net.exp_avg), P(net.exp_avg_sq), P(step), every, P(parts),
-                                                self.max_grad_norm, lr, b1, b2, eps, wd, P(self.clip[slot]), self._st()), "kr_adam_step_clipped")
-
-    def _adam(self, net, hyper, step=None):
-        lr, b1, b2, eps, wd = hyper
-        P = _sim._ptr
+    def _adam(self, net, step, every=None):
+        """net's Adam step for the update counted by `step`; every (TD3fD's actor): on every `every`-th update only, numbered step / every.
+        With max_grad_norm behind the global gradient-norm clip: the squared norm as 64 fp64 partial sums, then the step on g * coef."""
+        P, n = _sim._ptr, net.flat.numel()
+        state = (n, P(net.flat), P(net.grad), P(net.exp_avg), P(net.exp_avg_sq), P(step))
         if self.max_grad_norm is not None:
-            return self._adam_clipped(net, hyper, self.it if step is None else step, 1, 0 if net is self.actor else (1 if net is self.critic else 2))
-        self._chk(self.lib.kr_adam_step(net.flat.numel(), P(net.flat), P(net.grad), P(net.exp_avg), P(net.exp_avg_sq),
-                                        P(self.it if step is None else step), lr, b1, b2, eps, wd, self._st()), "kr_adam_step")
+            parts = self._partials[net.slot]
+            self._chk(self.lib.kr_grad_sqnorm(n, P(net.grad), P(parts), self._st()), "kr_grad_sqnorm")
+            self._chk(self.lib.kr_adam_step_clipped(*state, 1 if every is None else every, P(parts), self.max_grad_norm, *net.hyper,
+                                                    P(self.clip[net.slot]), self._st()), "kr_adam_step_clipped")
+        elif every is not None:
+            self._chk(self.lib.kr_adam_step_every(*state, every, *net.hyper, self._st()), "kr_adam_step_every")
+        else:
+            self._chk(self.lib.kr_adam_step(*state, *net.hyper, self._st()), "kr_adam_step")
 
     def _adam_actor(self, step):
-        """the actor's Adam step for the update counted by `step`; TD3fD: on every policy_freq-th update only, numbered step / policy_freq"""
-        if not self.td3:
-            return self._adam(self.actor, self.hyper_a, step=step)
-        if self.max_grad_norm is not None:
-            return self._adam_clipped(self.actor, self.hyper_a, step, self.p.policy_freq, 0)
-        lr, b1, b2, eps, wd = self.hyper_a
-        net, P = self.actor, _sim._ptr
-        self._chk(self.lib.kr_adam_step_every(net.flat.numel(), P(net.flat), P(net.grad), P(net.exp_avg), P(net.exp_avg_sq), P(step),
-                                              self.p.policy_freq, lr, b1, b2, eps, wd, self._st()), "kr_adam_step_every")
+        self._adam(self.actor, step, every=self.p.policy_freq if self.td3 else None)
 
     def _soft_updates(self, it):
         pol, P = self.p, _sim._ptr
-        pairs = ((self.critic, self.critic_t),) + (((self.critic2, self.critic2_t),) if self.td3 else ()) + ((self.actor, self.actor_t),)
-        for net, tgt in pairs:
+        for net, tgt in zip(self.critics + [self.actor], self.critic_targets + [self.actor_t]):
             self._chk(self.lib.kr_soft_update(net.flat.numel(), P(net.flat), P(tgt.flat), pol.tau, P(it), pol.network_repl_freq, self._st()),
                       "kr_soft_update")
 
@@ -307,13 +308,11 @@ class NativeDDPGfDUpdate:
     # -- the three phases ---------------------------------------------------------------------------------------------
     @torch.no_grad()
     def phase_critic(self, state, action, next_state, reward, weight=None, next_ends=None, priorities=None, target_noise=None):
-        """targets, critic forward, loss gradient, critic weight gradients -> self.critic.grad.  priorities (prioritized replay): a callable
-        (q, tq1, reward, weight) issued right after kr_critic_grad on that kernel's own operands - DeviceEpisodeReplay.update_priorities with
-        the batch's `picked` bound; None: the launch sequence has no such step.
-        With a TD3fD policy: the target actor's forward, kr_target_smooth on its output, both target critics on the smoothed action, both
-        critics' forward, ONE kr_twin_critic_grad, the backward and weight-gradient passes once per critic; returns six losses and
-        `priorities` receives (q1, tmin, reward, weight).  With q_bounds or huber_delta set: ONE kr_critic_grad_bounded in place of either
-        loss-gradient launch, and `priorities` receives (q, tboot, reward, weight), the clamped bootstrap.
+        """The target actor's forward (TD3fD: kr_target_smooth on its output), every target critic on that action, every critic's forward,
+        ONE loss-gradient launch (_loss_grad), the backward and weight-gradient passes per critic -> the critics' .grad.  Returns (critic
+        loss, L1, LN) per critic, views of self.losses.  priorities (prioritized replay): a callable (q, tq1, reward, weight) issued right
+        after the loss-gradient launch on that kernel's own operands - the first critic's Q and the bootstrap the launch used -
+        DeviceEpisodeReplay.update_priorities with the batch's `picked` bound; None: the launch sequence has no such step.
         target_noise [2R, 4]: the smoothing's N(0, 1) draws; None: the in-kernel stream keyed by (self.seed, self.it)."""
         pol, P = self.p, _sim._ptr
         R = reward.shape[0]
@@ -327,87 +326,59 @@ class NativeDDPGfDUpdate:
         # both target evaluations (1-step: next_state[:, 0], n-step: next_state[:, -1]) in one pass of the target nets
         # (next_ends: the sampler's own [2R, S] block of exactly these rows, kr_sample_windows_draw)
         nx = torch.cat([next_state[:, 0], next_state[:, -1]], 0) if next_ends is None else next_ends
-        if self.fork:
-            # branch 0: the two target networks (3200 rows each); the critic's own forward runs beside them on the phase's stream
-            c = self.critic
-            cl = list(zip(c.W, c.b))
-            s0, a0 = state[:, 0], action[:, 0]
-            reward = reward.contiguous()
-            with self._branch(0):
-                ta = _mlp.mlp3_forward(list(zip(self.actor_t.W, self.actor_t.b)), nx, act=_mlp.ACT_SIGMOID, scale=pol.max_action, **self._form)
-                tq = _mlp.mlp3_forward(list(zip(self.critic_t.W, self.critic_t.b)), nx, ta, act=_mlp.ACT_NONE, **self._form)
-            h1, h2 = s0.new_empty(R, c.W[0].shape[0]), s0.new_empty(R, c.W[1].shape[0])
-            q = _mlp.mlp3_forward(cl, s0, a0, act=_mlp.ACT_NONE, h1_out=h1, h2_out=h2, **self._form)
-            dq = torch.empty_like(q)
-            self._join(0)
-            self._chk(self.lib.kr_critic_grad(R, pol.n, P(q), P(tq), P(tq[R:]), P(reward), P(weight), P(self.wsum), pol.discount, P(dq), P(self.losses),
-                                              self._st()), "kr_critic_grad")
-            if priorities is not None:
-                priorities(q, tq, reward, weight)
-            with self._branch(0):                              # the last layer's weight gradient needs dq only: beside the data-gradient pass
-                _mlp.weight_grad(dq, h2, None, c.gW[2], c.gb[2])
-            dz2, dz1, _ = _mlp.mlp3_backward(cl, dq, h1, h2, lean=self.lean_kernels)
-            with self._branch(1):
-                _mlp.weight_grad(dz2, h1, None, c.gW[1], c.gb[1])
-            _mlp.weight_grad(dz1, s0, a0, c.gW[0], c.gb[0])
-            self._join(0, 1)
-            return self.losses[0], self.losses[1], self.losses[2]
-        ta = self._target_actions(nx)
-        c = self.critic
+        with self._branch(0):       # (the fork form: the target networks, 3200 rows each, beside the critic's own forward on the phase's stream)
+            ta = self._target_actions(nx, target_noise)
+            tqs = [self._target_q(ct, nx, ta) for ct in self.critic_targets]
+        qs, saved = zip(*[self._critic_forward(c, state, action) for c in self.critics])
+        self._join(0)
+        reward = reward.contiguous()
+        dqs, boot = self._loss_grad(qs, tqs, reward, weight)
+        if priorities is not None:
+            priorities(qs[0], boot, reward, weight)         # the bootstrap the update used
+        for c, dq, sv in zip(self.critics, dqs, saved):
+            self._critic_backward(c, dq, sv)
+        return tuple(self.losses[k] for k in range(3 * len(self.critics)))
+
+    # the passes of phase_critic, per network (TD3fD runs the critic's twice)
+    def _target_actions(self, nx, target_noise):
+        pol, P = self.p, _sim._ptr
+        if self.fused_targets:
+            # forward-only networks: one fused fp32-MFMA launch each (mlp.mlp3_forward) instead of 3 GEMMs + glue
+            ta = _mlp.mlp3_forward(self.actor_t.layers, nx, act=_mlp.ACT_SIGMOID, scale=pol.max_action, **self._targets_form)
+        else:
+            ta = self._actor_forward(self.actor_t, nx)[2]
         if self.td3:
-            # TD3fD: smoothed target actions, both target critics on them, both critics' forward, ONE loss-gradient launch on the targets' minimum
             assert ta.is_contiguous() and (target_noise is None or (target_noise.is_contiguous() and target_noise.dtype == torch.float32 and
                                                                     target_noise.device == ta.device and tuple(target_noise.shape) == tuple(ta.shape)))
             self._chk(self.lib.kr_target_smooth(ta.shape[0], P(ta), P(target_noise), self.seed, None if target_noise is not None else P(self.it),
                                                 pol.policy_noise, pol.noise_clip, pol.max_action, self._st()), "kr_target_smooth")
-            c2 = self.critic2
-            tq, tq2 = self._target_q(self.critic_t, nx, ta), self._target_q(self.critic2_t, nx, ta)
-            (q, saved), (q2, saved2) = self._critic_forward(c, state, action), self._critic_forward(c2, state, action)
-            dq, dq2, tmin = torch.empty_like(q), torch.empty_like(q2), q.new_empty(2 * R)
-            reward = reward.contiguous()
-            if self.bounded:
-                self._chk(self.lib.kr_critic_grad_bounded(R, pol.n, P(q), P(q2), P(tq), P(tq2), P(tq[R:]), P(tq2[R:]), P(reward), P(weight), P(self.wsum),
-                                                          pol.discount, self.q_lo, self.q_hi, self.huber_delta, P(dq), P(dq2), P(tmin), P(self.losses),
-                                                          self._st()), "kr_critic_grad_bounded")
-            else:
-                self._chk(self.lib.kr_twin_critic_grad(R, pol.n, P(q), P(q2), P(tq), P(tq2), P(tq[R:]), P(tq2[R:]), P(reward), P(weight), P(self.wsum),
-                                                       pol.discount, P(dq), P(dq2), P(tmin), P(self.losses), self._st()), "kr_twin_critic_grad")
-            if priorities is not None:
-                priorities(q, tmin, reward, weight)          # the target the update used
-            self._critic_backward(c, dq, saved)
-            self._critic_backward(c2, dq2, saved2)
-            return tuple(self.losses[k] for k in range(6))
-        tq = self._target_q(self.critic_t, nx, ta)
-        q, saved = self._critic_forward(c, state, action)
-        dq = torch.empty_like(q)
-        reward = reward.contiguous()
-        if self.bounded:
-            tboot = q.new_empty(2 * R)
-            self._chk(self.lib.kr_critic_grad_bounded(R, pol.n, P(q), None, P(tq), None, P(tq[R:]), None, P(reward), P(weight), P(self.wsum), pol.discount,
-                                                      self.q_lo, self.q_hi, self.huber_delta, P(dq), None, P(tboot), P(self.losses), self._st()),
-                      "kr_critic_grad_bounded")
-            if priorities is not None:
-                priorities(q, tboot, reward, weight)             # the bootstrap the update used
-            self._critic_backward(c, dq, saved)
-            return self.losses[0], self.losses[1], self.losses[2]
-        self._chk(self.lib.kr_critic_grad(R, pol.n, P(q), P(tq), P(tq[R:]), P(reward), P(weight), P(self.wsum), pol.discount, P(dq), P(self.losses),
-                                          self._st()), "kr_critic_grad")
-        if priorities is not None:
-            priorities(q, tq, reward, weight)
-        self._critic_backward(c, dq, saved)
-        return self.losses[0], self.losses[1], self.losses[2]
-
-    # the passes of phase_critic, per network (TD3fD runs the critic's twice)
-    def _target_actions(self, nx):
-        if self.fused_targets:
-            # forward-only networks: one fused fp32-MFMA launch each (mlp.mlp3_forward) instead of 3 GEMMs + glue
-            return _mlp.mlp3_forward(list(zip(self.actor_t.W, self.actor_t.b)), nx, act=_mlp.ACT_SIGMOID, scale=self.p.max_action, **self._targets_form)
-        return self._actor_forward(self.actor_t, nx)[2]
+        return ta
 
     def _target_q(self, ct, nx, ta):
         if self.fused_targets:
-            return _mlp.mlp3_forward(list(zip(ct.W, ct.b)), nx, ta, act=_mlp.ACT_NONE, **self._targets_form)
+            return _mlp.mlp3_forward(ct.layers, nx, ta, act=_mlp.ACT_NONE, **self._targets_form)
         return torch.addmm(ct.b[2], self._lin_relu(ct, 1, self._lin_relu(ct, 0, torch.cat([nx, ta], 1))), ct.W[2].t())
+
+    def _loss_grad(self, qs, tqs, reward, weight):
+        """ONE launch: the targets and every critic's dLoss/dQ from the critics' Q and their target critics' [2R] (1-step rows, then n-step),
+        the losses -> self.losses.  kr_critic_grad for one critic, kr_twin_critic_grad for two, kr_critic_grad_bounded for either when
+        self.bounded.  Returns the dqs and the bootstrap the launch used, which `priorities` must see: the target critic's own, or the [2R]
+        the kernel wrote where it took the minimum or clamped."""
+        pol, P, R = self.p, _sim._ptr, reward.shape[0]
+        twin = len(qs) == 2
+        dqs = [torch.empty_like(q) for q in qs]
+        boot = qs[0].new_empty(2 * R) if twin or self.bounded else tqs[0]
+        pair = lambda xs: [P(x) for x in xs] + [None] * (2 - len(xs))
+        nets = pair(qs) + pair(tqs) + pair([tq[R:] for tq in tqs])                # q1, q2, tq1_a, tq1_b, tqn_a, tqn_b
+        batch = (P(reward), P(weight), P(self.wsum), pol.discount)
+        if self.bounded:
+            name, args = "kr_critic_grad_bounded", (*nets, *batch, self.q_lo, self.q_hi, self.huber_delta, *pair(dqs), P(boot))
+        elif twin:
+            name, args = "kr_twin_critic_grad", (*nets, *batch, *pair(dqs), P(boot))
+        else:
+            name, args = "kr_critic_grad", (nets[0], nets[2], nets[4], *batch, P(dqs[0]))
+        self._chk(getattr(self.lib, name)(R, pol.n, *args, P(self.losses), self._st()), name)
+        return dqs, boot
 
     def _critic_forward(self, c, state, action):
         """Q of the windows' first rows; returns (q, what _critic_backward needs)"""
@@ -416,12 +387,12 @@ class NativeDDPGfDUpdate:
         if self.lds_free:
             # the whole critic step without LDS: forward, loss gradient, data and weight gradients (csrc/ks_mlp.hip)
             h1, h2 = s0.new_empty(R, c.W[0].shape[0]), s0.new_empty(R, c.W[1].shape[0])
-            q = _mlp.mlp3_forward(list(zip(c.W, c.b)), s0, a0, act=_mlp.ACT_NONE, h1_out=h1, h2_out=h2, **self._form)
+            q = _mlp.mlp3_forward(c.layers, s0, a0, act=_mlp.ACT_NONE, h1_out=h1, h2_out=h2, **self._form)
             return q, (s0, a0, h1, h2)
         x0 = torch.cat([s0, a0], 1)
         if self.fused_targets and self.fuse_critic_fwd:
             h1, h2 = x0.new_empty(R, c.W[0].shape[0]), x0.new_empty(R, c.W[1].shape[0])
-            q = _mlp.mlp3_forward(list(zip(c.W, c.b)), s0, a0, act=_mlp.ACT_NONE, h1_out=h1, h2_out=h2, **self._targets_form)
+            q = _mlp.mlp3_forward(c.layers, s0, a0, act=_mlp.ACT_NONE, h1_out=h1, h2_out=h2, **self._targets_form)
         else:
             h1 = self._lin_relu(c, 0, x0)
             h2 = self._lin_relu(c, 1, h1)
@@ -431,27 +402,37 @@ class NativeDDPGfDUpdate:
     def _critic_backward(self, c, dq, saved):
         """dq = dLoss/dQ -> c.grad"""
         if self.lds_free:
-            s0, a0, h1, h2 = saved
-            dz2, dz1, _ = _mlp.mlp3_backward(list(zip(c.W, c.b)), dq, h1, h2, lean=self.lean_kernels)
-            _mlp.weight_grad(dq, h2, None, c.gW[2], c.gb[2])
-            _mlp.weight_grad(dz2, h1, None, c.gW[1], c.gb[1])
-            _mlp.weight_grad(dz1, s0, a0, c.gW[0], c.gb[0])
+            self._backward(c, dq, *saved)
         else:
             self._weight_grads(c, *saved, dq)
+
+    def _backward(self, net, dz3, x, xa, h1, h2):
+        """LDS-free: dz3 = the gradient at the pre-activation of net's last layer, [x, xa] its input -> net.grad.  The fork form: the last
+        layer's weight gradient needs dz3 only and the second's dz2 only: on the side streams, beside the data-gradient pass and the first's."""
+        last = lambda: _mlp.weight_grad(dz3, h2, None, net.gW[2], net.gb[2])
+        if self.fork:
+            with self._branch(0):
+                last()
+        dz2, dz1, _ = _mlp.mlp3_backward(net.layers, dz3, h1, h2, lean=self.lean_kernels)
+        if not self.fork:
+            last()
+        with self._branch(1):
+            _mlp.weight_grad(dz2, h1, None, net.gW[1], net.gb[1])
+        _mlp.weight_grad(dz1, x, xa, net.gW[0], net.gb[0])
+        self._join(0, 1)
 
     @torch.no_grad()
     def phase_actor(self, state, weight=None):
         """critic Adam step, then the actor loss -mean_w Q(s, pi(s)) over all n-step rows -> self.actor.grad"""
         pol, P = self.p, _sim._ptr
-        self._adam(self.critic, self.hyper_c)
-        if self.td3:
-            self._adam(self.critic2, self.hyper_c2)
+        for net in self.critics:
+            self._adam(net, self.it)
         n = state.shape[1]
         sa = state.reshape(-1, state.shape[2])
         a_, c = self.actor, self.critic
         if self.lds_free:
             rows = sa.shape[0]
-            al, cl = list(zip(a_.W, a_.b)), list(zip(c.W, c.b))
+            al, cl = a_.layers, c.layers
             ha1, ha2 = sa.new_empty(rows, a_.W[0].shape[0]), sa.new_empty(rows, a_.W[1].shape[0])
             a = _mlp.mlp3_forward(al, sa, act=_mlp.ACT_SIGMOID, scale=pol.max_action, h1_out=ha1, h2_out=ha2, **self._form)
             hc1, hc2 = sa.new_empty(rows, c.W[0].shape[0]), sa.new_empty(rows, c.W[1].shape[0])
@@ -461,26 +442,14 @@ class NativeDDPGfDUpdate:
             dq = self.dq_actor
             # dLoss/d(actor pre-activation): through the critic to its action inputs, then through 0.8 * sigmoid
             _, _, dz3 = _mlp.mlp3_backward(cl, dq, hc1, hc2, want_dz=False, dx_cols=(sa.shape[1], a.shape[1]), act_out=a, scale=pol.max_action, lean=self.lean_kernels)
-            if self.fork:
-                with self._branch(0):
-                    _mlp.weight_grad(dz3, ha2, None, a_.gW[2], a_.gb[2])
-                dz2, dz1, _ = _mlp.mlp3_backward(al, dz3, ha1, ha2, lean=self.lean_kernels)
-                with self._branch(1):
-                    _mlp.weight_grad(dz2, ha1, None, a_.gW[1], a_.gb[1])
-                _mlp.weight_grad(dz1, sa, None, a_.gW[0], a_.gb[0])
-                self._join(0, 1)
-                return None
-            dz2, dz1, _ = _mlp.mlp3_backward(al, dz3, ha1, ha2, lean=self.lean_kernels)
-            _mlp.weight_grad(dz3, ha2, None, a_.gW[2], a_.gb[2])
-            _mlp.weight_grad(dz2, ha1, None, a_.gW[1], a_.gb[1])
-            _mlp.weight_grad(dz1, sa, None, a_.gW[0], a_.gb[0])
+            self._backward(a_, dz3, sa, None, ha1, ha2)
             return None
         if self.fused_targets and self.fuse_actor_fwd:
             rows = sa.shape[0]
             ha1, ha2 = sa.new_empty(rows, a_.W[0].shape[0]), sa.new_empty(rows, a_.W[1].shape[0])
-            a = _mlp.mlp3_forward(list(zip(a_.W, a_.b)), sa, act=_mlp.ACT_SIGMOID, scale=pol.max_action, h1_out=ha1, h2_out=ha2)
+            a = _mlp.mlp3_forward(a_.layers, sa, act=_mlp.ACT_SIGMOID, scale=pol.max_action, h1_out=ha1, h2_out=ha2)
             hc1, hc2 = sa.new_empty(rows, c.W[0].shape[0]), sa.new_empty(rows, c.W[1].shape[0])
-            _mlp.mlp3_forward(list(zip(c.W, c.b)), sa, a, act=_mlp.ACT_NONE, h1_out=hc1, h2_out=hc2)      # Q itself is not needed: dLoss/dQ is constant
+            _mlp.mlp3_forward(c.layers, sa, a, act=_mlp.ACT_NONE, h1_out=hc1, h2_out=hc2)      # Q itself is not needed: dLoss/dQ is constant
         else:
             ha1, ha2, a = self._actor_forward(a_, sa)
             hc1 = self._lin_relu(c, 0, torch.cat([sa, a], 1))
