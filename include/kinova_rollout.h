@@ -121,6 +121,46 @@ int kr_sample_windows_mixed(int32_t batch, int32_t batch_agent, int32_t horizon,
                             const float *u_ep, const float *u_start, uint64_t seed, const int64_t *draw, float *state, float *action,
                             float *next_state, float *reward, float *not_done, float *weight, float *next_ends, void *stream);
 
+/* kr_sample_windows_mixed's batch as EPISODE TABLES: the same draws (uniforms given or Philox keyed by seed / draw[0], the same episode and
+ * window-start rule), but each batch episode's `horizon` ring rows are written once and a window row is the index of its first state.  The
+ * batch * W * n_steps window states of a batch (W = horizon - n_steps) are rows of batch * horizon distinct ones: a learner that works on
+ * the tables evaluates each state once (learner_native: NativeDDPGfDUpdate.phase_*_tables).
+ *   table_state, table_next  [batch * horizon, 82]  row b * horizon + t = row t of the ring slot batch slot b drew, as the ring holds it
+ *   table_action             [batch * horizon, 4]   the same rows' actions (no update reads them beyond action0: they make the batch whole)
+ *   row_table  int32 [batch * W]   b * horizon + start of window row (b, w), padding rows included
+ *   slot_weight  [batch]           the weight every real window row of slot b carries (1; the prioritized forms: the episode's importance weight)
+ *   state0 [R, 82], action0 [R, 4], reward [R, n_steps], not_done [R, n_steps], weight [R]   (R = batch * W) the window rows' first state and
+ *                                  action and their columns of kr_sample_windows_mixed's batch: what the critic phase reads
+ * so that kr_sample_windows_mixed's state[r][k] = table_state[row_table[r] + k], next_state[r][k] = table_next[row_table[r] + k], action[r][k] = table_action[row_table[r] + k], in every
+ * bit.  next_ends (optional) [2 R, 82] as kr_sample_windows_mixed writes it.  KS_ERR_INVALID, nothing launched or written: what
+ * kr_sample_windows_mixed refuses, or a NULL output other than next_ends. */
+int kr_sample_tables_mixed(int32_t batch, int32_t batch_agent, int32_t horizon, int32_t n_steps, const kr_ring *agent, const kr_ring *expert,
+                           const float *u_ep, const float *u_start, uint64_t seed, const int64_t *draw, float *table_state, float *table_next,
+                           float *table_action, int32_t *row_table, float *slot_weight, float *state0, float *action0, float *reward, float *not_done, float *weight,
+                           float *next_ends, void *stream);
+/* The table form behind the other picks: kr_sample_windows_balanced's, _prioritized's and _balanced_prioritized's arguments and pick launch,
+ * kr_sample_tables_mixed's outputs (the table gather as second launch) and `picked` int32 [batch], which is required here.  The prioritized
+ * forms write the episode's importance weight to slot_weight[b] and to its real rows in `weight`.  Each equals its window sampler's batch
+ * in every bit, as kr_sample_tables_mixed equals kr_sample_windows_mixed's.  KS_ERR_INVALID, nothing launched or written: what the window
+ * entry refuses, a NULL output other than next_ends, a NULL picked. */
+int kr_sample_tables_balanced(int32_t batch, int32_t batch_agent, int32_t horizon, int32_t n_steps, const kr_ring *agent, const kr_ring *expert,
+                              const int32_t *agent_class, const int32_t *expert_class, int32_t n_classes, int32_t rotation, const float *u_ep,
+                              const float *u_start, uint64_t seed, const int64_t *draw, float *table_state, float *table_next, float *table_action,
+                              int32_t *row_table, float *slot_weight, float *state0, float *action0, float *reward, float *not_done, float *weight,
+                              float *next_ends, int32_t *picked, void *stream);
+int kr_sample_tables_prioritized(int32_t batch, int32_t batch_agent, int32_t horizon, int32_t n_steps, const kr_ring *agent, const kr_ring *expert,
+                                 const uint32_t *agent_prio, const uint32_t *expert_prio, const float *beta, const float *u_ep, const float *u_start,
+                                 uint64_t seed, const int64_t *draw, float *table_state, float *table_next, float *table_action, int32_t *row_table,
+                                 float *slot_weight, float *state0, float *action0, float *reward, float *not_done, float *weight, float *next_ends,
+                                 int32_t *picked, void *stream);
+int kr_sample_tables_balanced_prioritized(int32_t batch, int32_t batch_agent, int32_t horizon, int32_t n_steps, const kr_ring *agent,
+                                          const kr_ring *expert, const int32_t *agent_class, const int32_t *expert_class, int32_t n_classes,
+                                          int32_t rotation, const uint32_t *agent_prio, const uint32_t *expert_prio, const float *beta,
+                                          const float *u_ep, const float *u_start, uint64_t seed, const int64_t *draw, float *table_state,
+                                          float *table_next, float *table_action, int32_t *row_table, float *slot_weight, float *state0,
+                                          float *action0, float *reward, float *not_done, float *weight, float *next_ends, int32_t *picked,
+                                          void *stream);
+
 /* ---- replay batches balanced over the episodes' classes (no reference counterpart as a sampler: main_DDPGfD.py takes the stage's objects
  * in Latin-square order while COLLECTING, so that every object contributes the same number of episodes; a free-running or time-budgeted
  * rollout fills the ring at each object's own pace instead, and the balance is restored where the batch is drawn).
@@ -275,6 +315,17 @@ int kr_critic_grad(int32_t rows, int32_t n_steps, const float *q, const float *t
  * the head of the next one (learner_native.phase_head). */
 int kr_update_prologue(int32_t rows, int32_t n_steps, const float *weight, float *weight_sum, float *dq_actor, int64_t *it, int64_t *it_head,
                        int32_t pipelined, void *stream);
+/* kr_update_prologue for an update on episode tables (kr_sample_tables_mixed; rows = batch * W): weight_sum, it and it_head as there, and
+ *   dq_table [batch * horizon]    slot_weight[b] * (-1 / (weight_sum * n_steps)) for the rows of slot b - kr_update_prologue's own
+ *                                 expression, hence dq_actor's bits for every state of a real window row
+ *   row_index int32 [rows * n_steps]   the table row of window state (r, k): row_table[r] + k, or -1 where weight[r] == 0
+ * (what kr_weight_grad_indexed takes).  KS_ERR_INVALID, nothing launched or written: a NULL pointer or a non-positive size. */
+int kr_update_prologue_tables(int32_t rows, int32_t n_steps, int32_t batch, int32_t horizon, const float *weight, const float *slot_weight,
+                              const int32_t *row_table, float *weight_sum, float *dq_table, int32_t *row_index, int64_t *it, int64_t *it_head,
+                              int32_t pipelined, void *stream);
+/* the target critic's Q on the table rows (table_next) -> the [2 * rows] layout kr_critic_grad* take:
+ * tq[r] = tq_table[row_table[r]], tq[rows + r] = tq_table[row_table[r] + n_steps - 1].  KS_ERR_INVALID as above. */
+int kr_gather_table_q(int32_t rows, int32_t n_steps, const int32_t *row_table, const float *tq_table, float *tq, void *stream);
 int kr_relu_backward(int64_t count, const float *act, float *grad, void *stream);
 int kr_sigmoid_scale_backward(int64_t count, const float *a, float max_action, float *grad, void *stream);
 int kr_adam_step(int64_t count, float *param, const float *grad, float *exp_avg, float *exp_avg_sq, const int64_t *step, float lr,
@@ -426,6 +477,13 @@ int kr_mlp3_backward_split(int32_t n, int32_t in_dim, int32_t h1, int32_t h2, in
                            int32_t waves, void *stream);
 int kr_weight_grad_shadow(int32_t n, int32_t M, int32_t Na, int32_t Nb, const float *dz, const float *ha, int32_t lda, const float *hb,
                           int32_t ldb, int32_t chunks, float *workspace, float *dW, float *db, void *stream);
+/* kr_weight_grad_shadow over n TERMS read through an index: term r is row idx[r] of dz / ha / hb, which hold `rows` rows; an idx[r]
+ * outside [0, rows) reads as zeros.  Terms, order, chunks and rounds are kr_weight_grad_shadow's: the result is bit for bit what it
+ * gives on the gathered rows.  KS_ERR_INVALID, nothing launched: what kr_weight_grad_shadow refuses, a NULL idx, rows < 1, a row
+ * stride below its width, or rows * max(M, lda, ldb) * 4 >= 2^31. */
+int kr_weight_grad_indexed(int32_t n, int32_t rows, int32_t M, int32_t Na, int32_t Nb, const float *dz, const float *ha, int32_t lda,
+                           const float *hb, int32_t ldb, const int32_t *idx, int32_t chunks, float *workspace, float *dW, float *db,
+                           void *stream);
 
 /* The LEAN LDS-free forward and backward: kr_mlp3_forward_shadow / kr_mlp3_backward_shadow (same operand layouts, optional
  * outputs, act / scale handling and dx epilogue with the sigmoid backward) for the tile pair the one-wave kernels cannot take:

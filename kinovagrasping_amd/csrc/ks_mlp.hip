@@ -641,10 +641,17 @@ __global__ KS_LEAN_ATTR void k_mlp3_bwd_lean(
 // without LDS: a wave owns one 16-row tile of dW and TN 16-column tiles, and one chunk of the batch rows; A = dz^T
 // (lane: feature m, row k), B = h (lane: row k, column).  The chunk partials go to a workspace [chunk][M * N + M] that
 // k_wgrad_reduce sums in chunk order (deterministic, unlike atomics).
+//
+// INDEXED (kr_weight_grad_indexed): term r of the sums is row idx[r] of dz / ha / hb, which then hold `rows` rows - the learner's episode
+// tables, every state evaluated once and read by each of the ~4 window rows that hold it.  The n terms, their order, the chunks and the
+// rounds are those of the plain form, so the sums are its bits on the gathered rows; a term with idx[r] outside [0, rows) reads as
+// zeros.  The row advance moves from the scalar offset into the lane offset; the indices of round k + 1 are loaded ahead of round k's
+// operands.
 constexpr int WG_TN = 4;
+template <bool INDEXED>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_wgrad_wave(
-    int n, int M, int Na, int Nb, int rows_per_chunk, const float* __restrict__ dz, const float* __restrict__ ha, int lda,
-    const float* __restrict__ hb, int ldb, float* __restrict__ ws) {
+    int n, int rows, int M, int Na, int Nb, int rows_per_chunk, const float* __restrict__ dz, const float* __restrict__ ha, int lda,
+    const float* __restrict__ hb, int ldb, const int* __restrict__ idx, float* __restrict__ ws) {
     const int lane = threadIdx.x & 63, nn = lane & 15, q = lane >> 4;
     const int N = Na + Nb, n_blocks = (N + 16 * WG_TN - 1) / (16 * WG_TN);
     const int mt = blockIdx.x / n_blocks, nb = blockIdx.x % n_blocks, chunk = blockIdx.y;
@@ -653,29 +660,46 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) void
     // Raw buffer loads (as in k_mlp3_wave): per matrix ONE lane offset (row q of a 4-row group, this lane's column), the row
     // advance in the wave-uniform scalar offset; an element that does not exist gets an out-of-range lane offset (-> 0).
     // The flat-load version spent ~10 VALU + ~20 SALU instructions per MFMA on addresses and bounds branches.
-    const auto rZ = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(dz), 0, n * M * 4, 0x00020000);
-    const auto rA = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(ha), 0, ((n - 1) * lda + Na) * 4, 0x00020000);
-    const auto rB = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(hb ? hb : ha), 0, hb ? ((n - 1) * ldb + Nb) * 4 : 0, 0x00020000);
-    const int vz = m < M ? (q * M + m) * 4 : OOR;
+    const auto rZ = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(dz), 0, rows * M * 4, 0x00020000);
+    const auto rA = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(ha), 0, ((rows - 1) * lda + Na) * 4, 0x00020000);
+    const auto rB = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(hb ? hb : ha), 0, hb ? ((rows - 1) * ldb + Nb) * 4 : 0, 0x00020000);
+    const auto rI = __builtin_amdgcn_make_buffer_rsrc(const_cast<int*>(INDEXED ? idx : nullptr), 0, INDEXED ? n * 4 : 0, 0x00020000);
+    const int row_q = INDEXED ? 0 : q;            // (indexed: the lane's row comes with its index)
+    const int vz = m < M ? (row_q * M + m) * 4 : OOR;
     int va[WG_TN], vb[WG_TN];
 #pragma unroll
     for (int u = 0; u < WG_TN; u++) {
         const int c = (nb * WG_TN + u) * 16 + nn;
-        va[u] = c < Na ? (q * lda + c) * 4 : OOR;
-        vb[u] = (c >= Na && c < N) ? (q * ldb + c - Na) * 4 : OOR;
+        va[u] = c < Na ? (row_q * lda + c) * 4 : OOR;
+        vb[u] = (c >= Na && c < N) ? (row_q * ldb + c - Na) * 4 : OOR;
     }
     f32x4 acc[WG_TN];
 #pragma unroll
     for (int u = 0; u < WG_TN; u++) acc[u] = f32x4{0.f, 0.f, 0.f, 0.f};
     float colsum = 0.f;
     // four k-steps (16 rows) per round, all loads first; only the last round of a chunk can hold rows that do not exist
-    auto round = [&](int k0, auto guard, auto hasb) {
+    // (id: INDEXED, the table rows of this lane's four terms of the round)
+    auto round = [&](int k0, const int* id, auto guard, auto hasb) {
         constexpr bool GUARD = decltype(guard)::value, HASB = decltype(hasb)::value;
         float a[4], b[4][WG_TN];
 #pragma unroll
         for (int j = 0; j < 4; j++) {
             const int rj = k0 + 4 * j;                                 // wave-uniform; this lane's row is rj + q
-            const bool ok = !GUARD || rj + q < r1;
+            bool ok = !GUARD || rj + q < r1;
+            if constexpr (INDEXED) {
+                // the row's byte offset joins the lane offset; a term that is no row gets OOR there, and OOR plus a column offset - or
+                // plus another OOR - is still beyond every resource as the unsigned 32-bit offset the hardware compares
+                ok = ok && (unsigned)id[j] < (unsigned)rows;
+                const uint32_t oz = ok ? (uint32_t)(id[j] * M * 4) : OOR, oa = ok ? (uint32_t)(id[j] * lda * 4) : OOR;
+                a[j] = ldf(rZ, (uint32_t)vz + oz, 0);
+#pragma unroll
+                for (int u = 0; u < WG_TN; u++) {
+                    float v = ldf(rA, (uint32_t)va[u] + oa, 0);
+                    if (HASB) v += ldf(rB, (uint32_t)vb[u] + (ok ? (uint32_t)(id[j] * ldb * 4) : OOR), 0);
+                    b[j][u] = v;
+                }
+                continue;
+            }
             a[j] = ldf(rZ, ok ? vz : OOR, rj * M * 4);
 #pragma unroll
             for (int u = 0; u < WG_TN; u++) {
@@ -692,13 +716,29 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) void
         }
     };
     const int full_end = r0 + ((r1 - r0) >> 4 << 4);
-    if (Nb > 0) {
-        for (int k0 = r0; k0 < full_end; k0 += 16) round(k0, std::false_type{}, std::true_type{});
-        if (full_end < r1) round(full_end, std::true_type{}, std::true_type{});
-    } else {
-        for (int k0 = r0; k0 < full_end; k0 += 16) round(k0, std::false_type{}, std::false_type{});
-        if (full_end < r1) round(full_end, std::true_type{}, std::false_type{});
-    }
+    // the rounds of the chunk; INDEXED: the next round's indices are in flight before this round's operands are asked for (the row is in the
+    // lane offset, which the range check covers: an index at or past n is not read at all and comes back as 0; it is never used - the
+    // guarded round masks it, or the loop has ended)
+    auto rounds = [&](auto hasb) {
+        if constexpr (INDEXED) {
+            int cur[4], nxt[4];
+#pragma unroll
+            for (int j = 0; j < 4; j++) cur[j] = __builtin_amdgcn_raw_buffer_load_b32(rI, (r0 + 4 * j + q) * 4, 0, 0);
+            for (int k0 = r0; k0 < r1; k0 += 16) {
+#pragma unroll
+                for (int j = 0; j < 4; j++) nxt[j] = __builtin_amdgcn_raw_buffer_load_b32(rI, (k0 + 16 + 4 * j + q) * 4, 0, 0);
+                if (k0 < full_end) round(k0, cur, std::false_type{}, hasb);
+                else round(k0, cur, std::true_type{}, hasb);
+#pragma unroll
+                for (int j = 0; j < 4; j++) cur[j] = nxt[j];
+            }
+        } else {
+            for (int k0 = r0; k0 < full_end; k0 += 16) round(k0, nullptr, std::false_type{}, hasb);
+            if (full_end < r1) round(full_end, nullptr, std::true_type{}, hasb);
+        }
+    };
+    if (Nb > 0) rounds(std::true_type{});
+    else rounds(std::false_type{});
     float* out = ws + (long)chunk * ((long)M * N + M);
 #pragma unroll
     for (int u = 0; u < WG_TN; u++) {
@@ -922,8 +962,9 @@ int kr_mlp3_backward_lean(int32_t n, int32_t in_dim, int32_t h1, int32_t h2, int
     return launch_bwd(k, 64, stream, a, x.buf, x.rows);
 }
 
-int kr_weight_grad_shadow(int32_t n, int32_t M, int32_t Na, int32_t Nb, const float* dz, const float* ha, int32_t lda, const float* hb, int32_t ldb,
-                          int32_t chunks, float* workspace, float* dW, float* db, void* stream) {
+// the two launches behind kr_weight_grad_shadow (idx == nullptr: the n terms are the rows themselves) and kr_weight_grad_indexed
+static int weight_grad(int32_t n, int32_t rows, int32_t M, int32_t Na, int32_t Nb, const float* dz, const float* ha, int32_t lda, const float* hb,
+                       int32_t ldb, const int32_t* idx, int32_t chunks, float* workspace, float* dW, float* db, void* stream) {
     if (n <= 0 || M < 1 || Na < 1 || Nb < 0 || chunks < 1 || !dz || !ha || (Nb > 0 && !hb) || !workspace || !dW || !db) return KS_ERR_INVALID;
     hipStream_t s = (hipStream_t)stream;
     const int N = Na + Nb, n_blocks = (N + 16 * WG_TN - 1) / (16 * WG_TN), m_tiles = (M + 15) / 16;
@@ -932,10 +973,27 @@ int kr_weight_grad_shadow(int32_t n, int32_t M, int32_t Na, int32_t Nb, const fl
     // the rounding can leave trailing chunks that start at or past n: launch (and reduce) only the chunks that hold rows.  A chunk
     // with r0 > n would otherwise take full_end = r0 - 16 in k_wgrad_wave and add rows the previous chunk already counted.
     chunks = (n + rows_per_chunk - 1) / rows_per_chunk;
-    hipLaunchKernelGGL(k_wgrad_wave, dim3(m_tiles * n_blocks, chunks), dim3(64), 0, s, n, M, Na, Nb, rows_per_chunk, dz, ha, lda, hb, ldb, workspace);
+    const dim3 grid(m_tiles * n_blocks, chunks);
+    if (idx != nullptr)
+        hipLaunchKernelGGL(k_wgrad_wave<true>, grid, dim3(64), 0, s, n, rows, M, Na, Nb, rows_per_chunk, dz, ha, lda, hb, ldb, idx, workspace);
+    else
+        hipLaunchKernelGGL(k_wgrad_wave<false>, grid, dim3(64), 0, s, n, n, M, Na, Nb, rows_per_chunk, dz, ha, lda, hb, ldb, idx, workspace);
     const long total = (long)M * N + M;
     hipLaunchKernelGGL(k_wgrad_reduce, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (long)M * N, (long)M, chunks, workspace, dW, db);
     return hipGetLastError() == hipSuccess ? KS_OK : KS_ERR_HIP;
+}
+
+int kr_weight_grad_shadow(int32_t n, int32_t M, int32_t Na, int32_t Nb, const float* dz, const float* ha, int32_t lda, const float* hb, int32_t ldb,
+                          int32_t chunks, float* workspace, float* dW, float* db, void* stream) {
+    return weight_grad(n, n, M, Na, Nb, dz, ha, lda, hb, ldb, nullptr, chunks, workspace, dW, db, stream);
+}
+
+int kr_weight_grad_indexed(int32_t n, int32_t rows, int32_t M, int32_t Na, int32_t Nb, const float* dz, const float* ha, int32_t lda, const float* hb,
+                           int32_t ldb, const int32_t* idx, int32_t chunks, float* workspace, float* dW, float* db, void* stream) {
+    // (the lane offsets row * ld * 4 are 32-bit)
+    if (!idx || rows < 1 || M < 1 || lda < Na || (Nb > 0 && ldb < Nb) || (int64_t)rows * (M > lda ? (M > ldb ? M : ldb) : (lda > ldb ? lda : ldb)) * 4 >= (int64_t)OOR)
+        return KS_ERR_INVALID;
+    return weight_grad(n, rows, M, Na, Nb, dz, ha, lda, hb, ldb, idx, chunks, workspace, dW, db, stream);
 }
 
 int kr_actor_select(int32_t n, int32_t h1, int32_t h2, const float* obs, const float* prev_obs, const uint8_t* has_prev, const int64_t* t,

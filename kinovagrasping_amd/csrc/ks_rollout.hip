@@ -192,6 +192,17 @@ __device__ __forceinline__ long uniform_episode(float ue, long cnt, long head, i
     return ep < 0 ? ep + capacity : ep;
 }
 
+// where window w of the episode in ring slot `ep` starts (utils.py:283-301), and the episode's number of real windows: the one rule of
+// the window form (window_row) and of the table form (k_sample_tables)
+__device__ __forceinline__ long window_start(const Ring& g, long ep, float us, int H, int n_steps, int w, long& ceiling) {
+    ceiling = g.ep_len[ep] - n_steps;
+    ceiling = ceiling > 1 ? ceiling : 1;
+    long start = (long)(us * (float)ceiling);
+    start = start < H - n_steps ? start : H - n_steps;
+    if (w == ceiling - 1) start = ceiling;     // the final window of the episode
+    return start < H - n_steps ? start : H - n_steps;
+}
+
 // window row r = (b, w) of the batch, read from ring slot `ep`: the body k_sample_windows and k_gather_windows share
 __device__ __forceinline__ void window_row(const Ring& g, long ep, float us, bool none, int B, int H, int n_steps, int r, int w, int lane,
                                            float* __restrict__ next_ends, float* __restrict__ state, float* __restrict__ action,
@@ -199,12 +210,8 @@ __device__ __forceinline__ void window_row(const Ring& g, long ep, float us, boo
                                            float* weight, float real_weight = 1.0f) {
     const int W = H - n_steps;
     const float *ep_state = g.ep_state, *ep_next = g.ep_next, *ep_action = g.ep_action, *ep_reward = g.ep_reward, *ep_not_done = g.ep_not_done;
-    long ceiling = g.ep_len[ep] - n_steps;
-    ceiling = ceiling > 1 ? ceiling : 1;
-    long start = (long)(us * (float)ceiling);
-    start = start < H - n_steps ? start : H - n_steps;
-    if (w == ceiling - 1) start = ceiling;     // the final window of the episode (utils.py:283-301)
-    start = start < H - n_steps ? start : H - n_steps;
+    long ceiling;
+    const long start = window_start(g, ep, us, H, n_steps, w, ceiling);
     const long src = ep * H + start, dst = (long)r * n_steps;
     for (int k = lane; k < n_steps * S; k += WAVE) {
         state[dst * S + k] = ep_state[src * S + k];
@@ -242,6 +249,86 @@ __global__ __launch_bounds__(WAVE) void k_sample_windows(int B, int B_agent, int
     const float us = sample_uniform(u_start, r, 0x5a4eu, seed, draw);
     const long ep = uniform_episode(ue, cnt, g.head[0], g.capacity);
     window_row(g, ep, us, cnt < 2, B, H, n_steps, r, w, lane, next_ends, state, action, next_state, reward, not_done, weight);
+}
+
+// The batch as episode tables (kr_sample_tables_*): the window samplers' draws - the same uniforms, picks and window_start - but each batch
+// episode's H ring rows are copied ONCE (table_state / table_next [B * H, S], table_action [B * H, A], rows b * H + t) and a window row is
+// its first table row (row_table [B * W]).  A batch's B * W * n window states are drawn from these B * H rows, so what the learner computes
+// per state it computes once per table row.  Per window row only what the critic phase reads at R = B * W rows is written: state0, action0,
+// reward, not_done, weight; slot_weight [B] is the weight a real window row of slot b carries (real_weight: 1, or the episode's importance
+// weight).  Wave (b, w) copies the table rows w, w + W, ... of its episode.  table_row: window row r = (b, w) read from ring slot `ep`, the
+// body k_sample_tables and k_gather_tables share.
+struct Tables {
+    float *table_state, *table_next, *table_action;
+    int* row_table;
+    float *slot_weight, *state0, *action0, *reward, *not_done, *weight, *next_ends;
+};
+
+__device__ __forceinline__ void table_row(const Ring& g, long ep, float us, bool none, int B, int H, int n_steps, int r, int b, int w, int lane,
+                                          float real_weight, const Tables& o) {
+    const int W = H - n_steps;
+    long ceiling;
+    const long start = window_start(g, ep, us, H, n_steps, w, ceiling);
+    for (int t = w; t < H; t += W) {
+        const long src = (ep * H + t) * S, dst = ((long)b * H + t) * S;
+        for (int k = lane; k < S; k += WAVE) {
+            o.table_state[dst + k] = g.ep_state[src + k];
+            o.table_next[dst + k] = g.ep_next[src + k];
+        }
+        if (lane < A) o.table_action[((long)b * H + t) * A + lane] = g.ep_action[(ep * H + t) * A + lane];
+    }
+    const long src = ep * H + start;
+    for (int k = lane; k < S; k += WAVE) o.state0[(long)r * S + k] = g.ep_state[src * S + k];
+    // (a TD3fD learner's target pass keeps the window form's [2 B W, S] rows: its smoothing noise is keyed by the row)
+    if (o.next_ends != nullptr) {
+        for (int k = lane; k < S; k += WAVE) {
+            o.next_ends[(long)r * S + k] = g.ep_next[src * S + k];
+            o.next_ends[((long)B * W + r) * S + k] = g.ep_next[(src + n_steps - 1) * S + k];
+        }
+    }
+    if (lane < A) o.action0[(long)r * A + lane] = g.ep_action[src * A + lane];
+    if (lane < n_steps) {
+        o.reward[(long)r * n_steps + lane] = g.ep_reward[src + lane];
+        o.not_done[(long)r * n_steps + lane] = g.ep_not_done[src + lane];
+    }
+    if (lane == 0) {
+        o.weight[r] = (!none && w < ceiling) ? real_weight : 0.0f;
+        o.row_table[r] = b * H + (int)start;
+        if (w == 0) o.slot_weight[b] = real_weight;
+    }
+}
+
+__global__ __launch_bounds__(WAVE) void k_sample_tables(int B, int B_agent, int H, int n_steps, Ring ra, Ring re, const float* __restrict__ u_ep,
+                                                        const float* __restrict__ u_start, unsigned long long seed,
+                                                        const int64_t* __restrict__ draw, Tables o) {
+    const int W = H - n_steps;
+    const int r = blockIdx.x, lane = threadIdx.x;
+    if (r >= B * W) return;
+    const int b = r / W, w = r % W;
+    const Ring& g = b < B_agent ? ra : re;
+    const long cnt = g.count[0];
+    const float ue = sample_uniform(u_ep, b, 0x5a4du, seed, draw);
+    const float us = sample_uniform(u_start, r, 0x5a4eu, seed, draw);
+    const long ep = uniform_episode(ue, cnt, g.head[0], g.capacity);
+    table_row(g, ep, us, cnt < 2, B, H, n_steps, r, b, w, lane, 1.0f, o);
+}
+
+// The table gather behind a pick (kr_sample_tables_balanced, _prioritized, _balanced_prioritized): k_gather_windows' part with the episode
+// in picked[b].  with_weight: the pick left the episode's importance weight in every row of o.weight; each wave reads its own element
+// before it writes the row's weight there and touches no other.
+__global__ __launch_bounds__(WAVE) void k_gather_tables(int B, int B_agent, int H, int n_steps, Ring ra, Ring re, const int* __restrict__ picked,
+                                                        int with_weight, const float* __restrict__ u_start, unsigned long long seed,
+                                                        const int64_t* __restrict__ draw, Tables o) {
+    const int W = H - n_steps;
+    const int r = blockIdx.x, lane = threadIdx.x;
+    if (r >= B * W) return;
+    const int b = r / W, w = r % W;
+    const Ring& g = b < B_agent ? ra : re;
+    long ep = picked[b];
+    ep = ep < 0 ? 0 : (ep < g.capacity ? ep : g.capacity - 1);      // (the pick launch wrote a slot of this ring)
+    const float real_weight = with_weight ? o.weight[r] : 1.0f;
+    const float us = sample_uniform(u_start, r, 0x5a4eu, seed, draw);
+    table_row(g, ep, us, g.count[0] < 2, B, H, n_steps, r, b, w, lane, real_weight, o);
 }
 
 // ---- replay batches balanced over the episodes' classes (kr_sample_windows_balanced): the pick and the gather.
@@ -944,9 +1031,11 @@ __global__ __launch_bounds__(256) void k_target_smooth(int rows, float* __restri
     }
 }
 
-// start of an update's body: what used to be eight tiny library launches (sum, clamp, mul, div, copy, add, fill, copy)
-__global__ __launch_bounds__(WAVE) void k_update_prologue(int R, int n, const float* __restrict__ weight, float* __restrict__ wsum,
-                                                          float* __restrict__ dq_actor, int64_t* it, int64_t* it_head, int pipelined) {
+// start of an update's body: what used to be eight tiny library launches (sum, clamp, mul, div, copy, add, fill, copy).  The part
+// k_update_prologue and k_update_prologue_tables share: the sum of the weights, the counters; returns dLoss/dQ of the actor loss per unit
+// of weight.
+__device__ __forceinline__ float prologue_scale(int R, int n, const float* __restrict__ weight, float* __restrict__ wsum, int64_t* it,
+                                                int64_t* it_head, int pipelined) {
 #pragma clang fp contract(off)
     float s = 0;
     for (int r = threadIdx.x; r < R; r += WAVE) s += weight ? weight[r] : 1.0f;
@@ -957,8 +1046,41 @@ __global__ __launch_bounds__(WAVE) void k_update_prologue(int R, int n, const fl
         it[0] += 1;                                   // this update's number (Adam bias correction, soft-update phase)
         if (pipelined) it_head[0] = it[0];            // its actor step is applied by the NEXT update's head
     }
-    const float scale = -1.0f / (total * (float)n);   // d(-sum_r w_r sum_k Q_rk / (sum(w) n)) / dQ_rk
+    return -1.0f / (total * (float)n);                // d(-sum_r w_r sum_k Q_rk / (sum(w) n)) / dQ_rk
+}
+
+__global__ __launch_bounds__(WAVE) void k_update_prologue(int R, int n, const float* __restrict__ weight, float* __restrict__ wsum,
+                                                          float* __restrict__ dq_actor, int64_t* it, int64_t* it_head, int pipelined) {
+#pragma clang fp contract(off)
+    const float scale = prologue_scale(R, n, weight, wsum, it, it_head, pipelined);
     for (int i = threadIdx.x; i < R * n; i += WAVE) dq_actor[i] = (weight ? weight[i / n] : 1.0f) * scale;
+}
+
+// The prologue of an update on episode tables (k_sample_tables): dLoss/dQ per TABLE row - every real window row of batch slot b carries
+// slot_weight[b], so state (b, t) has the dq of k_update_prologue in every window that holds it - and the table row of each of the R * n
+// window states, -1 for the states of a weight-0 (padding) row, whose terms the window form adds as exact zeros.
+__global__ __launch_bounds__(WAVE) void k_update_prologue_tables(int R, int n, int B, int H, const float* __restrict__ weight,
+                                                                 const float* __restrict__ slot_weight, const int* __restrict__ row_table,
+                                                                 float* __restrict__ wsum, float* __restrict__ dq_table,
+                                                                 int* __restrict__ row_index, int64_t* it, int64_t* it_head, int pipelined) {
+#pragma clang fp contract(off)
+    const float scale = prologue_scale(R, n, weight, wsum, it, it_head, pipelined);
+    for (int i = threadIdx.x; i < B * H; i += WAVE) dq_table[i] = slot_weight[i / H] * scale;
+    for (int r = threadIdx.x; r < R; r += WAVE) {         // (by window row: no division per window state)
+        const bool real = weight[r] != 0.0f;
+        const int first = row_table[r];
+        for (int k = 0; k < n; k++) row_index[(long)r * n + k] = real ? first + k : -1;
+    }
+}
+
+// the target critic's Q of the table rows -> the [2R] layout the loss-gradient kernels take: the 1-step rows (the window's first next
+// state), then the n-step rows (its last)
+__global__ __launch_bounds__(WAVE) void k_gather_table_q(int R, int n, const int* __restrict__ row_table, const float* __restrict__ tq_table,
+                                                         float* __restrict__ tq) {
+    const int r = blockIdx.x * WAVE + threadIdx.x;
+    if (r >= R) return;
+    tq[r] = tq_table[row_table[r]];
+    tq[(long)R + r] = tq_table[row_table[r] + n - 1];
 }
 
 __global__ __launch_bounds__(256) void k_relu_backward(long count, const float* __restrict__ act, float* __restrict__ grad) {
@@ -1216,6 +1338,78 @@ int kr_sample_windows_mixed(int32_t batch, int32_t batch_agent, int32_t horizon,
     return launched();
 }
 
+// what every kr_sample_tables_* entry requires beyond sample_args_ok's terms, and its outputs as the kernels take them
+static bool tables_ok(const float* table_state, const float* table_next, const float* table_action, const int32_t* row_table, const float* slot_weight,
+                      const float* state0, const float* action0, const float* reward, const float* not_done, const float* weight) {
+    return table_state && table_next && table_action && row_table && slot_weight && state0 && action0 && reward && not_done && weight;
+}
+#define KR_TABLE_PARAMS float *table_state, float *table_next, float *table_action, int32_t *row_table, float *slot_weight, float *state0, float *action0, \
+                        float *reward, float *not_done, float *weight, float *next_ends
+#define KR_TABLE_ARGS table_state, table_next, table_action, row_table, slot_weight, state0, action0, reward, not_done, weight
+#define KR_TABLES Tables{table_state, table_next, table_action, row_table, slot_weight, state0, action0, reward, not_done, weight, next_ends}
+
+static int gather_tables(int32_t batch, int32_t batch_agent, int32_t horizon, int32_t n_steps, const kr_ring* agent, const kr_ring* expert,
+                         const int* picked, int with_weight, const float* u_start, uint64_t seed, const int64_t* draw, const Tables& o, void* stream) {
+    hipLaunchKernelGGL(k_gather_tables, dim3(batch * (horizon - n_steps)), dim3(WAVE), 0, (hipStream_t)stream, batch, batch_agent, horizon, n_steps,
+                       to_ring(agent), to_ring(expert), picked, with_weight, u_start, (unsigned long long)seed, draw, o);
+    return launched();
+}
+
+int kr_sample_tables_mixed(int32_t batch, int32_t batch_agent, int32_t horizon, int32_t n_steps, const kr_ring* agent, const kr_ring* expert,
+                           const float* u_ep, const float* u_start, uint64_t seed, const int64_t* draw, KR_TABLE_PARAMS, void* stream) {
+    if (!tables_ok(KR_TABLE_ARGS) ||
+        !sample_args_ok(batch, batch_agent, horizon, n_steps, agent, expert, u_ep, u_start, draw, table_state, action0, table_next, reward, not_done, weight))
+        return KS_ERR_INVALID;
+    hipLaunchKernelGGL(k_sample_tables, dim3(batch * (horizon - n_steps)), dim3(WAVE), 0, (hipStream_t)stream, batch, batch_agent, horizon, n_steps,
+                       to_ring(agent), to_ring(expert), u_ep, u_start, (unsigned long long)seed, draw, KR_TABLES);
+    return launched();
+}
+
+int kr_sample_tables_balanced(int32_t batch, int32_t batch_agent, int32_t horizon, int32_t n_steps, const kr_ring* agent, const kr_ring* expert,
+                              const int32_t* agent_class, const int32_t* expert_class, int32_t n_classes, int32_t rotation, const float* u_ep,
+                              const float* u_start, uint64_t seed, const int64_t* draw, KR_TABLE_PARAMS, int32_t* picked, void* stream) {
+    if (!picked || !tables_ok(KR_TABLE_ARGS) ||
+        !sample_args_ok(batch, batch_agent, horizon, n_steps, agent, expert, u_ep, u_start, draw, table_state, action0, table_next, reward, not_done, weight) ||
+        n_classes < 1 || n_classes > 64 || (batch_agent > 0 && !agent_class) || (batch_agent < batch && !expert_class))
+        return KS_ERR_INVALID;
+    hipLaunchKernelGGL(k_pick_balanced, dim3(batch), dim3(WAVE), 0, (hipStream_t)stream, batch, batch_agent, horizon - n_steps, to_ring(agent),
+                       to_ring(expert), agent_class, expert_class, n_classes, rotation, u_ep, (unsigned long long)seed, draw, picked, 0);
+    if (launched() != KS_OK) return KS_ERR_HIP;
+    return gather_tables(batch, batch_agent, horizon, n_steps, agent, expert, picked, 0, u_start, seed, draw, KR_TABLES, stream);
+}
+
+int kr_sample_tables_prioritized(int32_t batch, int32_t batch_agent, int32_t horizon, int32_t n_steps, const kr_ring* agent, const kr_ring* expert,
+                                 const uint32_t* agent_prio, const uint32_t* expert_prio, const float* beta, const float* u_ep, const float* u_start,
+                                 uint64_t seed, const int64_t* draw, KR_TABLE_PARAMS, int32_t* picked, void* stream) {
+    if (!picked || !tables_ok(KR_TABLE_ARGS) ||
+        !sample_args_ok(batch, batch_agent, horizon, n_steps, agent, expert, u_ep, u_start, draw, table_state, action0, table_next, reward, not_done, weight) ||
+        !beta || (batch_agent > 0 && (!agent_prio || agent->capacity > (1 << 20))) || (batch_agent < batch && (!expert_prio || expert->capacity > (1 << 20))))
+        return KS_ERR_INVALID;
+    // the pick hands every row its episode's importance weight in the weight output, where the gather wave of the row finds it
+    hipLaunchKernelGGL(k_pick_prioritized, dim3(batch), dim3(WAVE), 0, (hipStream_t)stream, batch, batch_agent, horizon - n_steps, n_steps, to_ring(agent),
+                       to_ring(expert), agent_prio, expert_prio, beta, u_ep, (unsigned long long)seed, draw, picked, reward, weight);
+    if (launched() != KS_OK) return KS_ERR_HIP;
+    return gather_tables(batch, batch_agent, horizon, n_steps, agent, expert, picked, 1, u_start, seed, draw, KR_TABLES, stream);
+}
+
+int kr_sample_tables_balanced_prioritized(int32_t batch, int32_t batch_agent, int32_t horizon, int32_t n_steps, const kr_ring* agent,
+                                          const kr_ring* expert, const int32_t* agent_class, const int32_t* expert_class, int32_t n_classes,
+                                          int32_t rotation, const uint32_t* agent_prio, const uint32_t* expert_prio, const float* beta,
+                                          const float* u_ep, const float* u_start, uint64_t seed, const int64_t* draw, KR_TABLE_PARAMS,
+                                          int32_t* picked, void* stream) {
+    if (!picked || !tables_ok(KR_TABLE_ARGS) ||
+        !sample_args_ok(batch, batch_agent, horizon, n_steps, agent, expert, u_ep, u_start, draw, table_state, action0, table_next, reward, not_done, weight) ||
+        n_classes < 1 || n_classes > 64 || !beta ||
+        (batch_agent > 0 && (!agent_class || !agent_prio || agent->capacity > (1 << 20))) ||
+        (batch_agent < batch && (!expert_class || !expert_prio || expert->capacity > (1 << 20))))
+        return KS_ERR_INVALID;
+    hipLaunchKernelGGL(k_pick_balanced_prioritized, dim3(batch), dim3(WAVE), 0, (hipStream_t)stream, batch, batch_agent, horizon - n_steps, n_steps,
+                       to_ring(agent), to_ring(expert), agent_class, expert_class, n_classes, rotation, agent_prio, expert_prio, beta, u_ep,
+                       (unsigned long long)seed, draw, picked, reward, weight);
+    if (launched() != KS_OK) return KS_ERR_HIP;
+    return gather_tables(batch, batch_agent, horizon, n_steps, agent, expert, picked, 1, u_start, seed, draw, KR_TABLES, stream);
+}
+
 int kr_commit_classes(int32_t n, int32_t capacity, const uint8_t* keep, const int64_t* rank, const int64_t* head, const int32_t* env_class,
                       int32_t* ep_class, void* stream) {
     if (n <= 0 || capacity <= 0 || !keep || !rank || !head || !env_class || !ep_class) return KS_ERR_INVALID;
@@ -1349,6 +1543,23 @@ int kr_update_prologue(int32_t rows, int32_t n_steps, const float* weight, float
                        int32_t pipelined, void* stream) {
     if (rows <= 0 || n_steps <= 0 || !weight_sum || !dq_actor || !it || !it_head) return KS_ERR_INVALID;
     hipLaunchKernelGGL(k_update_prologue, dim3(1), dim3(WAVE), 0, (hipStream_t)stream, rows, n_steps, weight, weight_sum, dq_actor, it, it_head, pipelined);
+    return launched();
+}
+
+int kr_update_prologue_tables(int32_t rows, int32_t n_steps, int32_t batch, int32_t horizon, const float* weight, const float* slot_weight,
+                              const int32_t* row_table, float* weight_sum, float* dq_table, int32_t* row_index, int64_t* it, int64_t* it_head,
+                              int32_t pipelined, void* stream) {
+    if (rows <= 0 || n_steps <= 0 || batch <= 0 || horizon < n_steps || !weight || !slot_weight || !row_table || !weight_sum || !dq_table ||
+        !row_index || !it || !it_head)
+        return KS_ERR_INVALID;
+    hipLaunchKernelGGL(k_update_prologue_tables, dim3(1), dim3(WAVE), 0, (hipStream_t)stream, rows, n_steps, batch, horizon, weight, slot_weight,
+                       row_table, weight_sum, dq_table, row_index, it, it_head, pipelined);
+    return launched();
+}
+
+int kr_gather_table_q(int32_t rows, int32_t n_steps, const int32_t* row_table, const float* tq_table, float* tq, void* stream) {
+    if (rows <= 0 || n_steps <= 0 || !row_table || !tq_table || !tq) return KS_ERR_INVALID;
+    hipLaunchKernelGGL(k_gather_table_q, dim3((rows + WAVE - 1) / WAVE), dim3(WAVE), 0, (hipStream_t)stream, rows, n_steps, row_table, tq_table, tq);
     return launched();
 }
 

@@ -32,6 +32,11 @@ where they coincide:
   coefficient from them, then the step on g * coef; `every` is 1 but for TD3fD's actor), self.clip [3, 2] holding the (norm, coef) of
   actor, critic and critic2.  In the pipelined form the actor's norm is taken at the head, on the gradient buffer the body left.
 
+On a batch drawn as episode tables (replay.TableBatch; phase_critic_tables / phase_actor_tables, the LDS-free forms) the passes whose result
+for a row depends on that row alone - the actor phase's forwards and data gradients, DDPGfD's target networks - run once per distinct state
+(B * H table rows) instead of once per window that holds it (B * W * n rows), and the actor's weight gradients read their terms through an
+index (kr_weight_grad_indexed): the window form's results bit for bit (docs/kernels.md).
+
 All of these are LDS-free.  With world_size > 1 the flat gradient buffers are all-reduced directly (no pack /
 unpack).  Same arithmetic as the reference (critic loss L1 + 0.5 LN on masked row means, actor loss -mean Q(s, pi(s))
 over all n-step rows, Adam lr 1e-4 / default lr + weight_decay 1e-4, soft target update every 10th call);
@@ -326,10 +331,46 @@ class NativeDDPGfDUpdate:
         # both target evaluations (1-step: next_state[:, 0], n-step: next_state[:, -1]) in one pass of the target nets
         # (next_ends: the sampler's own [2R, S] block of exactly these rows, kr_sample_windows_draw)
         nx = torch.cat([next_state[:, 0], next_state[:, -1]], 0) if next_ends is None else next_ends
+        return self._critic_phase(state[:, 0], action[:, 0], reward, weight, lambda: self._window_targets(nx, target_noise), priorities)
+
+    def _window_targets(self, nx, target_noise):
+        """every target critic's Q on the [2R] rows nx (the windows' first next states, then their last)"""
+        ta = self._target_actions(nx, target_noise)
+        return [self._target_q(ct, nx, ta) for ct in self.critic_targets]
+
+    def _table_targets(self, tb):
+        """DDPGfD on episode tables: the target networks on the T table rows of table_next - every next state once - and the [2R] rows the
+        loss gradient takes gathered from their Q (kr_gather_table_q).  Row-independent kernels: the bits of _window_targets."""
+        P, R = _sim._ptr, tb.weight.shape[0]
+        tq_table = self._window_targets(tb.table_next, None)[0]
+        tq = tq_table.new_empty(2 * R, 1)
+        self._chk(self.lib.kr_gather_table_q(R, tb.n_steps, P(tb.row_table), P(tq_table), P(tq), self._st()), "kr_gather_table_q")
+        return [tq]
+
+    @torch.no_grad()
+    def phase_critic_tables(self, tb, priorities=None, target_noise=None):
+        """phase_critic on a replay.TableBatch (LDS-free forms only): the same launches at R rows for the critics; the target networks see
+        the T = B * H table rows instead of 2R window ends (DDPGfD; TD3fD's smoothing noise is keyed by the row of [2R]: it keeps those
+        rows, tb.next_ends).  The prologue writes dLoss/dQ of the actor loss per table row and the window states' table rows for
+        phase_actor_tables.  Every result is bit for bit phase_critic's on tb.windows()."""
+        assert self.lds_free, "the table form runs on the LDS-free kernels"
+        pol, P = self.p, _sim._ptr
+        R, T = tb.weight.shape[0], tb.table_state.shape[0]
+        assert tb.n_steps == pol.n and (not self.td3 or tb.next_ends is not None)
+        self.weight, self.wsum = tb.weight, torch.empty(1, device=tb.weight.device)
+        self.dq_table = torch.empty(T, 1, device=tb.weight.device)
+        self.row_index = torch.empty(R * pol.n, dtype=torch.int32, device=tb.weight.device)
+        self._chk(self.lib.kr_update_prologue_tables(R, pol.n, T // tb.horizon, tb.horizon, P(tb.weight), P(tb.slot_weight), P(tb.row_table), P(self.wsum),
+                                                     P(self.dq_table), P(self.row_index), P(self.it), P(self.it_head), int(self.pipelined), self._st()),
+                  "kr_update_prologue_tables")
+        targets = (lambda: self._window_targets(tb.next_ends, target_noise)) if self.td3 else (lambda: self._table_targets(tb))
+        return self._critic_phase(tb.state0, tb.action0, tb.reward, tb.weight, targets, priorities)
+
+    def _critic_phase(self, s0, a0, reward, weight, targets, priorities):
+        """phase_critic behind its prologue: s0 / a0 [R, *] the windows' first state and action, targets() the target critics' [2R] Q"""
         with self._branch(0):       # (the fork form: the target networks, 3200 rows each, beside the critic's own forward on the phase's stream)
-            ta = self._target_actions(nx, target_noise)
-            tqs = [self._target_q(ct, nx, ta) for ct in self.critic_targets]
-        qs, saved = zip(*[self._critic_forward(c, state, action) for c in self.critics])
+            tqs = targets()
+        qs, saved = zip(*[self._critic_forward(c, s0, a0) for c in self.critics])
         self._join(0)
         reward = reward.contiguous()
         dqs, boot = self._loss_grad(qs, tqs, reward, weight)
@@ -380,9 +421,8 @@ class NativeDDPGfDUpdate:
         self._chk(getattr(self.lib, name)(R, pol.n, *args, P(self.losses), self._st()), name)
         return dqs, boot
 
-    def _critic_forward(self, c, state, action):
-        """Q of the windows' first rows; returns (q, what _critic_backward needs)"""
-        s0, a0 = state[:, 0], action[:, 0]
+    def _critic_forward(self, c, s0, a0):
+        """Q of the windows' first rows s0 / a0; returns (q, what _critic_backward needs)"""
         R = s0.shape[0]
         if self.lds_free:
             # the whole critic step without LDS: forward, loss gradient, data and weight gradients (csrc/ks_mlp.hip)
@@ -406,10 +446,11 @@ class NativeDDPGfDUpdate:
         else:
             self._weight_grads(c, *saved, dq)
 
-    def _backward(self, net, dz3, x, xa, h1, h2):
+    def _backward(self, net, dz3, x, xa, h1, h2, idx=None):
         """LDS-free: dz3 = the gradient at the pre-activation of net's last layer, [x, xa] its input -> net.grad.  The fork form: the last
-        layer's weight gradient needs dz3 only and the second's dz2 only: on the side streams, beside the data-gradient pass and the first's."""
-        last = lambda: _mlp.weight_grad(dz3, h2, None, net.gW[2], net.gb[2])
+        layer's weight gradient needs dz3 only and the second's dz2 only: on the side streams, beside the data-gradient pass and the first's.
+        idx (the table form): the weight gradients' terms are the rows idx[r] of these tensors (mlp.weight_grad)."""
+        last = lambda: _mlp.weight_grad(dz3, h2, None, net.gW[2], net.gb[2], idx=idx)
         if self.fork:
             with self._branch(0):
                 last()
@@ -417,8 +458,8 @@ class NativeDDPGfDUpdate:
         if not self.fork:
             last()
         with self._branch(1):
-            _mlp.weight_grad(dz2, h1, None, net.gW[1], net.gb[1])
-        _mlp.weight_grad(dz1, x, xa, net.gW[0], net.gb[0])
+            _mlp.weight_grad(dz2, h1, None, net.gW[1], net.gb[1], idx=idx)
+        _mlp.weight_grad(dz1, x, xa, net.gW[0], net.gb[0], idx=idx)
         self._join(0, 1)
 
     @torch.no_grad()
@@ -431,18 +472,7 @@ class NativeDDPGfDUpdate:
         sa = state.reshape(-1, state.shape[2])
         a_, c = self.actor, self.critic
         if self.lds_free:
-            rows = sa.shape[0]
-            al, cl = a_.layers, c.layers
-            ha1, ha2 = sa.new_empty(rows, a_.W[0].shape[0]), sa.new_empty(rows, a_.W[1].shape[0])
-            a = _mlp.mlp3_forward(al, sa, act=_mlp.ACT_SIGMOID, scale=pol.max_action, h1_out=ha1, h2_out=ha2, **self._form)
-            hc1, hc2 = sa.new_empty(rows, c.W[0].shape[0]), sa.new_empty(rows, c.W[1].shape[0])
-            q = _mlp.mlp3_forward(cl, sa, a, act=_mlp.ACT_NONE, h1_out=hc1, h2_out=hc2, **self._form)       # Q itself is not needed
-            if self.track_actor_loss:
-                self._set_actor_loss(q, n)
-            dq = self.dq_actor
-            # dLoss/d(actor pre-activation): through the critic to its action inputs, then through 0.8 * sigmoid
-            _, _, dz3 = _mlp.mlp3_backward(cl, dq, hc1, hc2, want_dz=False, dx_cols=(sa.shape[1], a.shape[1]), act_out=a, scale=pol.max_action, lean=self.lean_kernels)
-            self._backward(a_, dz3, sa, None, ha1, ha2)
+            self._actor_rows(sa, self.dq_actor, n, None)
             return None
         if self.fused_targets and self.fuse_actor_fwd:
             rows = sa.shape[0]
@@ -466,6 +496,35 @@ class NativeDDPGfDUpdate:
         self._chk(self.lib.kr_sigmoid_scale_backward(da.numel(), P(a), pol.max_action, P(da), self._st()), "kr_sigmoid_scale_backward")
         self._weight_grads(a_, sa, ha1, ha2, da)
         return None
+
+    def _actor_rows(self, sa, dq, n, idx):
+        """LDS-free: the actor phase's passes on the states sa with dLoss/dQ dq per row -> self.actor.grad.  idx None: sa are the window
+        states themselves; else (the table form) sa are table rows, each evaluated once, and the sums over the window states - the weight
+        gradients, the tracked loss - read row idx[r] for state r (-1: a padding row's, which adds exact zeros in the window form)."""
+        pol, a_, c = self.p, self.actor, self.critic
+        rows = sa.shape[0]
+        al, cl = a_.layers, c.layers
+        ha1, ha2 = sa.new_empty(rows, a_.W[0].shape[0]), sa.new_empty(rows, a_.W[1].shape[0])
+        a = _mlp.mlp3_forward(al, sa, act=_mlp.ACT_SIGMOID, scale=pol.max_action, h1_out=ha1, h2_out=ha2, **self._form)
+        hc1, hc2 = sa.new_empty(rows, c.W[0].shape[0]), sa.new_empty(rows, c.W[1].shape[0])
+        q = _mlp.mlp3_forward(cl, sa, a, act=_mlp.ACT_NONE, h1_out=hc1, h2_out=hc2, **self._form)       # Q itself is not needed
+        if self.track_actor_loss:
+            self._set_actor_loss(q if idx is None else q[idx.long().clamp(min=0)], n)
+        # dLoss/d(actor pre-activation): through the critic to its action inputs, then through 0.8 * sigmoid
+        _, _, dz3 = _mlp.mlp3_backward(cl, dq, hc1, hc2, want_dz=False, dx_cols=(sa.shape[1], a.shape[1]), act_out=a, scale=pol.max_action, lean=self.lean_kernels)
+        self._backward(a_, dz3, sa, None, ha1, ha2, idx=idx)
+
+    @torch.no_grad()
+    def phase_actor_tables(self, tb):
+        """phase_actor on a replay.TableBatch, after phase_critic_tables: the four per-row passes (actor and critic forward, the critic's data
+        gradient to the action columns, the actor's data gradient) run on the T = B * H table rows - a row's result depends on that row's
+        inputs only, and every real window of batch slot b carries the same dq -, the actor's three weight gradients keep their R * n
+        terms, order and chunks and read each term through its table row.  self.actor.grad is bit for bit phase_actor's on tb.windows()
+        (padding rows, which add exact zeros there, read as zeros here)."""
+        assert self.lds_free, "the table form runs on the LDS-free kernels"
+        for net in self.critics:
+            self._adam(net, self.it)
+        self._actor_rows(tb.table_state, self.dq_table, tb.n_steps, self.row_index)
 
     def _set_actor_loss(self, q, n):
         """-sum_r w_r sum_k Q_rk / (sum(w) n)  (DDPGfD.py:341: -critic(state, actor(state)).mean())"""
@@ -503,6 +562,17 @@ class NativeDDPGfDUpdate:
             return
         dist.all_reduce(g, op=dist.ReduceOp.SUM, group=self.p.process_group)
         g.div_(world)
+
+    def train_on_tables(self, tb, target_noise=None):
+        """train_on_batch on a replay.TableBatch: bit for bit train_on_batch(*tb.windows()) (the sign of an exactly-zero Adam moment aside)"""
+        losses = self.phase_critic_tables(tb, target_noise=target_noise)
+        self.allreduce("critic")
+        if self.td3:
+            self.allreduce("critic2")
+        self.phase_actor_tables(tb)
+        self.allreduce("actor")
+        self.phase_targets()
+        return losses
 
     def train_on_batch(self, state, action, next_state, reward, weight=None, target_noise=None):
         losses = self.phase_critic(state, action, next_state, reward, weight, target_noise=target_noise)

@@ -135,15 +135,24 @@ def mlp3_backward(layers, dz3: torch.Tensor, h1: torch.Tensor, h2: torch.Tensor,
     return dz2, dz1, dx
 
 
-def weight_grad(dz: torch.Tensor, ha: torch.Tensor, hb: torch.Tensor | None, dW: torch.Tensor, db: torch.Tensor, rows_per_chunk: int = 400):
-    """dW [M, N] = dz^T [ha | hb], db [M] = dz.sum(0) without LDS (kr_weight_grad_shadow), written in place."""
-    n, M = dz.shape
+def weight_grad(dz: torch.Tensor, ha: torch.Tensor, hb: torch.Tensor | None, dW: torch.Tensor, db: torch.Tensor, rows_per_chunk: int = 400,
+                idx: torch.Tensor | None = None):
+    """dW [M, N] = dz^T [ha | hb], db [M] = dz.sum(0) without LDS (kr_weight_grad_shadow), written in place.
+    idx int32 [n] (kr_weight_grad_indexed): the sums run over n terms, term r being row idx[r] of dz / ha / hb (zeros where idx[r] is not
+    a row) - bit for bit the plain form on dz[idx], ha[idx], hb[idx]."""
+    rows, M = dz.shape
+    n = rows if idx is None else idx.numel()
+    assert idx is None or (idx.dtype == torch.int32 and idx.is_contiguous() and idx.device == dz.device and ha.shape[0] == rows and (hb is None or hb.shape[0] == rows))
     Na, Nb = ha.shape[1], (0 if hb is None else hb.shape[1])
     assert dz.is_contiguous() and ha.stride(1) == 1 and (hb is None or hb.stride(1) == 1) and dW.is_contiguous() and tuple(dW.shape) == (M, Na + Nb)
     assert db.is_contiguous() and db.numel() == M
     chunks = max(1, (n + rows_per_chunk - 1) // rows_per_chunk)
     ws = torch.empty(chunks * (M * (Na + Nb) + M), device=dz.device, dtype=torch.float32)
     lib, P = _sim.load_library(), _sim._ptr
-    rc = lib.kr_weight_grad_shadow(n, M, Na, Nb, P(dz), P(ha), ha.stride(0), P(hb), 0 if hb is None else hb.stride(0), chunks, P(ws), P(dW), P(db), _stream(dz))
+    ld = (ha.stride(0), P(hb), 0 if hb is None else hb.stride(0))
+    if idx is None:
+        rc = lib.kr_weight_grad_shadow(n, M, Na, Nb, P(dz), P(ha), *ld, chunks, P(ws), P(dW), P(db), _stream(dz))
+    else:
+        rc = lib.kr_weight_grad_indexed(n, rows, M, Na, Nb, P(dz), P(ha), *ld, P(idx), chunks, P(ws), P(dW), P(db), _stream(dz))
     if rc != 0:
-        raise RuntimeError(f"kr_weight_grad_shadow failed ({rc})")
+        raise RuntimeError(f"kr_weight_grad_{'shadow' if idx is None else 'indexed'} failed ({rc})")

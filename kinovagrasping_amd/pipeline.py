@@ -75,7 +75,7 @@ def _concurrent_stream(main, dev, tries=8):
 class GraphedTrainer:
     def __init__(self, sim, policy, replay, engine, batch_episodes=64, overlap=True, learn_after=31, expert_replay=None, expert_prob=0.3,
                  updates_per_step=1, lean_learner=False, balanced=False, prioritized=False, per_alpha=0.3, per_beta=1.0, per_eps=1e-3,
-                 per_eps_expert=1.0):
+                 per_eps_expert=1.0, tables=None):
         """updates_per_step U / batch_episodes: the update-to-data knobs.  The reference makes 100 updates per 30-step episode of ONE
         env (main_DDPGfD.py:474-486: ~3 per stored transition); BASELINE config 3 - bench.py's workload - is ONE update on 64 episodes
         per env-step of 4096 envs.  U > 1 replays the captured update U times per env-step (the step becomes learner-bound beyond
@@ -99,7 +99,11 @@ class GraphedTrainer:
         (kr_update_priorities after kr_critic_grad).  Calls enable_priorities() on the ring(s); self.picked as with balanced;
         set_per_beta anneals beta, also under captured graphs.  Priorities are per rank: nothing about them is exchanged.
         balanced and prioritized: every batch is drawn with replay.sample_balanced_prioritized - the slot's class by the balanced rule, the
-        episode within the class by priority -, everything else as with prioritized."""
+        episode within the class by priority -, everything else as with prioritized.
+        tables: draw every batch as episode tables (replay.sample_tables, whichever sampler the trainer uses) and run the update on them
+        (NativeDDPGfDUpdate.phase_*_tables): each of a batch's B * H distinct states goes through the per-row passes once instead of once per
+        window that holds it, with the window form's results bit for bit.  None: whenever the learner is LDS-free and the rings are on the
+        device; False keeps the window form (A/B runs, tests).  self.batch is the window form either way (see the property)."""
         assert engine.gen is None, "graph capture uses the default CUDA generator"
         self.sim, self.policy, self.replay, self.eng = sim, policy, replay, engine
         self.expert_replay, self.expert_prob = expert_replay, float(expert_prob)
@@ -161,6 +165,11 @@ class GraphedTrainer:
             except ValueError:
                 pass                     # neither form: the caller decides (AsyncTrainer raises)
         self.native.pipelined = True
+        can_tables = bool(self.native.lds_free and replay.native)
+        if tables and not can_tables:
+            raise ValueError("tables=True needs the LDS-free learner kernels and device rings")
+        self.tables = can_tables if tables is None else bool(tables)
+        self._batch = self._tb = None
         # the gradient exchange between the ranks: an LDS-free all-reduce over peer-mapped memory where the ranks can map each
         # other's buffers (one process per GPU on a node) - it runs beside the stepping kernel, which a library collective
         # cannot (its kernels need LDS).  Self-tested against the process group at start-up; KS_P2P=0 keeps the library path.
@@ -189,8 +198,20 @@ class GraphedTrainer:
     # -- learner phases on the static batch -------------------------------------------------------------
     def _sample(self):
         # (uniforms drawn in the sampling kernel, keyed by the update count: no generator-state launches in the graph)
+        if self.tables:
+            self._tb = self.replay.sample_tables(self.mix, self.batch_episodes, self.expert_prob, draw=self.native.it, seed=self.sample_seed,
+                                                 next_ends=self.native.td3, balanced=self.balanced, prioritized=self.prioritized,
+                                                 beta=self.per_beta if self.prioritized else 1.0)
+            self.picked = self._tb.picked
+            return
         out = self._sampler(draw=self.native.it if self.replay.native else None, seed=self.sample_seed)
-        self.batch, self.picked = (out[:-1], out[-1]) if (self.prioritized or self.balanced) else (out, None)
+        self._batch, self.picked = (out[:-1], out[-1]) if (self.prioritized or self.balanced) else (out, None)
+
+    @property
+    def batch(self):
+        """the last update's batch in the window form.  The table form: rebuilt from the tables on EVERY access - three [R, n, *] gathers (the
+        tables change under a captured graph's replays, so nothing is kept) -, the same bits; for tests and inspection, not for a loop."""
+        return self._tb.windows() if self.tables and self._tb is not None else self._batch
 
     def set_per_beta(self, beta: float):
         """the importance weights' exponent from the next update on (a fill of the device scalar the sampler reads: fine between graph replays)"""
@@ -212,12 +233,18 @@ class GraphedTrainer:
         self._sample()
 
     def _phase1(self):
-        st, ac, ns, rw, nd, w = self.batch[:6]
-        self.loss_c = self.native.phase_critic(st, ac, ns, rw, w, next_ends=self.batch[6] if len(self.batch) > 6 else None,
+        if self.tables:
+            self.loss_c = self.native.phase_critic_tables(self._tb, priorities=self._update_priorities if self.prioritized else None)
+            return
+        st, ac, ns, rw, nd, w = self._batch[:6]
+        self.loss_c = self.native.phase_critic(st, ac, ns, rw, w, next_ends=self._batch[6] if len(self._batch) > 6 else None,
                                                priorities=self._update_priorities if self.prioritized else None)
 
     def _phase2(self):
-        self.native.phase_actor(self.batch[0], self.batch[5])     # (its actor Adam step runs in the next update's head: native.pipelined)
+        if self.tables:
+            self.native.phase_actor_tables(self._tb)
+            return
+        self.native.phase_actor(self._batch[0], self._batch[5])     # (its actor Adam step runs in the next update's head: native.pipelined)
 
     def _allreduce_critics(self):
         self.native.allreduce("critic")
@@ -464,8 +491,9 @@ class AsyncTrainer(GraphedTrainer):
 
     def __init__(self, sim, policy, replay, engine, batch_episodes=64, expert_replay=None, expert_prob=0.3, updates_per_step=1,
                  launch_synchronous=False, max_launch_steps=60, balanced=False, prioritized=False, per_alpha=0.3, per_beta=1.0, per_eps=1e-3,
-                 per_eps_expert=1.0):
-        """prioritized, per_*: as GraphedTrainer's (prioritized replay; commit_published gives the episodes it collects the ring's prio_max);
+                 per_eps_expert=1.0, tables=None):
+        """tables: as GraphedTrainer's (the update on episode tables; the default at every width AsyncTrainer takes).
+        prioritized, per_*: as GraphedTrainer's (prioritized replay; commit_published gives the episodes it collects the ring's prio_max);
         not with launch_synchronous, whose staging ring carries no priorities.
         balanced: as GraphedTrainer's (class-balanced batches: what lets a ring that a time-budgeted or free-running rollout fills at each
         object's own pace train every object alike); not with launch_synchronous, whose staging ring carries no classes.
@@ -482,7 +510,7 @@ class AsyncTrainer(GraphedTrainer):
             raise ValueError("AsyncTrainer: launch_synchronous stages episodes in a ring without priorities - not with prioritized=True")
         super().__init__(sim, policy, replay, engine, batch_episodes=batch_episodes, overlap=True, expert_replay=expert_replay, expert_prob=expert_prob,
                          updates_per_step=updates_per_step, lean_learner="auto", balanced=balanced, prioritized=prioritized, per_alpha=per_alpha,
-                         per_beta=per_beta, per_eps=per_eps, per_eps_expert=per_eps_expert)
+                         per_beta=per_beta, per_eps=per_eps, per_eps_expert=per_eps_expert, tables=tables)
         self.launch_synchronous = bool(launch_synchronous)
         if self.launch_synchronous and getattr(replay, "ep_class", None) is not None:
             raise ValueError("AsyncTrainer: launch_synchronous stages episodes in a ring without classes - not with a replay that has classes set")

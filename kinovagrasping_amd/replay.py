@@ -11,6 +11,7 @@ from __future__ import annotations
 import ctypes
 import json
 from pathlib import Path
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -126,6 +127,31 @@ def _i32_bits(value: int) -> int:
     """the int32 with the bit pattern of the uint32 `value` (torch's uint32 has few kernels: tables are written through an int32 view)"""
     value = int(value) & 0xFFFFFFFF
     return value - (1 << 32) if value >= (1 << 31) else value
+
+
+class TableBatch(NamedTuple):
+    """A replay batch as episode tables (DeviceEpisodeReplay.sample_tables; include/kinova_rollout.h: kr_sample_tables_mixed).  B batch
+    episodes, H = horizon, W = H - n_steps, R = B * W window rows."""
+    table_state: torch.Tensor      # [B * H, S] row b * H + t: row t of batch slot b's episode, as the ring holds it
+    table_next: torch.Tensor       # [B * H, S]
+    table_action: torch.Tensor     # [B * H, A]
+    row_table: torch.Tensor        # int32 [R]: b * H + start of window row (b, w), padding rows included
+    slot_weight: torch.Tensor      # [B]: the weight every real window row of slot b carries
+    state0: torch.Tensor           # [R, S] the window rows' first state ...
+    action0: torch.Tensor          # [R, A] ... and action
+    reward: torch.Tensor           # [R, n]
+    not_done: torch.Tensor         # [R, n]
+    weight: torch.Tensor           # [R]
+    n_steps: int
+    horizon: int
+    next_ends: torch.Tensor | None = None      # [2 R, S] on request: next_state[:, 0] and next_state[:, -1] stacked (a TD3fD learner's target rows)
+    picked: torch.Tensor | None = None         # int32 [B] behind a balanced or prioritized pick: the ring slot of every batch episode
+
+    def windows(self):
+        """the window form of the same batch: (state [R, n, S], action [R, n, A], next_state, reward, not_done, weight), every bit what
+        sample_mixed returns for the same draws"""
+        t = self.row_table.long().unsqueeze(1) + torch.arange(self.n_steps, device=self.row_table.device)
+        return self.table_state[t], self.table_action[t], self.table_next[t], self.reward, self.not_done, self.weight
 
 
 class DeviceEpisodeReplay:
@@ -498,16 +524,96 @@ class DeviceEpisodeReplay:
     def _windows_of(self, ep, u):
         """the window rows of the episodes in ring slots ep [B] with the start uniforms u [B, W] (torch path)"""
         n, W, batch_size = self.n_steps, self.horizon - self.n_steps, ep.shape[0]
+        start, weight = self._starts_of(ep, u)
+        t = start.unsqueeze(-1) + self._win                                  # [B,W,n]
+        e = ep.view(-1, 1, 1).expand(-1, W, n)
+        g = lambda x: x[e, t].reshape(batch_size * W, n, *x.shape[2:])
+        return g(self.ep_state), g(self.ep_action), g(self.ep_next), g(self.ep_reward), g(self.ep_not_done), weight
+
+    def _starts_of(self, ep, u):
+        """where the W windows of the episodes in ring slots ep [B] start, [B, W] (start uniforms u [B, W]), and the rows' 0 / 1 weights [B * W]"""
+        n, W = self.n_steps, self.horizon - self.n_steps
         ceiling = (self.ep_len[ep] - n).clamp(min=1)       # [B]
         row = self._row                                                      # [1,W]
         start = (u * ceiling.unsqueeze(1)).long().clamp(max=self.horizon - n)
         start = torch.where(row == (ceiling.unsqueeze(1) - 1), ceiling.unsqueeze(1).expand(-1, W), start)
         start = start.clamp(max=self.horizon - n)
         weight = ((row < ceiling.unsqueeze(1)) & (self._count >= 2)).float().reshape(-1)     # nothing to sample from < 2 episodes
-        t = start.unsqueeze(-1) + self._win                                  # [B,W,n]
-        e = ep.view(-1, 1, 1).expand(-1, W, n)
-        g = lambda x: x[e, t].reshape(batch_size * W, n, *x.shape[2:])
-        return g(self.ep_state), g(self.ep_action), g(self.ep_next), g(self.ep_reward), g(self.ep_not_done), weight
+        return start, weight
+
+    def sample_tables(self, expert, batch_size, prob=0.3, uniforms=None, draw=None, seed=0, generator=None, next_ends=False, balanced=False,
+                      prioritized=False, beta=1.0, rotation=0):
+        """sample_mixed's batch (expert None: sample_batch_nstep's; balanced / prioritized: sample_balanced's, sample_prioritized's or
+        sample_balanced_prioritized's, with their `rotation` and `beta`, their requirements of the rings, and `picked` in the result)
+        as EPISODE TABLES, a TableBatch: the same draws, but every batch episode's
+        `horizon` ring rows once (table_state / table_next [B * H, S], table_action [B * H, A]) and per window row the index of its first state (row_table), the
+        weight of the slot's real rows (slot_weight [B]) and what the critic phase reads at R = B * W rows (state0, action0, reward,
+        not_done, weight).  TableBatch.windows() is sample_mixed's batch bit for bit.  The learner evaluates the B * H table rows where
+        the window form makes it evaluate the B * W * n window states drawn from them (NativeDDPGfDUpdate.phase_critic_tables /
+        phase_actor_tables).  On the GPU one launch (kr_sample_tables_mixed), behind a pick two (kr_sample_tables_balanced, _prioritized,
+        _balanced_prioritized: the window samplers' pick, the table gather); the torch path is their checker."""
+        if expert is not None and (expert.horizon != self.horizon or expert.n_steps != self.n_steps):
+            raise ValueError("sample_tables: the expert ring must have the agent ring's horizon and n_steps")
+        both = [self] + ([expert] if expert is not None else [])
+        if balanced and (any(r.ep_class is None for r in both) or any(r.class_names != self.class_names for r in both)):
+            raise ValueError("sample_tables: balanced needs rings with the same classes (set_env_classes)")
+        if prioritized and any(r.ep_prio is None for r in both):
+            raise ValueError("sample_tables: prioritized needs rings with priorities (enable_priorities)")
+        if prioritized:
+            beta = self._beta_tensor(beta, "sample_tables")
+        b_agent = batch_size if expert is None else int(batch_size * (1 - prob))
+        n, H, W, dev = self.n_steps, self.horizon, self.horizon - self.n_steps, self.device
+        S, A = self.ep_state.shape[2], self.ep_action.shape[2]
+        R, T = batch_size * W, batch_size * H
+        if self.native and (expert is None or expert.native):
+            f = lambda *shape: torch.empty(*shape, device=dev)
+            out = TableBatch(f(T, S), f(T, S), f(T, A), torch.empty(R, dtype=torch.int32, device=dev), f(batch_size), f(R, S), f(R, A), f(R, n), f(R, n), f(R), n, H,
+                             f(2 * R, S) if next_ends else None, torch.empty(batch_size, dtype=torch.int32, device=dev) if (balanced or prioritized) else None)
+            if uniforms is None and draw is None:
+                uniforms = torch.rand(batch_size * (W + 1), device=dev, generator=generator)
+            u = None if uniforms is None else uniforms.contiguous()
+            P = self._ptr
+            ra = self._ring()
+            re = ra if expert is None else expert._ring()
+            other = lambda t: None if expert is None else P(getattr(expert, t))
+            pick_args = ((P(self.ep_class), other("ep_class"), len(self.class_names), int(rotation)) if balanced else ()) + \
+                        ((P(self.ep_prio), other("ep_prio"), P(beta)) if prioritized else ())
+            entry = "kr_sample_tables_" + ("_".join(k for k, on in (("balanced", balanced), ("prioritized", prioritized)) if on) or "mixed")
+            # (a pick rotates with the draw counter whatever the uniforms are, as in the window samplers; kr_sample_tables_mixed takes one or the other)
+            d = draw if (balanced or prioritized or u is None) else None
+            self._check(getattr(self._lib, entry)(batch_size, b_agent, H, n, ctypes.byref(ra), ctypes.byref(re), *pick_args, P(u),
+                                                  P(u[batch_size:]) if u is not None else None, int(seed) & (2 ** 64 - 1), P(d),
+                                                  *[P(t) for t in out[:10]], P(out.next_ends), *([P(out.picked)] if out.picked is not None else []),
+                                                  self._stream()), entry)
+            return out
+        if uniforms is None:
+            uniforms = torch.rand(batch_size * (W + 1), device=dev, generator=generator)
+        ue, us = uniforms[:batch_size], uniforms[batch_size:].view(batch_size, W)
+        parts, picks = [], []
+        for ring, lo, hi in ((self, 0, b_agent), (expert, b_agent, batch_size)):
+            if hi > lo:
+                w_ep, dd = None, (0 if draw is None else int(draw))
+                if balanced and prioritized:
+                    ep, w_ep = ring._pick_balanced_prioritized(ue[lo:hi], rotation, dd, beta)
+                elif prioritized:
+                    ep, w_ep = ring._pick_prioritized(ue[lo:hi], beta)
+                else:
+                    ep = ring._pick_balanced(ue[lo:hi], rotation, dd) if balanced else ring._pick_uniform(ue[lo:hi])
+                start, weight = ring._starts_of(ep, us[lo:hi])
+                if w_ep is not None:
+                    weight = weight * w_ep.repeat_interleave(W)                  # (0 / 1 times the episode's weight)
+                picks.append(ep.to(torch.int32))
+                src = (ep.view(-1, 1), start)                                    # the window rows' first ring rows
+                row_table = (torch.arange(lo, hi, device=dev).view(-1, 1) * H + start).reshape(-1).to(torch.int32)
+                parts.append((ring.ep_state[ep].reshape(-1, S), ring.ep_next[ep].reshape(-1, S), ring.ep_action[ep].reshape(-1, A), row_table, torch.ones(hi - lo, device=dev) if w_ep is None else w_ep,
+                              ring.ep_state[src].reshape(-1, S), ring.ep_action[src].reshape(-1, A),
+                              ring.ep_reward[ep.view(-1, 1, 1), start.unsqueeze(-1) + ring._win].reshape(-1, n),
+                              ring.ep_not_done[ep.view(-1, 1, 1), start.unsqueeze(-1) + ring._win].reshape(-1, n), weight))
+        tb = TableBatch(*[torch.cat([p[k] for p in parts], 0) for k in range(10)], n, H, None, torch.cat(picks) if (balanced or prioritized) else None)
+        if next_ends:
+            nx = tb.windows()[2]
+            tb = tb._replace(next_ends=torch.cat([nx[:, 0], nx[:, -1]], 0))
+        return tb
 
     def _pick_balanced(self, ue, rotation, d):
         """sample_balanced's pick on this ring (torch path, the checker of k_pick_balanced): the ring slot of every batch slot of the

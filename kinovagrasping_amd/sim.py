@@ -101,6 +101,7 @@ ROLLOUT_EXPORTS = ["kr_select_action", "kr_store_transition", "kr_rank_episodes"
                    "kr_target_smooth", "kr_twin_critic_grad", "kr_adam_step_every",
                    "kr_critic_grad_bounded", "kr_grad_sqnorm", "kr_adam_step_clipped",
                    "kr_mlp3_forward", "kr_mlp3_forward_shadow", "kr_mlp3_forward_split", "kr_mlp3_backward_shadow", "kr_mlp3_backward_split", "kr_weight_grad_shadow",
+                   "kr_sample_tables_mixed", "kr_sample_tables_balanced", "kr_sample_tables_prioritized", "kr_sample_tables_balanced_prioritized", "kr_update_prologue_tables", "kr_gather_table_q", "kr_weight_grad_indexed",
                    "kr_mlp3_forward_lean", "kr_mlp3_backward_lean",
                    "kr_actor_select", "kr_controller_select"]
 
@@ -203,6 +204,14 @@ def _bind(L):
     i64 = C.c_int64
     L.kr_critic_grad.argtypes = [i32, i32] + [vp] * 6 + [f32, vp, vp, vp]
     L.kr_update_prologue.argtypes = [i32, i32, vp, vp, vp, vp, vp, i32, vp]
+    L.kr_update_prologue_tables.argtypes = [i32] * 4 + [vp] * 8 + [i32, vp]
+    L.kr_gather_table_q.argtypes = [i32, i32, vp, vp, vp, vp]
+    L.kr_sample_tables_mixed.argtypes = [i32, i32, i32, i32, C.POINTER(KrRing), C.POINTER(KrRing), vp, vp, C.c_uint64, vp] + [vp] * 11 + [vp]
+    rings_ = [i32, i32, i32, i32, C.POINTER(KrRing), C.POINTER(KrRing)]
+    tail_ = [vp, vp, C.c_uint64, vp] + [vp] * 11 + [vp, vp]           # uniforms, seed, draw, the table outputs, picked, stream
+    L.kr_sample_tables_balanced.argtypes = rings_ + [vp, vp, i32, i32] + tail_
+    L.kr_sample_tables_prioritized.argtypes = rings_ + [vp, vp, vp] + tail_
+    L.kr_sample_tables_balanced_prioritized.argtypes = rings_ + [vp, vp, i32, i32, vp, vp, vp] + tail_
     L.kr_relu_backward.argtypes = [i64, vp, vp, vp]
     L.kr_sigmoid_scale_backward.argtypes = [i64, vp, f32, vp, vp]
     L.kr_adam_step.argtypes = [i64, vp, vp, vp, vp, vp, f32, f32, f32, f32, f32, vp]
@@ -222,6 +231,7 @@ def _bind(L):
     L.kr_mlp3_backward_split.argtypes = mlp_bwd + [vp, C.c_int64, i32, vp]
     L.kr_mlp3_backward_lean.argtypes = mlp_bwd + [vp, C.c_int64, vp]
     L.kr_weight_grad_shadow.argtypes = [i32] * 4 + [vp, vp, i32, vp, i32, i32, vp, vp, vp, vp]
+    L.kr_weight_grad_indexed.argtypes = [i32] * 5 + [vp, vp, i32, vp, i32, vp, i32, vp, vp, vp, vp]
     L.kr_actor_select.argtypes = [i32] * 3 + [vp] * 12 + [C.c_uint64, vp, f32, f32, i32] + [vp] * 5
     return L
 
