@@ -1,0 +1,462 @@
+"""Aimed contact-free states for the smooth dynamics and the contact-free solve (dynamics_rows, make_constraints, constrained_step and the Euler
+step of csrc/ks_core.h) - the analogue of tests/plane_poses.py for the stage between the collision code and the state update.
+
+Every state is built from the oracle and the model blob alone, with fixed seeds, and every input (qpos, qvel, qacc_warmstart, ctrl, action, hand
+quaternion, object mass) is rounded to fp32 before the oracle sees it: kernel and oracle start from the same numbers.  The hand is parked in the
+air (palm about PARK_Z above the floor, in each of the three named hand poses), the object flies at least 0.3 m from hand and floor.  No state has
+a contact: `clearance` certifies from the oracle's geom poses and the blob's hull tables that the floor and every hull pair stand CLEAR = 5 mm
+beyond the pair's margin and that the oracle's own ncon is 0; a state that misses either is dropped and counted (at most DROP_CAP of a class:
+tests/test_dynamics_cpu.py).
+
+Classes (states(cls, shape)):
+
+  free_flight   the object at random orientations, body-frame spin 8 - 30 rad/s, linear speed up to 2 m/s, the hand at rest; object mass 0.5 x,
+                1 x and 3 x nominal.  Shapes (SHAPE_ROLES): no asset has an isotropic inertia - CubeS (8.6, 8.6, 1.9e-5: axially symmetric, COM at
+                the origin) stands for the shape most tests use, Vase1S (ratio 16) and Cone1S (ratio 5) are clearly anisotropic, Cone1S has its COM
+                12 mm off the body origin with a turned inertial frame, BottleS (multi-geom library) has it 0.2 m off.
+                Aimed: w x I w with ms = mo / m.mass[9], w x (w x c), the quaternion step at |w| h up to 0.3.
+  finger_swing  proximal and distal speeds of 4 - 10 rad/s of either sign, one finger at a time and all three, the slides moving up to 0.5 m/s; joint angles at
+                tendon rest (q_p - 2 q_d = 0).  Aimed: the planar-chain a = w x (w x r) terms with the distal-origin term, the slide rows through
+                SCR_SB.
+  tendon        the tendon residual of each finger on TENDON_LADDER (in units of solimp's width: all three regimes of impedance(), both signs), at
+                zero and non-zero tendon velocity
+  limits_slide  each slide beyond each end of its range by BEYOND and inside it by INSIDE, with velocity into the limit, out of it and zero
+  limits_hinge  the same for the proximal hinges 3, 5 and 7 (the distal joint follows at tendon rest)
+  limits_multi  two and three limits at once, and a hinge limit together with an off-rest tendon
+  actuator      (ks_substep only) each of the nine controls at ACT_MULTIPLES times its clamp (act[2], act[4]; the feed-forward controls, which have no
+                clamp, times their nominal value) and one fp32 step inside and outside either clamp; the feed-forward controls non-zero
+  warm_start    states of the limit and tendon classes given as qacc_warmstart the oracle's solution, zero, the unconstrained qacc_smooth and a
+                vector 100 times too large: the problem is convex, the result is the same
+
+The three limit classes are one family: with every rung at every velocity it holds more states than one class may (300).
+BEYOND has one rung beside the decades, 7e-4: with solimp's width of 1e-3 the five decades reach only the first and the last regime of
+impedance() on a limit row.
+"""
+from __future__ import annotations
+
+import zlib
+from collections import namedtuple
+from functools import lru_cache
+
+import numpy as np
+
+from kinovagrasping_amd import scenarios
+from kinovagrasping_amd.sim import SOLVER_ITERATIONS
+from tests import contact_poses as cp, plane_ref as pr
+
+POSES = cp.NAMED_POSES
+SHAPE_ROLES = {"CubeS": "axially symmetric inertia, COM at the body origin (the shape of most tests)",
+               "Vase1S": "anisotropic inertia (16 : 1)",
+               "Cone1S": "anisotropic inertia (5 : 1), COM 12 mm off the body origin, turned inertial frame",
+               "BottleS": "multi-geom library; COM 0.2 m off the body origin"}
+FLIGHT_SHAPES = ("CubeS", "Vase1S", "Cone1S")
+MG_SHAPE = "BottleS"
+HAND_SHAPE = "CubeS"                      # the classes that aim at the hand do not depend on the object
+CLASSES = ("free_flight", "finger_swing", "tendon", "limits_slide", "limits_hinge", "limits_multi", "actuator", "warm_start")
+LIMIT_CLASSES = ("limits_slide", "limits_hinge", "limits_multi")
+MG_CLASSES = ("free_flight",) + LIMIT_CLASSES
+CLEAR = 5e-3                              # every pair and the floor this far beyond the pair's margin
+OBJECT_AWAY = 0.3                         # the object's distance from the hand and the floor
+DROP_CAP = 0.02
+UNDECIDABLE_CAP = 0.05
+PARK_Z = 0.40                             # palm height of the parked hand
+MASS_FACTORS = (0.5, 1.0, 3.0)
+BEYOND = (3e-6, 3e-5, 3e-4, 7e-4, 3e-3, 3e-2)
+INSIDE = (3e-6, 3e-5, 3e-4, 3e-3, 3e-2)
+TENDON_LADDER = (0.1, 0.3, 0.5, 0.7, 0.9, 1.0, 1.5, 5.0, 50.0)       # |residual| / solimp width: x <= 0.5, 0.5 < x < 1, x >= 1
+ACT_MULTIPLES = (-1.5, -1.0, -0.5, 0.0, 0.5, 1.0, 1.5)
+FF_NOMINAL = 0.733 * 10 / 25              # the env layer's feed-forward control on the vertical slide
+LIMIT_DOF = (0, 1, 2, 3, 5, 7)
+# A proximal hinge beyond the upper end of its range (2 rad) with the distal joint at tendon rest (1 rad) lies in the palm, and two fingers up
+# there lie in each other: the upper hinge limit is contact-free only one finger at a time with the distal joint opened to about -0.5 rad (8 mm
+# clear), the other fingers at 0.2 - 0.4.  Those states carry a tendon 3 rad off its rest.
+UPPER_DISTAL = -0.5
+MOVE = 1e-6                               # decidability: the oracle's active set survives moving the joint by this much
+
+States = namedtuple("States", "cls shape qpos qvel warm ctrl action hq mass tag clear")    # clear: per state (certified clearance, object distance)
+
+
+def f32(a):
+    return np.asarray(a, dtype=np.float32).astype(np.float64)
+
+
+def rng_for(cls, shape):
+    return np.random.default_rng([zlib.crc32(f"{cls}/{shape}".encode()), 7])
+
+
+def model(shape):
+    return cp._oracle(shape).M
+
+
+def constants(M):
+    """solimp (dmin, dmax, width), solref (timeconst, dampratio), dt, and the row constants b, k of aref = -b vel - k imp pos"""
+    opt = M["opt"]
+    dt, tc, dr, dmin, dmax, width = opt[0], max(opt[4], 2 * opt[0]), opt[5], opt[6], opt[7], opt[8]
+    return dict(dt=dt, dmin=dmin, dmax=dmax, width=width, b=2.0 / (dmax * tc), k=1.0 / (dmax * dmax * tc * tc * dr * dr))
+
+
+def limit_range(M, j):
+    """(lo, hi) of limited joint j of LIMIT_DOF, read from the blob"""
+    if j < 3:
+        return tuple(M["slide_range"][j])
+    assert M["hinge_limited"][2 * (j - 3)] != 0
+    return tuple(M["hinge_range"][2 * (j - 3)])
+
+
+# ---- the oracle at a state -------------------------------------------------------------------------------------------------------------
+def oracle_sim(shape, hq):
+    orc = cp._oracle(shape)
+    return orc.sim(hq)
+
+
+@lru_cache(maxsize=None)
+def slide_dirs(pose):
+    """(world direction of every slide [3, 3], palm position with the slides at 0) in a named hand pose"""
+    hq = f32(scenarios.hand_quat_for(pose))
+    orc = cp._oracle(HAND_SHAPE)
+    q = np.zeros(16)
+    q[12], q[9:12] = 1.0, cp.FAR
+    p0 = orc.geom_pose(hq, q, 1)[1]
+    D = np.zeros((3, 3))
+    for j in range(3):
+        qq = q.copy()
+        qq[j] = 0.1
+        D[j] = (orc.geom_pose(hq, qq, 1)[1] - p0) / 0.1
+    return D, p0
+
+
+def park(pose, rng, fixed=None):
+    """slide values with the palm PARK_Z above the floor; `fixed` {slide: value} are kept (a slide at its limit), the free ones carry the height
+    and a random horizontal offset.  None where the fixed slides leave the hand below 0.25 m."""
+    D, p0 = slide_dirs(pose)
+    fixed = fixed or {}
+    q = np.zeros(3)
+    free = [j for j in range(3) if j not in fixed]
+    for j, v in fixed.items():
+        q[j] = v
+    for j in free:
+        q[j] = rng.uniform(-0.12, 0.12)
+    w = D[free, 2]
+    if len(free) and np.abs(w).max() > 0.3:
+        need = PARK_Z - p0[2] - D[:, 2] @ q
+        q[free] += need * w / (w @ w)
+    q[free] = np.clip(q[free], -0.45, 0.45)
+    return q if p0[2] + D[:, 2] @ q >= 0.25 else None
+
+
+def hull_gap(A, B, dirs, enough=0.02):
+    """a lower bound of the distance of two convex point sets: the widest gap along any of the unit directions (and their refinements, until it
+    is `enough`)"""
+    best, bd = -np.inf, None
+    c = B.mean(0) - A.mean(0)
+    D = np.vstack([dirs, c / (np.linalg.norm(c) + 1e-300)])
+    for _ in range(3):
+        gap = (B @ D.T).min(0) - (A @ D.T).max(0)
+        i = int(np.argmax(gap))
+        if gap[i] > best:
+            best, bd = float(gap[i]), D[i]
+        if best >= enough:
+            break
+        D = bd + 0.15 * dirs
+        D /= np.linalg.norm(D, axis=1)[:, None]
+    return best
+
+
+@lru_cache(maxsize=None)
+def _sphere_dirs(n=200):
+    i = np.arange(n) + 0.5
+    phi, th = np.arccos(1 - 2 * i / n), np.pi * (1 + 5 ** 0.5) * i
+    return np.stack([np.cos(th) * np.sin(phi), np.sin(th) * np.sin(phi), np.cos(phi)], 1)
+
+
+_hand_gap_cache = {}
+
+
+def clearance(shape, hq, qpos):
+    """(the oracle's ncon, the smallest distance beyond its margin of the floor and of every hull pair - a certified lower bound -, the object's
+    distance from hand and floor) at a pose:
+    floor pairs from the lowest hull vertex, object-hand pairs from the bounding spheres, hand-hand pairs (a function of the finger angles alone)
+    from the widest separating gap over a set of directions"""
+    orc = cp._oracle(shape)
+    M = orc.M
+    o = orc.sim(hq)
+    o.set_state(qpos, np.zeros(15), np.zeros(15))
+    o.forward()
+    xmat, xpos = o.view("geom_xmat").reshape(-1, 3, 3).copy(), o.view("geom_xpos").reshape(-1, 3).copy()
+    worst = obj = np.inf
+    key = (shape,) + tuple(np.round(qpos[3:9], 9))
+    hand = []
+    for g1, g2, _, _, margin in np.asarray(M["pairs"]):
+        g1, g2 = int(g1), int(g2)
+        if g1 == 0:
+            d = float(pr.vertex_dist(xmat[g2], xpos[g2], pr.hull_of(M, g2)).min())
+        elif g2 >= 8:
+            d = float(np.linalg.norm(xpos[g1] - xpos[g2]) - M["geom_rbound"][g1] - M["geom_rbound"][g2])
+        else:
+            if key not in _hand_gap_cache:
+                hand.append((g1, g2, margin))
+            continue
+        worst = min(worst, d - margin)
+        if g2 >= 8:
+            obj = min(obj, d)
+    if key not in _hand_gap_cache:
+        W = {g: pr.hull_of(M, g) @ xmat[g].T + xpos[g] for g in range(1, 8)}
+        _hand_gap_cache[key] = min(hull_gap(W[a], W[b], _sphere_dirs()) - mg for a, b, mg in hand)
+    return int(o.s.ncon), min(worst, _hand_gap_cache[key]), obj
+
+
+# ---- building blocks -------------------------------------------------------------------------------------------------------------------
+def unit(rng, n=3):
+    v = rng.normal(size=n)
+    return v / np.linalg.norm(v)
+
+
+def base_state(shape, pose, rng, fixed=None, closure=None):
+    """a parked hand with the fingers at tendon rest, the object at rest far from it; None where `fixed` cannot be parked"""
+    s = park(pose, rng, fixed)
+    if s is None:
+        return None
+    q = np.zeros(16)
+    q[0:3] = s
+    a = rng.uniform(0.2, 1.0, 3) if closure is None else np.asarray(closure, dtype=np.float64)
+    q[3:9:2], q[4:9:2] = a, 0.5 * a
+    q[9:12] = [rng.uniform(1.3, 1.6), rng.uniform(1.3, 1.6), rng.uniform(0.9, 1.2)]
+    q[12:16] = unit(rng, 4)
+    return q
+
+
+class Builder:
+    def __init__(self, cls, shape):
+        self.cls, self.shape, self.rows, self.dropped, self.M = cls, shape, [], 0, model(shape)
+        self.redrawn = [0, 0]
+        self.nominal = float(self.M["body_mass"][9])
+
+    def add(self, pose, q, v=None, ctrl=None, warm=None, action=None, mass=1.0, tag=()):
+        hq = f32(scenarios.hand_quat_for(pose))
+        q = f32(q)
+        q[12:16] = f32(q[12:16] / np.linalg.norm(q[12:16]))
+        ncon, clear, obj = clearance(self.shape, hq, q)
+        if ncon != 0 or clear < CLEAR or obj < OBJECT_AWAY:
+            self.dropped += 1
+            return False
+        z = lambda a, n: np.zeros(n) if a is None else f32(a)
+        self.rows.append((q, z(v, 15), z(warm, 15), z(ctrl, 9), z(action, 4), hq, float(f32(mass * self.nominal)), (pose,) + tuple(tag), (clear, obj)))
+        return True
+
+    def done(self):
+        assert self.rows, (self.cls, self.shape)
+        col = lambda k: np.stack([r[k] for r in self.rows], 1)
+        s = States(self.cls, self.shape, col(0), col(1), col(2), col(3), col(4), col(5), np.array([r[6] for r in self.rows]), [r[7] for r in self.rows],
+                   np.array([r[8] for r in self.rows]))
+        _dropped[self.cls, self.shape] = self.dropped / (self.dropped + len(self.rows))
+        _redrawn[self.cls, self.shape] = self.redrawn
+        return s
+
+
+_dropped = {}
+_redrawn = {}
+
+
+def redraws(cls, shape):
+    """(draws of limits_multi set aside before a state was built because two fingers would stand beyond the upper end, because the pose cannot hold
+    the drawn slides in the air): no contact drops - nothing was generated -, counted all the same"""
+    states(cls, shape)
+    return _redrawn[cls, shape]
+
+
+def drop_share(cls, shape):
+    states(cls, shape)
+    return _dropped[cls, shape]
+
+
+def random_action(rng):
+    return rng.uniform(-0.6, 0.6, 4)
+
+
+# ---- the classes -----------------------------------------------------------------------------------------------------------------------
+def _free_flight(b, rng):
+    for i in range(180):
+        pose, mass = POSES[i % 3], MASS_FACTORS[(i // 3) % 3]
+        q = base_state(b.shape, pose, rng)
+        v = np.zeros(15)
+        v[9:12] = unit(rng) * rng.uniform(0.0, 2.0)
+        v[12:15] = unit(rng) * rng.uniform(8.0, 30.0)
+        b.add(pose, q, v, action=random_action(rng), mass=mass, tag=("mass", mass))
+
+
+def _finger_swing(b, rng):
+    for i in range(240):
+        pose, mode = POSES[i % 3], (i // 3) % 4          # mode 0 - 2: that finger alone, 3: all three
+        q = base_state(b.shape, pose, rng)
+        v = np.zeros(15)
+        v[0:3] = rng.uniform(-0.5, 0.5, 3)
+        for f in (range(3) if mode == 3 else (mode,)):
+            v[3 + 2 * f], v[4 + 2 * f] = rng.choice([-1, 1], 2) * rng.uniform(4, 10, 2)    # (below 4 rad/s the terms sink under 100 x the bound)
+        ctrl = np.zeros(9)
+        ctrl[0:6:2] = v[0:3]                             # the slide servos follow: no actuator force hides the slide rows
+        b.add(pose, q, v, ctrl=ctrl, action=random_action(rng), tag=("mode", mode))
+
+
+def _tendon(b, rng):
+    width = constants(b.M)["width"]
+    i = 0
+    for f in range(3):
+        for x in TENDON_LADDER:
+            for sign in (1, -1):
+                for rate in (0.0, 1.0, -1.0, 0.0):
+                    pose = POSES[i % 3]
+                    i += 1
+                    q = base_state(b.shape, pose, rng)
+                    r = sign * x * width
+                    q[4 + 2 * f] = 0.5 * (q[3 + 2 * f] - r)          # q_p - 2 q_d = r
+                    v = np.zeros(15)
+                    v[3 + 2 * f], v[4 + 2 * f] = 0.5 * rate, -0.25 * rate   # tendon velocity = rate
+                    ctrl = np.zeros(9)
+                    ctrl[6 + f] = v[3 + 2 * f]
+                    b.add(pose, q, v, ctrl=ctrl, action=random_action(rng), tag=("finger", f, "x", sign * x, "rate", rate))
+
+
+def limit_value(M, j, side, depth):
+    """joint value `depth` beyond (depth > 0) or inside (depth < 0) the lower (side 0) or upper (side 1) end of joint j's range"""
+    lo, hi = limit_range(M, j)
+    return lo - depth if side == 0 else hi + depth
+
+
+def _limit_state(b, rng, pose, specs, tendon=None):
+    """specs: [(joint j of LIMIT_DOF, side, depth, velocity into (+1) / out of (-1) the limit or 0)]; tendon: (finger, residual)"""
+    fixed = {j: limit_value(b.M, j, side, depth) for j, side, depth, _ in specs if j < 3}
+    upper = [j - 3 for j, side, _, _ in specs if j >= 3 and side == 1]
+    assert len(upper) <= 1
+    closure = rng.uniform(0.2, 0.4, 3) if upper else rng.uniform(0.3, 1.0, 3)
+    for j, side, depth, _ in specs:
+        if j >= 3:
+            closure[j - 3] = limit_value(b.M, j, side, depth)
+    q = base_state(b.shape, pose, rng, fixed, closure)
+    if q is None:
+        return None
+    for f in upper:
+        q[4 + 2 * f] = UPPER_DISTAL
+    v, ctrl = np.zeros(15), np.zeros(9)
+    for j, side, depth, vel in specs:
+        dof = LIMIT_DOF[j]
+        into = -1.0 if side == 0 else 1.0
+        if j < 3:
+            v[dof] = 0.1 * vel * into
+            ctrl[2 * j] = v[dof]                          # the servo follows: the row is not hidden behind 150 (ctrl - qvel)
+        else:
+            v[dof], v[dof + 1] = 0.5 * vel * into, 0.25 * vel * into
+            ctrl[6 + j - 3] = v[dof]
+    if tendon is not None:
+        f, r = tendon
+        q[4 + 2 * f] = 0.5 * (q[3 + 2 * f] - r)
+    return q, v, ctrl
+
+
+def _poses_for(M, rng, j, side):
+    """the named poses in which slide j can stand at this end of its range with the hand in the air (every pose for a hinge)"""
+    if j >= 3:
+        return list(POSES)
+    return [p for p in POSES if park(p, np.random.default_rng(0), {j: limit_value(M, j, side, 0.0)}) is not None]
+
+
+def _limits_single(b, rng, joints):
+    i = 0
+    for j in joints:
+        for side in (0, 1):
+            poses = _poses_for(b.M, rng, j, side)
+            assert poses, ("no hand pose holds the limit in the air", j, side)
+            for depth in BEYOND + tuple(-d for d in INSIDE):
+                for vel in (1, -1, 0):
+                    pose = poses[i % len(poses)]
+                    i += 1
+                    q, v, ctrl = _limit_state(b, rng, pose, [(j, side, depth, vel)])
+                    b.add(pose, q, v, ctrl=ctrl, action=random_action(rng), tag=("limit", ((j, side, depth, vel),)))
+
+
+def _limits_multi(b, rng):
+    n = 0
+    while n < 120:
+        k = 2 + n % 2
+        js = sorted(rng.choice(6, k, replace=False).tolist())
+        specs = [(j, int(rng.integers(2)), float(rng.choice(BEYOND)), int(rng.integers(-1, 2))) for j in js]
+        if sum(1 for j, side, _, _ in specs if j >= 3 and side == 1) > 1:
+            b.redrawn[0] += 1
+            continue                                       # two fingers beyond the upper end lie in each other
+        pose = POSES[int(rng.integers(3))]
+        st = _limit_state(b, rng, pose, specs)
+        if st is None:
+            b.redrawn[1] += 1
+            continue                                       # this pose cannot hold these slides in the air: draw again (no state is dropped)
+        n += 1
+        b.add(pose, *st[:2], ctrl=st[2], action=random_action(rng), tag=("limit", tuple(specs)))
+    width = constants(b.M)["width"]
+    for i in range(72):
+        j, side = 3 + i % 3, 0                             # (the upper end comes with an off-rest tendon of its own)
+        spec = (j, side, float(BEYOND[(i // 3) % len(BEYOND)]), int(i % 3) - 1)
+        x = TENDON_LADDER[i % len(TENDON_LADDER)] * (1 if (i // 2) % 2 else -1)
+        pose = POSES[i % 3]
+        q, v, ctrl = _limit_state(b, rng, pose, [spec], tendon=(j - 3, x * width))
+        b.add(pose, q, v, ctrl=ctrl, action=random_action(rng), tag=("limit", (spec,), "x", x))
+
+
+def act_clamps(M):
+    """the scale of each of the nine controls: its clamp, or for the feed-forward controls (no clamp) their nominal value"""
+    c = np.zeros(9)
+    c[0:6:2], c[1:6:2], c[6:9] = M["actuator"][2], FF_NOMINAL, M["actuator"][4]
+    return c
+
+
+def _actuator(b, rng):
+    clamp = act_clamps(b.M)
+    i = 0
+    for k in range(9):
+        c = np.float32(clamp[k])
+        edge = [np.nextafter(c, np.float32(0)), np.nextafter(c, np.float32(9)), np.nextafter(-c, np.float32(0)), np.nextafter(-c, np.float32(-9))]
+        for moving in (0, 1):
+            for val in [m * float(c) for m in ACT_MULTIPLES] + [float(e) for e in edge]:
+                pose = POSES[i % 3]
+                i += 1
+                q = base_state(b.shape, pose, rng)
+                v = np.zeros(15)
+                if moving:
+                    v[0:3] = rng.uniform(-0.2, 0.2, 3)
+                    a = rng.uniform(-0.4, 0.4, 3)
+                    v[3:9:2], v[4:9:2] = a, 0.5 * a
+                ctrl = np.zeros(9)
+                ctrl[0:6:2] = v[0:3]
+                ctrl[6:9] = v[3:9:2]
+                ctrl[1:6:2] = rng.choice([-1, 1], 3) * rng.uniform(0.1, 0.3, 3)
+                ctrl[k] = val
+                b.add(pose, q, v, ctrl=ctrl, tag=("ctrl", k, "value", val, "x", val / float(c)))
+
+
+WARM_KINDS = ("solution", "zero", "smooth", "x100")
+
+
+def _warm_start(b, rng):
+    from tests import dynamics_ref as dr
+    src = []                                               # 17 of each source, spread over the whole of it (the tendon's fingers, rungs and signs included)
+    for c in ("limits_slide", "limits_hinge", "limits_multi", "tendon"):
+        n = len(states(c, b.shape).tag)
+        src += [(c, (k * n) // 17 + (k % 5)) for k in range(17)]
+    for c, i in src:
+        s = states(c, b.shape)
+        ref = dr.reference(s, "substep")[i]
+        for kind in WARM_KINDS:
+            warm = dict(solution=ref.qacc, zero=np.zeros(15), smooth=ref.qacc_smooth, x100=100.0 * ref.qacc)[kind]
+            b.add(s.tag[i][0], s.qpos[:, i], s.qvel[:, i], ctrl=s.ctrl[:, i], action=s.action[:, i], warm=warm, tag=("warm", kind, "of", c, i) + tuple(s.tag[i][1:]))
+
+
+@lru_cache(maxsize=None)
+def states(cls: str, shape: str = HAND_SHAPE) -> States:
+    assert cls in CLASSES, cls
+    b, rng = Builder(cls, shape), rng_for(cls, shape)
+    dict(free_flight=_free_flight, finger_swing=_finger_swing, tendon=_tendon, limits_slide=lambda b, r: _limits_single(b, r, (0, 1, 2)),
+         limits_hinge=lambda b, r: _limits_single(b, r, (3, 4, 5)), limits_multi=_limits_multi, actuator=_actuator, warm_start=_warm_start)[cls](b, rng)
+    return b.done()
+
+
+def cases():
+    """[(class, shape)] of the standard library, then of the multi-geom library"""
+    out = [("free_flight", s) for s in FLIGHT_SHAPES] + [(c, HAND_SHAPE) for c in CLASSES[1:]]
+    return out + [(c, MG_SHAPE) for c in MG_CLASSES]

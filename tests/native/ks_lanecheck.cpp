@@ -40,10 +40,10 @@ template <typename T> struct SnapPut {
 
 template <typename T>
 static int substep_t(const Model<T>& m, double* qpos, double* qvel, double* warm, const double* ctrl, const double* hq, int iters, int* ncon,
-                     double* con, PairWarm* gw = nullptr) {
+                     double* con, PairWarm* gw = nullptr, double env_mass = 0) {   // env_mass > 0: the env's object mass (ks_set_env_params of the product)
     std::vector<T> scrbuf(SCR_TOTAL, T(0));
     Scratch<T> scr{scrbuf.data(), 1};
-    { T mass, mu; nominal_env_params(m, mass, mu); scr(SCR_ENVP) = mass; scr(SCR_ENVP + 1) = mu; }
+    { T mass, mu; nominal_env_params(m, mass, mu); scr(SCR_ENVP) = env_mass > 0 ? (T)env_mass : mass; scr(SCR_ENVP + 1) = mu; }
     LaneState<T> st;
     T c[NU], q4[4], R7[9];
     for (int i = 0; i < NQ; i++) st.qpos[i] = (T)qpos[i];
@@ -257,6 +257,12 @@ int lc_substep(void* h, int prec, double* qpos, double* qvel, double* warm, cons
     if (prec == 6432) return substep_mixed(l->d.m, l->f.m, qpos, qvel, warm, ctrl, hq, iters, ncon, con);
     return prec == 64 ? substep_t<double>(l->d.m, qpos, qvel, warm, ctrl, hq, iters, ncon, con)
                       : substep_t<float>(l->f.m, qpos, qvel, warm, ctrl, hq, iters, ncon, con, l->warm ? l->gw : nullptr);
+}
+// lc_substep with the env's object mass (0 = the model's own), fp64 and fp32 lanes
+int lc_substep_mass(void* h, int prec, double* qpos, double* qvel, double* warm, const double* ctrl, const double* hq, int iters, int* ncon, double* con, double obj_mass) {
+    LC* l = (LC*)h;
+    return prec == 64 ? substep_t<double>(l->d.m, qpos, qvel, warm, ctrl, hq, iters, ncon, con, nullptr, obj_mass)
+                      : substep_t<float>(l->f.m, qpos, qvel, warm, ctrl, hq, iters, ncon, con, l->warm ? l->gw : nullptr, obj_mass);
 }
 int lc_env_step(void* h, int prec, double* qpos, double* qvel, double* warm, const double* hq, const double* act, int frame_skip, int iters,
                 double* obs, double* reward, int* done, double* rays) {

@@ -23,6 +23,7 @@ def lanecheck_lib(multi_geom: bool = False):
     L.lc_create.argtypes = [C.c_char_p, C.c_size_t]
     L.lc_destroy.argtypes = [C.c_void_p]
     L.lc_substep.argtypes = [C.c_void_p, C.c_int, dp, dp, dp, dp, dp, C.c_int, C.POINTER(C.c_int), dp]
+    L.lc_substep_mass.argtypes = L.lc_substep.argtypes + [C.c_double]
     L.lc_env_step.argtypes = [C.c_void_p, C.c_int, dp, dp, dp, dp, dp, C.c_int, C.c_int, dp, dp, C.POINTER(C.c_int), dp]
     L.lc_reset_obs.argtypes = [C.c_void_p, C.c_int, dp, dp, dp, dp, dp, dp, C.POINTER(C.c_int), dp]
     L.lc_get_warm.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
@@ -45,13 +46,14 @@ class Lane:
         assert self.h, "lc_create failed (see stderr)"
         self.prec, self.iters = prec, iters
 
-    def substep(self, qpos, qvel, warm, ctrl, hq):
+    def substep(self, qpos, qvel, warm, ctrl, hq, obj_mass=0.0):
+        """obj_mass > 0: the env's object mass (ks_set_env_params of the product)"""
         a, b, c = (np.array(x, dtype=np.float64) for x in (qpos, qvel, warm))
         nc = C.c_int(0)
         ncm = self.L.lc_ncon_max()
         con = np.zeros(ncm * 20)
-        st = self.L.lc_substep(self.h, self.prec, P(a), P(b), P(c), P(np.array(ctrl, dtype=np.float64)), P(np.array(hq, dtype=np.float64)),
-                               self.iters, C.byref(nc), P(con))
+        args = (self.h, self.prec, P(a), P(b), P(c), P(np.array(ctrl, dtype=np.float64)), P(np.array(hq, dtype=np.float64)), self.iters, C.byref(nc), P(con))
+        st = self.L.lc_substep_mass(*args, C.c_double(obj_mass)) if obj_mass > 0 else self.L.lc_substep(*args)
         return a, b, c, nc.value, con.reshape(ncm, 20), st
 
     def env_step(self, qpos, qvel, warm, hq, act, frame_skip=15):
