@@ -86,16 +86,19 @@ static_assert(SCR_CON % 4 == 0 && SCR_STAGE % 4 == 0 && SCR_TOTAL % 4 == 0 && CO
 // per-pair / per-contact loops.  Teams are aligned groups of lanes of one wave.
 template <int SUBS> struct Team {
     int sub;
+    // The DPP controls used by sum / bcast / argmin (row_ror, quad_perm, row_newbcast) have a valid source lane for every lane, so
+    // bound_ctrl never fills anything in: it is set only so that the compiler need not initialise the destination (`old`) with a
+    // v_mov of its own in front of every DPP move.  scan's row_shr does mean its zero fill.
 #if defined(__HIP_DEVICE_COMPILE__)
     // x + (x of the lane this one is paired with under the DPP control word): one v_add_f32_dpp
     template <int CTRL> static __device__ __forceinline__ float dpp_add(float x) {
-        return x + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), CTRL, 0xf, 0xf, false));
+        return x + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), CTRL, 0xf, 0xf, true));
     }
 #endif
 #if defined(__HIP_DEVICE_COMPILE__)
     // x of the lane selected by the DPP control word (32-bit types)
     template <int CTRL, typename T> static __device__ __forceinline__ T dpp_get(T x) {
-        return __builtin_bit_cast(T, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), CTRL, 0xf, 0xf, false));
+        return __builtin_bit_cast(T, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), CTRL, 0xf, 0xf, true));
     }
 #endif
     template <typename T> KS_HD T sum(T x) const {
@@ -122,7 +125,7 @@ template <int SUBS> struct Team {
         if constexpr (SUBS == 1) return x;
         else if constexpr (sizeof(T) == 4) {
             static_assert(SUBS == 16, "row broadcast needs a full DPP row");
-            return __builtin_bit_cast(T, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x150 + SRC, 0xf, 0xf, false));
+            return __builtin_bit_cast(T, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x150 + SRC, 0xf, 0xf, true));
         } else return __shfl(x, SRC, SUBS);
 #else
         return x;
