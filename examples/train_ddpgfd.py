@@ -13,7 +13,7 @@
 
     python examples/train_ddpgfd.py --envs 1024 --steps 600 --hidden 256 256 (or 400 300: the reference's widths, free-running too) [--free-running] [--expert-prob 0] [--starts-per-env 64]
                                     [--success-map DIR] [--demonstrations free-running] [--randomize-params] [--prioritized]
-                                    [--q-bounds 0 50] [--huber-delta 10] [--max-grad-norm 10]
+                                    [--q-bounds 0 50] [--huber-delta 10] [--max-grad-norm 10] [--bc-weight 1 [--q-filter]]
 
 --success-map DIR (with --free-running): the stepping kernel logs every finished training episode (ks_set_episode_log); at every report
 the script folds the log (metrics.EpisodeLedger) and writes DIR/per_shape_success.jsonl and the success / fail start coordinates of the
@@ -99,6 +99,11 @@ def main():
                     "the critic stops growing at 2 D; default: the plain square")
     ap.add_argument("--max-grad-norm", type=float, default=None, metavar="G", help="clip each network's gradient to the global L2 norm G right before its Adam step "
                     "(torch.nn.utils.clip_grad_norm_; kr_grad_sqnorm + kr_adam_step_clipped); default: no clip")
+    ap.add_argument("--bc-weight", type=float, default=0.0, metavar="X", help="weight of the behaviour-cloning term of the actor loss on the expert episodes of every "
+                    "batch (Nair et al. 2018; kr_bc_actor_grad): pi(s) is pulled towards the demonstrated action; needs --expert-prob > 0; default 0: no such term. "
+                    "With --log-q the term and the filter's pass share are printed too")
+    ap.add_argument("--q-filter", action="store_true", help="with --bc-weight: only on the demonstration states where the critic rates the demonstrated action above "
+                    "the actor's own, Q(s, a) > Q(s, pi(s))")
     ap.add_argument("--expl-noise", type=float, default=0.1, help="exploration noise, std = 0.8 x this (main_DDPGfD.py:443-446: 0.1)")
     ap.add_argument("--dump-replay", default=None, help="write the replay (last 1500 agent + first 400 expert episodes) and the four networks as one .npz "
                     "(tools/r06/reference_learner_on_replay.py runs the REFERENCE's train_batch on it)")
@@ -106,7 +111,12 @@ def main():
     args = ap.parse_args()
     if args.success_map and not args.free_running:
         ap.error("--success-map needs --free-running")
-    bounded = dict(q_bounds=None if args.q_bounds is None else tuple(args.q_bounds), huber_delta=args.huber_delta, max_grad_norm=args.max_grad_norm)
+    if args.bc_weight > 0 and not args.expert_prob > 0:
+        ap.error("--bc-weight needs demonstrations in the batches: --expert-prob > 0")
+    if args.q_filter and not args.bc_weight > 0:
+        ap.error("--q-filter needs --bc-weight > 0")
+    bounded = dict(q_bounds=None if args.q_bounds is None else tuple(args.q_bounds), huber_delta=args.huber_delta, max_grad_norm=args.max_grad_norm,
+                   bc_weight=args.bc_weight, q_filter=args.q_filter)
     torch.manual_seed(args.seed)
     rng = np.random.RandomState(args.seed)
     dev = torch.device("cuda", 0)
@@ -150,7 +160,9 @@ def main():
         print(f"TD3fD: target smoothing noise {policy.policy_noise:g} clipped at {policy.noise_clip:g}, actor steps every {policy.policy_freq} update(s)")
     else:
         policy = DDPGfD(82, 4, 0.8, 5, tau=args.tau, batch_size=args.batch_episodes, hidden=tuple(args.hidden), device=dev, **bounded)
-    if any(v is not None for v in bounded.values()):
+    if policy.bc_weight > 0:
+        print(f"behaviour cloning on the expert episodes of every batch: weight {policy.bc_weight:g}, Q-filter {'on' if policy.q_filter else 'off'}")
+    if any(bounded[k] is not None for k in ("q_bounds", "huber_delta", "max_grad_norm")):
         print(f"bounded critic update: q_bounds {policy.q_bounds}, huber_delta {policy.huber_delta}, max_grad_norm {policy.max_grad_norm}")
     policy.network_repl_freq = args.target_every
     policy.actor_optimizer.param_groups[0]["lr"] = args.actor_lr
@@ -226,7 +238,12 @@ def main():
         dt = time.perf_counter() - t0 - t_eval
         ls = tr.native.losses.tolist()
         ev = ""
-        clip = ""
+        clip = bc = ""
+        mean_q = -tr.native.actor_loss.item() if args.log_q else 0.0
+        if args.log_q and args.bc_weight > 0:               # (the tracked actor loss holds the term as well)
+            bc_loss = tr.native.bc_loss.item()
+            mean_q += bc_loss
+            bc = f"  BC loss {bc_loss:8.5f} pass {tr.native.bc_pass.item():5.3f}"
         if args.log_q and args.max_grad_norm is not None:
             norm_c, coef_c = tr.native.clip[1].tolist()
             clip = f"  critic grad norm {norm_c:9.3f} coef {coef_c:6.4f}"
@@ -241,7 +258,7 @@ def main():
                 res = eval_policy(sim_eval, policy, sim_eval.reset(qe, hqe))
             ev = f"  eval (no noise, 1024 starts): lift success {res['num_success'] / 1024:.3f}"
             t_eval += time.perf_counter() - te
-        print(f"step {it + 60:5d}  episodes {d_ep:7d}  training lift rate {d_lift / max(1, d_ep):.3f}  critic loss {ls[0]:9.3f}{f' / {ls[3]:9.3f}' if args.td3 else ''}{f'  mean Q {-tr.native.actor_loss.item():8.3f}' if args.log_q else ''}{clip}  {n * (it + 60) / dt:9.0f} env-steps/s{ev}")
+        print(f"step {it + 60:5d}  episodes {d_ep:7d}  training lift rate {d_lift / max(1, d_ep):.3f}  critic loss {ls[0]:9.3f}{f' / {ls[3]:9.3f}' if args.td3 else ''}{f'  mean Q {mean_q:8.3f}' if args.log_q else ''}{bc}{clip}  {n * (it + 60) / dt:9.0f} env-steps/s{ev}")
     if args.free_running:
         c = tr.counts()
         print(f"free-running rollout: {c['episodes_finished']} episodes finished, {c['episodes_dropped']} dropped, {c['pacing_timeouts']} pacing time-outs, {tr.updates} updates")

@@ -419,6 +419,35 @@ int kr_adam_step_clipped(int64_t count, float *param, const float *grad, float *
                          const double *partials, float max_norm, float lr, float beta1, float beta2, float eps, float weight_decay,
                          float *clip_out, void *stream);
 
+/* ---- the behaviour-cloning term of the actor loss with its Q-filter (ddpgfd.DDPGfD / TD3fD with bc_weight, q_filter; Nair et al. 2018,
+ * "Overcoming Exploration in Reinforcement Learning with Demonstrations"): on the demonstration rows of a batch the actor loss gains
+ * bc_weight * sum_r w_r sum_k f_rk |pi(s_rk) - a_rk|^2 / (sum(w) n), whose coefficient per row is -dq[r] for the dq of kr_update_prologue
+ * (dq_actor) or kr_update_prologue_tables (dq_table).  One launch, fp32 without contraction, no LDS, no scratch, no atomics, vector loads
+ * and stores only (16 bytes per row of a [rows, 4] buffer); one thread per row, grid-stride.
+ *
+ *   kr_bc_actor_grad     adds the term's gradient to dz3 [rows, 4], dLoss/d(actor pre-activation), in place.  pi [rows, 4] the actor's
+ *                        output max_action * sigmoid(z), demo [rows, 4] the batch's actions, q_demo / q_pi [rows] the critic's Q(s, a) and
+ *                        Q(s, pi(s)) (both NULL: no filter), dq [rows].  Rows r < demo_from are agent rows.  Per row r >= demo_from:
+ *                          f       = 1 without the filter, else 1 where q_demo[r] > q_pi[r] and 0 otherwise - strict, on the floats as given;
+ *                                    a NaN on either side gives 0;
+ *                          pass[r] = f   (exact);
+ *                          d_j     = fl(pi_j - demo_j),  j = 0 .. 3;
+ *                          sq[r]   = fl(fl(fl(fl(d_0 d_0) + fl(d_1 d_1)) + fl(d_2 d_2)) + fl(d_3 d_3))  where f = 1, +0 where f = 0;
+ *                          and where f = 1, dq[r] != 0 (a NaN is not 0) and bc_weight != 0:
+ *                          c       = fl((2 bc_weight) * (-dq[r]))   - 2 bc_weight is exact -;
+ *                          s_j     = fl(pi_j * fl(1 - fl(pi_j / max_action)))   - kr_sigmoid_scale_backward's factor in its order -;
+ *                          dz3_j   = fl(dz3_j + fl(fl(c d_j) s_j)).
+ *                        Rows r < demo_from: sq[r] = pass[r] = +0.  A dz3 row that receives nothing - an agent row, f = 0, dq[r] = 0 (a
+ *                        padding row), bc_weight = 0 - is not stored and keeps every bit (a -0.0 and a NaN too); a row with f = 0 does
+ *                        not read pi, demo or dz3, so a NaN in pi reaches its own row only, and only where f = 1.  demo_from = rows: dz3 is
+ *                        untouched, sq and pass are all +0.  pi, demo, q_demo, q_pi and dq are not written.
+ *                        KS_ERR_INVALID, nothing launched or written: rows <= 0; demo_from outside [0, rows]; a NULL pi, demo, dq, dz3, sq
+ *                        or pass; a pi, demo or dz3 that is not 16-byte aligned; exactly one of q_demo / q_pi NULL; bc_weight negative or
+ *                        NaN; max_action <= 0 or NaN.
+ */
+int kr_bc_actor_grad(int32_t rows, int32_t demo_from, const float *pi, const float *demo, const float *q_demo, const float *q_pi, const float *dq,
+                     float bc_weight, float max_action, float *dz3, float *sq, float *pass, void *stream);
+
 /* ---- fused 3-layer MLP forward on the matrix cores (fp32 MFMA): Actor.forward (DDPGfD.py:29-32) and
  * Critic.forward (DDPGfD.py:47-50) as ONE launch each:
  *     out[n,out_dim] = f(W3 relu(W2 relu(W1 x + b1) + b2) + b3),   f = identity (KR_ACT_NONE) or scale * sigmoid

@@ -1091,6 +1091,37 @@ __global__ __launch_bounds__(256) void k_sigmoid_scale_backward(long count, cons
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < count; i += (long)gridDim.x * 256) grad[i] *= a[i] * (1.0f - a[i] / max_action);
 }
 
+// The behaviour-cloning term of the actor loss (Nair et al. 2018) added to dLoss/d(actor pre-activation), with its Q-filter: one thread per
+// row, the row of each [rows, 4] buffer as one 16-byte load / store.  A row below demo_from, a row the filter rejects and a row whose dq is
+// 0 (padding) add nothing, and their dz3 is not stored: it keeps every bit (a -0.0 too, which dz3 + 0 would not).  The order of the
+// operations is the contract of include/kinova_rollout.h.
+__global__ __launch_bounds__(256) void k_bc_actor_grad(int rows, int demo_from, const float* __restrict__ pi, const float* __restrict__ demo,
+                                                       const float* __restrict__ q_demo, const float* __restrict__ q_pi,
+                                                       const float* __restrict__ dq, float bc_weight, float max_action, float* __restrict__ dz3,
+                                                       float* __restrict__ sq, float* __restrict__ pass) {
+#pragma clang fp contract(off)
+    static_assert(A == 4, "one float4 per row");
+    const float two_w = 2.0f * bc_weight;
+    for (long r = (long)blockIdx.x * 256 + threadIdx.x; r < rows; r += (long)gridDim.x * 256) {
+        if (r < demo_from) { sq[r] = 0.0f; pass[r] = 0.0f; continue; }
+        const bool f = q_demo ? q_demo[r] > q_pi[r] : true;          // (strict; a NaN on either side fails the comparison)
+        pass[r] = f ? 1.0f : 0.0f;
+        if (!f) { sq[r] = 0.0f; continue; }
+        const float4 p4 = reinterpret_cast<const float4*>(pi)[r], a4 = reinterpret_cast<const float4*>(demo)[r];
+        const float p[A] = {p4.x, p4.y, p4.z, p4.w};
+        const float d[A] = {p4.x - a4.x, p4.y - a4.y, p4.z - a4.z, p4.w - a4.w};
+        sq[r] = ((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]) + d[3] * d[3];
+        const float g = dq[r];
+        if (!(g != 0.0f) || !(bc_weight != 0.0f)) continue;          // (a NaN dq is not 0: it reaches the row)
+        const float c = two_w * -g;                                  // d(bc term) / d(pi_j) = c * d_j
+        const float4 z4 = reinterpret_cast<const float4*>(dz3)[r];
+        float z[A] = {z4.x, z4.y, z4.z, z4.w};
+#pragma unroll
+        for (int j = 0; j < A; j++) z[j] += (c * d[j]) * (p[j] * (1.0f - p[j] / max_action));
+        reinterpret_cast<float4*>(dz3)[r] = make_float4(z[0], z[1], z[2], z[3]);
+    }
+}
+
 // torch.optim.Adam, single-tensor formulation, as step number t (bias corrections)
 // (CLIP: the gradient is g * coef, scaled before the weight-decay term as torch.nn.utils.clip_grad_norm_ does; g itself is not written)
 template <bool CLIP = false>
@@ -1620,6 +1651,16 @@ int kr_adam_step_clipped(int64_t count, float* param, const float* grad, float* 
                          void* stream) {
     return adam_launch(ADAM_CLIPPED, count, param, grad, exp_avg, exp_avg_sq, step, every, partials, max_norm, lr, beta1, beta2, eps, weight_decay,
                        clip_out, stream);
+}
+
+int kr_bc_actor_grad(int32_t rows, int32_t demo_from, const float* pi, const float* demo, const float* q_demo, const float* q_pi, const float* dq,
+                     float bc_weight, float max_action, float* dz3, float* sq, float* pass, void* stream) {
+    if (rows <= 0 || demo_from < 0 || demo_from > rows || !pi || !demo || !dq || !dz3 || !sq || !pass || (q_demo != nullptr) != (q_pi != nullptr) ||
+        !(bc_weight >= 0.0f) || !(max_action > 0.0f) || (((uintptr_t)pi | (uintptr_t)demo | (uintptr_t)dz3) & 15) != 0)
+        return KS_ERR_INVALID;
+    hipLaunchKernelGGL(k_bc_actor_grad, dim3(grid_for(rows)), dim3(256), 0, (hipStream_t)stream, rows, demo_from, pi, demo, q_demo, q_pi, dq, bc_weight,
+                       max_action, dz3, sq, pass);
+    return launched();
 }
 
 int kr_soft_update(int64_t count, const float* param, float* target, float tau, const int64_t* it, int32_t freq, void* stream) {

@@ -21,6 +21,9 @@ DDPGfD (the reference's four files plus two for the second critic).
 Both take three controls on the critic update, each None (off: the update as it was) by default: `q_bounds=(lo, hi)` clamps the
 bootstrapped target-critic value, `huber_delta` shapes the TD loss, `max_grad_norm` clips each network's gradient norm before its step
 (see DDPGfD's docstring; the native form: kr_critic_grad_bounded / kr_grad_sqnorm / kr_adam_step_clipped, learner_native.py).
+
+Both take the behaviour-cloning term of Nair et al. 2018 ("Overcoming Exploration in Reinforcement Learning with Demonstrations") on the
+actor update: `bc_weight` (0 = off: the update as it was) and `q_filter` (see DDPGfD's docstring; the native form: kr_bc_actor_grad).
 """
 from __future__ import annotations
 
@@ -95,17 +98,39 @@ def _bounded_settings(q_bounds, huber_delta, max_grad_norm):
     return q_bounds, huber_delta, max_grad_norm
 
 
+def _bc_settings(bc_weight, q_filter):
+    """the behaviour-cloning term's two settings, validated; bc_weight = 0 is today's code path"""
+    bc_weight, q_filter = float(bc_weight), bool(q_filter)
+    if not 0 <= bc_weight < float("inf"):                  # (a NaN fails the comparison)
+        raise ValueError("bc_weight must be finite and >= 0")
+    if q_filter and bc_weight == 0:
+        raise ValueError("q_filter=True needs bc_weight > 0: without the behaviour-cloning term there is nothing to filter")
+    return bc_weight, q_filter
+
+
 class DDPGfD:
     """q_bounds=(lo, hi): the target critic's output is clamped to [lo, hi] before it enters either target (the bootstrap, not the sum: a
     return the policy can attain lies in the range, so a correct critic is not changed).  huber_delta=d: per row and target the square
     e^2 becomes rho(e) = e^2 where not |e| > d, d (2 |e| - d) otherwise - twice the usual Huber function, d = inf is the square; its
     gradient is 2 clamp(e, -d, d).  max_grad_norm=g: torch.nn.utils.clip_grad_norm_(params, g) per network right before each
-    optimizer's step (after the gradient exchange).  All three default to None = the update as it was; there is no new state."""
+    optimizer's step (after the gradient exchange).  All three default to None = the update as it was; there is no new state.
+
+    bc_weight=c > 0: the actor loss gains the behaviour-cloning term on the batch's demonstration rows - the window rows r >= demo_from, as
+    the samplers lay a batch out: agent slots first, expert slots after -
+        c * sum_{r >= demo_from} w_r sum_k f_rk |pi(s_rk) - a_rk|^2 / (sum(w) n),
+    the square summed over the action's components, the normalisation that of the Q term.  f_rk = 1; with q_filter=True f_rk = 1 only
+    where Q(s_rk, a_rk) > Q(s_rk, pi(s_rk)) - strict, not differentiated through, a NaN gives 0 -, both from critic 1 behind this update's
+    critic step.  phase_actor then needs `action` and `demo_from`, returns the total loss and keeps the term in self.bc_loss and the
+    weighted share of demonstration states that passed the filter in self.bc_pass (0-d tensors, no host sync).  bc_weight=0 (the default)
+    is the update as it was in every bit; there is no new state and nothing new in checkpoints."""
 
     def __init__(self, state_dim=82, action_dim=4, max_action=0.8, n=5, discount=0.995, tau=0.0005, batch_size=64,
-                 hidden=(400, 300), device="cpu", process_group=None, capturable=False, q_bounds=None, huber_delta=None, max_grad_norm=None):
+                 hidden=(400, 300), device="cpu", process_group=None, capturable=False, q_bounds=None, huber_delta=None, max_grad_norm=None,
+                 bc_weight=0.0, q_filter=False):
         self.q_bounds, self.huber_delta, self.max_grad_norm = _bounded_settings(q_bounds, huber_delta, max_grad_norm)
+        self.bc_weight, self.q_filter = _bc_settings(bc_weight, q_filter)
         self.device = torch.device(device)
+        self.bc_loss, self.bc_pass = torch.zeros((), device=self.device), torch.zeros((), device=self.device)
         self.actor = Actor(state_dim, action_dim, max_action, hidden).to(self.device)
         self.actor_target = copy.deepcopy(self.actor)
         self._flat_params = {}
@@ -156,18 +181,19 @@ class DDPGfD:
             off += g.numel()
 
     # -- update ---------------------------------------------------------------------------------
-    def train_on_batch(self, state, action, next_state, reward, weight=None):
+    def train_on_batch(self, state, action, next_state, reward, weight=None, demo_from=None):
         """One DDPGfD update on already-sampled n-step windows: state/next_state [R, n, 82],
         action [R, n, 4], reward [R, n].  `weight` [R] (optional, 0/1) masks padding rows so that
         fixed-shape device batches keep the reference's per-row means.  Returns the four losses
-        (actor, critic, critic_L1, critic_LN) as 0-d tensors (no host sync).
+        (actor, critic, critic_L1, critic_LN) as 0-d tensors (no host sync).  demo_from (needed with bc_weight > 0): the
+        rows r >= demo_from are demonstration rows.
 
         The update is three phases with a gradient exchange after the first two (`phase_critic`,
         `phase_actor`, `phase_targets`); pipeline.GraphedTrainer captures the phases in HIP graphs and runs the
         exchanges between them."""
         losses_c = self.phase_critic(state, action, next_state, reward, weight)
         self._allreduce_grads(list(self.critic.parameters()))
-        actor_loss = self.phase_actor(state, weight)
+        actor_loss = self.phase_actor(state, weight, action, demo_from)
         self._allreduce_grads(list(self.actor.parameters()))
         self.phase_targets()
         return (actor_loss,) + losses_c
@@ -231,8 +257,27 @@ class DDPGfD:
         total.backward()
         return out
 
-    def phase_actor(self, state, weight=None):
-        """critic step, then actor loss + backward (DDPGfD.py:331-352)"""
+    def _bc_term(self, state, action, pi, q_pi, weight, demo_from):
+        """the behaviour-cloning term of the actor loss on the rows r >= demo_from (see the class docstring) and the weighted share of
+        their states that passed the filter; the critic is critic 1 as phase_actor holds it"""
+        R, n, d = state.shape[0], state.shape[1], int(demo_from)
+        sq = ((pi[d:] - action[d:]) ** 2).sum(-1)                        # [R - d, n]
+        if self.q_filter:
+            with torch.no_grad():
+                f = (self.critic(state[d:], action[d:]) > q_pi[d:]).squeeze(-1).to(sq.dtype)      # strict; a NaN compares false
+        else:
+            f = torch.ones_like(sq)
+        w = torch.ones(R, dtype=sq.dtype, device=sq.device) if weight is None else weight
+        wd = w[d:].unsqueeze(-1)
+        bc = self.bc_weight * (sq * f * wd).sum() / (w.sum().clamp_min(1.0) * n)
+        share = (f * wd).sum() / (wd.sum() * n).clamp_min(torch.finfo(sq.dtype).tiny)
+        return bc, share.detach()
+
+    def phase_actor(self, state, weight=None, action=None, demo_from=None):
+        """critic step, then actor loss + backward (DDPGfD.py:331-352); with bc_weight > 0 the loss has the behaviour-cloning term on the
+        rows r >= demo_from of `action` (self.bc_loss, self.bc_pass)"""
+        if self.bc_weight > 0:
+            return self._phase_actor_bc(state, weight, action, demo_from)
         self._clip(self.critic)
         self.critic_optimizer.step()
         # the critic is only a differentiable function here: no weight gradients for it (the reference computes and
@@ -244,6 +289,26 @@ class DDPGfD:
         actor_loss.backward()
         for p in self.critic.parameters():
             p.requires_grad_(True)
+        return actor_loss.detach()
+
+    def _phase_actor_bc(self, state, weight, action, demo_from):
+        if action is None or demo_from is None:
+            raise ValueError("bc_weight > 0: the actor phase needs the batch's actions and demo_from, the first demonstration row")
+        if not 0 <= int(demo_from) <= state.shape[0]:
+            raise ValueError("demo_from must lie in [0, rows]")
+        self._clip(self.critic)
+        self.critic_optimizer.step()
+        for p in self.critic.parameters():
+            p.requires_grad_(False)
+        pi = self.actor(state)
+        q_pi = self.critic(state, pi)
+        bc, share = self._bc_term(state, action, pi, q_pi.detach(), weight, demo_from)
+        actor_loss = -self._mean(q_pi, state.shape[1], weight) + bc
+        self.actor_optimizer.zero_grad()
+        actor_loss.backward()
+        for p in self.critic.parameters():
+            p.requires_grad_(True)
+        self.bc_loss, self.bc_pass = bc.detach(), share
         return actor_loss.detach()
 
     def phase_targets(self):
@@ -276,9 +341,12 @@ class DDPGfD:
             ag = replay_buffer.sample_batch_nstep(agent_bs)
             ex = expert_replay_buffer.sample_batch_nstep(self.batch_size - agent_bs)
             batch = tuple(torch.cat((a, e), 0) for a, e in zip(ag, ex))
+            demo_from = ag[0].shape[0]                     # agent rows first, expert rows after
         state, action, next_state, reward = (t.to(self.device) for t in batch[:4])
         weight = batch[5].to(self.device) if len(batch) > 5 else None
-        return tuple(x.item() for x in self.train_on_batch(state, action, next_state, reward, weight))
+        if replay_buffer is None or expert_replay_buffer is None:
+            demo_from = 0 if replay_buffer is None else state.shape[0]
+        return tuple(x.item() for x in self.train_on_batch(state, action, next_state, reward, weight, demo_from=demo_from))
 
     # -- checkpoints: the reference's four files (DDPGfD.py:371-382) ---------------------------------
     def save(self, filename):
@@ -328,9 +396,9 @@ class TD3fD(DDPGfD):
 
     def __init__(self, state_dim=82, action_dim=4, max_action=0.8, n=5, discount=0.995, tau=0.0005, batch_size=64, hidden=(400, 300),
                  device="cpu", process_group=None, capturable=False, policy_noise=None, noise_clip=None, policy_freq=2, q_bounds=None,
-                 huber_delta=None, max_grad_norm=None):
+                 huber_delta=None, max_grad_norm=None, bc_weight=0.0, q_filter=False):
         super().__init__(state_dim, action_dim, max_action, n, discount, tau, batch_size, hidden, device, process_group, capturable,
-                         q_bounds=q_bounds, huber_delta=huber_delta, max_grad_norm=max_grad_norm)
+                         q_bounds=q_bounds, huber_delta=huber_delta, max_grad_norm=max_grad_norm, bc_weight=bc_weight, q_filter=q_filter)
         self.critic2 = Critic(state_dim, action_dim, hidden).to(self.device)
         self.critic2_target = copy.deepcopy(self.critic2)
         self.critic2_optimizer = torch.optim.Adam(self.critic2.parameters(), weight_decay=1e-4, capturable=self.capturable)
@@ -342,12 +410,12 @@ class TD3fD(DDPGfD):
         if not (self.policy_noise >= 0 and self.noise_clip >= 0 and self.policy_freq >= 1):
             raise ValueError("TD3fD: policy_noise and noise_clip must be >= 0, policy_freq >= 1")
 
-    def train_on_batch(self, state, action, next_state, reward, weight=None, target_noise=None):
+    def train_on_batch(self, state, action, next_state, reward, weight=None, target_noise=None, demo_from=None):
         """As DDPGfD.train_on_batch; returns (actor, critic, critic_L1, critic_LN, critic2, critic2_L1, critic2_LN).  target_noise: the
         N(0, 1) draws of the target smoothing, [2R, 4] (None: torch.randn)."""
         losses_c = self.phase_critic(state, action, next_state, reward, weight, target_noise)
         self._allreduce_grads(list(self.critic.parameters()) + list(self.critic2.parameters()))
-        actor_loss = self.phase_actor(state, weight)
+        actor_loss = self.phase_actor(state, weight, action, demo_from)
         self._allreduce_grads(list(self.actor.parameters()))
         self.phase_targets()
         return (actor_loss,) + losses_c
@@ -363,11 +431,13 @@ class TD3fD(DDPGfD):
     def _critics(self):
         return ((self.critic, self.critic_optimizer), (self.critic2, self.critic2_optimizer))
 
-    def phase_actor(self, state, weight=None):
-        """both critics' steps, then the actor loss through critic 1 + backward"""
+    def phase_actor(self, state, weight=None, action=None, demo_from=None):
+        """both critics' steps, then the actor loss through critic 1 (the behaviour-cloning term and its filter too) + backward"""
+        if self.bc_weight > 0 and (action is None or demo_from is None or not 0 <= int(demo_from) <= state.shape[0]):
+            raise ValueError("bc_weight > 0: the actor phase needs the batch's actions and demo_from, the first demonstration row, in [0, rows]")
         self._clip(self.critic2)
         self.critic2_optimizer.step()
-        return super().phase_actor(state, weight)
+        return super().phase_actor(state, weight, action, demo_from)
 
     def phase_targets(self):
         """the actor's step on every policy_freq-th call + soft update of the three target networks on every 10th call"""

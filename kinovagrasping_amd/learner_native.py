@@ -32,6 +32,12 @@ where they coincide:
   coefficient from them, then the step on g * coef; `every` is 1 but for TD3fD's actor), self.clip [3, 2] holding the (norm, coef) of
   actor, critic and critic2.  In the pipelined form the actor's norm is taken at the head, on the gradient buffer the body left.
 
+* the behaviour-cloning term (the policy's bc_weight > 0; 0 by default: the launch sequence as it was): ONE launch, kr_bc_actor_grad, between
+  the critic's data-gradient pass and the actor's own backward, adds the term's gradient on the demonstration rows (r >= demo_from) to
+  dLoss/d(actor pre-activation) in place, from the actor's output and the Q the actor phase computes anyway; with q_filter one more critic
+  forward, on the demonstration rows only (a contiguous tail), gives the filter's Q(s, a).  In the table form the rows are the B * H table
+  rows, the actions tb.table_action, the first demonstration row b_agent * H.
+
 On a batch drawn as episode tables (replay.TableBatch; phase_critic_tables / phase_actor_tables, the LDS-free forms) the passes whose result
 for a row depends on that row alone - the actor phase's forwards and data gradients, DDPGfD's target networks - run once per distinct state
 (B * H table rows) instead of once per window that holds it (B * W * n rows), and the actor's weight gradients read their terms through an
@@ -106,6 +112,10 @@ class NativeDDPGfDUpdate:
         # (norm, coef) of the last clipped step of actor, critic, critic2 (zeros while max_grad_norm is None) and kr_grad_sqnorm's partial sums
         self.clip = torch.zeros(3, 2, device=policy.device)
         self._partials = torch.zeros(3, _sim.KR_NORM_PARTS, dtype=torch.float64, device=policy.device) if self.max_grad_norm is not None else None
+        # the behaviour-cloning term of the actor loss (ddpgfd: bc_weight, q_filter; 0 = the launch sequence as it was); with track_actor_loss
+        # self.bc_loss holds the term and self.bc_pass the weighted share of demonstration states that passed the filter
+        self.bc_weight, self.q_filter = float(getattr(policy, "bc_weight", 0.0)), bool(getattr(policy, "q_filter", False))
+        self.bc_loss, self.bc_pass = torch.zeros((), device=policy.device), torch.zeros((), device=policy.device)
         self.p = policy
         self.lib = _sim.load_library()
         fp = policy._flat_params
@@ -462,17 +472,72 @@ class NativeDDPGfDUpdate:
         _mlp.weight_grad(dz1, x, xa, net.gW[0], net.gb[0], idx=idx)
         self._join(0, 1)
 
+    def _bc_rows(self, action, demo_from, window_rows, per):
+        """None while bc_weight is 0; else (demo [rows, 4], the first demonstration row among the actor phase's rows, demo_from) - per =
+        (window rows, actor-phase rows) of one unit of the batch: (1, n) for window states, (W, H) for a batch slot's table rows"""
+        if not self.bc_weight > 0:
+            return None
+        if action is None or demo_from is None:
+            raise ValueError("bc_weight > 0: the actor phase needs the batch's actions and demo_from, the first demonstration row")
+        d = int(demo_from)
+        if not 0 <= d <= window_rows:
+            raise ValueError("demo_from must lie in [0, rows]")
+        assert d % per[0] == 0, "the table form: demo_from is a whole number of batch slots (b_agent * W window rows)"
+        demo = action.reshape(-1, action.shape[-1])
+        assert demo.dtype == torch.float32 and demo.is_contiguous() and demo.shape[1] == 4
+        return demo, d // per[0] * per[1], d
+
+    def _critic_q(self, s, a, out):
+        """critic 1's Q on the rows (s, a) -> out [rows, 1], on the kernels of the form in use (the filter's Q(s, a) on the demonstration rows)"""
+        c = self.critic
+        if self.lds_free:
+            _mlp.mlp3_forward(c.layers, s, a, act=_mlp.ACT_NONE, out=out, **self._form)
+        elif self.fused_targets and self.fuse_actor_fwd:
+            _mlp.mlp3_forward(c.layers, s, a, act=_mlp.ACT_NONE, out=out)
+        else:
+            torch.addmm(c.b[2], self._lin_relu(c, 1, self._lin_relu(c, 0, torch.cat([s, a], 1))), c.W[2].t(), out=out)
+
+    def _bc(self, sa, pi, q_pi, dq, dz3, n, idx, demo, first, demo_from):
+        """the behaviour-cloning term on the actor phase's rows (_bc_rows): dz3 += its gradient on the rows r >= first (kr_bc_actor_grad, one
+        launch; with q_filter behind the critic's forward on those rows' demonstrated actions).  demo_from, in window rows, is what the
+        tracked pass share is normalised by."""
+        P, rows = _sim._ptr, sa.shape[0]
+        assert demo.shape[0] == rows and 0 <= first <= rows and pi.is_contiguous() and dz3.is_contiguous() and tuple(dz3.shape) == (rows, 4)
+        q_demo = None
+        if self.q_filter:
+            q_demo = pi.new_empty(rows, 1)                   # (the kernel reads the rows r >= first only)
+            if first < rows:
+                self._critic_q(sa[first:], demo[first:], q_demo[first:])
+        sq, passed = pi.new_empty(rows), pi.new_empty(rows)
+        self._chk(self.lib.kr_bc_actor_grad(rows, first, P(pi), P(demo), P(q_demo), P(q_pi) if self.q_filter else None, P(dq), self.bc_weight,
+                                            self.p.max_action, P(dz3), P(sq), P(passed), self._st()), "kr_bc_actor_grad")
+        if self.track_actor_loss:
+            if idx is not None:
+                rows_of = idx.long().clamp(min=0)
+                sq, passed = sq[rows_of], passed[rows_of]
+            self._set_bc_loss(sq, passed, n, demo_from)
+
+    def _set_bc_loss(self, sq, passed, n, demo_from):
+        """bc_weight sum_{r >= demo_from} w_r sum_k f_rk |pi - a|^2 / (sum(w) n), added to the tracked actor loss, and the weighted share of
+        demonstration states with f = 1; sq and passed per window state (zero on the agent rows)"""
+        w = self.weight
+        self.bc_loss = self.bc_weight * (sq.view(-1, n).sum(1) * w).sum() / (self.wsum[0] * float(n))
+        self.bc_pass = (passed.view(-1, n).sum(1) * w).sum() / (w[demo_from:].sum() * float(n)).clamp_min(torch.finfo(torch.float32).tiny)
+        self.actor_loss = self.actor_loss + self.bc_loss
+
     @torch.no_grad()
-    def phase_actor(self, state, weight=None):
-        """critic Adam step, then the actor loss -mean_w Q(s, pi(s)) over all n-step rows -> self.actor.grad"""
+    def phase_actor(self, state, weight=None, action=None, demo_from=None):
+        """critic Adam step, then the actor loss -mean_w Q(s, pi(s)) over all n-step rows -> self.actor.grad; with the policy's bc_weight > 0
+        plus the behaviour-cloning term on the rows r >= demo_from of `action` [R, n, 4] (ValueError without them, before any launch)"""
         pol, P = self.p, _sim._ptr
+        n = state.shape[1]
+        bc = self._bc_rows(action, demo_from, state.shape[0], (1, n))
         for net in self.critics:
             self._adam(net, self.it)
-        n = state.shape[1]
         sa = state.reshape(-1, state.shape[2])
         a_, c = self.actor, self.critic
         if self.lds_free:
-            self._actor_rows(sa, self.dq_actor, n, None)
+            self._actor_rows(sa, self.dq_actor, n, None, bc)
             return None
         if self.fused_targets and self.fuse_actor_fwd:
             rows = sa.shape[0]
@@ -484,8 +549,9 @@ class NativeDDPGfDUpdate:
             ha1, ha2, a = self._actor_forward(a_, sa)
             hc1 = self._lin_relu(c, 0, torch.cat([sa, a], 1))
             hc2 = self._lin_relu(c, 1, hc1)
+        q = torch.addmm(c.b[2], hc2, c.W[2].t()) if (self.track_actor_loss or (bc is not None and self.q_filter)) else None
         if self.track_actor_loss:
-            self._set_actor_loss(torch.addmm(c.b[2], hc2, c.W[2].t()), n)
+            self._set_actor_loss(q, n)
         # d(-sum_r w_r sum_k Q_rk / (sum(w) n)) / dQ_rk  (kr_update_prologue)
         dq = self.dq_actor
         dh2 = torch.mm(dq, c.W[2])
@@ -494,13 +560,16 @@ class NativeDDPGfDUpdate:
         self._relu_bwd(hc1, dh1)
         da = torch.mm(dh1, c.W[0][:, sa.shape[1]:])                       # only the action columns of the critic's first layer
         self._chk(self.lib.kr_sigmoid_scale_backward(da.numel(), P(a), pol.max_action, P(da), self._st()), "kr_sigmoid_scale_backward")
+        if bc is not None:
+            self._bc(sa, a, q, dq, da, n, None, *bc)
         self._weight_grads(a_, sa, ha1, ha2, da)
         return None
 
-    def _actor_rows(self, sa, dq, n, idx):
+    def _actor_rows(self, sa, dq, n, idx, bc=None):
         """LDS-free: the actor phase's passes on the states sa with dLoss/dQ dq per row -> self.actor.grad.  idx None: sa are the window
         states themselves; else (the table form) sa are table rows, each evaluated once, and the sums over the window states - the weight
-        gradients, the tracked loss - read row idx[r] for state r (-1: a padding row's, which adds exact zeros in the window form)."""
+        gradients, the tracked loss - read row idx[r] for state r (-1: a padding row's, which adds exact zeros in the window form).
+        bc (_bc_rows): the behaviour-cloning term's gradient joins dz3 before the actor's own backward."""
         pol, a_, c = self.p, self.actor, self.critic
         rows = sa.shape[0]
         al, cl = a_.layers, c.layers
@@ -512,19 +581,24 @@ class NativeDDPGfDUpdate:
             self._set_actor_loss(q if idx is None else q[idx.long().clamp(min=0)], n)
         # dLoss/d(actor pre-activation): through the critic to its action inputs, then through 0.8 * sigmoid
         _, _, dz3 = _mlp.mlp3_backward(cl, dq, hc1, hc2, want_dz=False, dx_cols=(sa.shape[1], a.shape[1]), act_out=a, scale=pol.max_action, lean=self.lean_kernels)
+        if bc is not None:
+            self._bc(sa, a, q, dq, dz3, n, idx, *bc)
         self._backward(a_, dz3, sa, None, ha1, ha2, idx=idx)
 
     @torch.no_grad()
-    def phase_actor_tables(self, tb):
+    def phase_actor_tables(self, tb, demo_from=None):
         """phase_actor on a replay.TableBatch, after phase_critic_tables: the four per-row passes (actor and critic forward, the critic's data
         gradient to the action columns, the actor's data gradient) run on the T = B * H table rows - a row's result depends on that row's
         inputs only, and every real window of batch slot b carries the same dq -, the actor's three weight gradients keep their R * n
         terms, order and chunks and read each term through its table row.  self.actor.grad is bit for bit phase_actor's on tb.windows()
-        (padding rows, which add exact zeros there, read as zeros here)."""
+        (padding rows, which add exact zeros there, read as zeros here).  demo_from (the policy's bc_weight > 0): the first demonstration
+        WINDOW row, b_agent * W, as phase_actor takes it; the term's rows here are the table rows from b_agent * H on, its actions
+        tb.table_action and its coefficient dq_table - the indexed weight gradients give each table row its multiplicity."""
         assert self.lds_free, "the table form runs on the LDS-free kernels"
+        bc = self._bc_rows(tb.table_action, demo_from, tb.weight.shape[0], (tb.horizon - tb.n_steps, tb.horizon))
         for net in self.critics:
             self._adam(net, self.it)
-        self._actor_rows(tb.table_state, self.dq_table, tb.n_steps, self.row_index)
+        self._actor_rows(tb.table_state, self.dq_table, tb.n_steps, self.row_index, bc)
 
     def _set_actor_loss(self, q, n):
         """-sum_r w_r sum_k Q_rk / (sum(w) n)  (DDPGfD.py:341: -critic(state, actor(state)).mean())"""
@@ -563,23 +637,23 @@ class NativeDDPGfDUpdate:
         dist.all_reduce(g, op=dist.ReduceOp.SUM, group=self.p.process_group)
         g.div_(world)
 
-    def train_on_tables(self, tb, target_noise=None):
+    def train_on_tables(self, tb, target_noise=None, demo_from=None):
         """train_on_batch on a replay.TableBatch: bit for bit train_on_batch(*tb.windows()) (the sign of an exactly-zero Adam moment aside)"""
         losses = self.phase_critic_tables(tb, target_noise=target_noise)
         self.allreduce("critic")
         if self.td3:
             self.allreduce("critic2")
-        self.phase_actor_tables(tb)
+        self.phase_actor_tables(tb, demo_from)
         self.allreduce("actor")
         self.phase_targets()
         return losses
 
-    def train_on_batch(self, state, action, next_state, reward, weight=None, target_noise=None):
+    def train_on_batch(self, state, action, next_state, reward, weight=None, target_noise=None, demo_from=None):
         losses = self.phase_critic(state, action, next_state, reward, weight, target_noise=target_noise)
         self.allreduce("critic")
         if self.td3:
             self.allreduce("critic2")
-        self.phase_actor(state, weight)
+        self.phase_actor(state, weight, action, demo_from)
         self.allreduce("actor")
         self.phase_targets()
         return losses

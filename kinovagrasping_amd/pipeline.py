@@ -103,7 +103,10 @@ class GraphedTrainer:
         tables: draw every batch as episode tables (replay.sample_tables, whichever sampler the trainer uses) and run the update on them
         (NativeDDPGfDUpdate.phase_*_tables): each of a batch's B * H distinct states goes through the per-row passes once instead of once per
         window that holds it, with the window form's results bit for bit.  None: whenever the learner is LDS-free and the rings are on the
-        device; False keeps the window form (A/B runs, tests).  self.batch is the window form either way (see the property)."""
+        device; False keeps the window form (A/B runs, tests).  self.batch is the window form either way (see the property).
+        A policy with bc_weight > 0 (ddpgfd: the behaviour-cloning term, q_filter) gets the term on the expert slots of every batch - the
+        window rows from int(batch_episodes * (1 - expert_prob)) * W on -, its launches inside the captured update; it needs an expert ring
+        and expert_prob > 0, else ValueError."""
         assert engine.gen is None, "graph capture uses the default CUDA generator"
         self.sim, self.policy, self.replay, self.eng = sim, policy, replay, engine
         self.expert_replay, self.expert_prob = expert_replay, float(expert_prob)
@@ -126,6 +129,10 @@ class GraphedTrainer:
             raise ValueError("GraphedTrainer: the expert mix needs device rings (DeviceEpisodeReplay on the GPU)")
         # the sampler of every update, chosen once; self.mix: the expert ring when batches mix its episodes in, else None
         self.mix = expert_replay if (expert_replay is not None and self.expert_prob > 0) else None
+        if getattr(policy, "bc_weight", 0.0) > 0 and self.mix is None:
+            raise ValueError("the policy's bc_weight > 0 needs demonstrations in every batch: an expert_replay and expert_prob > 0")
+        # the first demonstration row of every batch in window rows (the samplers: agent slots first, expert slots after); None without the term
+        self.demo_from = int(batch_episodes * (1 - self.expert_prob)) * (replay.horizon - replay.n_steps) if getattr(policy, "bc_weight", 0.0) > 0 else None
         if self.prioritized and self.balanced:
             self._sampler = partial(replay.sample_balanced_prioritized, self.mix, batch_episodes, self.expert_prob, self.per_beta)
         elif self.prioritized:
@@ -242,9 +249,10 @@ class GraphedTrainer:
 
     def _phase2(self):
         if self.tables:
-            self.native.phase_actor_tables(self._tb)
+            self.native.phase_actor_tables(self._tb, self.demo_from)
             return
-        self.native.phase_actor(self._batch[0], self._batch[5])     # (its actor Adam step runs in the next update's head: native.pipelined)
+        # (its actor Adam step runs in the next update's head: native.pipelined)
+        self.native.phase_actor(self._batch[0], self._batch[5], self._batch[1] if self.demo_from is not None else None, self.demo_from)
 
     def _allreduce_critics(self):
         self.native.allreduce("critic")
