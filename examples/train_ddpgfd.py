@@ -14,6 +14,7 @@
     python examples/train_ddpgfd.py --envs 1024 --steps 600 --hidden 256 256 (or 400 300: the reference's widths, free-running too) [--free-running] [--expert-prob 0] [--starts-per-env 64]
                                     [--success-map DIR] [--demonstrations free-running] [--randomize-params] [--prioritized]
                                     [--q-bounds 0 50] [--huber-delta 10] [--max-grad-norm 10] [--bc-weight 1 [--q-filter]]
+                                    [--obs-norm [--obs-norm-eps 1e-2] [--obs-norm-freeze-after N]]
 
 --success-map DIR (with --free-running): the stepping kernel logs every finished training episode (ks_set_episode_log); at every report
 the script folds the log (metrics.EpisodeLedger) and writes DIR/per_shape_success.jsonl and the success / fail start coordinates of the
@@ -104,6 +105,12 @@ def main():
                     "With --log-q the term and the filter's pass share are printed too")
     ap.add_argument("--q-filter", action="store_true", help="with --bc-weight: only on the demonstration states where the critic rates the demonstrated action above "
                     "the actor's own, Q(s, a) > Q(s, pi(s))")
+    ap.add_argument("--obs-norm", action="store_true", help="running observation normalisation: a running mean and standard deviation per observation component "
+                    "from the batches' window-first states, every network on the normalised state, the rollout on the actor with the map folded into its first "
+                    "layer (kr_obs_stats_update / kr_obs_normalize / kr_fold_obs_norm); default: raw observations. With --log-q the smallest and largest "
+                    "per-column standard deviation are printed too")
+    ap.add_argument("--obs-norm-eps", type=float, default=None, metavar="E", help="with --obs-norm: the floor of the standard deviation (default 1e-2)")
+    ap.add_argument("--obs-norm-freeze-after", type=int, default=None, metavar="N", help="with --obs-norm: the statistics stop changing after N updates")
     ap.add_argument("--expl-noise", type=float, default=0.1, help="exploration noise, std = 0.8 x this (main_DDPGfD.py:443-446: 0.1)")
     ap.add_argument("--dump-replay", default=None, help="write the replay (last 1500 agent + first 400 expert episodes) and the four networks as one .npz "
                     "(tools/r06/reference_learner_on_replay.py runs the REFERENCE's train_batch on it)")
@@ -115,8 +122,12 @@ def main():
         ap.error("--bc-weight needs demonstrations in the batches: --expert-prob > 0")
     if args.q_filter and not args.bc_weight > 0:
         ap.error("--q-filter needs --bc-weight > 0")
+    if (args.obs_norm_eps is not None or args.obs_norm_freeze_after is not None) and not args.obs_norm:
+        ap.error("--obs-norm-eps / --obs-norm-freeze-after need --obs-norm")
     bounded = dict(q_bounds=None if args.q_bounds is None else tuple(args.q_bounds), huber_delta=args.huber_delta, max_grad_norm=args.max_grad_norm,
                    bc_weight=args.bc_weight, q_filter=args.q_filter)
+    if args.obs_norm:
+        bounded.update(obs_norm=True, obs_norm_freeze_after=args.obs_norm_freeze_after, **({} if args.obs_norm_eps is None else dict(obs_norm_eps=args.obs_norm_eps)))
     torch.manual_seed(args.seed)
     rng = np.random.RandomState(args.seed)
     dev = torch.device("cuda", 0)
@@ -160,6 +171,8 @@ def main():
         print(f"TD3fD: target smoothing noise {policy.policy_noise:g} clipped at {policy.noise_clip:g}, actor steps every {policy.policy_freq} update(s)")
     else:
         policy = DDPGfD(82, 4, 0.8, 5, tau=args.tau, batch_size=args.batch_episodes, hidden=tuple(args.hidden), device=dev, **bounded)
+    if policy.obs_norm is not None:
+        print(f"running observation normalisation: eps {policy.obs_norm.eps:g}, freeze after {policy.obs_norm.freeze_after}")
     if policy.bc_weight > 0:
         print(f"behaviour cloning on the expert episodes of every batch: weight {policy.bc_weight:g}, Q-filter {'on' if policy.q_filter else 'off'}")
     if any(bounded[k] is not None for k in ("q_bounds", "huber_delta", "max_grad_norm")):
@@ -247,6 +260,9 @@ def main():
         if args.log_q and args.max_grad_norm is not None:
             norm_c, coef_c = tr.native.clip[1].tolist()
             clip = f"  critic grad norm {norm_c:9.3f} coef {coef_c:6.4f}"
+        if args.log_q and policy.obs_norm is not None:
+            sd = policy.obs_norm.std()
+            clip += f"  obs std {sd.min().item():.3g} .. {sd.max().item():.3g} ({int(policy.obs_norm.count.item())} rows)"
         if args.eval_every and (it + 60) % args.eval_every == 0:
             te = time.perf_counter()
             tr.flush(finish_update=True)                     # the actor the next rollout step would use
@@ -259,6 +275,8 @@ def main():
             ev = f"  eval (no noise, 1024 starts): lift success {res['num_success'] / 1024:.3f}"
             t_eval += time.perf_counter() - te
         print(f"step {it + 60:5d}  episodes {d_ep:7d}  training lift rate {d_lift / max(1, d_ep):.3f}  critic loss {ls[0]:9.3f}{f' / {ls[3]:9.3f}' if args.td3 else ''}{f'  mean Q {mean_q:8.3f}' if args.log_q else ''}{bc}{clip}  {n * (it + 60) / dt:9.0f} env-steps/s{ev}")
+    if args.log_q and policy.obs_norm is not None:
+        print("obs std per column: " + " ".join(f"{v:.3g}" for v in policy.obs_norm.std().tolist()))
     if args.free_running:
         c = tr.counts()
         print(f"free-running rollout: {c['episodes_finished']} episodes finished, {c['episodes_dropped']} dropped, {c['pacing_timeouts']} pacing time-outs, {tr.updates} updates")

@@ -448,6 +448,37 @@ int kr_adam_step_clipped(int64_t count, float *param, const float *grad, float *
 int kr_bc_actor_grad(int32_t rows, int32_t demo_from, const float *pi, const float *demo, const float *q_demo, const float *q_pi, const float *dq,
                      float bc_weight, float max_action, float *dz3, float *sq, float *pass, void *stream);
 
+/* ---- running observation normalisation (ddpgfd.DDPGfD / TD3fD with obs_norm): a running mean and standard deviation per observation
+ * component, as the HER / DDPG baselines behind Nair et al. 2018 keep them, without clipping - so the map is affine and folds into the
+ * actor's first layer, and the rollout kernels act with the folded copy unchanged.  Three launches, no LDS, no scratch, no atomics, fixed
+ * reduction order (the results are a function of the inputs alone), stream-ordered and capturable.  fp32 and fp64 without contraction.
+ *
+ *   kr_obs_stats_update  the statistics (count, mean [dim], m2 [dim]; fp64) take the rows of x [rows, >= dim] (row stride lda floats)
+ *                        whose weight [rows] is not 0 (NULL: every row), and mean32 / inv32 [dim] are derived.  With nb such rows:
+ *                          mb_c    = (sum_r x_rc) / nb,  q_c = sum_r (x_rc - mb_c)^2      in fp64, two passes; per column PH = 64 / ceil(dim / 4)
+ *                                    lanes of one wave add the rows p, p + PH, ... each in ascending order, and their sums are added in ascending p;
+ *                          n       = count + nb,  delta = mb_c - mean_c;
+ *                          mean_c  = mean_c + delta * (nb / n);
+ *                          m2_c    = (m2_c + q_c) + (delta * delta) * (count * (nb / n));
+ *                          count   = n;
+ *                          mean32_c = fp32(mean_c),  inv32_c = fp32(1 / max(sqrt(m2_c / n), eps)).
+ *                        A row with weight 0 is not read into any sum (a NaN in it changes nothing).  nb = 0, or it != NULL and freeze_after
+ *                        > 0 and it[0] >= freeze_after (the device's update count: a captured launch keeps its gate): every output keeps
+ *                        every bit.  One workgroup of 256 lanes.  KS_ERR_INVALID, nothing launched or written: rows <= 0, dim <= 0, dim > 256,
+ *                        lda < dim, a NULL x, count, mean, m2, mean32 or inv32, eps not finite or <= 0, freeze_after < 0.
+ *   kr_obs_normalize     x_rc = fl(fl(x_rc - mean32_c) * inv32_c) in place for c < dim; the columns c >= dim of a wider row (lda > dim) are
+ *                        neither read nor written.  KS_ERR_INVALID: rows <= 0, dim <= 0, lda < dim, a NULL pointer.
+ *   kr_fold_obs_norm     the first layer W1 [h1, in_dim], b1 [h1] that takes raw inputs:  W1_out_jk = fl(W1_jk * inv32_k) for k < norm_dim,
+ *                        W1_jk bit for bit for k >= norm_dim (a critic's action columns);  b1_out_j = fp32(b1_j - sum_k W1_out_jk * mean32_k),
+ *                        the products exact in fp64, the sum in fp64 in ascending k, the difference rounded to fp64 and then to fp32.
+ *                        KS_ERR_INVALID, nothing launched or written: h1 <= 0, in_dim <= 0, norm_dim outside [0, in_dim], a NULL pointer,
+ *                        or an output that overlaps an input or the other output. */
+int kr_obs_stats_update(int32_t rows, int32_t dim, const float *x, int32_t lda, const float *weight, const int64_t *it, int64_t freeze_after,
+                        double *count, double *mean, double *m2, float *mean32, float *inv32, double eps, void *stream);
+int kr_obs_normalize(int32_t rows, int32_t dim, float *x, int32_t lda, const float *mean32, const float *inv32, void *stream);
+int kr_fold_obs_norm(int32_t h1, int32_t in_dim, int32_t norm_dim, const float *W1, const float *b1, const float *mean32, const float *inv32,
+                     float *W1_out, float *b1_out, void *stream);
+
 /* ---- fused 3-layer MLP forward on the matrix cores (fp32 MFMA): Actor.forward (DDPGfD.py:29-32) and
  * Critic.forward (DDPGfD.py:47-50) as ONE launch each:
  *     out[n,out_dim] = f(W3 relu(W2 relu(W1 x + b1) + b2) + b3),   f = identity (KR_ACT_NONE) or scale * sigmoid

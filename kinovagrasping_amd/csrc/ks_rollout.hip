@@ -1213,6 +1213,126 @@ __global__ __launch_bounds__(256) void k_soft_update(long count, const float* __
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < count; i += (long)gridDim.x * 256) tp[i] = tau * p[i] + (1.0f - tau) * tp[i];
 }
 
+// Running observation normalisation (ddpgfd: obs_norm), three launches of the learner's stream; the arithmetic is the contract of
+// include/kinova_rollout.h.  The statistics: ONE workgroup of four waves - every wave reads the scalar count before one of them replaces it,
+// which a barrier orders and a second workgroup could not -, one wave per SIMD, so the workgroup is resident within what k_rollout<25,19>
+// leaves.  Wave w owns the CW = ceil(dim / 4) adjacent columns from w CW on; its lanes are PH = 64 / CW row phases of CW columns each, so
+// that one load covers PH rows of CW adjacent floats (a few cache lines, not one per lane).  Lane (p, c) adds its rows p, p + PH, ... in fp64
+// in ascending order; the phases' sums are added in ascending p (the same in every lane); the lanes of phase 0 merge their columns: a
+// function of the inputs alone.
+constexpr int OBS_WAVES = 4;
+constexpr int OBS_MAX_DIM = OBS_WAVES * WAVE;
+
+__device__ __forceinline__ double obs_phase_sum(double x, int cw, int ph, int col) {
+#pragma clang fp contract(off)
+    double t = 0.0;
+    for (int p = 0; p < ph; p++) t += __shfl(x, p * cw + col);        // (uniform trip count; every lane of a column gets the same bits)
+    return t;
+}
+
+// one lane's pass over its rows p, p + ph, ...: the sum of x (SQ false) or of (x - mb)^2 (SQ true) over the counted rows, in ascending order.
+// The loads of OBS_BATCH rows are issued together - every row of the buffer may be read, only what is added depends on the weight -, so a
+// pass is rows / (ph OBS_BATCH) memory round trips and not one per row.
+constexpr int OBS_BATCH = 16;
+
+template <bool SQ>
+__device__ __forceinline__ double obs_column_pass(const float* __restrict__ xc, int lda, const float* __restrict__ weight, int rows, int phase,
+                                                  int ph, double mb) {
+#pragma clang fp contract(off)
+    double acc = 0.0;
+    int r = phase;
+    for (; r + (OBS_BATCH - 1) * ph < rows; r += OBS_BATCH * ph) {
+        float v[OBS_BATCH], w[OBS_BATCH];
+#pragma unroll
+        for (int u = 0; u < OBS_BATCH; u++) {
+            v[u] = xc[(long)(r + u * ph) * lda];
+            w[u] = weight ? weight[r + u * ph] : 1.0f;
+        }
+#pragma unroll
+        for (int u = 0; u < OBS_BATCH; u++) {
+            const double d = SQ ? (double)v[u] - mb : (double)v[u];
+            acc += w[u] != 0.0f ? (SQ ? d * d : d) : 0.0;                             // (a padding row's value is never added, a NaN neither)
+        }
+    }
+    for (; r < rows; r += ph) {
+        const float v = xc[(long)r * lda];
+        const bool on = !weight || weight[r] != 0.0f;
+        const double d = SQ ? (double)v - mb : (double)v;
+        acc += on ? (SQ ? d * d : d) : 0.0;
+    }
+    return acc;
+}
+
+__global__ __launch_bounds__(OBS_WAVES * WAVE) void k_obs_stats_update(int rows, int dim, const float* __restrict__ x, int lda,
+                                                                       const float* __restrict__ weight, const int64_t* __restrict__ it,
+                                                                       int64_t freeze_after, double* count, double* __restrict__ mean,
+                                                                       double* __restrict__ m2, float* __restrict__ mean32,
+                                                                       float* __restrict__ inv32, double eps) {
+#pragma clang fp contract(off)
+    if (it && freeze_after > 0 && it[0] >= freeze_after) return;                     // frozen: nothing is touched (uniform)
+    const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE;
+    double nb = 0.0;                                                                 // counted rows: exact
+    for (int r = lane; r < rows; r += WAVE) nb += (!weight || weight[r] != 0.0f) ? 1.0 : 0.0;
+    nb = wave_sum_f64(nb);
+    const double na = __hip_atomic_load(count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // every wave, before the barrier
+    __syncthreads();
+    if (!(nb > 0.0)) return;                                                         // all padding: nothing is touched (uniform)
+    const double n = na + nb;
+    const int cw = (dim + OBS_WAVES - 1) / OBS_WAVES, ph = WAVE / cw;                 // 1 <= cw <= 64
+    const int phase = lane / cw, col = lane - phase * cw, c = wave * cw + col;
+    const bool mine = phase < ph && c < dim;                                         // (lanes beyond ph * cw, columns beyond dim: idle)
+    const float* __restrict__ xc = x + (mine ? c : 0);
+    const double s = mine ? obs_column_pass<false>(xc, lda, weight, rows, phase, ph, 0.0) : 0.0;
+    const double mb = obs_phase_sum(s, cw, ph, col) / nb;
+    double q = mine ? obs_column_pass<true>(xc, lda, weight, rows, phase, ph, mb) : 0.0;
+    q = obs_phase_sum(q, cw, ph, col);
+    if (mine && phase == 0) {
+        // Chan et al.: (na, mean, m2) + (nb, mb, q)
+        const double ma = mean[c], delta = mb - ma;
+        const double mn = ma + delta * (nb / n);
+        const double qn = (m2[c] + q) + (delta * delta) * (na * (nb / n));
+        mean[c] = mn;
+        m2[c] = qn;
+        mean32[c] = (float)mn;
+        const double sd = sqrt(qn / n);
+        inv32[c] = (float)(1.0 / (sd > eps ? sd : eps));
+    }
+    if (threadIdx.x == 0) count[0] = n;
+}
+
+// in place on the first `dim` columns of every row: one subtract, one multiply (no contraction: the two fp32 operations of the host)
+__global__ __launch_bounds__(256) void k_obs_normalize(long rows, int dim, float* __restrict__ x, int lda, const float* __restrict__ mean32,
+                                                       const float* __restrict__ inv32) {
+#pragma clang fp contract(off)
+    const long count = rows * dim;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < count; i += (long)gridDim.x * 256) {
+        const long r = i / dim;
+        const int c = (int)(i - r * dim);
+        float* p = x + r * lda + c;
+        *p = (*p - mean32[c]) * inv32[c];
+    }
+}
+
+// W1 (x - mean) * inv = (W1 * inv) x + (b1 - (W1 * inv) mean): a thread per output row, the bias sum in fp64 in ascending k, rounded once
+__global__ __launch_bounds__(256) void k_fold_obs_norm(int h1, int in_dim, int norm_dim, const float* __restrict__ W1, const float* __restrict__ b1,
+                                                       const float* __restrict__ mean32, const float* __restrict__ inv32,
+                                                       float* __restrict__ W1_out, float* __restrict__ b1_out) {
+#pragma clang fp contract(off)
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= h1) return;
+    const float* __restrict__ w = W1 + (long)j * in_dim;
+    float* __restrict__ wo = W1_out + (long)j * in_dim;
+    double acc = 0.0;
+#pragma unroll 4
+    for (int k = 0; k < norm_dim; k++) {
+        const float f = w[k] * inv32[k];
+        wo[k] = f;
+        acc += (double)f * (double)mean32[k];
+    }
+    for (int k = norm_dim; k < in_dim; k++) wo[k] = w[k];
+    b1_out[j] = (float)((double)b1[j] - acc);
+}
+
 // one wave, no LDS: every lane scans its share of the values (agent-scope loads: the writers' stores are device-visible), the wave takes
 // the minimum with shuffles; the launch ends when it has reached the target or the wall clock runs out
 __global__ __launch_bounds__(64) void k_wait_min(const int64_t* __restrict__ values, int n, int64_t target, long long ticks, int64_t* timeouts) {
@@ -1660,6 +1780,42 @@ int kr_bc_actor_grad(int32_t rows, int32_t demo_from, const float* pi, const flo
         return KS_ERR_INVALID;
     hipLaunchKernelGGL(k_bc_actor_grad, dim3(grid_for(rows)), dim3(256), 0, (hipStream_t)stream, rows, demo_from, pi, demo, q_demo, q_pi, dq, bc_weight,
                        max_action, dz3, sq, pass);
+    return launched();
+}
+
+int kr_obs_stats_update(int32_t rows, int32_t dim, const float* x, int32_t lda, const float* weight, const int64_t* it, int64_t freeze_after,
+                        double* count, double* mean, double* m2, float* mean32, float* inv32, double eps, void* stream) {
+    if (rows <= 0 || dim <= 0 || dim > OBS_MAX_DIM || lda < dim || !x || !count || !mean || !m2 || !mean32 || !inv32 || !(eps > 0.0) || !(eps < INFINITY) || freeze_after < 0)
+        return KS_ERR_INVALID;
+    hipLaunchKernelGGL(k_obs_stats_update, dim3(1), dim3(OBS_WAVES * WAVE), 0, (hipStream_t)stream, rows, dim, x, lda, weight, it, freeze_after, count,
+                       mean, m2, mean32, inv32, eps);
+    return launched();
+}
+
+int kr_obs_normalize(int32_t rows, int32_t dim, float* x, int32_t lda, const float* mean32, const float* inv32, void* stream) {
+    if (rows <= 0 || dim <= 0 || lda < dim || !x || !mean32 || !inv32) return KS_ERR_INVALID;
+    hipLaunchKernelGGL(k_obs_normalize, dim3(grid_for((long)rows * dim)), dim3(256), 0, (hipStream_t)stream, (long)rows, dim, x, lda, mean32, inv32);
+    return launched();
+}
+
+int kr_fold_obs_norm(int32_t h1, int32_t in_dim, int32_t norm_dim, const float* W1, const float* b1, const float* mean32, const float* inv32,
+                     float* W1_out, float* b1_out, void* stream) {
+    if (h1 <= 0 || in_dim <= 0 || norm_dim < 0 || norm_dim > in_dim || !W1 || !b1 || !mean32 || !inv32 || !W1_out || !b1_out) return KS_ERR_INVALID;
+    // the outputs may not overlap an input (the kernel's pointers are restrict, and a row's bias reads what its weights wrote)
+    const size_t wb = (size_t)h1 * in_dim * sizeof(float), bb = (size_t)h1 * sizeof(float), nb = (size_t)norm_dim * sizeof(float);
+    const auto overlap = [](const void* a, size_t na, const void* b, size_t nb_) {
+        const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+        return x < y + nb_ && y < x + na;
+    };
+    const void* outs[2] = {W1_out, b1_out};
+    const size_t out_bytes[2] = {wb, bb};
+    for (int o = 0; o < 2; o++)
+        if (overlap(outs[o], out_bytes[o], W1, wb) || overlap(outs[o], out_bytes[o], b1, bb) || overlap(outs[o], out_bytes[o], mean32, nb) ||
+            overlap(outs[o], out_bytes[o], inv32, nb))
+            return KS_ERR_INVALID;
+    if (overlap(W1_out, wb, b1_out, bb)) return KS_ERR_INVALID;
+    hipLaunchKernelGGL(k_fold_obs_norm, dim3((h1 + 255) / 256), dim3(256), 0, (hipStream_t)stream, h1, in_dim, norm_dim, W1, b1, mean32, inv32, W1_out,
+                       b1_out);
     return launched();
 }
 

@@ -142,6 +142,9 @@ def run_stage(plan, policy, n_envs: int = 1024, rounds: int = 10, updates_per_ro
     trainer enables priorities on the agent ring and on the expert ring; with balanced each batch is drawn by sample_balanced_prioritized, the
     shapes' shares by the balanced rule and the episode within a shape by priority.  The result gains `priority_max`: {"agent": ...,
     "expert": ... (None without an expert mix)}, the largest priority an update has written to each ring, in units of 1 / 65536.
+    A policy with obs_norm (ddpgfd: running observation normalisation) keeps it through the stage on either path: the previous stage's
+    statistics are loaded with its weights (<prefix>_obs_norm), keep running over this stage's batches - whose object-size and rangefinder
+    columns are distributed differently - and are saved with the policy; the result gains `obs_std` (min, max over the components).
     Returns a dict (num_success, num_total, paths, ...)."""
     import torch
 
@@ -315,6 +318,9 @@ def run_stage(plan, policy, n_envs: int = 1024, rounds: int = 10, updates_per_ro
         out.update(episodes=ledger.episodes, per_shape_success=ledger.per_object(shapes))
     if trainer is not None:
         out.update(free_out)
+    if getattr(policy, "obs_norm", None) is not None:
+        sd = policy.obs_norm.std()
+        out["obs_std"] = (float(sd.min()), float(sd.max()))
     if param_ranges is not None:
         out["param_success"] = {"mass_edges": mass_edges.tolist(), "mu_edges": mu_edges.tolist(), "attempts": p_attempts.tolist(),
                                 "successes": p_successes.tolist()}

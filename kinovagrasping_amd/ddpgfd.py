@@ -24,6 +24,10 @@ bootstrapped target-critic value, `huber_delta` shapes the TD loss, `max_grad_no
 
 Both take the behaviour-cloning term of Nair et al. 2018 ("Overcoming Exploration in Reinforcement Learning with Demonstrations") on the
 actor update: `bc_weight` (0 = off: the update as it was) and `q_filter` (see DDPGfD's docstring; the native form: kr_bc_actor_grad).
+
+Both take running observation normalisation, `obs_norm` (False = off: every launch and bit as it was): a running mean and standard deviation
+per observation component (ObsNorm below - the specification of kr_obs_stats_update / kr_obs_normalize / kr_fold_obs_norm), every network on
+the normalised state, and the rollout acting with a copy of the actor whose first layer has the affine map folded in (acting_flat).
 """
 from __future__ import annotations
 
@@ -108,6 +112,94 @@ def _bc_settings(bc_weight, q_filter):
     return bc_weight, q_filter
 
 
+def _obs_norm_settings(obs_norm, eps, freeze_after):
+    """running observation normalisation's three settings, validated; obs_norm = False is today's code path.  An eps other than the default or a
+    freeze_after without obs_norm=True is refused: it would silently do nothing"""
+    obs_norm, eps = bool(obs_norm), float(eps)
+    if not 0 < eps < float("inf"):                         # (a NaN fails the comparison)
+        raise ValueError("obs_norm_eps must be finite and > 0")
+    if freeze_after is not None:
+        if isinstance(freeze_after, bool) or not isinstance(freeze_after, int) or freeze_after < 1:
+            raise ValueError("obs_norm_freeze_after must be None or an int >= 1")
+    if not obs_norm and (eps != OBS_NORM_EPS or freeze_after is not None):
+        raise ValueError("obs_norm_eps / obs_norm_freeze_after need obs_norm=True")
+    return obs_norm, eps, freeze_after
+
+
+OBS_NORM_EPS = 1e-2        # the floor of the standard deviation: a hyper-parameter default (the folded fp32 first layer's rounding grows like
+                           # |x| / sigma, and 1e-2 sits at the smallest genuine spread of an observation component, positions in metres)
+
+
+class ObsNorm:
+    """Running mean and standard deviation per observation component (the HER / DDPG baselines behind Nair et al. 2018), without clipping:
+    the map x -> (x - mean32) * inv32 is affine and folds into a first layer, W1 ((x - m) * s) + b1 = (W1 * s) x + (b1 - (W1 * s) m).
+
+    State: count [1], mean [S], m2 [S] in fp64 (rows so far, running mean, running sum of squared deviations) and the derived fp32 vectors
+    mean32 = fp32(mean), inv32 = fp32(1 / max(sqrt(m2 / count), eps)); zeros and ones at the start: the identity.  update() takes a batch's
+    rows whose weight is not 0 - two passes in fp64, batch mean then squared deviations about it, merged with Chan's parallel formula - and
+    is skipped, on the device, for an all-padding batch and while `it` (updates done) has reached freeze_after.  Fixed shapes and no host
+    read: it can be captured in a graph."""
+
+    def __init__(self, dim, eps=OBS_NORM_EPS, freeze_after=None, device="cpu"):
+        self.dim, self.eps, self.freeze_after = int(dim), float(eps), freeze_after
+        f64 = dict(dtype=torch.float64, device=device)
+        self.count, self.mean, self.m2 = torch.zeros(1, **f64), torch.zeros(dim, **f64), torch.zeros(dim, **f64)
+        self.mean32, self.inv32 = torch.zeros(dim, device=device), torch.ones(dim, device=device)
+
+    def tensors(self):
+        return (self.count, self.mean, self.m2, self.mean32, self.inv32)
+
+    @torch.no_grad()
+    def update(self, x, weight=None, it=None):
+        """x [rows, S]; weight [rows] or None (every row counts); it: the updates done so far, an int or a 0-d / 1-element device tensor"""
+        on = torch.ones(x.shape[0], dtype=torch.bool, device=x.device) if weight is None else weight != 0
+        do = on.any()
+        if self.freeze_after is not None and it is not None:
+            do = do & (torch.as_tensor(it, device=x.device).reshape(()) < self.freeze_after)
+        col = on.unsqueeze(1)
+        zero = torch.zeros((), dtype=torch.float64, device=x.device)
+        xd = torch.where(col, x.double(), zero)                    # (a padding row's content never enters a sum, a NaN neither)
+        nb = on.sum().double()
+        mb = xd.sum(0) / nb.clamp_min(1.0)
+        d = torch.where(col, xd - mb, zero)
+        q = (d * d).sum(0)
+        na = self.count[0]
+        n = (na + nb).clamp_min(1.0)
+        delta = mb - self.mean
+        mean = self.mean + delta * (nb / n)
+        m2 = (self.m2 + q) + (delta * delta) * (na * (nb / n))
+        self.mean.copy_(torch.where(do, mean, self.mean))
+        self.m2.copy_(torch.where(do, m2, self.m2))
+        self.count.copy_(torch.where(do, na + nb, na))
+        self.derive(do)
+
+    @torch.no_grad()
+    def derive(self, do=None):
+        """mean32 / inv32 from the fp64 state (where `do`, a 0-d bool tensor, when given)"""
+        mean32 = self.mean.float()
+        sd = torch.sqrt(self.m2 / self.count.clamp_min(1.0))
+        inv32 = (1.0 / torch.where(sd > self.eps, sd, torch.full_like(sd, self.eps))).float()
+        self.mean32.copy_(mean32 if do is None else torch.where(do, mean32, self.mean32))
+        self.inv32.copy_(inv32 if do is None else torch.where(do, inv32, self.inv32))
+
+    def normalize(self, x):
+        """(x - mean32) * inv32 in x's dtype: an fp64 policy normalises by the same fp32-rounded numbers"""
+        return (x - self.mean32.to(x.dtype)) * self.inv32.to(x.dtype)
+
+    @torch.no_grad()
+    def fold(self, W1, b1):
+        """the first layer that takes raw inputs: W1 * inv32 on the first S columns, b1 - (W1 * inv32) mean32 (the sum in fp64)"""
+        S = self.dim
+        Wf = W1.clone()
+        Wf[:, :S] = W1[:, :S] * self.inv32.to(W1.dtype)
+        bf = (b1.double() - (Wf[:, :S].double() * self.mean32.double()).sum(1)).to(b1.dtype)
+        return Wf, bf
+
+    def std(self):
+        """the running standard deviation per component (fp64; zeros before the first update)"""
+        return torch.sqrt(self.m2 / self.count.clamp_min(1.0))
+
+
 class DDPGfD:
     """q_bounds=(lo, hi): the target critic's output is clamped to [lo, hi] before it enters either target (the bootstrap, not the sum: a
     return the policy can attain lies in the range, so a correct critic is not changed).  huber_delta=d: per row and target the square
@@ -122,14 +214,29 @@ class DDPGfD:
     where Q(s_rk, a_rk) > Q(s_rk, pi(s_rk)) - strict, not differentiated through, a NaN gives 0 -, both from critic 1 behind this update's
     critic step.  phase_actor then needs `action` and `demo_from`, returns the total loss and keeps the term in self.bc_loss and the
     weighted share of demonstration states that passed the filter in self.bc_pass (0-d tensors, no host sync).  bc_weight=0 (the default)
-    is the update as it was in every bit; there is no new state and nothing new in checkpoints."""
+    is the update as it was in every bit; there is no new state and nothing new in checkpoints.
+
+    obs_norm=True: running observation normalisation (ObsNorm; obs_norm_eps the floor of the standard deviation, obs_norm_freeze_after=N: the
+    statistics stop after N updates).  Once per update, before any network pass, the statistics take the batch's window-first states
+    state[:, 0] whose weight is not 0; then every network - actor, critics, all targets - sees (x - mean32) * inv32 of the S state columns
+    (the critic's action columns stay).  The phases keep taking raw states.  Whatever acts on raw observations goes through act() - or, for
+    the rollout kernels, through acting_flat() / acting_layers(): a copy of the actor with the map folded into its first layer, rewritten
+    after every update.  One more checkpoint file, <prefix>_obs_norm.  Not with a process group of more than one rank: per-rank statistics
+    would give the ranks different functions under shared weights.  obs_norm=False (the default): nothing of this exists."""
 
     def __init__(self, state_dim=82, action_dim=4, max_action=0.8, n=5, discount=0.995, tau=0.0005, batch_size=64,
                  hidden=(400, 300), device="cpu", process_group=None, capturable=False, q_bounds=None, huber_delta=None, max_grad_norm=None,
-                 bc_weight=0.0, q_filter=False):
+                 bc_weight=0.0, q_filter=False, obs_norm=False, obs_norm_eps=OBS_NORM_EPS, obs_norm_freeze_after=None):
         self.q_bounds, self.huber_delta, self.max_grad_norm = _bounded_settings(q_bounds, huber_delta, max_grad_norm)
         self.bc_weight, self.q_filter = _bc_settings(bc_weight, q_filter)
+        obs_norm, obs_norm_eps, obs_norm_freeze_after = _obs_norm_settings(obs_norm, obs_norm_eps, obs_norm_freeze_after)
+        if obs_norm:
+            import torch.distributed as dist
+            if dist.is_available() and dist.is_initialized() and dist.get_world_size(process_group) > 1:
+                raise ValueError("obs_norm=True keeps its statistics per rank: not with a process group of more than one rank")
         self.device = torch.device(device)
+        self.obs_norm = ObsNorm(state_dim, obs_norm_eps, obs_norm_freeze_after, self.device) if obs_norm else None
+        self._acting = self._acting_views = None             # obs_norm: the actor with the normalisation folded into its first layer
         self.bc_loss, self.bc_pass = torch.zeros((), device=self.device), torch.zeros((), device=self.device)
         self.actor = Actor(state_dim, action_dim, max_action, hidden).to(self.device)
         self.actor_target = copy.deepcopy(self.actor)
@@ -153,6 +260,7 @@ class DDPGfD:
         self.process_group = process_group
         self._flat = None
         self._native = None          # learner_native.NativeDDPGfDUpdate attached to this policy (keeps its own flat Adam state)
+        self.refresh_acting()
 
     # -- inference ------------------------------------------------------------------------------
     @torch.no_grad()
@@ -160,8 +268,54 @@ class DDPGfD:
         """state: [..., 82] tensor/array -> actions [..., 4] (stays on the device for tensors)"""
         if not torch.is_tensor(state):
             s = torch.as_tensor(state, dtype=torch.float32, device=self.device).reshape(1, -1)
-            return self.actor(s).cpu().numpy().flatten()
-        return self.actor(state)
+            return self.act(s).cpu().numpy().flatten()
+        return self.act(state)
+
+    def _norm(self, state):
+        """what the networks see of raw states (obs_norm; else the states themselves)"""
+        return state if self.obs_norm is None else self.obs_norm.normalize(state)
+
+    def act(self, state):
+        """the actor on RAW observations: the one place that evaluates it on them (select_action, the rollout's torch paths, evaluation)"""
+        return self.actor(self._norm(state))
+
+    def acting_flat(self):
+        """the flat parameter buffer the rollout acts with, in the actor's own layout: the actor's itself, or with obs_norm the copy whose
+        first layer has the normalisation folded in (refresh_acting; the native learner rewrites it with kr_fold_obs_norm every update)"""
+        return self._flat_params["actor"] if self.obs_norm is None else self._acting_buffer()
+
+    def acting_layers(self):
+        """[(weight, bias)] x 3 of acting_flat(), as mlp.layers_of gives the actor's"""
+        if self.obs_norm is None:
+            return [(getattr(self.actor, k).weight.data, getattr(self.actor, k).bias.data) for k in ("l1", "l2", "l3")]
+        self._acting_buffer()
+        return self._acting_views
+
+    def _acting_buffer(self):
+        flat = self._flat_params["actor"]
+        if self._acting is None or self._acting.shape != flat.shape or self._acting.dtype != flat.dtype or self._acting.device != flat.device:
+            self._acting = flat.clone()
+            views, off = [], 0
+            for k in ("l1", "l2", "l3"):
+                lin = getattr(self.actor, k)
+                w = self._acting[off:off + lin.weight.numel()].view_as(lin.weight)
+                off += lin.weight.numel()
+                b = self._acting[off:off + lin.bias.numel()].view_as(lin.bias)
+                off += lin.bias.numel()
+                views.append((w, b))
+            self._acting_views = views
+        return self._acting
+
+    @torch.no_grad()
+    def refresh_acting(self):
+        """obs_norm: acting_flat() <- fold(the actor as it is, the statistics as they are); the torch form of kr_fold_obs_norm"""
+        if self.obs_norm is None:
+            return
+        self._acting_buffer().copy_(self._flat_params["actor"])
+        (w1, b1), _, _ = self._acting_views
+        wf, bf = self.obs_norm.fold(self.actor.l1.weight.data, self.actor.l1.bias.data)
+        w1.copy_(wf)
+        b1.copy_(bf)
 
     # -- gradient exchange (SURVEY 8e): one all-reduce over a flat buffer holding both networks ---
     def _allreduce_grads(self, params):
@@ -234,7 +388,11 @@ class DDPGfD:
         return ((self.critic, self.critic_optimizer),)
 
     def phase_critic(self, state, action, next_state, reward, weight=None, target_noise=None):
-        """targets + critic loss + backward (DDPGfD.py:256-330).  Returns (critic, L1, LN) losses, per critic of _critics()."""
+        """targets + critic loss + backward (DDPGfD.py:256-330).  Returns (critic, L1, LN) losses, per critic of _critics().  obs_norm: the
+        statistics take state[:, 0] first - this phase opens the update -, then the networks see the normalised states."""
+        if self.obs_norm is not None:
+            self.obs_norm.update(state[:, 0], weight, self._it_dev if self.capturable else self.total_it)
+            state, next_state = self._norm(state), self._norm(next_state)
         reward = reward.unsqueeze(-1)
         with torch.no_grad():
             # both target evaluations (1-step: next_state[:, 0], n-step: next_state[:, -1]) in one pass of the target nets
@@ -276,6 +434,7 @@ class DDPGfD:
     def phase_actor(self, state, weight=None, action=None, demo_from=None):
         """critic step, then actor loss + backward (DDPGfD.py:331-352); with bc_weight > 0 the loss has the behaviour-cloning term on the
         rows r >= demo_from of `action` (self.bc_loss, self.bc_pass)"""
+        state = self._norm(state)
         if self.bc_weight > 0:
             return self._phase_actor_bc(state, weight, action, demo_from)
         self._clip(self.critic)
@@ -328,6 +487,7 @@ class DDPGfD:
             elif self.total_it % self.network_repl_freq == 0:
                 for p, tp in pairs:
                     tp.copy_(self.tau * p + (1 - self.tau) * tp)
+        self.refresh_acting()
 
     def train_batch(self, episode_step, expert_replay_buffer, replay_buffer, num_trajectories=5, prob=0.3):
         """Reference signature (DDPGfD.py:219): samples agent (1-prob) / expert (prob) episodes from
@@ -356,11 +516,18 @@ class DDPGfD:
         torch.save(self.critic_optimizer.state_dict(), filename + "_critic_optimizer")
         torch.save(self.actor.state_dict(), filename + "_actor")
         torch.save(self.actor_optimizer.state_dict(), filename + "_actor_optimizer")
+        if self.obs_norm is not None:
+            on = self.obs_norm
+            torch.save({"count": on.count.cpu(), "mean": on.mean.cpu(), "m2": on.m2.cpu(), "eps": on.eps, "freeze_after": on.freeze_after},
+                       filename + "_obs_norm")
 
     def load(self, filename, weights_only=True, sync_targets=False):
         """Like the reference, loading leaves the target networks untouched (DDPGfD.py:378-382);
-        sync_targets=True copies the loaded weights into them."""
+        sync_targets=True copies the loaded weights into them.  obs_norm: <prefix>_obs_norm must be there (the weights mean nothing without
+        the statistics they were trained on) and its eps / freeze_after are adopted; without obs_norm the file is neither needed nor read."""
         import os
+        if self.obs_norm is not None and not os.path.exists(filename + "_obs_norm"):
+            raise FileNotFoundError(f"{filename}_obs_norm is missing: a policy with obs_norm=True needs the statistics its weights were trained on")
         self.critic.load_state_dict(torch.load(filename + "_critic", map_location=self.device, weights_only=weights_only))
         self.actor.load_state_dict(torch.load(filename + "_actor", map_location=self.device, weights_only=weights_only))
         if os.path.exists(filename + "_critic_optimizer"):
@@ -371,8 +538,16 @@ class DDPGfD:
             self.critic_target.load_state_dict(self.critic.state_dict())
             self.actor_target.load_state_dict(self.actor.state_dict())
         self._load_extra(filename, weights_only, sync_targets)
+        if self.obs_norm is not None:
+            on, st = self.obs_norm, torch.load(filename + "_obs_norm", map_location=self.device, weights_only=weights_only)
+            if tuple(st["mean"].shape) != (on.dim,):
+                raise ValueError(f"{filename}_obs_norm holds statistics of {tuple(st['mean'].shape)} components, the policy has {on.dim}")
+            on.count.copy_(st["count"]); on.mean.copy_(st["mean"]); on.m2.copy_(st["m2"])
+            on.eps, on.freeze_after = _obs_norm_settings(True, st["eps"], st["freeze_after"])[1:]
+            on.derive()
         if self._native is not None:
             self._native.import_optimizer_state()     # ... and back: the native learner continues from the loaded Adam state
+        self.refresh_acting()
 
     def _load_extra(self, filename, weights_only, sync_targets):
         """files beyond the reference's four (TD3fD's second critic); they are ignored here, so a TD3fD checkpoint loads into a DDPGfD"""
@@ -396,9 +571,10 @@ class TD3fD(DDPGfD):
 
     def __init__(self, state_dim=82, action_dim=4, max_action=0.8, n=5, discount=0.995, tau=0.0005, batch_size=64, hidden=(400, 300),
                  device="cpu", process_group=None, capturable=False, policy_noise=None, noise_clip=None, policy_freq=2, q_bounds=None,
-                 huber_delta=None, max_grad_norm=None, bc_weight=0.0, q_filter=False):
+                 huber_delta=None, max_grad_norm=None, bc_weight=0.0, q_filter=False, obs_norm=False, obs_norm_eps=OBS_NORM_EPS, obs_norm_freeze_after=None):
         super().__init__(state_dim, action_dim, max_action, n, discount, tau, batch_size, hidden, device, process_group, capturable,
-                         q_bounds=q_bounds, huber_delta=huber_delta, max_grad_norm=max_grad_norm, bc_weight=bc_weight, q_filter=q_filter)
+                         q_bounds=q_bounds, huber_delta=huber_delta, max_grad_norm=max_grad_norm, bc_weight=bc_weight, q_filter=q_filter,
+                         obs_norm=obs_norm, obs_norm_eps=obs_norm_eps, obs_norm_freeze_after=obs_norm_freeze_after)
         self.critic2 = Critic(state_dim, action_dim, hidden).to(self.device)
         self.critic2_target = copy.deepcopy(self.critic2)
         self.critic2_optimizer = torch.optim.Adam(self.critic2.parameters(), weight_decay=1e-4, capturable=self.capturable)
@@ -464,6 +640,7 @@ class TD3fD(DDPGfD):
                 fire = self._it_dev % self.network_repl_freq == 0
                 for p, tp in pairs:
                     tp.copy_(torch.where(fire, self.tau * p + (1 - self.tau) * tp, tp))
+            self.refresh_acting()
             return
         if self.total_it % self.policy_freq == 0:
             self._clip(self.actor)
@@ -472,6 +649,7 @@ class TD3fD(DDPGfD):
             with torch.no_grad():
                 for p, tp in pairs:
                     tp.copy_(self.tau * p + (1 - self.tau) * tp)
+        self.refresh_acting()
 
     def save(self, filename):
         super().save(filename)

@@ -82,7 +82,7 @@ def eval_policy_free_running(sim, policy, episodes_per_env: int = 1, obs0: torch
     if eng._fused_actor_layers() is None:
         raise ValueError("eval_policy_free_running needs the in-kernel actor: a 3-layer MLP at a width ks_rollout supports (256-256, 400-300, 128-128, 64-64)")
     eng.start(sim.obs if obs0 is None else obs0)
-    flat = policy._flat_params["actor"]
+    flat = policy.acting_flat()              # (obs_norm: the copy with the normalisation folded into the first layer)
     pub = torch.zeros(3, (flat.numel() + 3) // 4 * 4, device=dev)
     pub[0, :flat.numel()].copy_(flat)
     pub_ver = torch.zeros(1, dtype=torch.long, device=dev)

@@ -38,6 +38,14 @@ where they coincide:
   forward, on the demonstration rows only (a contiguous tail), gives the filter's Q(s, a).  In the table form the rows are the B * H table
   rows, the actions tb.table_action, the first demonstration row b_agent * H.
 
+* running observation normalisation (the policy's obs_norm; off by default: the launch sequence as it was): ONE kr_obs_stats_update in front
+  of the update's prologue - the statistics take the windows' first states, gated on the device by the update count where freeze_after is set -,
+  one kr_obs_normalize IN PLACE per gathered state buffer the update reads (the batch buffers are the samplers' copies of ring rows; the
+  ring keeps raw observations, and so does nothing else: a caller that reuses a batch hands in a fresh copy), every pass as it was on those
+  buffers, and ONE kr_fold_obs_norm behind the actor's Adam launch (phase_targets; pipelined: phase_head) that writes the first layer of the
+  policy's acting copy (ddpgfd.DDPGfD.acting_flat: what the rollout acts with), the other layers copied - every update, so that the copy is
+  fold(current actor, current statistics) under TD3fD's delayed actor and under a freeze too.
+
 On a batch drawn as episode tables (replay.TableBatch; phase_critic_tables / phase_actor_tables, the LDS-free forms) the passes whose result
 for a row depends on that row alone - the actor phase's forwards and data gradients, DDPGfD's target networks - run once per distinct state
 (B * H table rows) instead of once per window that holds it (B * W * n rows), and the actor's weight gradients read their terms through an
@@ -116,6 +124,10 @@ class NativeDDPGfDUpdate:
         # self.bc_loss holds the term and self.bc_pass the weighted share of demonstration states that passed the filter
         self.bc_weight, self.q_filter = float(getattr(policy, "bc_weight", 0.0)), bool(getattr(policy, "q_filter", False))
         self.bc_loss, self.bc_pass = torch.zeros((), device=policy.device), torch.zeros((), device=policy.device)
+        # running observation normalisation (ddpgfd: obs_norm; None = the launch sequence as it was)
+        self.obs_norm = getattr(policy, "obs_norm", None)
+        if self.obs_norm is not None and fork:
+            raise ValueError("NativeDDPGfDUpdate: the fork form (KS_LEARNER_FORK=1) has no obs_norm variant")
         self.p = policy
         self.lib = _sim.load_library()
         fp = policy._flat_params
@@ -243,6 +255,32 @@ class NativeDDPGfDUpdate:
     def _adam_actor(self, step):
         self._adam(self.actor, step, every=self.p.policy_freq if self.td3 else None)
 
+    def _obs_stats(self, x, lda, weight):
+        """obs_norm, in front of the prologue (self.it: the updates done): the statistics take the rows of x [R, >= S] whose weight is not 0"""
+        on, P = self.obs_norm, _sim._ptr
+        assert x.dtype == torch.float32 and x.stride(-1) == 1 and (weight is None or (weight.dtype == torch.float32 and weight.is_contiguous()))
+        self._chk(self.lib.kr_obs_stats_update(x.shape[0], on.dim, P(x), lda, P(weight), P(self.it), on.freeze_after or 0, P(on.count), P(on.mean), P(on.m2),
+                                               P(on.mean32), P(on.inv32), on.eps, self._st()), "kr_obs_stats_update")
+
+    def _obs_normalize(self, *buffers):
+        """obs_norm: each gathered state buffer [..., S] (contiguous) -> (x - mean32) * inv32, in place"""
+        on, P = self.obs_norm, _sim._ptr
+        for x in buffers:
+            assert x.dtype == torch.float32 and x.is_contiguous() and x.shape[-1] == on.dim
+            self._chk(self.lib.kr_obs_normalize(x.numel() // on.dim, on.dim, P(x), on.dim, P(on.mean32), P(on.inv32), self._st()), "kr_obs_normalize")
+
+    def _fold(self):
+        """obs_norm, behind the actor's Adam launch: the policy's acting copy <- the actor with the normalisation folded into its first layer"""
+        if self.obs_norm is None:
+            return
+        on, P, a = self.obs_norm, _sim._ptr, self.actor
+        acting = self.p.acting_flat()
+        (w1, b1), _, _ = self.p.acting_layers()
+        h1, in_dim = a.W[0].shape
+        self._chk(self.lib.kr_fold_obs_norm(h1, in_dim, on.dim, P(a.W[0]), P(a.b[0]), P(on.mean32), P(on.inv32), P(w1), P(b1), self._st()), "kr_fold_obs_norm")
+        first = h1 * in_dim + h1
+        acting[first:].copy_(a.flat[first:])
+
     def _soft_updates(self, it):
         pol, P = self.p, _sim._ptr
         for net, tgt in zip(self.critics + [self.actor], self.critic_targets + [self.actor_t]):
@@ -323,7 +361,9 @@ class NativeDDPGfDUpdate:
     # -- the three phases ---------------------------------------------------------------------------------------------
     @torch.no_grad()
     def phase_critic(self, state, action, next_state, reward, weight=None, next_ends=None, priorities=None, target_noise=None):
-        """The target actor's forward (TD3fD: kr_target_smooth on its output), every target critic on that action, every critic's forward,
+        """obs_norm: the statistics take state[:, 0] and `state` and `next_state` (`next_ends` when given: next_state is then not read) are
+        normalised IN PLACE - phase_actor takes the same `state` buffer as it is then.
+        The target actor's forward (TD3fD: kr_target_smooth on its output), every target critic on that action, every critic's forward,
         ONE loss-gradient launch (_loss_grad), the backward and weight-gradient passes per critic -> the critics' .grad.  Returns (critic
         loss, L1, LN) per critic, views of self.losses.  priorities (prioritized replay): a callable (q, tq1, reward, weight) issued right
         after the loss-gradient launch on that kernel's own operands - the first critic's Q and the bootstrap the launch used -
@@ -333,6 +373,10 @@ class NativeDDPGfDUpdate:
         R = reward.shape[0]
         if weight is None:
             weight = torch.ones(R, device=reward.device)
+        if self.obs_norm is not None:
+            assert state.is_contiguous()
+            self._obs_stats(state[:, 0], state.shape[1] * state.shape[2], weight)
+            self._obs_normalize(state, next_state if next_ends is None else next_ends)
         # one launch: update counter, sum of the row weights, dLoss/dQ of the actor loss (and, pipelined, the pending mark)
         self.weight, self.wsum = weight, torch.empty(1, device=reward.device)
         self.dq_actor = torch.empty(R * pol.n, 1, device=reward.device)
@@ -367,6 +411,9 @@ class NativeDDPGfDUpdate:
         pol, P = self.p, _sim._ptr
         R, T = tb.weight.shape[0], tb.table_state.shape[0]
         assert tb.n_steps == pol.n and (not self.td3 or tb.next_ends is not None)
+        if self.obs_norm is not None:
+            self._obs_stats(tb.state0, tb.state0.shape[1], tb.weight)
+            self._obs_normalize(tb.table_state, tb.state0, tb.next_ends if self.td3 else tb.table_next)     # (TD3fD does not read table_next)
         self.weight, self.wsum = tb.weight, torch.empty(1, device=tb.weight.device)
         self.dq_table = torch.empty(T, 1, device=tb.weight.device)
         self.row_index = torch.empty(R * pol.n, dtype=torch.int32, device=tb.weight.device)
@@ -611,6 +658,7 @@ class NativeDDPGfDUpdate:
         counter `it_head` (set by mark_pending at the end of an update's body, cleared here): a no-op when no actor step is
         pending."""
         self._adam_actor(self.it_head)
+        self._fold()
         self._soft_updates(self.it_head)
         # (no clearing here: in the pipelined form every body re-marks it_head and a head always runs between two bodies;
         # finish_pending, the eager caller, clears it)
@@ -619,6 +667,7 @@ class NativeDDPGfDUpdate:
     def phase_targets(self):
         """actor Adam step + soft target update on every network_repl_freq-th update"""
         self._adam_actor(self.it)
+        self._fold()
         self.p.total_it += 1
         self._soft_updates(self.it)
 

@@ -235,6 +235,13 @@ class GraphedTrainer:
         rings = [r for r in (self.replay, self.expert_replay) if r is not None and getattr(r, "ep_prio", None) is not None] if self.prioritized else []
         return [(t, t.clone()) for r in rings for t in (r.ep_prio, r.prio_max)]
 
+    def _obs_norm_state(self):
+        """a policy with obs_norm: its statistics and its acting copy (capture()'s warm-up updates are undone on them too)"""
+        pol = self.policy
+        if getattr(pol, "obs_norm", None) is None:
+            return []
+        return [(t, t.clone()) for t in pol.obs_norm.tensors() + (pol.acting_flat(),)]
+
     def _head(self):
         self.native.phase_head()
         self._sample()
@@ -291,7 +298,7 @@ class GraphedTrainer:
         saved = {k: v.clone() for k, v in pol._flat_params.items()}
         saved_opt = [(net, net.grad.clone(), net.exp_avg.clone(), net.exp_avg_sq.clone()) for net in self._opt_nets()]
         saved_it, saved_head, saved_total = nat.it.clone(), nat.it_head.clone(), pol.total_it
-        saved_prio = self._priority_state()
+        saved_prio = self._priority_state() + self._obs_norm_state()
         s = torch.cuda.Stream(self.dev)
         s.wait_stream(self.main)
         with torch.cuda.stream(s):
@@ -460,7 +467,7 @@ def rollout_args(sim, policy, eng, pub, pub_ver, steps_total, counters, replay=N
     P = lambda t: t.data_ptr()
     a = KsRolloutArgs()
     if getattr(eng, "controller", None) is None or policy is not None:
-        flat, actor = policy._flat_params["actor"], policy.actor
+        flat, actor = policy._flat_params["actor"], policy.actor      # (the offsets: pub has the actor's layout, and so has policy.acting_flat())
         off = lambda t: (t.data_ptr() - flat.data_ptr()) // 4
         a.actor_pub, a.actor_ver, a.actor_stride = P(pub), P(pub_ver), pub.shape[1]
         a.off_w1, a.off_b1, a.off_w2, a.off_b2, a.off_w3, a.off_b3 = (off(actor.l1.weight), off(actor.l1.bias), off(actor.l2.weight), off(actor.l2.bias),
@@ -564,7 +571,7 @@ class AsyncTrainer(GraphedTrainer):
                                        f"{self.library_allreduce_chunk} env-steps (the learner lags by at most one launch)")
         if not (eng.native and eng.device_noise and eng._fused_actor_layers() is not None and sim.cfg.auto_reset and sim.obs_env_major):
             raise ValueError("AsyncTrainer needs the fused actor path (3-layer MLP at a supported width, in-kernel noise), auto_reset and env-major obs")
-        flat = policy._flat_params["actor"]
+        flat = policy.acting_flat()              # what the rollout acts with: the actor, or with obs_norm its folded copy
         self.actor_flat = flat
         stride = (flat.numel() + 3) // 4 * 4
         self.pub = torch.zeros(3, stride, device=dev)
@@ -661,7 +668,7 @@ class AsyncTrainer(GraphedTrainer):
         saved = {k: v.clone() for k, v in pol._flat_params.items()}
         saved_opt = [(net, net.grad.clone(), net.exp_avg.clone(), net.exp_avg_sq.clone()) for net in self._opt_nets()]
         saved_it, saved_head, saved_total = nat.it.clone(), nat.it_head.clone(), pol.total_it
-        saved_prio = self._priority_state()
+        saved_prio = self._priority_state() + self._obs_norm_state()
         s = torch.cuda.Stream(self.dev)
         s.wait_stream(self.main)
         with torch.cuda.stream(s):

@@ -138,7 +138,7 @@ class RolloutEngine:
                 if rc != 0:
                     raise RuntimeError(f"kr_actor_select failed ({rc})")
                 return
-            a = self.policy.actor(self.obs).contiguous()
+            a = self._act(self.obs).contiguous()
             noise = torch.randn(a.shape, device=a.device, generator=self.gen)
             P = self._ptr
             rc = self._lib.kr_select_action(self.n, P(self.obs), P(self.prev_obs), P(self.has_prev), P(self.t), P(self.ready), P(a), P(noise),
@@ -150,21 +150,27 @@ class RolloutEngine:
         timestep = self.t + 1                                              # main_DDPGfD.py:425
         chk = check_grasp(self.prev_obs[:, 9:17], self.obs[:, 9:17]) & (timestep >= SKIP_NUM_TS) & self.has_prev
         self.ready |= chk
-        a = self.policy.actor(self.obs)
+        a = self._act(self.obs)
         noise = torch.randn(a.shape, device=a.device, generator=self.gen) * self.sigma
         a = (a + noise).clamp_(0.0, self.max_action)
         self.action.copy_(torch.where(self.ready.unsqueeze(1), self.lift_action, a))
         self.action_t.copy_(self.action.t())
         self.lifting.copy_(self.ready)
 
+    def _act(self, obs):
+        """the torch paths' actor on raw observations: the policy's act() (ddpgfd: normalised first where obs_norm is on), or a bare actor"""
+        act = getattr(self.policy, "act", None)
+        return act(obs) if act is not None else self.policy.actor(obs)
+
     def _fused_actor_layers(self):
-        """the actor's (weight, bias) x 3 when it is the reference's 3-layer MLP at a width the fused kernel supports
-        (max_action * sigmoid output), else None"""
+        """the (weight, bias) x 3 the rollout acts with - the actor's, or the policy's acting copy (ddpgfd: obs_norm folded into the first
+        layer) - when the actor is the reference's 3-layer MLP at a width the fused kernel supports (max_action * sigmoid output), else None"""
         actor = self.policy.actor
         if not all(hasattr(actor, k) for k in ("l1", "l2", "l3")):
             return None
         from . import mlp
-        layers = mlp.layers_of(actor)
+        acting = getattr(self.policy, "acting_layers", None)
+        layers = acting() if acting is not None else mlp.layers_of(actor)
         ok = mlp.supported(layers, self.obs.shape[1]) and layers[2][0].shape[0] == 4 and float(getattr(actor, "max_action", -1.0)) == float(self.max_action)
         return layers if ok else None
 

@@ -100,6 +100,7 @@ ROLLOUT_EXPORTS = ["kr_select_action", "kr_store_transition", "kr_rank_episodes"
                    "kr_xchg_destroy", "kr_critic_grad", "kr_update_prologue", "kr_relu_backward", "kr_sigmoid_scale_backward", "kr_adam_step", "kr_soft_update",
                    "kr_target_smooth", "kr_twin_critic_grad", "kr_adam_step_every",
                    "kr_critic_grad_bounded", "kr_grad_sqnorm", "kr_adam_step_clipped", "kr_bc_actor_grad",
+                   "kr_obs_stats_update", "kr_obs_normalize", "kr_fold_obs_norm",
                    "kr_mlp3_forward", "kr_mlp3_forward_shadow", "kr_mlp3_forward_split", "kr_mlp3_backward_shadow", "kr_mlp3_backward_split", "kr_weight_grad_shadow",
                    "kr_sample_tables_mixed", "kr_sample_tables_balanced", "kr_sample_tables_prioritized", "kr_sample_tables_balanced_prioritized", "kr_update_prologue_tables", "kr_gather_table_q", "kr_weight_grad_indexed",
                    "kr_mlp3_forward_lean", "kr_mlp3_backward_lean",
@@ -222,6 +223,9 @@ def _bind(L):
     L.kr_critic_grad_bounded.argtypes = [i32, i32] + [vp] * 9 + [f32] * 4 + [vp] * 5
     L.kr_grad_sqnorm.argtypes = [i64, vp, vp, vp]
     L.kr_bc_actor_grad.argtypes = [i32, i32] + [vp] * 5 + [f32, f32] + [vp] * 4
+    L.kr_obs_stats_update.argtypes = [i32, i32, vp, i32, vp, vp, i64] + [vp] * 5 + [C.c_double, vp]
+    L.kr_obs_normalize.argtypes = [i32, i32, vp, i32, vp, vp, vp]
+    L.kr_fold_obs_norm.argtypes = [i32, i32, i32] + [vp] * 6 + [vp]
     L.kr_adam_step_clipped.argtypes = [i64, vp, vp, vp, vp, vp, i32, vp, f32, f32, f32, f32, f32, f32, vp, vp]
     mlp_fwd = [i32] * 6 + [vp, i32, vp, i32] + [vp] * 6 + [i32, f32, vp, vp, vp]      # n .. h2_out of every kr_mlp3_forward*
     mlp_bwd = [i32] * 5 + [vp] * 8 + [i32, i32, vp, f32, vp]                          # n .. dx_out of every kr_mlp3_backward*
