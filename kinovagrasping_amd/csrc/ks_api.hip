@@ -1743,7 +1743,29 @@ __global__ __launch_bounds__(WAVE) void k_obs(const Model<T>* __restrict__ model
     KS_UNROLL
     for (int i = 0; i < NRAY; i++) rays[i] = b.rays[(long)i * N + env];
     if constexpr (sizeof(T) == 8) obs_epilogue_f64(models[b.obj_id[env]], b, env, N, mode, o, rays);
-    else obs_epilogue(models[b.obj_id[env]], b, env, N, mode, o, snap, rays, Scratch<T, KS_LDS T*>{(KS_LDS T*)rlds + threadIdx.x, WAVE});
+    else {
+        const Model<T>& m = models[b.obj_id[env]];
+        const Scratch<T, KS_LDS T*> rscr{(KS_LDS T*)rlds + threadIdx.x, WAVE};
+        if (mode == 0) {
+            // after a step (KS_OBS_IN_STEP=0): the observation is written as the stepping kernel's tail writes it (wg_obs) - part by part, the
+            // part and the snapshot's address run-time values - so that the compiler meets build_obs in the shape it has there and contracts the
+            // same multiply-adds: a context returns the same bits whichever of the two finishes its steps.  (With part = -1 known at compile
+            // time the wrist frame came out an ulp apart in 8 % of the values.)
+            // A HEURISTIC, not a guarantee: nothing forces the compiler to contract two copies of one source alike, and a compiler update or
+            // a change near either call site can part them again - tests/test_gpu_obs.py (test_in_step_paths_return_the_same_bits_per_state)
+            // is the guard.  One compiled copy for both callers would be the guarantee; it puts a call into the stepping kernel's tail.
+            // The price is paid here only: the four passes each form the common prefix of build_obs again (palm pose, wrist frame, object
+            // centre, lift test, the 17 range slots' selects) - at most four times build_obs' arithmetic, one thread per env, once per
+            // env-step, in contexts that do not finish the step in the stepping kernel.  Not measured: bench.py never launches this mode.
+            for (int p = 0; p < 4; p++) {
+                int part = p;
+                const T* sp = b.snap + env;
+                asm volatile("" : "+v"(part), "+v"(sp));
+                obs_write(m, b, env, N, 0, o, Col<T>{sp, N}, rays, part);
+            }
+            obs_finish(m, b, env, N, 0, o, snap, rscr);
+        } else obs_epilogue(m, b, env, N, mode, o, snap, rays, rscr);
+    }
 }
 
 // The tail of the stepping kernel (fp32 / LDS variant, after the rays): the workgroup finishes its envs' step - the 82-d

@@ -8,11 +8,38 @@
 #include <cstring>
 #include <vector>
 
+// -DKS_LC_OBS_ONLY: the observation entry (lc_build_obs) alone, from ks_obs.h - a build of seconds for tests/test_obs_cpu.py's copies of
+// the source with one deliberate error each
+#ifdef KS_LC_OBS_ONLY
+#include "../../kinovagrasping_amd/csrc/ks_obs.h"
+#else
 #include "../../kinovagrasping_amd/csrc/ks_env.h"
+#endif
 #include "../../kinovagrasping_amd/csrc/ks_model_host.h"
 
 using namespace ks;
 
+// build_obs on a GIVEN snapshot [105] and rays [17] (fp32 numbers in float64 storage): part -1 everything, 0..3 that quarter of the slots.
+// Slots that the call does not write keep what `obs` held; written[j] counts the writes of slot j.
+template <typename T>
+static void build_obs_t(const Model<T>& m, const double* snap, const double* rays, int part, double* obs, int* written, double* reward, int* lifted2, double* info) {
+    T s[SNAP_TOTAL], r[NRAY], rew = 0, inf[3] = {0, 0, 0};
+    for (int i = 0; i < SNAP_TOTAL; i++) s[i] = (T)snap[i];
+    for (int i = 0; i < NRAY; i++) r[i] = (T)rays[i];
+    bool lifted = false;
+    build_obs(m, Col<T>{s, 1}, r, [&](int j, T v) { obs[j] = (double)v; written[j]++; }, rew, lifted, inf, part);
+    *reward = (double)rew;
+    // the lift test twice: bit 0 build_obs' own, bit 1 object_lifted's copy (obs_finish decides with it).  Not the kernels' `done`, whose bit 1 is the time limit.
+    *lifted2 = (lifted ? 1 : 0) | (object_lifted(m, Col<T>{s, 1}) ? 2 : 0);
+    for (int i = 0; i < 3; i++) info[i] = (double)inf[i];
+}
+
+#ifdef KS_LC_OBS_ONLY
+struct LC {
+    HostModel<float> f;
+    HostModel<double> d;
+};
+#else
 struct LC {
     HostModel<float> f;
     HostModel<double> d;
@@ -197,6 +224,7 @@ static int env_step_t(const Model<T>& m, double* qpos, double* qvel, double* war
     return status;
 }
 
+#endif  // !KS_LC_OBS_ONLY
 #ifdef KS_PLANE_HOOK
 // experiment: the deepest vertex of a plane pair from the fp64 tables on the fp32 lane's pose (the oracle's rule: lowest index within 1e-12)
 static const Model<double>* g_hook_model = nullptr;
@@ -249,6 +277,12 @@ void* lc_create(const void* blob, size_t n) {
     return h;
 }
 void lc_destroy(void* h) { delete (LC*)h; }
+void lc_build_obs(void* h, int prec, const double* snap, const double* rays, int part, double* obs, int* written, double* reward, int* lifted2, double* info) {
+    LC* l = (LC*)h;
+    if (prec == 64) build_obs_t<double>(l->d.m, snap, rays, part, obs, written, reward, lifted2, info);
+    else build_obs_t<float>(l->f.m, snap, rays, part, obs, written, reward, lifted2, info);
+}
+#ifndef KS_LC_OBS_ONLY
 int lc_substep(void* h, int prec, double* qpos, double* qvel, double* warm, const double* ctrl, const double* hq, int iters, int* ncon, double* con) {
     LC* l = (LC*)h;
 #ifdef KS_PLANE_HOOK
@@ -290,4 +324,5 @@ long lc_gjk_ids_out_of_range() { return -1; }           // (the study builds of 
 void lc_set_mixed_variant(int v) { g_mixed_variant = v % 10; g_state_rounding = v / 10; }
 int lc_con_stride() { return CON_STRIDE; }
 int lc_ncon_max() { return NCON_MAX; }
+#endif  // !KS_LC_OBS_ONLY
 }

@@ -30,7 +30,37 @@ def lanecheck_lib(multi_geom: bool = False):
     L.lc_put_warm.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
     L.lc_set_warm.argtypes = [C.c_void_p, C.c_int]
     L.lc_gjk_ids_out_of_range.restype = C.c_long
+    _obs_entry(L)
     return L
+
+
+def _obs_entry(L):
+    ip = C.POINTER(C.c_int)
+    L.lc_create.restype = C.c_void_p
+    L.lc_create.argtypes = [C.c_char_p, C.c_size_t]
+    L.lc_destroy.argtypes = [C.c_void_p]
+    L.lc_build_obs.argtypes = [C.c_void_p, C.c_int, dp, dp, C.c_int, dp, ip, dp, ip, dp]
+    L.lc_build_obs.restype = None
+
+
+def obs_lane_lib(root: Path, so: Path):
+    """the observation entry alone (-DKS_LC_OBS_ONLY) of the tree under `root` (tests/native/ks_lanecheck.cpp and kinovagrasping_amd/csrc
+    below it) -> so.  tests/test_obs_cpu.py builds copies of the source with one deliberate error each this way."""
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-DKS_LC_OBS_ONLY", "-o", str(so), str(Path(root) / "tests" / "native" / "ks_lanecheck.cpp")])
+    L = C.CDLL(str(so))
+    _obs_entry(L)
+    return L
+
+
+def build_obs_lane(L, h, prec, snap, rays, part=-1, obs=None, written=None):
+    """lc_build_obs of one snapshot [105] and its rays [17]: (obs [82], writes per slot [82], reward, the lift test twice - bit 0 build_obs' own, bit 1 object_lifted's -, info [3]); obs / written
+    given: filled on top of what they hold (the four parts one after the other)"""
+    obs = np.full(82, np.nan) if obs is None else obs
+    written = np.zeros(82, dtype=np.int32) if written is None else written
+    rew, done, info = C.c_double(0), C.c_int(0), np.zeros(3)
+    L.lc_build_obs(h, prec, P(np.ascontiguousarray(snap, dtype=np.float64)), P(np.ascontiguousarray(rays, dtype=np.float64)), part, P(obs),
+                   written.ctypes.data_as(C.POINTER(C.c_int)), C.byref(rew), C.byref(done), P(info))
+    return obs, written, rew.value, done.value, info
 
 
 def P(a):
