@@ -981,8 +981,8 @@ __global__ void k_rollout_queue_init(int* __restrict__ queue, int n_groups) {
 // (policy | 15 substeps | rays | observation | replay write), so every env-step costs the workgroup its SLOWEST wave (measured model,
 // profiles/r05_wave_sorting.txt: workgroup cost 1408 k cycles per env-step against 1091 k for the mean wave).  Nothing in an env-step
 // needs the other waves: per-env data is private to the wave's own four env blocks, the model and the hull tables are read-only.
-// Here the unit of the persistent loop is ONE WAVE with its four envs: the actor forward for its own four rows (a 16-column MFMA
-// tile a quarter full, bit-equal per row to the 4-wave tile), its own rays (the same work-sharing queue among 64 lanes), its own
+// Here the unit of the persistent loop is ONE WAVE with its four envs: the actor forward for its own four rows (4-row MFMA blocks,
+// kmlp::mlp3_rows_wave: bit-equal per row to the 4-wave tile), its own rays (the same work-sharing queue among 64 lanes), its own
 // observation and replay rows - and no s_barrier between kernel entry and exit.  Scratch of the tails: the wave's own four (then
 // dead) env blocks.
 template <int NT1, int NT2>
@@ -992,6 +992,7 @@ __device__ __noinline__ void rollout_policy_wave(const ks_rollout_args* __restri
     constexpr int NR = 4;
     kmlp::f32x4(*H1)[NR] = (kmlp::f32x4(*)[NR])(float*)wblocks;
     kmlp::f32x4(*H2)[NR] = H1 + NT1 * 4;
+    kmlp::f32x4(*X)[NR] = H2 + NT2 * 4;
     const int lane = threadIdx.x & 63;
     for (;;) {
         // (the wave's own look at the version counter: waves of a workgroup may act on different - each complete - weight versions)
@@ -999,8 +1000,12 @@ __device__ __noinline__ void rollout_policy_wave(const ks_rollout_args* __restri
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
         const float* pw = ra.actor_pub + (ver % 3) * ra.actor_stride;
         kmlp::f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
-        const bool mine = kmlp::mlp3_rows_wave<NT1, NT2, true, NR>(lane, (long)row_env, S, ra.h1, ra.h2, A, ra.obs, S, kmlp::x_bytes(N, 0, S, S), pw + ra.off_w1,
-                                                                     pw + ra.off_b1, pw + ra.off_w2, pw + ra.off_b2, pw + ra.off_w3, H1, H2, z4);
+        // (lane and row opaque per attempt: what the forward derives from them is then computed where it is used, not ahead of this loop
+        // and held in registers across the whole forward)
+        int ln = lane, rw = row_env;
+        asm volatile("" : "+v"(ln), "+v"(rw));
+        const bool mine = kmlp::mlp3_rows_wave<NT1, NT2, true, NR>(ln, (long)rw, S, ra.h1, ra.h2, A, ra.obs, S, kmlp::x_bytes(N, 0, S, S), pw + ra.off_w1,
+                                                                     pw + ra.off_b1, pw + ra.off_w2, pw + ra.off_b2, pw + ra.off_w3, X, H1, H2, z4);
         float y[4] = {0.f, 0.f, 0.f, 0.f};
         if (mine) policy_squash(ra, z4, pw + ra.off_b3, y);
         // every read of buffer ver % 3 by this wave has been consumed by the arithmetic above; the acquire keeps the second look at
@@ -2429,10 +2434,10 @@ template <typename T> struct Ctx : CtxBase {
         return KS_OK;
     }
     // LDS of the policy phase for hidden widths h1-h2 (16-column tiles): as a workgroup (rollout_policy) H1, H2 and P, [tiles * 4 + 4][16]
-    // float4, and the version box; as one wave (rollout_policy_wave) H1 and H2, [tiles * 4][4] float4
+    // float4, and the version box; as one wave (rollout_policy_wave) H1, H2 and the input rows, [tiles * 4 + 24][4] float4
     static constexpr int policy_tiles(int h1, int h2) { return (h1 + 15) / 16 + (h2 + 15) / 16; }
     static constexpr size_t policy_lds_bytes(int h1, int h2) { return (size_t)(policy_tiles(h1, h2) * 4 + 4) * 16 * 16 + 16; }
-    static constexpr size_t policy_wave_lds_bytes(int h1, int h2) { return (size_t)(policy_tiles(h1, h2) * 4) * 4 * 16; }
+    static constexpr size_t policy_wave_lds_bytes(int h1, int h2) { return (size_t)(policy_tiles(h1, h2) * 4 + kmlp::KS_IN_MAX * 4) * 4 * 16; }
     // The hidden widths the rollout kernels are instantiated for, as pairs of 16-column tiles: launch(Tiles<NT1, NT2>) launches the
     // caller's kernel family at the pair that serves h1-h2.
     template <int A, int B> struct Tiles { static constexpr int NT1 = A, NT2 = B; };

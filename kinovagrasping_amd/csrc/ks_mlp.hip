@@ -16,6 +16,9 @@
 //
 // Arithmetic: every output is a k-ordered fp32 fma chain (MFMA f32 is bitwise an fmaf chain), so results differ
 // from the library GEMMs only by summation order (~1e-7 relative); tests/test_gpu_parity.py checks against torch.
+// Pinned on dense random data: the free-running waves run the same chains ONE k per instruction on v_mfma_f32_4x4x1_16B_f32
+// (ks_mlp_tile.h: mlp3_rows_wave) and equal this kernel bit for bit at six widths (tests/test_gpu_actor_wave_rows4.py) - so the
+// 16x16x4 instruction is, per output, the fma chain of its four k in the order k = 0, 1, 2, 3.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 

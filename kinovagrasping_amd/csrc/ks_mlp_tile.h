@@ -1,6 +1,8 @@
 // ks_mlp_tile.h -- the 3-layer MLP forward of ONE 16-row tile on the matrix cores, as a device function: the body of k_mlp3
 // (ks_mlp.hip: kr_mlp3_forward / kr_actor_select) and of the in-kernel actor of the free-running rollout kernel (ks_api.hip:
 // k_rollout), so that both are the same k-ordered fp32 fma chains bit for bit.  See ks_mlp.hip for the layout.
+// Two forms: mlp3_rows16 (a workgroup of NW waves, 16 batch rows, v_mfma_f32_16x16x4_f32) and mlp3_rows_wave (ONE wave, its own
+// <= 4 batch rows, v_mfma_f32_4x4x1_16B_f32: no zero columns) - the second spells out, one k per instruction, the chains of the first.
 //
 // How the operands arrive.  Every matrix, bias vector and input block is read through a raw buffer resource of exactly its own
 // bytes, with the addressing rule of the section below: the tile and k steps go into the (wave-uniform) scalar offset, the lane
@@ -259,121 +261,220 @@ __device__ __forceinline__ bool mlp3_rows16(const int wave_id, const int lane, c
     return false;
 }
 
-// The same three layers by ONE wave for the first NR rows of a tile (the free-running rollout kernel's waves each own four envs and
-// never meet a barrier): every output element is the chain of MFMAs mlp3_rows16 runs for it - same k order, the same two accumulators
-// per tile, layer 3 as NW partial sums added in wave order - so a row's result is the 4-wave kernel's bit for bit (an MFMA's output
-// column depends on its own B column only; columns >= NR read zeros and are discarded).  xa: [.][lda] rows of in_dim columns, xa_bytes
-// as x_bytes() gives them.  H1 / H2: the wave's own scratch, [NT1 * 4][NR], [NT2 * 4][NR] float4.  Returns true on the lanes that hold
-// a row's layer-3 sums (first quarter, row valid).  W3's quads are not held across layer 2 (its two register sets of NT1 quads and the
-// NT1 B quads leave no room): they leave as one batch behind its loop.
+// ---- the 4-row form: the same three layers by ONE wave for its own NR <= 4 batch rows (the free-running rollout kernel's waves each own
+// four envs and never meet a barrier), on v_mfma_f32_4x4x1_16B_f32: 16 blocks of (4 x 1)(1 x 4), i.e. per instruction ONE k of 64 output
+// features x 4 batch rows.  Transposed as above: A = the weight of the lane's own feature (lane l is feature o0 + l of a 64-feature
+// group), B = the activation of batch row l % 4 (all 16 blocks read the same four), D = the features 4 (l / 4) .. + 3 of row l % 4 in the
+// lane's four registers - after bias + ReLU again ONE float4 to LDS at [feature quad][row], which the next layer reads back as its B
+// quads (one ds_read_b128 per four k).  One such MFMA is one fma per output, so every output element is spelled out as the chain the
+// 16-row tile runs for it (mlp3_rows16): two accumulators per output, even 16-wide k-steps s into the first and odd s into the second;
+// within a k-step k = 16 s + 4 q + x with x = 0..3 outer and q = 0..3 inner (the order in which mfma4 feeds the quads' components to the
+// 16x16x4 instruction, whose four k are q); (acc0 + acc1) + bias, ReLU; layer 3 as NW partial sums over the k-steps w, w + NW, ..,
+// added in wave order.  A row's result is the 4-wave kernel's bit for bit.
+//
+// The stream.  A batch is ONE k-step of G <= 4 feature groups (4 G quads per lane: 64 bytes of the lane's own row per group), so a pass
+// over K runs G independent accumulator chains at a time; two register sets take turns as above.  The weights do not depend on the
+// activations, so the batches run across pass and layer boundaries: the last two k-steps of a pass issue the first two batches of the
+// next pass or layer (W3 behind layer 2), and nothing but the input rows is waited for with nothing to compute.
+__device__ __forceinline__ f32x4 mfma1(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_4x4x1f32(a, b, c, 0, 0, 0); }
+
+struct Rows4Set {
+    f32x4 w[16];        // [group][quarter] of a k-step (layer 3: the lane's quads in k order)
+};
+
+// one batch: k-step s of the G groups of 64 rows at row0 (W = [nrow][K]); lane = row within the group
+template <int G>
+__device__ __forceinline__ void rows4_issue(Rows4Set& t, rsrc_t rW, int lane, int row0, int nrow, int s, int K) {
+    __builtin_amdgcn_sched_barrier(0);          // (behind the MFMAs that read the set: the batch takes their registers, not new ones)
+#pragma unroll
+    for (int g = 0; g < G; g++)
+#pragma unroll
+        for (int q = 0; q < 4; q++) t.w[4 * g + q] = ldq(rW, quad_off(lane, q, row0 + 64 * g, nrow, 16 * s, K), tile_soff(row0 + 64 * g, 16 * s, K));
+    __builtin_amdgcn_sched_barrier(0);
+}
+// the words of the rows' tails (wt: [G][3]), once per pass: they leave with the pass's second batch
+template <int G>
+__device__ __forceinline__ void rows4_tails(float* wt, rsrc_t rW, int lane, int row0, int nrow, int K) {
+#pragma unroll
+    for (int g = 0; g < G; g++)
+#pragma unroll
+        for (int j = 0; j < 3; j++) wt[3 * g + j] = ldf(rW, tail_off(lane, row0 + 64 * g, nrow, K, j), tile_soff(row0 + 64 * g, 0, K));
+    __builtin_amdgcn_sched_barrier(0);
+}
+
+// the 16 G MFMAs of k-step s: B = the quads 4 s .. 4 s + 3 of the lane's batch row in Bsrc ([k quad][NR])
+template <int G, bool TAIL, int NR>
+__device__ __forceinline__ void rows4_kstep(const Rows4Set& t, const float* wt, f32x4 (&acc)[G], const f32x4 (*Bsrc)[NR], int lane, int s, int K) {
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+    const bool col_ok = (lane & 3) < NR;
+    f32x4 b[4], a[G][4];
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+        b[q] = col_ok ? Bsrc[4 * s + q][col_ok ? lane & 3 : 0] : zero;
+#pragma unroll
+        for (int g = 0; g < G; g++)
+            a[g][q] = (TAIL && tail_here(q, 16 * s, K)) ? f32x4{wt[3 * g], wt[3 * g + 1], wt[3 * g + 2], 0.f} : t.w[4 * g + q];
+    }
+#pragma unroll
+    for (int x = 0; x < 4; x++)
+#pragma unroll
+        for (int q = 0; q < 4; q++)
+#pragma unroll
+            for (int g = 0; g < G; g++) acc[g] = mfma1(a[g][q][x], b[q][x], acc[g]);
+}
+
+// One hidden layer: NP passes of G groups over the NS k-steps of K.  On entry the sets a / b hold (in flight) the k-steps 0 / 1 of the
+// first pass and wt its tail words (TAILW); next_a / next_b issue the first two batches of whatever follows the layer.  Hout: [NQ][NR], feature quads of this layer.
+template <int G, int NP, int NS, bool TAILW, bool TAILB, int NR, int NQ, class FA, class FB>
+__device__ __forceinline__ void rows4_layer(rsrc_t rW, rsrc_t rB, int lane, int nfeat, int K, const f32x4 (*Bsrc)[NR], f32x4 (*Hout)[NR], Rows4Set& a,
+                                            Rows4Set& b, float* wt, FA next_a, FB next_b) {
+    constexpr int NSE = (NS + 1) & ~1;
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+    const int fq = lane >> 2;
+#pragma unroll
+    for (int p = 0; p < NP; p++) {
+        const int o0 = 64 * G * p;
+        f32x4 acc0[G], acc1[G];
+#pragma unroll
+        for (int g = 0; g < G; g++) acc0[g] = acc1[g] = zero;
+#pragma unroll 1
+        for (int s = 0; s + 2 < NSE; s += 2) {
+            rows4_kstep<G, TAILW, NR>(a, wt, acc0, Bsrc, lane, s, K);
+            rows4_issue<G>(a, rW, lane, o0, nfeat, s + 2, K);
+            rows4_kstep<G, TAILW, NR>(b, wt, acc1, Bsrc, lane, s + 1, K);
+            rows4_issue<G>(b, rW, lane, o0, nfeat, s + 3, K);           // (s + 3 == NS, NS odd: beyond K, nothing is read)
+        }
+        // the pass's bias quads, then its last two k-steps, each followed by a batch of what comes next
+        f32x4 bq[G];
+        float bt[3];
+#pragma unroll
+        for (int g = 0; g < G; g++) bq[g] = ldq(rB, quad_off(0, fq, 0, 1, o0 + 64 * g, nfeat), tile_soff(0, o0 + 64 * g, nfeat));
+        if (TAILB) {
+#pragma unroll
+            for (int j = 0; j < 3; j++) bt[j] = ldf(rB, tail_off(0, 0, 1, nfeat, j), 0);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        rows4_kstep<G, TAILW, NR>(a, wt, acc0, Bsrc, lane, NSE - 2, K);
+        if (p + 1 < NP) rows4_issue<G>(a, rW, lane, o0 + 64 * G, nfeat, 0, K);
+        else next_a();
+        if (NSE - 1 < NS) rows4_kstep<G, TAILW, NR>(b, wt, acc1, Bsrc, lane, NSE - 1, K);
+        if (p + 1 < NP) {
+            rows4_issue<G>(b, rW, lane, o0 + 64 * G, nfeat, 1, K);
+            if (TAILW) rows4_tails<G>(wt, rW, lane, o0 + 64 * G, nfeat, K);
+        } else next_b();
+#pragma unroll
+        for (int g = 0; g < G; g++) {
+            const int f = o0 + 64 * g + 4 * fq;
+            const f32x4 bias = (TAILB && tail_here(fq, o0 + 64 * g, nfeat)) ? f32x4{bt[0], bt[1], bt[2], 0.f} : bq[g];
+            const f32x4 hq = bias_relu(acc0[g] + acc1[g], bias, f, nfeat);
+            if ((lane & 3) < NR && (f >> 2) < NQ) Hout[f >> 2][lane & 3] = hq;
+        }
+    }
+}
+
+__device__ __forceinline__ void rows4_join() {       // the wave's own LDS stores before its own LDS loads
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// groups of 64 features per pass and passes of a layer of NT 16-feature tiles (256: 4 x 1, 400: 4 x 2, 300: 3 x 2, 128: 2 x 1, 64: 1 x 1)
+constexpr int rows4_passes(int NT) { return ((NT + 3) / 4 + 3) / 4; }
+constexpr int rows4_groups(int NT) { return ((NT + 3) / 4 + rows4_passes(NT) - 1) / rows4_passes(NT); }
+
+// `row` = the batch row of lane l < NR (< 0: no such row; the other lanes' are ignored).  xa: [.][lda] rows of in_dim columns, xa_bytes
+// as x_bytes() gives them.  X / H1 / H2: the wave's own scratch, [KS_IN_MAX * 4][NR], [NT1 * 4][NR], [NT2 * 4][NR] float4.  Returns true on
+// the lanes that hold a row's layer-3 sums z4 (lane < NR, row valid).
 template <int NT1, int NT2, bool VEC, int NR>
 __device__ __forceinline__ bool mlp3_rows_wave(const int lane, const long row, int in_dim, int h1, int h2, int out_dim, const float* __restrict__ xa, int lda,
                                                uint32_t xa_bytes, const float* __restrict__ W1, const float* __restrict__ b1,
                                                const float* __restrict__ W2, const float* __restrict__ b2, const float* __restrict__ W3,
-                                               f32x4 (*H1)[NR], f32x4 (*H2)[NR], f32x4& z4) {
-    const int nn = lane & 15, q = lane >> 4;
-    const bool row_ok = row >= 0, col_ok = nn < NR;
+                                               f32x4 (*X)[NR], f32x4 (*H1)[NR], f32x4 (*H2)[NR], f32x4& z4) {
+    static_assert(NR >= 1 && NR <= 4, "one MFMA block holds four batch rows");
+    constexpr int G1 = rows4_groups(NT1), NP1 = rows4_passes(NT1), G2 = rows4_groups(NT2), NP2 = rows4_passes(NT2);
+    constexpr int NJ = (NT2 + NW - 1) / NW, NQ3 = 4 * NJ;          // layer 3: k-steps and quads per partial sum
+    static_assert(NQ3 <= 32, "layer 3's quads fill at most the two register sets");
     const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
     in_dim = uni(in_dim), h1 = uni(h1), h2 = uni(h2), out_dim = uni(out_dim), lda = uni(lda);
     const rsrc_t rW1 = rsrc(W1, (uint32_t)(h1 * in_dim) * 4u), rB1 = rsrc(b1, (uint32_t)h1 * 4u), rW2 = rsrc(W2, (uint32_t)(h2 * h1) * 4u),
                  rB2 = rsrc(b2, (uint32_t)h2 * 4u), rW3 = rsrc(W3, (uint32_t)(out_dim * h2) * 4u);
-    // the first batch: the input rows, the first tile of W1, and the first tile of W2, which arrives while layer 1 computes
-    f32x4 bx[KS_IN_MAX];
+    // the first batch: the NR input rows word by word (word i of the [NR][16 KS_IN_MAX] block goes to lane i % 64), and W1's first two k-steps
+    constexpr int XW = 16 * KS_IN_MAX, XN = (NR * XW + 63) / 64;
+    float xv[XN];
     {
         const rsrc_t rXa = rsrc(xa, xa_bytes);
 #pragma unroll
-        for (int s = 0; s < KS_IN_MAX; s++) {
-            float v[4];
-#pragma unroll
-            for (int j = 0; j < 4; j++) v[j] = ldf(rXa, x_off(row, 16 * s + 4 * q + j, 0, in_dim, lda), 0);
-            bx[s] = f32x4{v[0], v[1], v[2], v[3]};
+        for (int j = 0; j < XN; j++) {
+            const int i = lane + 64 * j, r = i / XW;
+            const int rowr = __shfl((int)row, r < NR ? r : 0);
+            xv[j] = ldf(rXa, x_off(r < NR ? (long)rowr : -1L, i % XW, 0, in_dim, lda), 0);
         }
     }
-    Tile<NT1, !VEC> a2, b2t;
-    {
-        Tile<KS_IN_MAX, true> a1, b1t;
-        a1.issue(rW1, rB1, nn, q, 0, h1, in_dim);
-        a2.issue(rW2, rB2, nn, q, 0, h2, h1);
-        auto tile1 = [&](const Tile<KS_IN_MAX, true>& w, int t) {
-            f32x4 acc0 = zero, acc1 = zero;
+    Rows4Set a, b;
+    float wt[12], wt3[3];
+    rows4_issue<G1>(a, rW1, lane, 0, h1, 0, in_dim);
+    rows4_issue<G1>(b, rW1, lane, 0, h1, 1, in_dim);
+    rows4_tails<G1>(wt, rW1, lane, 0, h1, in_dim);
 #pragma unroll
-            for (int s = 0; s < KS_IN_MAX; s++) {
-                if (s & 1) acc1 = mfma4(w.quad(s, q, in_dim), bx[s], acc1);
-                else acc0 = mfma4(w.quad(s, q, in_dim), bx[s], acc0);
-            }
-            const f32x4 hq = bias_relu(acc0 + acc1, w.bias(q, 16 * t, h1), t * 16 + 4 * q, h1);
-            if (col_ok) H1[t * 4 + q][nn] = hq;
-        };
-#pragma unroll 1
-        for (int t = 0; t < NT1; t += 2) {
-            b1t.issue(rW1, rB1, nn, q, 16 * (t + 1), h1, in_dim);
-            tile1(a1, t);
-            a1.issue(rW1, rB1, nn, q, 16 * (t + 2), h1, in_dim);
-            if (t + 1 < NT1) tile1(b1t, t + 1);
-        }
+    for (int j = 0; j < XN; j++) {
+        const int i = lane + 64 * j, r = i / XW, k = i % XW;
+        if (r < NR) ((float*)X)[((k >> 2) * NR + r) * 4 + (k & 3)] = xv[j];
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    rows4_join();
+    rows4_layer<G1, NP1, KS_IN_MAX, true, !VEC, NR, NT1 * 4>(
+        rW1, rB1, lane, h1, in_dim, X, H1, a, b, wt, [&] { rows4_issue<G2>(a, rW2, lane, 0, h2, 0, h1); },
+        [&] {
+            rows4_issue<G2>(b, rW2, lane, 0, h2, 1, h1);
+            if (!VEC) rows4_tails<G2>(wt, rW2, lane, 0, h2, h1);
+        });
+    rows4_join();
 
-    // layer 2: the B operands are the same for every tile - read once and held where that leaves room for two tiles of weights (up to
-    // 16 k-steps: 64 registers), else read again for every tile (400-300: 100 registers, which the kernel's budget does not have)
-    constexpr bool HOLD_B = NT1 <= 16;
-    f32x4 hb[HOLD_B ? NT1 : 1];
-    if (HOLD_B) {
+    // layer 3 puts its NW partial sums side by side: block w = lane / 4 of the MFMA runs the chain of the k-steps w, w + NW, .. with
+    // A = W3's row lane % 4 (the output) and B = H2 of batch row lane % 4; the blocks w >= NW compute on zeros and are discarded.
+    // The lane's NQ3 quads of W3, in the order of its chain, are the last two batches of the stream.
+    const int w3 = lane >> 2, r3 = w3 < NW ? lane & 3 : -1;
+    const auto issue3 = [&](Rows4Set& t, int i0) {
+        __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int s = 0; s < NT1; s++) hb[s] = col_ok ? H1[s * 4 + q][nn] : zero;
-    }
-    auto tile2 = [&](const Tile<NT1, !VEC>& w, int t) {
-        f32x4 acc0 = zero, acc1 = zero;
+        for (int i = i0; i < NQ3 && i < i0 + 16; i++) t.w[i - i0] = ldq(rW3, quad_off(r3, 4 * (w3 + NW * (i >> 2)) + (i & 3), 0, out_dim, 0, h2), 0);
+        if (!VEC && i0 == 0) {
 #pragma unroll
-        for (int s = 0; s < NT1; s++) {
-            const f32x4 b = HOLD_B ? hb[HOLD_B ? s : 0] : (col_ok ? H1[s * 4 + q][nn] : zero);
-            if (s & 1) acc1 = mfma4(w.quad(s, q, h1), b, acc1);
-            else acc0 = mfma4(w.quad(s, q, h1), b, acc0);
+            for (int j = 0; j < 3; j++) wt3[j] = ldf(rW3, tail_off(r3, 0, out_dim, h2, j), 0);
         }
-        const f32x4 hq = bias_relu(acc0 + acc1, w.bias(q, 16 * t, h2), t * 16 + 4 * q, h2);
-        if (col_ok) H2[t * 4 + q][nn] = hq;
+        __builtin_amdgcn_sched_barrier(0);
     };
-#pragma unroll 1
-    for (int t = 0; t < NT2; t += 2) {
-        b2t.issue(rW2, rB2, nn, q, 16 * (t + 1), h2, h1);
-        tile2(a2, t);
-        a2.issue(rW2, rB2, nn, q, 16 * (t + 2), h2, h1);
-        if (t + 1 < NT2) tile2(b2t, t + 1);
-    }
-    // layer 3's operands: all of W3 as one batch
-    f32x4 w3[NT2];
-    float w3t[3];
-#pragma unroll
-    for (int s = 0; s < NT2; s++) w3[s] = ldq(rW3, quad_off(nn, q, 0, out_dim, 16 * s, h2), tile_soff(0, 16 * s, h2));
-    if (!VEC) {
-#pragma unroll
-        for (int j = 0; j < 3; j++) w3t[j] = ldf(rW3, tail_off(nn, 0, out_dim, h2, j), 0);
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    rows4_layer<G2, NP2, NT1, !VEC, !VEC, NR, NT2 * 4>(rW2, rB2, lane, h2, h1, H1, H2, a, b, wt, [&] { issue3(a, 0); }, [&] { issue3(b, 16); });
+    rows4_join();
 
-    // layer 3: the NW partial sums of the 4-wave kernel (tiles w, w + NW, ...), added in wave order
-    f32x4 part[NW];
+    f32x4 acc = zero;
+    const bool col_ok = (lane & 3) < NR;
 #pragma unroll
-    for (int w = 0; w < NW; w++) {
-        f32x4 acc = zero;
+    for (int j = 0; j < NJ; j++) {
+        const int s = w3 + NW * j;
+        const bool ok = w3 < NW && s < NT2;             // (a partial sum without this k-step keeps its value: the 4-wave kernel skips it)
+        f32x4 hq[4], wq[4], n = acc;
 #pragma unroll
-        for (int j = 0; j < (NT2 + NW - 1) / NW; j++)
-            if (w + NW * j < NT2) {
-                const int s = w + NW * j;
-                const f32x4 wq = (!VEC && tail_here(q, 16 * s, h2)) ? f32x4{w3t[0], w3t[1], w3t[2], 0.f} : w3[s];
-                acc = mfma4(wq, col_ok ? H2[s * 4 + q][nn] : zero, acc);
-            }
-        part[w] = acc;
+        for (int q = 0; q < 4; q++) {
+            hq[q] = (ok && col_ok) ? H2[(ok ? s : 0) * 4 + q][col_ok ? lane & 3 : 0] : zero;
+            const int i = 4 * j + q;
+            wq[q] = i < 16 ? a.w[i < 16 ? i : 0] : b.w[i < 16 ? 0 : i - 16];
+            if (!VEC) wq[q] = tail_here(4 * s + q, 0, h2) ? f32x4{wt3[0], wt3[1], wt3[2], 0.f} : wq[q];
+        }
+#pragma unroll
+        for (int x = 0; x < 4; x++)
+#pragma unroll
+            for (int q = 0; q < 4; q++) n = mfma1(wq[q][x], hq[q][x], n);
+        acc = (NT2 % NW == 0 || j + 1 < NJ || ok) ? n : acc;
     }
-    if (q == 0 && row_ok && col_ok) {
-        z4 = part[0];
+    // lane 4 w + r holds partial sum w of batch row r (its four registers: the outputs); the rows' lanes add them in wave order
+    f32x4 z = acc;
 #pragma unroll
-        for (int w = 1; w < NW; w++) z4 += part[w];
+    for (int w = 1; w < NW; w++) {
+        const int src = 4 * w + (lane & 3);
+        z += f32x4{__shfl(acc.x, src), __shfl(acc.y, src), __shfl(acc.z, src), __shfl(acc.w, src)};
+    }
+    if (lane < NR && row >= 0) {
+        z4 = z;
         return true;
     }
     return false;
