@@ -343,6 +343,11 @@ typedef struct {
      * advanced by two or more while the forward read buffer (ver % 3) - once per deciding workgroup (KS_PLAN_WORKGROUPS / queue / deals)
      * or per wave (KS_PLAN_WAVES).  Diagnostic of the weight hand-off above; every word of counters[] is taken. */
     int64_t *repeats;
+    /* Optional (NULL = not counted): int64 [3], KS_PLAN_WAVES only - [0] runs of envs that a wave which had done its env-steps of the launch took
+     * over from a slower wave of its workgroup, [1] waits for such a hand-over that ended on the clock (50 ms), [2] of [0]: taken from a run of two
+     * envs (a second split).  Every env still does exactly n_iter env-steps on its lock-step trajectory; KS_ROLLOUT_TAKEOVER=0 (read when the
+     * context is created) or a time budget switches the hand-overs off. */
+    int64_t *takeovers;
 } ks_rollout_args;
 int ks_rollout(ks_ctx *ctx, int32_t n_iter, const ks_rollout_args *args_host, void *stream);
 

@@ -13,7 +13,7 @@ CSRC = PKG / "csrc"
 LIB = PKG / "libkinova_sim.so"
 LIB_MG = PKG / "libkinova_sim_mg.so"
 SOURCES = ["ks_api.hip", "ks_rollout.hip", "ks_mlp.hip", "ks_xchg.hip"]
-HEADERS = ["ks_math.h", "ks_model.h", "ks_model_host.h", "ks_core.h", "ks_obs.h", "ks_env.h", "ks_mlp_tile.h", "../../include/kinova_sim.h", "../../include/kinova_rollout.h"]
+HEADERS = ["ks_math.h", "ks_model.h", "ks_model_host.h", "ks_core.h", "ks_obs.h", "ks_env.h", "ks_mlp_tile.h", "ks_select.h", "ks_controller.h", "ks_takeover.h", "../../include/kinova_sim.h", "../../include/kinova_rollout.h"]
 
 
 def hipcc_path() -> str:

@@ -34,6 +34,7 @@
 #include "ks_env.h"
 #include "ks_mlp_tile.h"
 #include "ks_select.h"
+#include "ks_takeover.h"
 #include "ks_model_host.h"
 
 using namespace ks;
@@ -1027,13 +1028,13 @@ __device__ __noinline__ void rollout_policy_wave(const ks_rollout_args* __restri
 #define KS_RS(i)
 #endif
 // One env-step (the body of k_rollout's loop) by one crew: the workgroup with the 16 envs of group grp (WAVE_SCOPE = false: joined by
-// barriers), or ONE WAVE with its own four of them (slots grp * epw + 4 * wave ..: the barrier-free loop).  Five phases - policy |
+// barriers), or ONE WAVE with cnt <= 4 of them (slots sbase ..; the env blocks are the physical wave's own: the barrier-free loop).  Five phases - policy |
 // 15 substeps | rays | observation | replay write - that differ between the two only in who joins, which slots and env blocks the
 // crew owns, and which policy function runs.
 template <int NT1, int NT2, bool WAVE_SCOPE>
 __device__ __forceinline__ void rollout_iter(const Model<float>& m, const Hulls<float>& hu, const Buffers<float>* __restrict__ bdev, int N, int frame_skip,
                                              int iters, int epw, int pair_memory, const ObsOut<float>* __restrict__ out,
-                                             const ks_rollout_args* __restrict__ rap, KS_LDS float* blocks, int grp) {
+                                             const ks_rollout_args* __restrict__ rap, KS_LDS float* blocks, int grp, int sbase, int cnt) {
     using T = float;
     using C = Crew<WAVE_SCOPE>;
     const Buffers<T>& b = *bdev;
@@ -1041,11 +1042,13 @@ __device__ __forceinline__ void rollout_iter(const Model<float>& m, const Hulls<
     const Team<SUBS> team{(int)threadIdx.x % LANE_STRIDE};
     // (the env ids are re-read from the slot list in every iteration rather than kept in registers across the stepping phase)
     // grp: the 16-env group of the slot list this workgroup steps now (its own, blockIdx.x, unless the launch has fewer workgroups than groups)
-    const int env = e < epw ? b.slot_env[grp * epw + e] : -1;
+    // (a wave: the cnt envs of slots sbase .., one per 16-lane team - its own four of the group, or what a hand-over left or gave it, ks_takeover.h)
+    const int wteam = (int)(threadIdx.x & (WAVE - 1)) >> 4;
+    const int env = WAVE_SCOPE ? (wteam < cnt ? b.slot_env[sbase + wteam] : -1) : (e < epw ? b.slot_env[grp * epw + e] : -1);
     const bool active = !(team.sub >= SUBS || env < 0);
     // the crew's slots of the list and its env blocks: scratch of the policy and of the tails while the blocks are dead
     const int wave = WAVE_SCOPE ? (int)(threadIdx.x >> 6) : 0;
-    const int slot0 = grp * epw + 4 * wave, cepw = WAVE_SCOPE ? (epw - 4 * wave < 4 ? (epw - 4 * wave < 0 ? 0 : epw - 4 * wave) : 4) : epw;
+    const int slot0 = WAVE_SCOPE ? sbase : grp * epw, cepw = WAVE_SCOPE ? cnt : epw;
     KS_LDS T* cblocks = blocks + 4 * wave * SCR_TOTAL;
     KS_LDS unsigned* w = (KS_LDS unsigned*)cblocks;
     // the crew's join between two phases (a wave on its own: Crew::sync's fence + wave barrier is all of it)
@@ -1147,6 +1150,46 @@ __device__ __noinline__ int rollout_restage(const Model<float>* __restrict__ mp,
     return (hull_words >> 2) << 2;
 }
 
+// The free waves' hand-over (ks_takeover.h) between two env-steps: the wave comes with the run it has just stepped (packed: kstk::pack_run;
+// at the start of a launch its own envs with n_iter + 1 left) and gets the run of its next env-step - the same with one step less, without the
+// envs a sibling asked for meanwhile, or, once that run is done, what a sibling hands over - or 0: nobody has envs to give, the wave leaves.
+// Lane 0 runs the protocol's state machine on the workgroup's twelve LDS words; it sleeps between polls while it waits as a helper.  Out of
+// line: nothing of it may stay in registers across the stepping phase.
+struct TakeoverLds {
+    KS_LDS uint32_t* w;
+    __device__ __forceinline__ uint32_t load(int i) { return __hip_atomic_load(w + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
+    __device__ __forceinline__ void store(int i, uint32_t v) { __hip_atomic_store(w + i, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
+    __device__ __forceinline__ bool cas(int i, uint32_t expect, uint32_t v) {
+        return __hip_atomic_compare_exchange_strong(w + i, &expect, v, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+    // the envs' state travels through global memory: everything the granting wave has stored, before the grant; nothing of the taking wave's
+    // loads ahead of it (the waves share a CU and its L1: agent scope writes through and invalidates it)
+    __device__ __forceinline__ void release() { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent"); }
+    __device__ __forceinline__ void acquire() { __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent"); }
+    __device__ __forceinline__ int64_t deadline_ticks() const { return 5000000; }      // 50 ms of the 100 MHz clock
+};
+__device__ __noinline__ uint32_t rollout_takeover_next(uint32_t run, KS_LDS uint32_t* words, const ks_rollout_args* __restrict__ rap) {
+    uint32_t next = 0u;
+    if ((threadIdx.x & (WAVE - 1)) == 0) {
+        TakeoverLds mem{words};
+        kstk::Wave w = kstk::resume((int)(threadIdx.x >> 6), run);
+        for (;;) {
+            w.idle = 0;
+            const kstk::Event ev = kstk::advance(w, mem, (int64_t)wall_clock64());
+            if (ev == kstk::STEP) { next = kstk::pack_run(w.off, w.cnt, w.left); break; }
+            if (ev == kstk::EXIT) break;
+            if (w.idle) __builtin_amdgcn_s_sleep(64);
+        }
+        // [0] runs taken, [1] waits that ended on the clock, [2] runs taken from a run of two envs (a second-level split)
+        if (int64_t* tk = rap->takeovers) {
+            if (w.grants) atomicAdd((unsigned long long*)&tk[0], (unsigned long long)w.grants);
+            if (w.expiries) atomicAdd((unsigned long long*)&tk[1], (unsigned long long)w.expiries);
+            if (w.grants_from_pairs) atomicAdd((unsigned long long*)&tk[2], (unsigned long long)w.grants_from_pairs);
+        }
+    }
+    return (uint32_t)__builtin_amdgcn_readfirstlane((int)next);
+}
+
 template <int NT1, int NT2>
 __global__ __launch_bounds__(WG) KS_ROLLOUT_REGS void k_rollout(const Model<float>* __restrict__ models, Buffers<float> b, const Buffers<float>* __restrict__ bdev, int N,
                                                 int frame_skip, int iters, int epw, int pair_memory, const ObsOut<float>* __restrict__ out,
@@ -1167,6 +1210,9 @@ __global__ __launch_bounds__(WG) KS_ROLLOUT_REGS void k_rollout(const Model<floa
     int staged = __builtin_amdgcn_readfirstlane(b.wg_model[deal.g0]);
     const Model<T>* ml = stage_model_and_tables<T, WG>(models + staged, lds0);
     int hull_words = 0;
+    // the hand-over protocol's words of the free waves (ks_takeover.h), set in front of the staging barrier: no wave looks at them before it
+    __shared__ uint32_t s_tko[kstk::WORDS];
+    if (wave_free == 2 && threadIdx.x < kstk::WORDS) s_tko[threadIdx.x] = kstk::initial_word((int)threadIdx.x, epw, n_iter);
     __syncthreads();
     stage_hulls<T, true>(*ml, lds, hull_words, *hup, true);
     KS_LDS T* blocks = env_blocks(lds, hull_words);                 // the 16 env blocks; scratch of the tails between the steps
@@ -1181,26 +1227,33 @@ __global__ __launch_bounds__(WG) KS_ROLLOUT_REGS void k_rollout(const Model<floa
     // (<= 168 registers) must fit beside this kernel on every SIMD.
     // (a macro, not a lambda: as a closure, the queue's push then reading grp for want of the laundered gi, the kernel took 368 bytes of
     // scratch per lane instead of 352 and up to three more spills)
-#define KS_STEP_GROUP(WAVE_SCOPE, GRP)                                                                                      \
+#define KS_STEP_GROUP(WAVE_SCOPE, GRP, SBASE, CNT)                                                                          \
     const Model<T>* mi = ml;                                                                                                \
     Hulls<T>* hi = hup;                                                                                                     \
     const Buffers<T>* bi = bdev;                                                                                            \
     const ObsOut<T>* oi = out;                                                                                              \
     const ks_rollout_args* ri = rap;                                                                                        \
     KS_LDS T* ki = blocks;                                                                                                  \
-    int gi = GRP;                                                                                                           \
-    asm volatile("" : "+s"(mi), "+s"(hi), "+s"(bi), "+s"(oi), "+s"(ri), "+s"(gi));                                          \
+    int gi = GRP, si = SBASE, ci = CNT;                                                                                     \
+    asm volatile("" : "+s"(mi), "+s"(hi), "+s"(bi), "+s"(oi), "+s"(ri), "+s"(gi), "+s"(si), "+s"(ci));                      \
     asm volatile("" : "+v"(ki));                                                                                            \
-    rollout_iter<NT1, NT2, WAVE_SCOPE>(*mi, *hi, bi, N, frame_skip, iters, epw, pair_memory, oi, ri, ki, gi)
+    rollout_iter<NT1, NT2, WAVE_SCOPE>(*mi, *hi, bi, N, frame_skip, iters, epw, pair_memory, oi, ri, ki, gi, si, ci)
     if (wave_free) {
         // ---- ONE GROUP PER WORKGROUP (4096 envs on 256 CUs, the metric's shape), round 6: from here on the four waves never meet again -
         // each loops over its own four envs (rollout_iter<.., true>) and leaves when it has done its n_iter env-steps.
         // (opt-in time budget, ks_rollout_args.budget_ticks: the wave starts no further env-step once the budget has passed - at least one)
+        // wave_free == 2: a wave that has done its env-steps takes over half the envs of its workgroup's least-advanced wave (ks_takeover.h;
+        // rollout_takeover_next hands the wave its run for the next env-step, 0 when nobody has envs to give any more).
         const long long budget = rap->budget_ticks, t_end = wall_clock64() + budget;
+        const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+        uint32_t run = kstk::pack_run(4 * wave, kstk::initial_cnt(wave, epw), wave_free == 2 ? n_iter + 1 : n_iter);
 #pragma clang loop unroll(disable)
-        for (int it = 0; it < n_iter; it++) {
-            if (budget > 0 && it > 0 && wall_clock64() - t_end > 0) break;
-            KS_STEP_GROUP(true, deal.g0);
+        for (int it = 0;; it++) {
+            if (wave_free == 2) {
+                run = (uint32_t)__builtin_amdgcn_readfirstlane((int)rollout_takeover_next(run, (KS_LDS uint32_t*)s_tko, rap));      // (a call's result: uniform, in a vector register)
+                if (run == 0u) break;
+            } else if (it >= n_iter || (budget > 0 && it > 0 && wall_clock64() - t_end > 0)) break;
+            KS_STEP_GROUP(true, deal.g0, __builtin_amdgcn_readfirstlane(deal.g0 * epw + kstk::run_off(run)), __builtin_amdgcn_readfirstlane(kstk::run_cnt(run)));
         }
         return;
     }
@@ -1243,7 +1296,7 @@ __global__ __launch_bounds__(WG) KS_ROLLOUT_REGS void k_rollout(const Model<floa
             if (grp < 0) break;
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");              // the group's state as its last env-step - on whatever CU - left it
             if (object_differs(bdev->wg_model, grp, staged)) blocks = lds + rollout_restage(models + staged, lds0, hup);
-            KS_STEP_GROUP(false, grp);
+            KS_STEP_GROUP(false, grp, 0, 0);
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");              // every wave: its stores of this env-step, before the group is handed on
             __syncthreads();
             if (threadIdx.x == 0) {
@@ -1265,7 +1318,7 @@ __global__ __launch_bounds__(WG) KS_ROLLOUT_REGS void k_rollout(const Model<floa
         for (int grp = deal.g0; grp < deal.g1; grp += deal.gstep) {
             // another group of this workgroup: restage the tables when its object differs from the one in LDS (~10 us)
             if (deal.several() && object_differs(bdev->wg_model, grp, staged)) blocks = lds + rollout_restage(models + staged, lds0, hup);
-            KS_STEP_GROUP(false, grp);
+            KS_STEP_GROUP(false, grp, 0, 0);
         }
     }
 #undef KS_STEP_GROUP
@@ -2248,6 +2301,7 @@ template <typename T> struct Ctx : CtxBase {
                                           // (measured, round 5).  That context is bound by its slowest groups' SEQUENTIAL env-steps anyway (every env does the
                                           // same number of env-steps per launch): no dealing helps it.  KS_ROLLOUT_DEAL=queue forces the queue.
     bool rollout_waves = !(getenv("KS_ROLLOUT_WAVES") && getenv("KS_ROLLOUT_WAVES")[0] == '0');      // free-running waves (one group per workgroup)
+    bool rollout_takeover = !(getenv("KS_ROLLOUT_TAKEOVER") && getenv("KS_ROLLOUT_TAKEOVER")[0] == '0');      // free waves: finished waves take over envs of their workgroup's slowest (ks_takeover.h)
     int rollout_phase_deal = getenv("KS_ROLLOUT_PHASE_DEAL") ? atoi(getenv("KS_ROLLOUT_PHASE_DEAL")) : 1;      // free waves, one object: slots sorted by episode step before every launch (1: within every workgroup's sixteen, 2: the whole list, 0: env order)
     bool rollout_round_robin = false;     // how k_rollout deals the env groups to its persistent workgroups: contiguous runs (default) or round-robin (KS_ROLLOUT_DEAL=rr)
     int lpw = WAVE;
@@ -2270,6 +2324,8 @@ template <typename T> struct Ctx : CtxBase {
         const size_t lds_max = 160 * 1024;
         const size_t hull_bytes = (size_t)hull_words * sizeof(T) + (USE_LDS ? (size_t)model_words<T>() * sizeof(T) : 0);
         const size_t per_env = USE_LDS ? (size_t)SCR_TOTAL * sizeof(T) : 0;
+        // (64 bytes beside the dynamic LDS: k_rollout's static words - the queue form's s_grp and the free waves' hand-over words)
+        static_assert(16 + kstk::WORDS * sizeof(uint32_t) <= 64, "k_rollout's static LDS");
         int cap = USE_LDS ? (int)((lds_max - hull_bytes - 64) / per_env) : EPW_MAX;
         if (cap > EPW_MAX) cap = EPW_MAX;
         if (cap < 1) { error = "hull tables do not fit in LDS"; return KS_ERR_MODEL; }
@@ -2513,7 +2569,9 @@ template <typename T> struct Ctx : CtxBase {
                 using W = decltype(tiles);
                 return launch_rollout(k_rollout<W::NT1, W::NT2>, step_lds, s, d_model, b, (const Buffers<T>*)d_b, N, cfg.frame_skip, cfg.solver_iterations, lpw,
                                       (int)cfg.pair_memory, (const ObsOut<T>*)d_out, (const ks_rollout_args*)d_ra, n_iter,
-                                      (use_queue || !rollout_round_robin) ? n_groups : -n_groups, use_queue ? d_queue : (int*)nullptr, (int)wave_free);
+                                      (use_queue || !rollout_round_robin) ? n_groups : -n_groups, use_queue ? d_queue : (int*)nullptr,
+                                      // 0 workgroups | 1 free waves | 2 free waves with hand-overs: exact step counts only (no time budget)
+                                      wave_free ? ((rollout_takeover && ra->budget_ticks == 0 && n_iter < kstk::LEFT_MAX) ? 2 : 1) : 0);
             });
         }
     }

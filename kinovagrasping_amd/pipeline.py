@@ -454,7 +454,7 @@ class GraphedTrainer:
             self.native.exchange.check()
 
 
-def rollout_args(sim, policy, eng, pub, pub_ver, steps_total, counters, replay=None, repeats=None, sigma=None):
+def rollout_args(sim, policy, eng, pub, pub_ver, steps_total, counters, replay=None, repeats=None, sigma=None, takeovers=None):
     """The ks_rollout_args record (include/kinova_sim.h) of a free-running launch on `sim`: the actor's published parameter buffers
     (pub [3, stride] with the layout of policy's flat actor parameters, pub_ver the version counter), the engine's state tensors,
     the context's output buffers and - with a replay in its asynchronous form - the open-episode buffers (with_replay = 1); without
@@ -486,6 +486,8 @@ def rollout_args(sim, policy, eng, pub, pub_ver, steps_total, counters, replay=N
     a.counters = P(counters)
     if repeats is not None:
         a.repeats = P(repeats)
+    if takeovers is not None:                      # int64 [3]: the free waves' hand-overs (ks_rollout_args.takeovers)
+        a.takeovers = P(takeovers)
     return a
 
 
@@ -580,10 +582,12 @@ class AsyncTrainer(GraphedTrainer):
         self.pub[0, :flat.numel()].copy_(flat)
         replay.enable_async()
         self.steps_total = torch.zeros(eng.n, dtype=torch.long, device=dev)
-        self.counters = torch.zeros(8 + 4 * 512 + 8 + (eng.n if os.environ.get("KS_DEBUG_DROPS") else 0), dtype=torch.long, device=dev)      # episodes finished, lifted, kept, dropped (+ 4 phase timers and 4 x 512
-                                                                          # per-workgroup stamps of the -DKS_ROLLOUT_STAMP diagnostic build)
+        self.counters = torch.zeros(8 + 4 * 512 + 8 + (eng.n if os.environ.get("KS_DEBUG_DROPS") else 0) + 3, dtype=torch.long, device=dev)  # episodes finished, lifted, kept, dropped (+ 4 phase timers and 4 x 512
+                                                                          # per-workgroup stamps of the -DKS_ROLLOUT_STAMP diagnostic build); the last three
+                                                                          # words: the free waves' hand-overs (takeovers())
         self.repeats = torch.zeros(1, dtype=torch.long, device=dev)          # actor forwards repeated because two versions were published meanwhile
-        a = rollout_args(sim, policy, eng, self.pub, self.pub_ver, self.steps_total, self.counters, replay=replay, repeats=self.repeats)
+        a = rollout_args(sim, policy, eng, self.pub, self.pub_ver, self.steps_total, self.counters, replay=replay, repeats=self.repeats,
+                         takeovers=self.counters[-3:])
         # pacing: the learner's stream waits (kr_wait_min on the envs' step counters) so that update k of a launch starts when EVERY env
         # has done k - lead env-steps.  Without it the learner (0.9 ms per update) finishes its share of a long launch far ahead of the
         # rollout (1.1 ms per env-step) and nobody collects the episodes published after that.
@@ -812,6 +816,13 @@ class AsyncTrainer(GraphedTrainer):
         """in-kernel actor forwards repeated so far because the version counter advanced by two or more while they read the weights (the
         rollout kernel's torn-read guard; host sync).  Kept out of counts(), whose content is the bench line's."""
         return int(self.repeats.item())
+
+    def takeovers(self):
+        """(runs taken, waits that expired, runs taken from a run of two envs) so far: how often a wave of the free-running rollout kernel that
+        had done its env-steps of a launch took over envs of a slower wave of its workgroup, how often it waited 50 ms for that in vain, and how
+        many of the hand-overs were second splits (csrc/ks_takeover.h; host sync).  All zero with KS_ROLLOUT_TAKEOVER=0 and in the other
+        scheduling forms.  Kept out of counts(), whose content is the bench line's."""
+        return tuple(self.counters[-3:].tolist())
 
     def counts(self):
         c = self.counters[:4].tolist()

@@ -42,7 +42,7 @@ class KsRolloutArgs(C.Structure):
                                            "done_out", "sim_obs", "sim_reward", "sim_done", "sim_info", "sim_final_obs")] +
                 [("horizon", C.c_int32), ("n_steps", C.c_int32)] +
                 [(k, C.c_void_p) for k in ("cur_state", "cur_next", "cur_action", "cur_reward", "cur_not_done", "cur_len", "cur_sel", "pub_len", "counters")] +
-                [("budget_ticks", C.c_int64), ("repeats", C.c_void_p)])
+                [("budget_ticks", C.c_int64), ("repeats", C.c_void_p), ("takeovers", C.c_void_p)])
 
 
 class KsEpisodeRecord(C.Structure):

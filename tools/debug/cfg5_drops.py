@@ -32,7 +32,7 @@ replay = DeviceEpisodeReplay(n, capacity=4 * n, horizon=30, device=sim.device)
 eng = RolloutEngine(sim, policy, replay, expl_noise=0.1)
 eng.start(obs0)
 tr = AsyncTrainer(sim, policy, replay, eng, batch_episodes=64)
-if len(tr.counters) > 8 + 4 * 512 + 8:
+if len(tr.counters) > 8 + 4 * 512 + 8 + 3:      # (KS_DEBUG_DROPS: n more words in front of the three hand-over words)
     tr.counters[6] = 1 << 40
 tr.capture()
 tr.run(36, learn=False); tr.flush(); torch.cuda.synchronize()
@@ -68,6 +68,6 @@ for it in range(6):
           f"dropped +{c['episodes_dropped'] - prev['episodes_dropped']} timeouts {c['pacing_timeouts']}; steps_total min {int(st.min())} max {int(st.max())}; "
           f"pub_len>0: {int((replay.pub_len > 0).sum())}, both buffers published: {int(((replay.pub_len[0] > 0) & (replay.pub_len[1] > 0)).sum())}")
     prev = c
-    if len(tr.counters) > 8 + 4 * 512 + 8:
+    if len(tr.counters) > 8 + 4 * 512 + 8 + 3:      # (KS_DEBUG_DROPS: n more words in front of the three hand-over words)
         d = tr.counters[4:8].tolist()
         print(f"   drops {d[1]}: mean env-steps since the env's previous publication {d[0] / max(1, d[1]):.1f}, smallest {d[2]}; other buffer free on a second look: {d[3]}")
