@@ -42,7 +42,7 @@ U = 2.0 ** -24
 C_FP32 = 69
 FP64 = dict(qpos=1e-9, qvel=1e-7, warm=1e-9)
 
-Ref = namedtuple("Ref", "qpos qvel qacc qacc_smooth ncon nefc efc_type efc_J efc_R efc_aref efc_force M bias passive actuator converged iters ctrl h damping weight")
+Ref = namedtuple("Ref", "qpos qvel qacc qacc_smooth ncon nefc efc_type efc_J efc_R efc_aref efc_force M bias passive actuator converged iters ctrl h damping weight con_geom con_dist con_pos con_mu con_margin con_force", defaults=(None,) * 6)   # con_*: per contact of the step's forward pass (geom pair, dist, pos, mu of the two tangents, margin, force in its frame)
 
 
 def step_ctrl(shape, hq, qpos, action):
@@ -65,10 +65,13 @@ def oracle_step(shape, hq, mass, qpos, qvel, warm, ctrl) -> Ref:
         o.s.obj_mass = 0.0
     n = o.s.nefc
     v = lambda k: o.view(k).copy()
+    cs = [o.s.contact[i] for i in range(o.s.ncon)]
+    con = (np.array([(c.geom1, c.geom2) for c in cs], dtype=int).reshape(-1, 2), np.array([c.dist for c in cs]), np.array([c.pos[:] for c in cs]).reshape(-1, 3),
+           np.array([c.mu[:2] for c in cs]).reshape(-1, 2), np.array([c.margin for c in cs]), o.contact_forces())
     return Ref(v("qpos"), v("qvel"), v("qacc"), v("qacc_smooth"), int(o.s.ncon), n, v("efc_type")[:n], v("efc_J").reshape(-1, 15)[:n], v("efc_R")[:n],
                v("efc_aref")[:n], v("efc_force")[:n], v("M").reshape(15, 15), v("qfrc_bias"), v("qfrc_passive"), v("qfrc_actuator"),
                int(o.s.newton_converged), int(o.s.newton_iters_used), np.array(ctrl, dtype=np.float64), float(M["opt"][0]), np.asarray(M["dof_damping"], dtype=np.float64),
-               weight(M, mass, o.view("M").reshape(15, 15), np.asarray(qvel, dtype=np.float64)))
+               weight(M, mass, o.view("M").reshape(15, 15), np.asarray(qvel, dtype=np.float64)), *con)
 
 
 def weight(M, obj_mass, Mm, qvel):
@@ -220,10 +223,11 @@ def ratios(ref: Ref, got, precision, first_form=False):
     return out
 
 
-def between(refs, got, precision):
-    """an undecidable state: every output lies between the references of the moved states, widened by their bounds"""
+def between(refs, got, precision, bounds_of=None):
+    """an undecidable state: every output lies between the references of the moved states, widened by their bounds (bounds_of(ref, precision):
+    another bound than `bounds`, tests/contact_solve_ref.py)"""
     want = lambda r: dict(qpos=r.qpos, qvel=r.qvel, warm=r.qacc)
-    bs = [bounds(r, precision) for r in refs]
+    bs = [(bounds_of or bounds)(r, precision) for r in refs]
     for k in ("qpos", "qvel", "warm"):
         lo = np.min([want(r)[k] - b[k] for r, b in zip(refs, bs)], 0)
         hi = np.max([want(r)[k] + b[k] for r, b in zip(refs, bs)], 0)

@@ -172,11 +172,12 @@ def _sphere_dirs(n=200):
 _hand_gap_cache = {}
 
 
-def clearance(shape, hq, qpos):
+def clearance(shape, hq, qpos, floor=True):
     """(the oracle's ncon, the smallest distance beyond its margin of the floor and of every hull pair - a certified lower bound -, the object's
     distance from hand and floor) at a pose:
     floor pairs from the lowest hull vertex, object-hand pairs from the bounding spheres, hand-hand pairs (a function of the finger angles alone)
-    from the widest separating gap over a set of directions"""
+    from the widest separating gap over a set of directions.  floor=False: the hull pairs alone (tests/contact_solve_states.py: states that stand
+    on the floor)"""
     orc = cp._oracle(shape)
     M = orc.M
     o = orc.sim(hq)
@@ -189,6 +190,8 @@ def clearance(shape, hq, qpos):
     for g1, g2, _, _, margin in np.asarray(M["pairs"]):
         g1, g2 = int(g1), int(g2)
         if g1 == 0:
+            if not floor:
+                continue
             d = float(pr.vertex_dist(xmat[g2], xpos[g2], pr.hull_of(M, g2)).min())
         elif g2 >= 8:
             d = float(np.linalg.norm(xpos[g1] - xpos[g2]) - M["geom_rbound"][g1] - M["geom_rbound"][g2])
